@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
 """bench.py — the headline benchmark of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on): 10 000 000 rows x FLOAT[768], metric
 cosine, top-10, batches of 1024 queries, one MI355X.  A "step" is ONE pass of the hot path over one batch: one
 HNSW_INDEX_JOIN-style probe of 1024 queries (vss_search_batch_device) against the resident index, inputs already in
 HBM.  Reported: queries/s at the recall@10 measured on HELD-OUT batches against the exact MFMA brute-force path (ef_search =
-the smallest of EF_SWEEP whose recall on two selection batches clears 0.95 by two standard errors), plus index build rows/s,
-the HBM roofline of the search kernel and a CPU baseline (the reference's own usearch build, one thread, on the very graph
-the engine built) whose answers must agree with the engine's cell by cell: a differing cell has to be a near-tie in the
-reference's arithmetic, or its query must replay bit-identically in the oracle's wave-order restatement — else the run fails.
+the smallest of EF_SWEEP whose recall on two selection batches clears 0.95 by two standard errors), plus index build rows/s
+and the HBM roofline of the search kernel over the timed launches.
 
-The default single-GPU run then releases its index and attaches, as objects of the same JSON line, the other BASELINE
-configurations in compact form — c2 (configs[1]), c4 (configs[3] on one GPU), c5 (one shard of configs[4]), a13 (the three
-array_* functions) and the headline workload on the reference's DEFAULT index options — each measured by `bench.py --config
-...` in a process of its own (`--extras none` = just the headline).
+A plain run does only that: build, select ef_search, warm up, time the steps, print ONE JSON line.  `--dump-outputs DIR`
+also writes what the last timed step returned (row ids, distances, result counts) as DIR/<name>.npy.  `--full` adds
+everything else the benchmark measures: the spread of repeated timed regions, other launch regimes, the host-pointer API
+and one-query latencies, a timing of the exact path alone, a CPU baseline (the reference's own usearch build, one thread,
+on the very graph the engine built) whose answers must agree with the engine's cell by cell — a differing cell has to be
+a near-tie in the reference's arithmetic, or its query must replay bit-identically in the oracle's wave-order
+restatement, else the run fails — and, on the single-GPU headline, the other BASELINE configurations in compact form:
+c2 (configs[1]), c4 (configs[3] on one GPU), c5 (one shard of configs[4]), a13 (the three array_* functions) and the
+headline workload on the reference's DEFAULT index options, each measured by `bench.py --full --config ...` in a process
+of its own (`--extras none` = just the headline).  With --full, stdout carries {"detail": ...} lines before the headline
+and the complete object goes to a sidecar file.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): BASELINE.json configs[3] — the same 10M x 768 rows (l2sq)
 row-range sharded across the ranks, every rank answers every query on its shard, ONE RCCL all-gather per launch of the
@@ -87,6 +92,132 @@ class Mixture:
         if self.normalize:
             x = x / x.norm(dim=1, keepdim=True)
         return x.contiguous()
+
+
+INDEX_CACHE_FORMAT = 2
+DIGEST_ROWS = 1024
+
+
+def index_cache_path(pkg, n_total, dim, metric, M, M0, efc):
+    """Where the headline index's graph is cached (the user's cache directory), keyed by everything that decides it: the
+    engine library's bytes, this file's bytes (the generator, the staging and the build driver), the index options and
+    the generator's constants."""
+    import hashlib
+    h = hashlib.sha256()
+    for path in (pkg.LIB_PATH, os.path.abspath(__file__)):
+        with open(path, "rb") as f:
+            h.update(f.read())
+    h.update(repr((INDEX_CACHE_FORMAT, n_total, dim, metric, M, M0, efc, DATA_SEED, INTRINSIC_DIM, SPREAD, CENTRE_SCALE,
+                   CHUNK)).encode())
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    return os.path.join(base, "duckdb-vss_amd", "bench_index_" + h.hexdigest()[:24])
+
+
+def digest_rows(n_rows):
+    """The rows whose bytes stand for all vectors of an n_rows index: the first, the last and a seeded sample."""
+    pick = np.random.default_rng(0xD16E57).integers(0, n_rows, DIGEST_ROWS)
+    return np.unique(np.concatenate([[0, n_rows - 1], pick]))
+
+
+def vector_digest(row_bytes):
+    """sha256 over the digest rows' float32 bytes, rows in digest_rows() order."""
+    import hashlib
+    return hashlib.sha256(row_bytes).hexdigest()
+
+
+def generator_rows(gen, n_rows, idx):
+    """The generator's rows idx (sorted) of an n_rows index, chunk by chunk as the build stages them, as bytes."""
+    out = []
+    for ci in range((n_rows + CHUNK - 1) // CHUNK):
+        sel = idx[(idx >= ci * CHUNK) & (idx < (ci + 1) * CHUNK)] - ci * CHUNK
+        if len(sel):
+            out.append(gen.rows(DATA_SEED, ci, CHUNK)[torch.from_numpy(sel).to(gen.device)].cpu().numpy())
+    return np.concatenate(out).tobytes()
+
+
+def save_index_cache(pkg, ix, path, gen, record):
+    """ix's serialized stream minus its vectors (they are regenerated from their seeds) as path.graph, the build's figures
+    and a digest of the stream's vectors as path.json — under temporary names first.  Written only if the stream's vectors
+    are the generator's (same digest); older caches of the same workload (another engine or bench.py) are removed."""
+    import ctypes as C
+    rows, dim = record["rows"], record["dim"]
+    row_bytes, skip = dim * 4, 8 + rows * dim * 4
+    idx = digest_rows(rows)
+    picked, state = {}, {"off": 0}
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path + ".graph.tmp", "wb") as f:
+        def write(ctx, data, size):
+            at = state["off"]
+            if at < skip and at + size > 8:  # vector bytes: keep the digest rows (slabs hold whole rows)
+                r0, r1 = (max(at, 8) - 8) // row_bytes, (min(at + size, skip) - 8) // row_bytes
+                for r in idx[(idx >= r0) & (idx < r1)]:
+                    picked[int(r)] = C.string_at(data + 8 + int(r) * row_bytes - at, row_bytes)
+            if at + size > skip:
+                lo = max(0, skip - at)
+                f.write(C.string_at(data + lo, size - lo))
+            state["off"] += size
+            return 1
+        cb = pkg.WRITE_CB(write)
+        ix._check(ix.lib.vss_save(ix.h, cb, None))
+    stream_digest = vector_digest(b"".join(picked[int(r)] for r in idx)) if len(picked) == len(idx) else None
+    if stream_digest != vector_digest(generator_rows(gen, rows, idx)):
+        os.remove(path + ".graph.tmp")
+        raise RuntimeError("the index's vectors are not the generator's: no cache written")
+    with open(path + ".json.tmp", "w") as f:
+        json.dump(dict(record, vector_digest=stream_digest), f)
+    os.replace(path + ".graph.tmp", path + ".graph")
+    os.replace(path + ".json.tmp", path + ".json")
+    import glob
+    for old in glob.glob(os.path.join(os.path.dirname(path), "bench_index_*.json")):
+        if old == path + ".json":
+            continue
+        try:
+            o = json.load(open(old))
+            same = o.get("workload") == record.get("workload")
+        except (OSError, ValueError):
+            same = True  # unreadable: a broken entry
+        if same:
+            for ext in (".json", ".graph"):
+                try:
+                    os.remove(old[:-len(".json")] + ext)
+                except OSError:
+                    pass
+
+
+def load_index_cache(pkg, ix, path, gen, device):
+    """Restore the cached index into the empty ix through vss_load: the stream's vectors are regenerated on the device and
+    copied straight into the engine's buffer, its graph comes from path.graph.  Returns the build's recorded figures, or
+    None (ix untouched) when the regenerated vectors' digest is not the one the graph was saved with."""
+    import ctypes as C
+    record = json.load(open(path + ".json"))
+    rows, dim = record["rows"], record["dim"]
+    x = torch.empty((rows, dim), dtype=torch.float32, device=device)
+    for pos in range(0, rows, CHUNK):
+        x[pos:pos + CHUNK] = gen.rows(DATA_SEED, pos // CHUNK, CHUNK)[:min(CHUNK, rows - pos)]
+    idx = digest_rows(rows)
+    if vector_digest(x[torch.from_numpy(idx).to(device)].cpu().numpy().tobytes()) != record.get("vector_digest"):
+        return None
+    torch.cuda.synchronize()
+    graph = np.fromfile(path + ".graph", dtype=np.uint8)
+    head = np.array([rows, dim * 4], dtype=np.uint32)
+
+    class Pieces(C.Structure):
+        _fields_ = [("ptr", C.c_void_p * 4), ("len", C.c_uint64 * 4), ("on_device", C.c_int32 * 4), ("count", C.c_int32),
+                    ("at", C.c_int32), ("off", C.c_uint64), ("copy", C.c_void_p)]
+    lib = pkg.load_library()
+    helper = C.CDLL(os.path.join(ROOT, "duckdb-vss_amd", "host", "libstream_pieces.so"))
+    p = Pieces()
+    p.ptr[0], p.len[0] = head.ctypes.data, head.nbytes
+    p.ptr[1], p.len[1], p.on_device[1] = x.data_ptr(), rows * dim * 4, 1
+    p.ptr[2], p.len[2] = graph.ctypes.data, graph.nbytes
+    p.count = 3
+    p.copy = C.cast(lib.hipMemcpy, C.c_void_p).value  # the HIP runtime the engine and torch share
+    read = pkg.READ_CB(C.cast(helper.stream_pieces_read, C.c_void_p).value)
+    ix._check(lib.vss_load(ix.h, read, C.addressof(p)))
+    if p.at != p.count:
+        raise RuntimeError("index cache %s: the stream was not read to its end" % path)
+    del x, graph
+    return record
 
 
 def recall_at_k(got, truth):
@@ -447,19 +578,19 @@ def cpu_baseline(pkg, args, gen, dim, metric, k, ef, device, M, M0, efc, shards=
 # The driver keeps a bounded tail of stdout (8 000 characters) and parses the LAST JSON line of it.  Round 4 lost its
 # headline to a 24 kB line.  The contract since round 5 (tests/test_bench_helpers.py holds it):
 #   * the LAST stdout line is the compact headline object, at most LINE_LIMIT characters;
-#   * everything else — ef sweep, launch regimes, latency shapes, the host API leg, each extra configuration — is printed
-#     on EARLIER lines of its own, each a small JSON object starting with {"detail": ...} or {"extra": ...}, short enough
-#     that all of them together with the headline fit the driver's tail;
-#   * the complete, unabridged result goes to a sidecar file (--sidecar, default gpurun_out/bench_full_<config>.json).
+#   * with --full, everything else — ef sweep, launch regimes, latency shapes, the host API leg, each extra configuration — is
+#     printed on EARLIER lines of its own, each a small JSON object starting with {"detail": ...} or {"extra": ...}, short
+#     enough that all of them together with the headline fit the driver's tail; a plain run prints the headline line alone;
+#   * the complete, unabridged result goes to a sidecar file (--sidecar; with --full the default is default_sidecar()'s).
 LINE_LIMIT = 3500      # the last line
 SIDE_LINE_LIMIT = 540  # every {"detail": ...} / {"extra": ...} line
 AGREEMENT_SCALARS = ("queries", "id_match_frac", "query_match_frac", "rank_distance_max_rel_err", "mismatching_cells",
                      "unexplained_mismatches")
 HEADLINE_KEYS = ("metric", "config_id", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                  "multi_gpu_mode", "vs_baseline", "dtype", "data", "recall_at_10", "recall_at_10_se", "recall_at_100",
-                 "recall_at_100_se", "recall_measured_on", "ef_search", "repeat", "plateau", "build_rows_per_s", "build", "rccl_ranks",
-                 "collective_backend", "collectives_per_launch", "collectives_timed", "rank_pci", "config", "roofline", "cpu_baseline",
-                 "exit_code", "wall_s")
+                 "recall_at_100_se", "recall_measured_on", "ef_search", "repeat", "plateau", "build_rows_per_s", "build_measured",
+                 "build", "rccl_ranks", "collective_backend", "collectives_per_launch", "collectives_timed", "rank_pci", "config",
+                 "roofline", "cpu_baseline", "exit_code", "wall_s")
 ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "traffic_over_algorithmic", "traffic_source",
                  "algorithmic_bytes_per_launch", "avg_kernel_ms", "launches", "frac_over_wall", "distances_per_query",
                  "expansions_per_query", "visited_set", "latency_bound", "us_per_expansion", "slowest_leg")
@@ -608,20 +739,40 @@ def detail_lines(result, limit=SIDE_LINE_LIMIT):
     return lines
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: array} as out_dir/<name>.npy — floating arrays as float32, integer ones (row ids, counts)
+    as float64, which holds every id below 2^53 exactly.  These are copies of what the last timed step returned."""
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype.kind == "f" else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def default_sidecar(config_id):
     return os.path.join(ROOT, "gpurun_out", "bench_full_%s.json" % config_id)
 
 
-def emit(result, sidecar=None, extras=()):
-    """Print a result the way the contract above says and return the compact last line.  `extras` = [(name, object)]."""
-    side = sidecar or default_sidecar(result.get("config_id", "c3"))
-    try:
-        os.makedirs(os.path.dirname(side), exist_ok=True)
-        with open(side, "w") as f:
-            json.dump(result, f, indent=1)
-    except OSError as e:  # a read-only tree must not cost the line
-        sys.stderr.write("bench.py: sidecar %s not written: %r\n" % (side, e))
-    for line in detail_lines(result):
+def emit(result, sidecar=None, extras=(), full=True):
+    """Print a result the way the contract above says and return the compact last line.  `extras` = [(name, object)].
+    A plain run (full=False) prints the compact line alone and writes a sidecar only if one was named."""
+    side = sidecar or (default_sidecar(result.get("config_id", "c3")) if full else None)
+    if side:
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(side)), exist_ok=True)
+            with open(side, "w") as f:
+                json.dump(result, f, indent=1)
+        except OSError as e:  # a read-only tree must not cost the line
+            sys.stderr.write("bench.py: sidecar %s not written: %r\n" % (side, e))
+    for line in (detail_lines(result) if full else []):
         print(json.dumps(line))
     for name, obj in extras:
         print(json.dumps(extra_line(name, obj)))
@@ -633,9 +784,9 @@ def emit(result, sidecar=None, extras=()):
     return last
 
 
-def finish(result, sidecar=None):
+def finish(result, sidecar=None, full=True):
     """Print the lines; a run whose reference answers disagree with the engine's is a FAILED run (exit code 4)."""
-    emit(result, sidecar)
+    emit(result, sidecar, full=full)
     a = (result.get("cpu_baseline") or {}).get("agreement")
     if a is not None and not agreement_ok(a):
         sys.stderr.write("bench.py: reference agreement below the bar: %s\n" % json.dumps(a))
@@ -734,6 +885,8 @@ def main_c5(args):
     probe(max(1, (args.warmup + G - 1) // G))
     elapsed, kernel_ms, dists, expans = probe(n_launches)
     steps = n_launches * G
+    if args.dump_outputs:  # the last batch of the last timed launch, before the CRUD steps reuse the buffers
+        dump_outputs(args.dump_outputs, {"ids": outs[G - 1][0], "distances": outs[G - 1][1], "counts": outs[G - 1][2]})
     bytes_per_launch = (dists * (4 * dim + 4) + expans * (4 + 4 * M0)) / n_launches
     # the CRUD part of the configuration, each step followed by recall against a fresh exact answer and one timed launch
     crud = []
@@ -848,7 +1001,7 @@ def main_c5(args):
                                    ref_distance=make_ref_distance(lib, metric, dim),
                                    replay=make_wave_order_replay(lambda: [stream_of(pre)], dim, metric, M, M0, efc, k, ef, qh))}
         pre.close()
-    finish(result, args.sidecar)
+    finish(result, args.sidecar, args.full)
 
 
 def main_c2(args):
@@ -888,9 +1041,11 @@ def main_c2(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):  # one HNSW_INDEX_SCAN probe per step
-        index.search(Q[i % nq], k, ef)
+        last = index.search(Q[i % nq], k, ef)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ids": last})  # vss_search returns the row ids of one query
     kms, nk = 0.0, 512  # kernel time of the same calls (hipEvents on the probe's stream), outside the timed region
     index.set_search_probe_wait(False)  # wait on the stream, with events around the kernel
     for i in range(nk):
@@ -966,7 +1121,7 @@ def main_c2(args):
                                                          ref_distance=make_ref_distance(lib, metric, dim),
                                                          replay=make_wave_order_replay(lambda: [stream_of(index)], dim, metric, M,
                                                                                        M0, efc, k, ef, Q))}
-    finish(result, args.sidecar)
+    finish(result, args.sidecar, args.full)
 
 
 def main_a13(args):
@@ -1043,7 +1198,7 @@ def main_a13(args):
         "parity": "UNPINNED: DuckDB v1.4.3 core source absent from the reference tree (SURVEY §8c); README values + fp64 formula only",
         "cpu_baseline": None,
     }
-    finish(result, args.sidecar)
+    finish(result, args.sidecar, args.full)
 
 
 def a13_host_chunks(pkg, lib, args):
@@ -1234,7 +1389,7 @@ def main_quality(args):
         "plateau": {"M": default["M"], "ef_construction": default["ef_construction"], "rows": rows, "at_ef_search": efs[-1],
                     "engine": default["per_ef"][-1]["B"], "reference": default["per_ef"][-1]["A"]},
         "roofline": None, "cpu_baseline": None, "study_wall_s": round(time.perf_counter() - t0, 1),
-    }, args.sidecar)
+    }, args.sidecar, args.full)
 
 
 def small_launches(index, gen, k, ef, B_join):
@@ -1307,7 +1462,7 @@ def run_extras(which, budget_s, started):
         try:
             if os.path.exists(side):
                 os.remove(side)
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--sidecar", side] + argv,
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--sidecar", side] + argv,
                                capture_output=True, text=True, timeout=min(limit, left))
             lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
             if lines:
@@ -1326,7 +1481,7 @@ def run_extras(which, budget_s, started):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 128 batches; 4000 queries for --config c2)")
@@ -1353,15 +1508,17 @@ def main():
     ap.add_argument("--coalesce", type=int, default=int(os.environ.get("VSS_BENCH_COALESCE", 32)),
                     help="probe batches answered by one launch of the search engine (vss_search_multi_device_begin); 1 = one "
                          "launch per batch")
-    ap.add_argument("--regimes", default="",
+    ap.add_argument("--regimes", default=None,
                     help="extra (batches per launch)x(launches in flight) combinations measured after the timed region and "
                          "reported under roofline.regimes, e.g. 4x1,8x2,8x2u (u = not gated); the word none = not even the "
-                         "two default ones (1x1 and 1x3u)")
-    ap.add_argument("--extras", default=os.environ.get("VSS_BENCH_EXTRAS", "auto"),
+                         "two default ones (1x1 and 1x3u); default: the two default ones with --full, none otherwise")
+    ap.add_argument("--extras", default=os.environ.get("VSS_BENCH_EXTRAS"),
                     help="other configurations measured after the headline and attached to the same JSON line as objects, each "
                          "in a process of its own: comma list of c2,c4,c5,a13; auto = all of them on the full single-GPU c3 run, "
-                         "none = just the headline")
-    ap.add_argument("--extras-budget-s", type=float, default=1320.0, help="no extra is started once the run is this old")
+                         "none = just the headline; default: auto with --full, none otherwise")
+    ap.add_argument("--extras-budget-s", type=float, default=540.0,
+                    help="no extra is started once the run is this old, and a running one is stopped there (a --full run ends "
+                         "within 10 minutes)")
     ap.add_argument("--quality-rows", type=int, default=200_000, help="--config quality: rows of the prefix both builds index")
     ap.add_argument("--quality-options", default="", help="--config quality: M/ef_construction pairs, e.g. 16/128,32/384 (default: both)")
     ap.add_argument("--quality-efs", default="", help="--config quality: the ef_search grid, comma separated")
@@ -1373,28 +1530,57 @@ def main():
     ap.add_argument("--reorder-after-build", action="store_true",
                     help="finish the bulk build with the reference's (level, cluster) compaction order (vss_set_build_reorder); its "
                          "time is part of build_s")
-    ap.add_argument("--host-api-seconds", type=float, default=2.0,
-                    help="seconds of the concurrent host-pointer vss_search_batch leg (PCIe-inclusive, reported beside value)")
+    ap.add_argument("--host-api-seconds", type=float, default=None,
+                    help="seconds of the concurrent host-pointer vss_search_batch leg (PCIe-inclusive, reported beside value); "
+                         "default: 2 with --full, 0 otherwise")
     ap.add_argument("--mode", default="sharded", choices=["sharded", "replicated"],
                     help="N>1: row-range shards + RCCL all-gather merge (configs[3], strong scaling) or one full "
                          "index per GPU with its own query batches (throughput mode, weak scaling, no collective)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-sample-rows", type=int, default=200_000)
     ap.add_argument("--cpu-mt-build-rows", type=int, default=300_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-small-launches", action="store_true", help="skip the one-query / join-chunk latency leg")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--no-cpu-baseline", action="store_true", default=None, help="skip the CPU baseline (always skipped without --full)")
+    ap.add_argument("--no-small-launches", action="store_true", default=None,
+                    help="skip the one-query / join-chunk latency leg (always skipped without --full)")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="after the timed region, run the same number of steps this many more times on other batches and report "
-                         "[min, median, max] queries/s (`value` stays the first region)")
+                         "[min, median, max] queries/s (`value` stays the first region); default: 5 with --full, 0 otherwise")
     ap.add_argument("--wide-ef-sweep", action="store_true",
                     help="let the ef_search sweep go on beyond 512 (640 ... 1536: candidate lists in HBM, MemList) — the reference-"
                          "default index needs that to reach the target recall, if it reaches it at all")
     ap.add_argument("--build-only", action="store_true", help="stop after the bulk build and report rows/s with its roofline")
     ap.add_argument("--sidecar", default=None,
-                    help="file the complete result object is written to (default gpurun_out/bench_full_<config>.json); stdout "
-                         "carries small detail lines and, LAST, the compact headline line (<= %d characters)" % LINE_LIMIT)
+                    help="file the complete result object is written to (with --full by default, see default_sidecar()); stdout "
+                         "carries, with --full, small detail lines and, LAST, the compact headline line (<= %d characters)" % LINE_LIMIT)
     ap.add_argument("--cpu-prefix-only", action="store_true", help="CPU baseline on a prefix index even if RAM allows the full one")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not just the headline: CPU baseline and its agreement gate, repeated timed regions, "
+                         "other launch regimes, host-pointer API and latency legs, the exact path alone, the extra configurations, "
+                         "detail lines and the sidecar file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (ids, distances, counts) as DIR/<name>.npy, "
+                         "float32 / float64")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.config in ("a13", "quality") or args.build_only):
+        ap.error("--dump-outputs needs a configuration with timed search steps (not a13, quality or --build-only)")
+    # what a plain run leaves out, unless asked for one by one
+    if args.extras is None:
+        args.extras = "auto" if args.full else "none"
+    if args.regimes is None:
+        args.regimes = "" if args.full else "none"
+    if args.host_api_seconds is None:
+        args.host_api_seconds = 2.0 if args.full else 0.0
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 0
+    if args.no_cpu_baseline is None:
+        args.no_cpu_baseline = not args.full
+    if args.no_small_launches is None:
+        args.no_small_launches = not args.full
+    return args
+
+
+def main():
+    args = parse_args()
     t_run0 = time.perf_counter()
     if args.config == "a13":
         return main_a13(args)
@@ -1466,6 +1652,12 @@ def main():
     gen = Mixture(n_total, dim, metric != "l2sq", device)
 
     # ---------------------------------------------------------------- build (timed separately: rows/s)
+    # one index on one rank, plain run: its graph is cached after a build (build() makes one), and the next plain run restores
+    # it from there instead of spending most of its time on a build it does not time; --full always builds, and caches nothing
+    cache_path = (index_cache_path(pkg, n_total, dim, metric, M, M0, efc) if n_local == 1 and world == 1 and not force and
+                  not args.full and not args.reorder_after_build and not args.build_only else None)
+    cached = (cache_path if cache_path and os.path.exists(cache_path + ".json") and os.path.exists(cache_path + ".graph")
+              else None)
     # local shard s of this rank is global shard rank * n_local + s and owns the row range shard_range(...) gives it
     ranges = [shardlib.shard_range(rank * n_local + s, n_shards, n_total) if sharded else (0, n_total) for s in range(n_local)]
     shards, streams = [], []
@@ -1475,54 +1667,73 @@ def main():
         ix.set_stream(st.cuda_stream)
         if args.reorder_after_build:
             ix.set_build_reorder(True)
-        ix.reserve(hi - lo)
+        if not cached:  # (vss_load sizes the index itself)
+            ix.reserve(hi - lo)
         shards.append(ix)
         streams.append(st)
     index, stream = shards[0], streams[0]
     n_local_rows = sum(hi - lo for lo, hi in ranges)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for (lo, hi), ix in zip(ranges, shards):
-        pos = lo
-        while pos < hi:  # rows are generated chunk by chunk straight into the index (inputs resident in HBM)
-            ci = pos // CHUNK
-            x = gen.rows(DATA_SEED, ci, CHUNK)
-            a, b = pos - ci * CHUNK, min(hi, (ci + 1) * CHUNK) - ci * CHUNK
-            x = x[a:b].contiguous()
-            ids = torch.arange(pos, pos + (b - a), dtype=torch.int64, device=device)
-            torch.cuda.synchronize()
-            ix.stage_device(ids.data_ptr(), x.data_ptr(), b - a)
-            pos += b - a
-            del x, ids
-    torch.cuda.synchronize()
-    t_stage = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    if n_local == 1:
-        index.build_finalize()
-    else:  # co-resident shards link at the same time, one host thread and one stream each (the devices of an 8-GPU node would
-        import threading  # do the same side by side): the small first batches and the tail of every batch overlap
-        errors = []
+    if cached:  # a plain run restores the index an earlier build of the same options and engine left in the cache
+        record = load_index_cache(pkg, index, cached, gen, device)
+        if record is None:  # the regenerated vectors are not the ones that graph was built on: build afresh, replace it
+            sys.stderr.write("bench.py: index cache %s does not match the generator's rows: rebuilding\n" % cached)
+            cached = None
+            index.reserve(n_total)
+        else:
+            t_stage, t_build = record["stage_s"], record["build_s"]
+            build_timing, build_work = record["build_timing"], record["build_work"]
+            index.timing(reset=True)
+    if not cached:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for (lo, hi), ix in zip(ranges, shards):
+            pos = lo
+            while pos < hi:  # rows are generated chunk by chunk straight into the index (inputs resident in HBM)
+                ci = pos // CHUNK
+                x = gen.rows(DATA_SEED, ci, CHUNK)
+                a, b = pos - ci * CHUNK, min(hi, (ci + 1) * CHUNK) - ci * CHUNK
+                x = x[a:b].contiguous()
+                ids = torch.arange(pos, pos + (b - a), dtype=torch.int64, device=device)
+                torch.cuda.synchronize()
+                ix.stage_device(ids.data_ptr(), x.data_ptr(), b - a)
+                pos += b - a
+                del x, ids
+        torch.cuda.synchronize()
+        t_stage = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        if n_local == 1:
+            index.build_finalize()
+        else:  # co-resident shards link at the same time, one host thread and one stream each (the devices of an 8-GPU node would
+            import threading  # do the same side by side): the small first batches and the tail of every batch overlap
+            errors = []
 
-        def link(ix):
+            def link(ix):
+                try:
+                    ix.build_finalize()
+                except Exception as e:  # noqa: BLE001
+                    errors.append(e)
+            ths = [threading.Thread(target=link, args=(ix,)) for ix in shards]
+            for th in ths:
+                th.start()
+            for th in ths:
+                th.join()
+            if errors:
+                raise errors[0]
+        torch.cuda.synchronize()
+        t_build = time.perf_counter() - t0
+        build_timing, build_work = {}, {}
+        for ix in shards:
+            for key, v in ix.timing(reset=True).items():
+                build_timing[key] = build_timing.get(key, 0) + v
+            for key, v in ix.build_work().items():
+                build_work[key] = build_work.get(key, 0) + v
+        if cache_path:
             try:
-                ix.build_finalize()
-            except Exception as e:  # noqa: BLE001
-                errors.append(e)
-        ths = [threading.Thread(target=link, args=(ix,)) for ix in shards]
-        for th in ths:
-            th.start()
-        for th in ths:
-            th.join()
-        if errors:
-            raise errors[0]
-    torch.cuda.synchronize()
-    t_build = time.perf_counter() - t0
-    build_timing, build_work = {}, {}
-    for ix in shards:
-        for key, v in ix.timing(reset=True).items():
-            build_timing[key] = build_timing.get(key, 0) + v
-        for key, v in ix.build_work().items():
-            build_work[key] = build_work.get(key, 0) + v
+                save_index_cache(pkg, index, cache_path, gen, {"rows": n_total, "dim": dim, "stage_s": t_stage, "build_s": t_build,
+                                                           "build_timing": build_timing, "build_work": build_work,
+                                                           "workload": [n_total, dim, metric, M, M0, efc]})
+            except Exception as e:  # noqa: BLE001  (a full disk must not cost the run)
+                sys.stderr.write("bench.py: index cache not written: %r\n" % (e,))
     if world > 1 or force:
         tb = torch.tensor([t_build], device=device)
         dist.all_reduce(tb, op=dist.ReduceOp.MAX)
@@ -1552,7 +1763,7 @@ def main():
                     "roofline": {"bound": "hbm", "kernel": "k_build_phase_a", "unit": "GB/s", "peak": HBM_PEAK_GBS,
                                  "achieved": build_summary()["phase_a_frac_of_hbm"] * HBM_PEAK_GBS,
                                  "frac": build_summary()["phase_a_frac_of_hbm"], "traffic": None},
-                    "cpu_baseline": None}, args.sidecar)
+                    "cpu_baseline": None}, args.sidecar, args.full)
         return
 
     # ---------------------------------------------------------------- queries + ground truth
@@ -1598,15 +1809,17 @@ def main():
     t_exact = (time.perf_counter() - t0) / 2
     # the exact path by itself (BASELINE configs[2]'s "MFMA distance tile"; SURVEY §8d: flops = 2 B N dim, f32 matrix peak 157.3
     # TFLOP/s): one more batch now that the row norms and every scratch buffer exist — scores, select and re-rank over wall clock
-    t0 = time.perf_counter()
-    probe(Q[0], 0, exact=True)
-    torch.cuda.synchronize()
-    t_exact_warm = time.perf_counter() - t0
-    exact_info = {"batch_s": t_exact_warm, "first_two_batches_s": t_exact,
-                  "tflops_over_wall": 2.0 * B * n_local_rows * dim / t_exact_warm / 1e12,
-                  "frac_of_f32_mfma_peak": 2.0 * B * n_local_rows * dim / t_exact_warm / 1e12 / 157.3,
-                  "kernel": "k_exact_scores_v4 (persistent 128x128 MFMA tile, LDS-DMA operands) + k_exact_select + k_exact_rerank",
-                  "kernel_only_evidence": "profiles/r05h_exact_tile_kernel_only_rocprofv3.txt"}
+    exact_info = None
+    if args.full:
+        t0 = time.perf_counter()
+        probe(Q[0], 0, exact=True)
+        torch.cuda.synchronize()
+        t_exact_warm = time.perf_counter() - t0
+        exact_info = {"batch_s": t_exact_warm, "first_two_batches_s": t_exact,
+                      "tflops_over_wall": 2.0 * B * n_local_rows * dim / t_exact_warm / 1e12,
+                      "frac_of_f32_mfma_peak": 2.0 * B * n_local_rows * dim / t_exact_warm / 1e12 / 157.3,
+                      "kernel": "k_exact_scores_v4 (persistent 128x128 MFMA tile, LDS-DMA operands) + k_exact_select + k_exact_rerank",
+                      "kernel_only_evidence": "profiles/r05h_exact_tile_kernel_only_rocprofv3.txt"}
 
     # ---------------------------------------------------------------- ef_search: smallest that reaches the target recall
     # (a shard returns its own top-k, so the merged result of G shards reaches the target at a smaller per-shard ef:
@@ -1707,6 +1920,16 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     collectives_timed = collectives_so_far() - coll0  # all-gathers actually issued by the timed launches (counted, not assumed)
+    if args.dump_outputs and rank == 0:
+        # the last step = the last batch of the last timed launch, in the buffers of the context that launch ran on (what follows
+        # the timed region reuses them); sharded: its merged answers, as the exchange returned them
+        launches = shardlib.plan_launches(args.steps, G)
+        px_last, b_last = exchanges[G][(len(launches) - 1) % depth], launches[-1][1] - launches[-1][0] - 1
+        if sharded:
+            last = {"ids": px_last.out_i.view(G, B, k)[b_last], "distances": px_last.out_d.view(G, B, k)[b_last]}
+        else:
+            last = {"ids": px_last.ids(b_last), "distances": px_last.dists(b_last), "counts": px_last.counts[0, b_last]}
+        dump_outputs(args.dump_outputs, last)
 
     # ---- the timed region once more, REPEATS times, each on other batches of the probe stream: the spread of `value` (VERDICT
     # r05: three runs of one tree gave 940.6k / 966.0k / 971.1k and the line carried no dispersion).  `value` stays the FIRST
@@ -1748,7 +1971,7 @@ def main():
     # the SAME timed region once more at ef 512 — the largest limit of the 8-register list's kernels, the operating point the
     # reference-default extra reported until round 5 — so that the line carries both
     at_ef_512 = None
-    if args.wide_ef_sweep and ef > 512 and world == 1 and not args.ef:
+    if args.full and args.wide_ef_sweep and ef > 512 and world == 1 and not args.ef:
         ef_chosen, ef = ef, 512  # (run_steps' closures read `ef` when they launch)
         run_steps(args.warmup, depth, G)
         torch.cuda.synchronize()
@@ -1879,6 +2102,8 @@ def main():
         workload = ("configs[%d]: 10M rows FLOAT[768] %s top-10, batched 1024 queries, %s" %
                     (3 if sharded else 2, metric, where)) if full else \
             "DEVELOPMENT RUN (not the benchmark): %d rows FLOAT[%d] %s top-%d, batch %d, %s" % (n_total, dim, metric, k, B, where)
+        build_measured = "when the cached index was built" if cached else "in this run"  # build_rows_per_s, build_s, stage_s
+        build_info = dict(build_summary(), measured=build_measured)
         result = {
             "metric": "queries/sec at recall@10, 10M×768 FLOAT top-10; index build rows/sec",  # BASELINE.json, verbatim
             "config_id": "c4" if co_resident else "c3",
@@ -1889,8 +2114,8 @@ def main():
             "multi_gpu_mode": args.mode if (world > 1 or force) else None, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "recall_at_10": round(recall, 4), "recall_at_10_se": round(recall_se, 5), "recall": recall_info,
             "ef_search": ef, "ef_sweep": sweep_log,
-            "build_rows_per_s": n_total * (world if replicated else 1) / t_build, "build_s": t_build, "stage_s": t_stage,
-            "build": build_summary(),
+            "build_rows_per_s": n_total * (world if replicated else 1) / t_build, "build_measured": build_measured,
+            "build_s": t_build, "stage_s": t_stage, "build": build_info,
             "build_kernel_ms": {"phase_a": build_timing["build_phase_a_ms"], "phase_b": build_timing["build_phase_b_ms"],
                                 "batches": build_timing["build_batches"], "retries": build_timing["build_retries"]},
             "build_roofline": {
@@ -1983,7 +2208,7 @@ def main():
             result[name] = obj
     failed = False
     if rank == 0:
-        emit(result, args.sidecar, extra_objects)
+        emit(result, args.sidecar, extra_objects, args.full)
         a = (result.get("cpu_baseline") or {}).get("agreement")
         if a is not None and not agreement_ok(a):
             sys.stderr.write("bench.py: reference agreement below the bar: %s\n" % json.dumps(a))

@@ -316,3 +316,124 @@ def test_visited_set_form_follows_the_engines_sizing_rule(monkeypatch):
     assert bench.visited_set_form(600, 12_500_000) == "32-bit cells in HBM"      # the list itself lives in HBM there
     monkeypatch.setenv("VSS_VISITED_COMPACT", "0")
     assert bench.visited_set_form(480, 12_500_000) == "32-bit cells in HBM"
+
+
+def test_a_plain_run_measures_the_headline_alone():
+    """`bench.py --gpus 1 --steps N --warmup W` times the headline and nothing else; --full restores every other leg with the
+    defaults it always had, and a leg asked for by name still runs without --full."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.steps == 20 and plain.warmup == 5 and plain.dump_outputs is None
+    assert (plain.extras, plain.regimes, plain.host_api_seconds, plain.repeats) == ("none", "none", 0.0, 0)
+    assert plain.no_cpu_baseline and plain.no_small_launches
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and (full.extras, full.regimes, full.host_api_seconds, full.repeats) == ("auto", "", 2.0, 5)
+    assert not full.no_cpu_baseline and not full.no_small_launches
+    assert bench.parse_args(["--repeats", "2", "--regimes", "8x2"]).repeats == 2
+    assert bench.parse_args(["--regimes", "8x2"]).regimes == "8x2"
+    assert bench.parse_args(["--full", "--no-cpu-baseline", "--extras", "none"]).no_cpu_baseline
+    assert bench.parse_args(["--full", "--no-cpu-baseline", "--extras", "none"]).extras == "none"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--config", "a13", "--dump-outputs", "out"])
+
+
+def test_a_plain_run_prints_one_line_and_writes_no_sidecar(capsys, tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "default_sidecar", lambda config_id: str(tmp_path / ("bench_full_%s.json" % config_id)))
+    result = {"metric": "m", "value": 1.0, "unit": "u", "n_gpus": 1, "steps": 4, "warmup": 1, "ms_per_step": 2.0,
+              "higher_is_better": True, "dtype": "f32", "ef_sweep": [{"ef": 16, "recall": 0.9}],
+              "recall": {"reported": "held-out"}, "config_id": "c3"}
+    bench.emit(result, None, full=False)
+    lines = capsys.readouterr().out.strip().splitlines()
+    assert len(lines) == 1 and json.loads(lines[0])["ms_per_step"] == 2.0
+    assert not os.listdir(tmp_path)
+    bench.emit(result, None)  # --full: detail lines first, the complete object in the default sidecar
+    lines = capsys.readouterr().out.strip().splitlines()
+    assert len(lines) == 3 and json.loads(lines[0])["detail"] == "ef_sweep" and json.loads(lines[-1])["value"] == 1.0
+    assert json.load(open(tmp_path / "bench_full_c3.json")) == result
+    side = str(tmp_path / "named.json")
+    bench.emit(result, side, full=False)  # a sidecar asked for by name is written either way
+    assert len(capsys.readouterr().out.strip().splitlines()) == 1 and json.load(open(side)) == result
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    ids = torch.tensor([[3, 9_999_999, 2 ** 40], [7, 1, 0]], dtype=torch.int64)
+    dist = torch.tensor([[0.25, 0.5, 1.0], [0.0, 0.125, 2.0]], dtype=torch.float32)
+    counts = torch.tensor([3, 3], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "out"), {"ids": ids, "distances": dist, "counts": counts})
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("ids", "distances", "counts")}
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"].astype(np.int64), ids.numpy())
+    assert got["distances"].dtype == np.float32 and np.array_equal(got["distances"], dist.numpy())
+    assert got["counts"].dtype == np.float64 and np.array_equal(got["counts"], [3, 3])
+    with pytest.raises(RuntimeError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_extras_run_with_everything_they_measured_before(monkeypatch, tmp_path):
+    """The extra configurations are `bench.py --full --config ...` processes: a plain run never starts them, a --full run's
+    extras keep their CPU baselines and agreement gates."""
+    import subprocess
+    seen = []
+
+    class Done:
+        returncode, stdout, stderr = 0, '{"value": 1.0}\n', ""
+
+    def fake_run(cmd, **kw):
+        seen.append(cmd)
+        return Done()
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    monkeypatch.setattr(bench, "default_sidecar", lambda config_id: str(tmp_path / ("bench_full_%s.json" % config_id)))
+    out = bench.run_extras(["c2"], 1e9, 0.0)
+    assert out["c2"]["value"] == 1.0 and len(seen) == 1
+    assert seen[0][1].endswith("bench.py") and seen[0].count("--full") == 1
+    assert seen[0][-len(bench.EXTRA_CONFIGS["c2"][0]):] == bench.EXTRA_CONFIGS["c2"][0]
+
+
+def test_stream_pieces_read_joins_its_pieces_across_any_read_sizes():
+    """The vss_read_cb of the index cache: consecutive pieces read back in reads that straddle them, a device piece through
+    the copy function it is given, and a read past the end refused."""
+    import ctypes as C
+    import subprocess
+    src = os.path.join(ROOT, "duckdb-vss_amd", "host", "stream_pieces.cpp")
+    lib_path = os.path.join(ROOT, "duckdb-vss_amd", "host", "libstream_pieces.so")
+    if not os.path.exists(lib_path) or os.path.getmtime(lib_path) < os.path.getmtime(src):
+        subprocess.check_call(["make", "-s", "-C", os.path.dirname(src), lib_path])
+    helper = C.CDLL(lib_path)
+
+    class Pieces(C.Structure):
+        _fields_ = [("ptr", C.c_void_p * 4), ("len", C.c_uint64 * 4), ("on_device", C.c_int32 * 4), ("count", C.c_int32),
+                    ("at", C.c_int32), ("off", C.c_uint64), ("copy", C.c_void_p)]
+    copy_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
+    kinds = []
+
+    def fake_copy(dst, src_, n, kind):
+        kinds.append(kind)
+        C.memmove(dst, src_, n)
+        return 0
+    keep = copy_fn(fake_copy)
+    parts = [np.arange(8, dtype=np.uint8), np.arange(100, 140, dtype=np.uint8), np.arange(200, 213, dtype=np.uint8)]
+    p = Pieces()
+    for i, a in enumerate(parts):
+        p.ptr[i], p.len[i] = a.ctypes.data, a.nbytes
+    p.on_device[1], p.count = 1, 3
+    p.copy = C.cast(keep, C.c_void_p).value
+    read = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)(C.cast(helper.stream_pieces_read, C.c_void_p).value)
+    out = np.zeros(61, dtype=np.uint8)
+    at = 0
+    for n in (5, 20, 30, 6):
+        assert read(C.addressof(p), out.ctypes.data + at, n) == 1
+        at += n
+    assert np.array_equal(out, np.concatenate(parts)) and p.at == 3 and set(kinds) == {2}
+    assert read(C.addressof(p), out.ctypes.data, 1) == 0
+
+
+def test_index_cache_digest_rows_are_the_generators_rows():
+    """The vector digest an index cache is checked by: a fixed set of rows (first, last, a seeded sample), taken chunk by
+    chunk exactly as the build stages them."""
+    n, dim = 1_200_000, 8
+    idx = bench.digest_rows(n)
+    assert idx[0] == 0 and idx[-1] == n - 1 and np.all(np.diff(idx) > 0) and np.array_equal(idx, bench.digest_rows(n))
+    gen = bench.Mixture(n, dim, True, torch.device("cpu"))
+    want = np.concatenate([gen.rows(bench.DATA_SEED, int(r) // bench.CHUNK, bench.CHUNK)[int(r) % bench.CHUNK].numpy()[None]
+                           for r in idx[::97]])
+    got = np.frombuffer(bench.generator_rows(gen, n, idx), dtype=np.float32).reshape(len(idx), dim)[::97]
+    assert np.array_equal(got, want)

@@ -625,7 +625,7 @@ def test_two_rank_sharded_bench():
     env = dict(os.environ, VSS_BENCH_SAME_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29617", os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "300000", "--dim", "128",
-           "--steps", "6", "--warmup", "2", "--no-cpu-baseline"]
+           "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -648,7 +648,7 @@ def test_one_rank_rccl_collective_through_bench():
                LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--rows", "200000", "--dim", "64", "--steps", "6",
            "--warmup", "3", "--coalesce", "2", "--no-cpu-baseline", "--extras", "none", "--heldout-batches", "1",
-           "--host-api-seconds", "0", "--regimes", "none", "--no-small-launches"]
+           "--host-api-seconds", "0", "--regimes", "none", "--no-small-launches", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     res = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -670,7 +670,7 @@ def test_one_rank_rccl_replicated_mode_through_bench():
                LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--mode", "replicated", "--rows", "200000", "--dim", "64",
            "--steps", "6", "--warmup", "3", "--coalesce", "2", "--no-cpu-baseline", "--extras", "none", "--heldout-batches", "1",
-           "--host-api-seconds", "0", "--regimes", "none", "--no-small-launches"]
+           "--host-api-seconds", "0", "--regimes", "none", "--no-small-launches", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -680,6 +680,80 @@ def test_one_rank_rccl_replicated_mode_through_bench():
     assert res["collectives_per_launch"] == 0 and res["collectives_timed"] == 0  # no exchange on the data path
     assert res["config"]["parallelism"] == "replica1" and res["scaling"] == "weak" and len(res["rank_pci"]) == 1
     assert res["recall_at_10"] >= 0.95 and res["value"] > 0 and res["roofline"]["frac"] > 0
+
+
+def test_plain_bench_run_dumps_its_last_step_and_restores_its_index(tmp_path):
+    """A plain bench.py run prints ONE line and, with --dump-outputs, writes what its last timed step returned: the answers
+    to the last probe batch (6 steps in launches of 2 on 3 contexts: batch 5 of the probe stream), regenerated here from the
+    seeds and checked against the rows the ids name and against the exact top-10.  The same runs pin the index cache down, in
+    a cache directory of the test's own: the first run builds and caches the graph, the second restores it and must answer
+    exactly as the fresh build did; a cache whose vector digest is not the generator's is refused (rebuilt and replaced),
+    and an older cache of the same workload is removed when a new one is written."""
+    import glob
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    rows, dim, B, k = 200_000, 64, 1024, 10
+    cache = tmp_path / "cache"
+    env = dict(os.environ, XDG_CACHE_HOME=str(cache))
+
+    def run(tag):
+        out = str(tmp_path / tag)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--rows", str(rows), "--dim", str(dim), "--steps",
+               "6", "--warmup", "3", "--coalesce", "2", "--heldout-batches", "1", "--dump-outputs", out]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0]), [np.load(os.path.join(out, n + ".npy")) for n in ("ids", "distances", "counts")]
+
+    def entries():
+        return sorted(glob.glob(str(cache / "duckdb-vss_amd" / "bench_index_*")))
+
+    res, (ids, dist, counts) = run("built")
+    assert res["build_measured"] == "in this run" and res["build"]["measured"] == "in this run"
+    assert [os.path.basename(e).split(".")[-1] for e in entries()] == ["graph", "json"]
+    assert res["steps"] == 6 and res["ms_per_step"] > 0 and res.get("cpu_baseline") is None
+    assert res["value"] == pytest.approx(6 * B / (6 * res["ms_per_step"] / 1e3), rel=1e-3)
+    assert ids.dtype == np.float64 and dist.dtype == np.float32 and counts.dtype == np.float64
+    assert ids.shape == (B, k) and dist.shape == (B, k) and np.all(counts == k)
+    ids_i = ids.astype(np.int64)
+    assert ids_i.min() >= 0 and ids_i.max() < rows and np.all(np.diff(dist, axis=1) >= 0)
+    gen = bench.Mixture(rows, dim, True, torch.device("cuda"))
+    X = gen.rows(bench.DATA_SEED, 0, bench.CHUNK)[:rows].double()
+    q = gen.rows(bench.QUERY_SEED, 5, B).double()
+    want = (1.0 - (q[:, None, :] * X[torch.from_numpy(ids_i).cuda()]).sum(-1)).cpu().numpy()
+    assert np.max(np.abs(dist - want)) < 1e-4
+    exact = torch.topk(q @ X.T, k, dim=1).indices.cpu().numpy()
+    assert np.mean([len(set(ids_i[i]) & set(exact[i])) / k for i in range(B)]) >= 0.9
+
+    # the second run restores the cached graph: the same operating point, the same answers bit for bit
+    again, (ids2, dist2, counts2) = run("restored")
+    assert again["build_measured"] == "when the cached index was built" and again["build"]["measured"] == again["build_measured"]
+    assert again["build_rows_per_s"] == res["build_rows_per_s"]
+    assert (again["ef_search"], again["recall_at_10"], again["recall_at_10_se"]) == (res["ef_search"], res["recall_at_10"],
+                                                                                  res["recall_at_10_se"])
+    assert np.array_equal(ids2, ids) and np.array_equal(dist2.view(np.uint32), dist.view(np.uint32))
+    assert np.array_equal(counts2, counts)
+
+    # a cache whose vectors are not the generator's is not used; the rebuilt graph replaces it, and an older cache of the
+    # same workload goes
+    meta = [e for e in entries() if e.endswith(".json")][0]
+    record = json.load(open(meta))
+    json.dump(dict(record, vector_digest="0" * 64), open(meta, "w"))
+    stale = str(cache / "duckdb-vss_amd" / "bench_index_older")
+    json.dump(record, open(stale + ".json", "w"))
+    open(stale + ".graph", "wb").close()
+    third, (ids3, dist3, _) = run("rebuilt")
+    assert third["build_measured"] == "in this run"
+    assert np.array_equal(ids3, ids) and np.array_equal(dist3.view(np.uint32), dist.view(np.uint32))
+    assert entries() == sorted([meta, meta[:-len(".json")] + ".graph"])
+    assert json.load(open(meta))["vector_digest"] == record["vector_digest"]
 
 
 def test_properties_at_scale():

@@ -5,7 +5,7 @@ O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 600 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "compact or variants or both_engine_shapes or tombstones or reference_sql or harness or several_batches or pipelined or limits_beyond or fuzz") > $O/r3b_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3b_pytest.txt
 timeout 300 python tools/gpu_solo_probe.py 1000000 128 l2sq 16 128 64 > $O/r3b_solo_1m128.txt 2>&1; echo "solo probe rc $?"; cat $O/r3b_solo_1m128.txt
-(timeout 300 python bench.py --config c2) > $O/r3b_bench_c2.json 2> $O/r3b_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3b_bench_c2.err
+(timeout 300 python bench.py --full --config c2) > $O/r3b_bench_c2.json 2> $O/r3b_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3b_bench_c2.err
 python - <<'PY'
 import json
 try:

@@ -9,8 +9,8 @@ VSS_LIBRARY=duckdb-vss_amd/libvssgpu_prof.so timeout 300 python tools/gpu_solo_p
 TOMB_OUT=/tmp/t_a.npy timeout 300 python tools/gpu_tomb_probe.py 2000000 1536 448 > $O/r3d_tomb_regq.txt 2>&1; cat $O/r3d_tomb_regq.txt
 TOMB_OUT=/tmp/t_b.npy VSS_SEARCH_REG_QUEUE_MAX=256 timeout 300 python tools/gpu_tomb_probe.py 2000000 1536 448 > $O/r3d_tomb_hbmq.txt 2>&1; cat $O/r3d_tomb_hbmq.txt
 python -c "import numpy as np; print('same answers either queue:', np.array_equal(np.load('/tmp/t_a.npy'), np.load('/tmp/t_b.npy')))"
-(timeout 300 python bench.py --config c2) > $O/r3d_bench_c2.json 2> $O/r3d_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3d_bench_c2.err
-(timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5) > $O/r3d_bench_c3.json 2> $O/r3d_bench_c3.err; echo "bench c3 rc $?"; tail -c 300 $O/r3d_bench_c3.err
+(timeout 300 python bench.py --full --config c2) > $O/r3d_bench_c2.json 2> $O/r3d_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3d_bench_c2.err
+(timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5) > $O/r3d_bench_c3.json 2> $O/r3d_bench_c3.err; echo "bench c3 rc $?"; tail -c 300 $O/r3d_bench_c3.err
 python - <<'PY'
 import json
 try:

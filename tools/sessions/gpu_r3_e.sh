@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 (time timeout 600 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r3e_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3e_pytest.txt
 timeout 300 python tools/gpu_solo_probe.py 1000000 128 l2sq 16 128 64 > $O/r3e_solo_1m128.txt 2>&1; echo "solo probe rc $?"; grep -E "single|  32:|1024|build" $O/r3e_solo_1m128.txt
 VSS_LIBRARY=duckdb-vss_amd/libvssgpu_prof.so timeout 300 python tools/gpu_solo_phase_probe.py 1000000 128 l2sq 16 128 64 > $O/r3e_solo_phase_1m128.txt 2>&1; echo "phase probe rc $?"; cat $O/r3e_solo_phase_1m128.txt
-(timeout 300 python bench.py --config c2) > $O/r3e_bench_c2.json 2> $O/r3e_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3e_bench_c2.err
+(timeout 300 python bench.py --full --config c2) > $O/r3e_bench_c2.json 2> $O/r3e_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3e_bench_c2.err
 python - <<'PY'
 import json
 try:

@@ -15,7 +15,7 @@ if [ "$1" != "nosuite" ]; then
   cat $O/config_tests.txt
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/r3_final_smoke.txt 2>&1; tail -n 2 $O/r3_final_smoke.txt
 fi
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $P/bench_plain.json 2> $P/bench_plain.err; echo "driver-style bench rc $?"
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $P/bench_plain.json 2> $P/bench_plain.err; echo "driver-style bench rc $?"
 EF=$(python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out/prof_r03"
@@ -23,11 +23,11 @@ print(json.loads([l for l in open(O + "/bench_plain.json") if l.startswith("{")]
 PY
 )
 echo "ef_search chosen by the sweep: $EF"
-timeout 600 python bench.py --no-cpu-baseline --host-api-seconds 0 --regimes 8x1,16x1 > $O/r3_final_bench_default.json 2> $O/r3_final_bench_default.err; echo "default bench rc $?"
+timeout 600 python bench.py --full --no-cpu-baseline --host-api-seconds 0 --regimes 8x1,16x1 > $O/r3_final_bench_default.json 2> $O/r3_final_bench_default.err; echo "default bench rc $?"
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $P/kt -o bench -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --ef $EF --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_under_rocprof.json 2> $P/kt.err; echo "rocprof rc $?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $P/kt -o bench -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --ef $EF --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_under_rocprof.json 2> $P/kt.err; echo "rocprof rc $?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --ef $EF --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_pmc_$c.json 2> $P/pmc_$c.err; echo "pmc $c rc $?"
+  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --ef $EF --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_pmc_$c.json 2> $P/pmc_$c.err; echo "pmc $c rc $?"
 done
 cd $R && python - <<'PY'
 import csv, json, os, sqlite3
@@ -89,7 +89,7 @@ print(json.dumps({k: v for k, v in summary.items() if k != "all_launches_FETCH_S
 PY
 rm -rf $P/kt $P/pmc_FETCH_SIZE $P/pmc_WRITE_SIZE
 cd $R
-timeout 300 python bench.py --config c2 > $O/r3_final_bench_c2.json 2> $O/r3_final_bench_c2.err; echo "bench c2 rc $?"
+timeout 300 python bench.py --full --config c2 > $O/r3_final_bench_c2.json 2> $O/r3_final_bench_c2.err; echo "bench c2 rc $?"
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

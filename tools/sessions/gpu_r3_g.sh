@@ -7,8 +7,8 @@ export TMPDIR=/tmp
 VSS_SEARCH_SOLO=2 timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_parity2.py -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark and not two_rank and not variants" > $O/r3g_pytest_solo_forced.txt 2>&1; echo "solo-forced pytest rc $?"; tail -n 2 $O/r3g_pytest_solo_forced.txt
 timeout 300 python tools/gpu_solo_probe.py 1000000 128 l2sq 16 128 64 > $O/r3g_solo_1m128.txt 2>&1; echo "solo probe rc $?"; grep -E "single|  32:|1024|build" $O/r3g_solo_1m128.txt
 VSS_LIBRARY=duckdb-vss_amd/libvssgpu_prof.so timeout 300 python tools/gpu_solo_phase_probe.py 1000000 128 l2sq 16 128 64 > $O/r3g_solo_phase_1m128.txt 2>&1; echo "phase probe rc $?"; cat $O/r3g_solo_phase_1m128.txt
-(timeout 300 python bench.py --config c2) > $O/r3g_bench_c2.json 2> $O/r3g_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3g_bench_c2.err
-(timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline) > $O/r3g_bench_c3.json 2> $O/r3g_bench_c3.err; echo "bench c3 rc $?"; tail -c 300 $O/r3g_bench_c3.err
+(timeout 300 python bench.py --full --config c2) > $O/r3g_bench_c2.json 2> $O/r3g_bench_c2.err; echo "bench c2 rc $?"; tail -c 300 $O/r3g_bench_c2.err
+(timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline) > $O/r3g_bench_c3.json 2> $O/r3g_bench_c3.err; echo "bench c3 rc $?"; tail -c 300 $O/r3g_bench_c3.err
 python - <<'PY'
 import json
 try:

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 VSS_SEARCH_SOLO=2 timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_parity2.py -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark and not two_rank and not variants" > $O/r3j_pytest_solo_forced.txt 2>&1; echo "solo-forced pytest rc $?"; tail -n 2 $O/r3j_pytest_solo_forced.txt
 VSS_SEARCH_OVERLAP=0 timeout 300 python tools/gpu_solo_probe.py 1000000 128 l2sq 16 128 64 > $O/r3j_solo_overlap_off.txt 2>&1; echo "overlap off:"; grep -E "solo" $O/r3j_solo_overlap_off.txt | grep -E "single|  32:|1024"
 timeout 300 python tools/gpu_solo_probe.py 1000000 128 l2sq 16 128 64 > $O/r3j_solo_overlap_on.txt 2>&1; echo "overlap on:"; grep -E "single|  32:|1024|build" $O/r3j_solo_overlap_on.txt
-(timeout 300 python bench.py --config c2) > $O/r3j_bench_c2.json 2> $O/r3j_bench_c2.err; echo "bench c2 rc $?"
+(timeout 300 python bench.py --full --config c2) > $O/r3j_bench_c2.json 2> $O/r3j_bench_c2.err; echo "bench c2 rc $?"
 python - <<'PY'
 import json
 try:

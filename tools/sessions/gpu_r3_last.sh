@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 rm -f $O/config_tests.txt
 (time timeout 1200 python -m pytest tests -q -m gpu -x -p no:cacheprovider) > $O/r3_last_tests.txt 2>&1; echo "pytest rc $?"; tail -n 6 $O/r3_last_tests.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -n 1
-(time timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5) > $O/r3_last_bench.json 2> $O/r3_last_bench.err; echo "bench rc $?"
+(time timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5) > $O/r3_last_bench.json 2> $O/r3_last_bench.err; echo "bench rc $?"
 python - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r3_last_bench.json") if l.startswith("{")][-1])

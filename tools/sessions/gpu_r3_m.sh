@@ -4,8 +4,8 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r3m_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3m_pytest.txt
-timeout 300 python bench.py --config c2 --steps 4000 > $O/r3m_c2_flag.json 2> $O/r3m_c2_flag.err; echo "c2 flag rc $?"
-VSS_PROBE_FLAG_WAIT=0 timeout 300 python bench.py --config c2 --steps 4000 --no-cpu-baseline > $O/r3m_c2_stream.json 2> $O/r3m_c2_stream.err; echo "c2 stream rc $?"
+timeout 300 python bench.py --full --config c2 --steps 4000 > $O/r3m_c2_flag.json 2> $O/r3m_c2_flag.err; echo "c2 flag rc $?"
+VSS_PROBE_FLAG_WAIT=0 timeout 300 python bench.py --full --config c2 --steps 4000 --no-cpu-baseline > $O/r3m_c2_stream.json 2> $O/r3m_c2_stream.err; echo "c2 stream rc $?"
 python - <<'PY'
 import json
 for f in ("r3m_c2_flag", "r3m_c2_stream"):

@@ -4,9 +4,9 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r3n_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3n_pytest.txt
-timeout 300 python bench.py --config c2 --steps 4000 > $O/r3n_c2_touch.json 2> $O/r3n_c2_touch.err; echo "c2 touch rc $?"
-VSS_SEARCH_TOUCH_ROWS=0 timeout 300 python bench.py --config c2 --steps 4000 --no-cpu-baseline > $O/r3n_c2_notouch.json 2> $O/r3n_c2_notouch.err; echo "c2 no-touch rc $?"
-VSS_SEARCH_TOUCH_ROWS=0 VSS_PROBE_FLAG_WAIT=0 timeout 300 python bench.py --config c2 --steps 4000 --no-cpu-baseline > $O/r3n_c2_neither.json 2> $O/r3n_c2_neither.err; echo "c2 neither rc $?"
+timeout 300 python bench.py --full --config c2 --steps 4000 > $O/r3n_c2_touch.json 2> $O/r3n_c2_touch.err; echo "c2 touch rc $?"
+VSS_SEARCH_TOUCH_ROWS=0 timeout 300 python bench.py --full --config c2 --steps 4000 --no-cpu-baseline > $O/r3n_c2_notouch.json 2> $O/r3n_c2_notouch.err; echo "c2 no-touch rc $?"
+VSS_SEARCH_TOUCH_ROWS=0 VSS_PROBE_FLAG_WAIT=0 timeout 300 python bench.py --full --config c2 --steps 4000 --no-cpu-baseline > $O/r3n_c2_neither.json 2> $O/r3n_c2_neither.err; echo "c2 neither rc $?"
 python - <<'PY'
 import json
 for f in ("r3n_c2_touch", "r3n_c2_notouch", "r3n_c2_neither"):

@@ -5,7 +5,7 @@ O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r3p_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3p_pytest.txt
 for team in 1 0; do for touch in 0 1; do
-  VSS_SEARCH_TEAM=$team VSS_SEARCH_TOUCH_ROWS=$touch timeout 300 python bench.py --config c2 --steps 4000 --no-cpu-baseline > $O/r3p_c2_team${team}_touch${touch}.json 2> $O/r3p_c2_team${team}_touch${touch}.err; echo "c2 team $team touch $touch rc $?"
+  VSS_SEARCH_TEAM=$team VSS_SEARCH_TOUCH_ROWS=$touch timeout 300 python bench.py --full --config c2 --steps 4000 --no-cpu-baseline > $O/r3p_c2_team${team}_touch${touch}.json 2> $O/r3p_c2_team${team}_touch${touch}.err; echo "c2 team $team touch $touch rc $?"
   echo "VSS_SEARCH_TEAM=$team VSS_SEARCH_TOUCH_ROWS=$touch" | tee -a $O/r3p_phase.txt
   VSS_SEARCH_TEAM=$team VSS_SEARCH_TOUCH_ROWS=$touch VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_prof.so timeout 300 python tools/gpu_solo_phase_probe.py 1000000 128 l2sq 16 128 64 2>&1 | grep -v amdgpu | grep "solo  *B=   1" | tee -a $O/r3p_phase.txt
 done; done

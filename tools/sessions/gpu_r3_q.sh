@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r3q_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3q_pytest.txt
 run() { # name lib-suffix env...
   local name=$1 suf=$2; shift 2
-  env "$@" VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu$suf.so timeout 300 python bench.py --config c2 --steps 4000 --no-cpu-baseline > $O/r3q_c2_$name.json 2> $O/r3q_c2_$name.err; echo "c2 $name rc $?"
+  env "$@" VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu$suf.so timeout 300 python bench.py --full --config c2 --steps 4000 --no-cpu-baseline > $O/r3q_c2_$name.json 2> $O/r3q_c2_$name.err; echo "c2 $name rc $?"
   local psuf=_prof; [ "$suf" = "_t8" ] && psuf=_prof8
   echo "$name" | tee -a $O/r3q_phase.txt
   env "$@" VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu$psuf.so timeout 300 python tools/gpu_solo_phase_probe.py 1000000 128 l2sq 16 128 64 2>&1 | grep -v amdgpu | grep "solo  *B=   1" | tee -a $O/r3q_phase.txt

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r3r_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3r_pytest.txt
 run() { # name lib-suffix env...
   local name=$1 suf=$2; shift 2
-  env "$@" VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu$suf.so timeout 300 python bench.py --config c2 --steps 4000 --no-cpu-baseline > $O/r3r_c2_$name.json 2> $O/r3r_c2_$name.err; echo "c2 $name rc $?"
+  env "$@" VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu$suf.so timeout 300 python bench.py --full --config c2 --steps 4000 --no-cpu-baseline > $O/r3r_c2_$name.json 2> $O/r3r_c2_$name.err; echo "c2 $name rc $?"
 }
 run t8_default "" A=1
 run t8_rows0 "" VSS_SEARCH_TOUCH_ROWS=0
@@ -14,7 +14,7 @@ run t8_rows0_lists0 "" VSS_SEARCH_TOUCH_ROWS=0 VSS_SEARCH_TOUCH_LISTS=0
 run t4_default _t4 A=1
 run t8_default_again "" A=1
 run one_wave "" VSS_SEARCH_TEAM=0
-timeout 300 python bench.py --config c2 --steps 4000 > $O/r3r_c2_full.json 2> $O/r3r_c2_full.err; echo "c2 full rc $?"
+timeout 300 python bench.py --full --config c2 --steps 4000 > $O/r3r_c2_full.json 2> $O/r3r_c2_full.err; echo "c2 full rc $?"
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r3r_c2_*.json")):

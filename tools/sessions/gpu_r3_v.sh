@@ -5,7 +5,7 @@ O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r3v_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r3v_pytest.txt
 run() { local name=$1; shift
-  env "$@" timeout 300 python bench.py --config c2 --steps 4000 --no-cpu-baseline > $O/r3v_c2_$name.json 2> $O/r3v_c2_$name.err; echo "c2 $name rc $?"; }
+  env "$@" timeout 300 python bench.py --full --config c2 --steps 4000 --no-cpu-baseline > $O/r3v_c2_$name.json 2> $O/r3v_c2_$name.err; echo "c2 $name rc $?"; }
 run follow A=1
 run follow_nolisttouch VSS_SEARCH_TOUCH_LISTS=0
 run nofollow VSS_SEARCH_TOUCH_FOLLOW=0

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "not config and not full_benchmark") > $O/r4c_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 6 $O/r4c_pytest.txt
 timeout 400 python tools/gpu_crew_probe.py 3000000 768 cosine 32 256 80 2>&1 | grep -v amdgpu | tee $O/r4c_crew_probe_3m768.txt
 VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_prof.so timeout 400 python tools/gpu_crew_probe.py 3000000 768 cosine 32 256 80 2>&1 | grep -v amdgpu | tee $O/r4c_crew_probe_3m768_phase_ticks.txt
-(time timeout 600 python bench.py --rows 1000000 --dim 768 --steps 20 --warmup 5 --cpu-seconds 4 --extras c2,a13 --host-api-seconds 1) > $O/r4c_bench_dev.json 2> $O/r4c_bench_dev.err; echo "dev bench rc $?"; tail -c 1500 $O/r4c_bench_dev.err
+(time timeout 600 python bench.py --full --rows 1000000 --dim 768 --steps 20 --warmup 5 --cpu-seconds 4 --extras c2,a13 --host-api-seconds 1) > $O/r4c_bench_dev.json 2> $O/r4c_bench_dev.err; echo "dev bench rc $?"; tail -c 1500 $O/r4c_bench_dev.err
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

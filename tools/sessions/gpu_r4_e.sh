@@ -4,7 +4,7 @@ ulimit -c 0
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 export TMPDIR=/tmp
-(time timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5) > $O/r4e_bench_driver_cmd.json 2> $O/r4e_bench_driver_cmd.err; echo "bench rc $?"; tail -c 600 $O/r4e_bench_driver_cmd.err
+(time timeout 1700 python3 bench.py --full --gpus 1 --steps 20 --warmup 5) > $O/r4e_bench_driver_cmd.json 2> $O/r4e_bench_driver_cmd.err; echo "bench rc $?"; tail -c 600 $O/r4e_bench_driver_cmd.err
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

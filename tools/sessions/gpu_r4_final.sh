@@ -15,7 +15,7 @@ if [ "$1" != "nosuite" ]; then
   cat $O/config_tests.txt 2>/dev/null
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/r4_final_smoke.txt 2>&1; tail -n 2 $O/r4_final_smoke.txt
 fi
-(time timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5) > $P/bench_plain.json 2> $P/bench_plain.err; echo "driver-style bench rc $?"; tail -n 4 $P/bench_plain.err
+(time timeout 1700 python3 bench.py --full --gpus 1 --steps 20 --warmup 5) > $P/bench_plain.json 2> $P/bench_plain.err; echo "driver-style bench rc $?"; tail -n 4 $P/bench_plain.err
 EF=$(python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out/prof_r04"
@@ -25,12 +25,12 @@ PY
 echo "ef_search chosen by the rule: $EF"
 BARE="--gpus 1 --steps 20 --warmup 5 --ef $EF --regimes none --no-cpu-baseline --host-api-seconds 0 --extras none --no-small-launches --heldout-batches 0"
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $P/kt -o bench -- python3 $R/bench.py $BARE > $P/bench_under_rocprof.json 2> $P/kt.err; echo "rocprof rc $?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $P/kt -o bench -- python3 $R/bench.py --full $BARE > $P/bench_under_rocprof.json 2> $P/kt.err; echo "rocprof rc $?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py $BARE > $P/bench_pmc_$c.json 2> $P/pmc_$c.err; echo "pmc $c rc $?"
+  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py --full $BARE > $P/bench_pmc_$c.json 2> $P/pmc_$c.err; echo "pmc $c rc $?"
 done
-timeout 200 rocprofv3 --kernel-trace --stats -d $P/a13_kt -o a13 -- python3 $R/bench.py --config a13 --steps 20 > $P/a13_under_rocprof.json 2> $P/a13_kt.err; echo "a13 rocprof rc $?"
-timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --kernel-include-regex k_array_distance -d $P/a13_pmc -o pmc -- python3 $R/bench.py --config a13 --steps 20 > $P/a13_pmc.json 2> $P/a13_pmc.err; echo "a13 pmc rc $?"
+timeout 200 rocprofv3 --kernel-trace --stats -d $P/a13_kt -o a13 -- python3 $R/bench.py --full --config a13 --steps 20 > $P/a13_under_rocprof.json 2> $P/a13_kt.err; echo "a13 rocprof rc $?"
+timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --kernel-include-regex k_array_distance -d $P/a13_pmc -o pmc -- python3 $R/bench.py --full --config a13 --steps 20 > $P/a13_pmc.json 2> $P/a13_pmc.err; echo "a13 pmc rc $?"
 cd $R && python - <<'PY'
 import csv, json, os, sqlite3
 P = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out/prof_r04"

@@ -7,9 +7,9 @@ O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "variants or both_engine_shapes or sql or host_harness or rccl or sharded_index or several_batches or reference_built") > $O/r4g_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 5 $O/r4g_pytest.txt
 for solo in 1 0; do
-  VSS_SEARCH_SOLO=$solo timeout 300 python bench.py --config c2 --steps 3000 --cpu-seconds 3 > $O/r4g_bench_c2_solo$solo.json 2> $O/r4g_bench_c2_solo$solo.err; echo "c2 solo=$solo rc $?"
+  VSS_SEARCH_SOLO=$solo timeout 300 python bench.py --full --config c2 --steps 3000 --cpu-seconds 3 > $O/r4g_bench_c2_solo$solo.json 2> $O/r4g_bench_c2_solo$solo.err; echo "c2 solo=$solo rc $?"
 done
-(time timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --extras none) > $O/r4g_bench_c3_efc384.json 2> $O/r4g_bench_c3_efc384.err; echo "c3 rc $?"; tail -c 400 $O/r4g_bench_c3_efc384.err
+(time timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --extras none) > $O/r4g_bench_c3_efc384.json 2> $O/r4g_bench_c3_efc384.err; echo "c3 rc $?"; tail -c 400 $O/r4g_bench_c3_efc384.err
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

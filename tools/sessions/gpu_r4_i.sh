@@ -6,9 +6,9 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 600 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "array or exact or sql") > $O/r4i_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 4 $O/r4i_pytest.txt
-for w in 0 1; do VSS_ARRAY_WIDE=$w timeout 120 python bench.py --config a13 --steps 20 > $O/r4i_a13_wide$w.json 2> /dev/null; echo "a13 wide=$w rc $?"; done
-timeout 600 python bench.py --config c5 --steps 32 --warmup 16 --cpu-seconds 8 > $O/r4i_bench_c5.json 2> $O/r4i_bench_c5.err; echo "c5 rc $?"; tail -c 300 $O/r4i_bench_c5.err
-timeout 300 python bench.py --config c5 --rows 3000000 --steps 32 --warmup 16 --no-cpu-baseline > $O/r4i_bench_c5_3m_rows.json 2> /dev/null; echo "c5 3M rc $?"
+for w in 0 1; do VSS_ARRAY_WIDE=$w timeout 120 python bench.py --full --config a13 --steps 20 > $O/r4i_a13_wide$w.json 2> /dev/null; echo "a13 wide=$w rc $?"; done
+timeout 600 python bench.py --full --config c5 --steps 32 --warmup 16 --cpu-seconds 8 > $O/r4i_bench_c5.json 2> $O/r4i_bench_c5.err; echo "c5 rc $?"; tail -c 300 $O/r4i_bench_c5.err
+timeout 300 python bench.py --full --config c5 --rows 3000000 --steps 32 --warmup 16 --no-cpu-baseline > $O/r4i_bench_c5_3m_rows.json 2> /dev/null; echo "c5 3M rc $?"
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "variants or wide_lists or limits_beyond or both_engine_shapes or option_space_fuzz or register_queue or several_batches or tombstones or config4") > $O/r4k_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 5 $O/r4k_pytest.txt
-timeout 600 python bench.py --config c5 --steps 32 --warmup 16 --cpu-seconds 8 > $O/r4k_bench_c5.json 2> $O/r4k_bench_c5.err; echo "c5 rc $?"
+timeout 600 python bench.py --full --config c5 --steps 32 --warmup 16 --cpu-seconds 8 > $O/r4k_bench_c5.json 2> $O/r4k_bench_c5.err; echo "c5 rc $?"
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

@@ -4,7 +4,7 @@ ulimit -c 0
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 export TMPDIR=/tmp
-(time timeout 900 python bench.py --extras none --no-cpu-baseline --host-api-seconds 0 --regimes 4x1,8x1,16x1,8x2,8x3) > $O/r4_bench_default_128_steps.json 2> $O/r4_bench_default_128_steps.err; echo "rc $?"
+(time timeout 900 python bench.py --full --extras none --no-cpu-baseline --host-api-seconds 0 --regimes 4x1,8x1,16x1,8x2,8x3) > $O/r4_bench_default_128_steps.json 2> $O/r4_bench_default_128_steps.err; echo "rc $?"
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

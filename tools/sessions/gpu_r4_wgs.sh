@@ -5,7 +5,7 @@ ulimit -c 0
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 export TMPDIR=/tmp
-run() { echo "== $@"; env "$@" timeout 300 python bench.py --rows 3000000 --extras none --no-cpu-baseline --host-api-seconds 0 --no-small-launches --heldout-batches 1 --ef 64 --steps 20 --warmup 5 --regimes 1x1,16x1,8x3 2>/dev/null | python -c "
+run() { echo "== $@"; env "$@" timeout 300 python bench.py --full --rows 3000000 --extras none --no-cpu-baseline --host-api-seconds 0 --no-small-launches --heldout-batches 1 --ef 64 --steps 20 --warmup 5 --regimes 1x1,16x1,8x3 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r = d['roofline']
 print('   20 steps: %.0f q/s, frac/launch %.3f, over wall %.3f' % (d['value'], r['frac'], r['frac_over_wall']))

@@ -7,10 +7,10 @@ O=gpurun_out
 export TMPDIR=/tmp
 mkdir -p $O
 for c in 1 0; do
-  VSS_VISITED_COMPACT=$c timeout 600 python bench.py --config c5 --steps 32 --warmup 16 --cpu-seconds 8 --sidecar $O/r5a_c5_compact$c.full.json > $O/r5a_bench_c5_compact$c.json 2> $O/r5a_bench_c5_compact$c.err; echo "c5 compact=$c rc $?"
+  VSS_VISITED_COMPACT=$c timeout 600 python bench.py --full --config c5 --steps 32 --warmup 16 --cpu-seconds 8 --sidecar $O/r5a_c5_compact$c.full.json > $O/r5a_bench_c5_compact$c.json 2> $O/r5a_bench_c5_compact$c.err; echo "c5 compact=$c rc $?"
   tail -c 1500 $O/r5a_bench_c5_compact$c.json
 done
-(time timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5 --sidecar $O/r5a_driver_cmd.full.json > $O/r5a_bench_driver_cmd.json 2> $O/r5a_bench_driver_cmd.err); echo "driver cmd rc $?"
+(time timeout 1700 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --sidecar $O/r5a_driver_cmd.full.json > $O/r5a_bench_driver_cmd.json 2> $O/r5a_bench_driver_cmd.err); echo "driver cmd rc $?"
 tail -c 8000 $O/r5a_bench_driver_cmd.json > $O/r5a_driver_tail_8000.txt
 python - <<'PY'
 import json, os

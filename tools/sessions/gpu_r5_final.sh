@@ -14,7 +14,7 @@ if [ "$1" != "nosuite" ]; then
   tail -n 14 $O/r5_final_tests.txt
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/r5_final_smoke.txt 2>&1; tail -n 2 $O/r5_final_smoke.txt
 fi
-(time timeout 1700 python3 bench.py --gpus 1 --steps 20 --warmup 5 --sidecar $P/summary/r05_bench_latest_sidecar.json) > $P/bench_plain.jsonl 2> $P/bench_plain.err; echo "driver-style bench rc $?"; tail -n 4 $P/bench_plain.err
+(time timeout 1700 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --sidecar $P/summary/r05_bench_latest_sidecar.json) > $P/bench_plain.jsonl 2> $P/bench_plain.err; echo "driver-style bench rc $?"; tail -n 4 $P/bench_plain.err
 tail -c 8000 $P/bench_plain.jsonl > $P/summary/r05_bench_latest_last_8000_chars.txt
 cp $P/bench_plain.jsonl $P/summary/r05_bench_latest_stdout.jsonl
 EF=$(python - <<'PY'
@@ -26,9 +26,9 @@ PY
 echo "ef_search chosen by the rule: $EF"
 BARE="--gpus 1 --steps 20 --warmup 5 --ef $EF --regimes none --no-cpu-baseline --host-api-seconds 0 --extras none --no-small-launches --heldout-batches 0"
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace -d $P/kt -o bench -- python3 $R/bench.py $BARE --sidecar $P/kt_full.json > $P/bench_under_rocprof.jsonl 2> $P/kt.err; echo "rocprof rc $?"
+timeout 600 rocprofv3 --kernel-trace -d $P/kt -o bench -- python3 $R/bench.py --full $BARE --sidecar $P/kt_full.json > $P/bench_under_rocprof.jsonl 2> $P/kt.err; echo "rocprof rc $?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py $BARE --sidecar $P/pmc_${c}_full.json > $P/bench_pmc_$c.jsonl 2> $P/pmc_$c.err; echo "pmc $c rc $?"
+  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py --full $BARE --sidecar $P/pmc_${c}_full.json > $P/bench_pmc_$c.jsonl 2> $P/pmc_$c.err; echo "pmc $c rc $?"
 done
 cd $R && python - <<'PY'
 import csv, glob, json, os, sqlite3

@@ -12,9 +12,9 @@ export TMPDIR=/tmp
 mkdir -p $O
 (time timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider) > $O/r5a_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 4 $O/r5a_pytest.txt
 for c in 1 0; do
-  VSS_VISITED_COMPACT=$c timeout 600 python bench.py --config c5 --steps 32 --warmup 16 --cpu-seconds 8 > $O/r5a_bench_c5_compact$c.json 2> $O/r5a_bench_c5_compact$c.err; echo "c5 compact=$c rc $?"
+  VSS_VISITED_COMPACT=$c timeout 600 python bench.py --full --config c5 --steps 32 --warmup 16 --cpu-seconds 8 > $O/r5a_bench_c5_compact$c.json 2> $O/r5a_bench_c5_compact$c.err; echo "c5 compact=$c rc $?"
 done
-timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r5a_bench_driver_cmd.json 2> $O/r5a_bench_driver_cmd.err; echo "driver cmd rc $?"
+timeout 1500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r5a_bench_driver_cmd.json 2> $O/r5a_bench_driver_cmd.err; echo "driver cmd rc $?"
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

@@ -13,6 +13,6 @@ mkdir -p $O
 echo "pytest rc $?"; tail -n 4 $O/r5k_pytest.txt
 VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_prof.so timeout 600 python tools/gpu_wide_list_probe.py 10000000 768 cosine 16 128 10 512 > $O/r5k_wide_lists_phase_ticks_10m768.txt 2>&1; echo "probe 768 rc $?"; grep -v "^built\|amdgpu.ids" $O/r5k_wide_lists_phase_ticks_10m768.txt
 for lib in libvssgpu.so libvssgpu_b4.so; do
-  VSS_LIBRARY=$PWD/duckdb-vss_amd/$lib timeout 400 python bench.py --config c3 --build-only --extras none --sidecar $O/r5k_build_$lib.full.json > $O/r5k_build_$lib.jsonl 2> $O/r5k_build_$lib.err; echo "build $lib rc $?"
+  VSS_LIBRARY=$PWD/duckdb-vss_amd/$lib timeout 400 python bench.py --full --config c3 --build-only --extras none --sidecar $O/r5k_build_$lib.full.json > $O/r5k_build_$lib.jsonl 2> $O/r5k_build_$lib.err; echo "build $lib rc $?"
   tail -n 1 $O/r5k_build_$lib.jsonl | cut -c1-700
 done

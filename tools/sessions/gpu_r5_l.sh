@@ -12,9 +12,9 @@ export TMPDIR=/tmp
 (time timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -p no:cacheprovider -k "one_rank_rccl or exact_search_over_many or bulk_build_graph or sequential_build") > $O/r5l_pytest.txt 2>&1; echo "pytest rc $?"; tail -n 3 $O/r5l_pytest.txt
 BARE="--config c5 --steps 32 --warmup 16 --ef 480 --no-cpu-baseline"
 cd /tmp
-timeout 500 rocprofv3 --kernel-trace -d $P/kt -o c5 -- python3 $R/bench.py $BARE --sidecar $P/kt_full.json > $P/c5_under_rocprof.jsonl 2> $P/kt.err; echo "rocprof rc $?"
+timeout 500 rocprofv3 --kernel-trace -d $P/kt -o c5 -- python3 $R/bench.py --full $BARE --sidecar $P/kt_full.json > $P/c5_under_rocprof.jsonl 2> $P/kt.err; echo "rocprof rc $?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py $BARE --sidecar $P/pmc_${c}_full.json > $P/c5_pmc_$c.jsonl 2> $P/pmc_$c.err; echo "pmc $c rc $?"
+  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc_$c -o pmc -- python3 $R/bench.py --full $BARE --sidecar $P/pmc_${c}_full.json > $P/c5_pmc_$c.jsonl 2> $P/pmc_$c.err; echo "pmc $c rc $?"
 done
 cd $R && python - <<'PY'
 import glob, json, os, sqlite3

@@ -37,5 +37,5 @@ json.dump(out, open(R + "/gpurun_out/r05_exact_mfma_busy.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
 PY
 rm -rf $P/pmc_2 $P/pmc_5
-timeout 900 python bench.py --no-cpu-baseline --host-api-seconds 0 --extras none --no-small-launches --regimes 4x1,8x1,16x1,8x2,8x3 --sidecar $O/r05_bench_default_128_steps_regimes_sidecar.json > $O/r05_bench_default_128_steps_regimes.jsonl 2> $O/r05_default.err; echo "default bench rc $?"
+timeout 900 python bench.py --full --no-cpu-baseline --host-api-seconds 0 --extras none --no-small-launches --regimes 4x1,8x1,16x1,8x2,8x3 --sidecar $O/r05_bench_default_128_steps_regimes_sidecar.json > $O/r05_bench_default_128_steps_regimes.jsonl 2> $O/r05_default.err; echo "default bench rc $?"
 grep '"regime"\|"metric"' $O/r05_bench_default_128_steps_regimes.jsonl | cut -c1-330

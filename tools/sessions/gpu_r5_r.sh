@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 cd $R
 export TMPDIR=/tmp
-(time timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --sidecar $O/r5r_bench_sidecar.json) > $O/r5r_bench_stdout.jsonl 2> $O/r5r_bench.err; echo "bench rc $?"; tail -n 3 $O/r5r_bench.err
+(time timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --sidecar $O/r5r_bench_sidecar.json) > $O/r5r_bench_stdout.jsonl 2> $O/r5r_bench.err; echo "bench rc $?"; tail -n 3 $O/r5r_bench.err
 tail -c 8000 $O/r5r_bench_stdout.jsonl > $O/r5r_bench_last_8000_chars.txt
 python - <<'PY'
 import json, os

@@ -24,5 +24,5 @@ for lib in r5_prof prof; do
   VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_$lib.so timeout 300 python tools/gpu_solo_phase_probe.py 1000000 128 l2sq 16 128 64 > $O/r6b_solo_phase_1m128_$lib.txt 2>&1; echo "solo probe $lib rc $?"
   grep -v "amdgpu.ids" $O/r6b_solo_phase_1m128_$lib.txt | cut -c1-330 | head -12
 done
-(time timeout 900 python bench.py --config quality --quality-rows 1000000 --quality-options 16/128 --quality-efs 64,128,256,512,1024,1536 \
+(time timeout 900 python bench.py --full --config quality --quality-rows 1000000 --quality-options 16/128 --quality-efs 64,128,256,512,1024,1536 \
    --sidecar $O/r6b_quality_1m_sidecar.json) > $O/r6b_quality_1m.jsonl 2> $O/r6b_quality_1m.err; tail -n 1 $O/r6b_quality_1m.jsonl | cut -c1-1500

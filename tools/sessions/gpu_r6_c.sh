@@ -27,5 +27,5 @@ for lib in prof rf_prof; do
   VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_$lib.so timeout 300 python tools/gpu_solo_phase_probe.py 1000000 128 l2sq 16 128 64 > $O/r6c_solo_phase_1m128_$lib.txt 2>&1; echo "solo probe $lib rc $?"
   grep "^solo" $O/r6c_solo_phase_1m128_$lib.txt | cut -c1-330 | head -4
 done
-(time timeout 600 python bench.py --config c4 --build-only --extras none --sidecar $O/r6c_c4_build_4q.json) > $O/r6c_c4_build_4_queues.jsonl 2>&1; tail -n 1 $O/r6c_c4_build_4_queues.jsonl | cut -c1-400
-(time GPU_MAX_HW_QUEUES=8 timeout 600 python bench.py --config c4 --build-only --extras none --sidecar $O/r6c_c4_build_8q.json) > $O/r6c_c4_build_8_queues.jsonl 2>&1; tail -n 1 $O/r6c_c4_build_8_queues.jsonl | cut -c1-400
+(time timeout 600 python bench.py --full --config c4 --build-only --extras none --sidecar $O/r6c_c4_build_4q.json) > $O/r6c_c4_build_4_queues.jsonl 2>&1; tail -n 1 $O/r6c_c4_build_4_queues.jsonl | cut -c1-400
+(time GPU_MAX_HW_QUEUES=8 timeout 600 python bench.py --full --config c4 --build-only --extras none --sidecar $O/r6c_c4_build_8q.json) > $O/r6c_c4_build_8_queues.jsonl 2>&1; tail -n 1 $O/r6c_c4_build_8_queues.jsonl | cut -c1-400

@@ -14,6 +14,6 @@ VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_prof.so timeout 300 python tools/gpu_s
 grep -v "amdgpu.ids" $O/r6j_solo_phase_1m128_prof.txt | cut -c1-330 | head -8
 VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_prof.so timeout 600 python tools/gpu_wide_list_probe.py 10000000 768 cosine 16 128 10 512,288 > $O/r6j_wide_lists_phase_ticks_10m768_prof.txt 2>&1; echo "wide probe rc $?"
 grep -v "^built\|amdgpu.ids" $O/r6j_wide_lists_phase_ticks_10m768_prof.txt | grep -A1 "retry in place" | cut -c1-330
-(time timeout 400 python bench.py --config c2 --steps 2000 --cpu-seconds 3 --sidecar $O/r6j_c2_sidecar.json) > $O/r6j_c2.jsonl 2> $O/r6j_c2.err; tail -n 1 $O/r6j_c2.jsonl | cut -c1-700
-(time timeout 900 python bench.py --config c5 --steps 32 --warmup 16 --cpu-seconds 4 --sidecar $O/r6j_c5_sidecar.json) > $O/r6j_c5.jsonl 2> $O/r6j_c5.err; tail -n 1 $O/r6j_c5.jsonl | cut -c1-1200
-(time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --extras none --cpu-seconds 4 --sidecar $O/r6j_c3_sidecar.json) > $O/r6j_c3.jsonl 2> $O/r6j_c3.err; grep '"detail": "regime"\|small_launches\|"detail": "repeat"' $O/r6j_c3.jsonl | cut -c1-400; tail -n 1 $O/r6j_c3.jsonl | cut -c1-1500
+(time timeout 400 python bench.py --full --config c2 --steps 2000 --cpu-seconds 3 --sidecar $O/r6j_c2_sidecar.json) > $O/r6j_c2.jsonl 2> $O/r6j_c2.err; tail -n 1 $O/r6j_c2.jsonl | cut -c1-700
+(time timeout 900 python bench.py --full --config c5 --steps 32 --warmup 16 --cpu-seconds 4 --sidecar $O/r6j_c5_sidecar.json) > $O/r6j_c5.jsonl 2> $O/r6j_c5.err; tail -n 1 $O/r6j_c5.jsonl | cut -c1-1200
+(time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --extras none --cpu-seconds 4 --sidecar $O/r6j_c3_sidecar.json) > $O/r6j_c3.jsonl 2> $O/r6j_c3.err; grep '"detail": "regime"\|small_launches\|"detail": "repeat"' $O/r6j_c3.jsonl | cut -c1-400; tail -n 1 $O/r6j_c3.jsonl | cut -c1-1500

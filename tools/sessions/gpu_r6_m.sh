@@ -13,4 +13,4 @@ grep "per call" $O/r6m_crew_probe_3m768_prof.txt | grep "crews+pipe plain" | cut
 grep "x 1024 queries per launch, crews+pipe plain" $O/r6m_crew_probe_3m768_prof.txt
 VSS_LIBRARY=$PWD/duckdb-vss_amd/libvssgpu_prof.so timeout 300 python tools/gpu_solo_phase_probe.py 1000000 128 l2sq 16 128 64 > $O/r6m_solo_phase_1m128_prof.txt 2>&1; echo "solo probe rc $?"
 grep -v "amdgpu.ids" $O/r6m_solo_phase_1m128_prof.txt | cut -c1-330 | head -8
-(time timeout 400 python bench.py --config c2 --steps 2000 --cpu-seconds 3 --sidecar $O/r6m_c2_sidecar.json) > $O/r6m_c2.jsonl 2> $O/r6m_c2.err; tail -n 1 $O/r6m_c2.jsonl | cut -c1-300
+(time timeout 400 python bench.py --full --config c2 --steps 2000 --cpu-seconds 3 --sidecar $O/r6m_c2_sidecar.json) > $O/r6m_c2.jsonl 2> $O/r6m_c2.err; tail -n 1 $O/r6m_c2.jsonl | cut -c1-300

@@ -11,9 +11,9 @@ timeout 900 python -m pytest tests -q -m gpu -x --durations=5 > $O/s14_tests.txt
 tail -n 9 $O/s14_tests.txt
 cat $O/config_tests.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/s14_smoke.txt 2>&1; tail -n 2 $O/s14_smoke.txt
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $P/bench_plain.json 2> $P/bench_plain.err; echo "driver-style bench rc $?"
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $P/bench_plain.json 2> $P/bench_plain.err; echo "driver-style bench rc $?"
 if [ "$1" = "quick" ]; then
-  timeout 300 python bench.py --config c2 > $O/s14_bench_c2.json 2> $O/s14_bench_c2.err; echo "bench c2 rc $?"
+  timeout 300 python bench.py --full --config c2 > $O/s14_bench_c2.json 2> $O/s14_bench_c2.err; echo "bench c2 rc $?"
   python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"
@@ -27,13 +27,13 @@ print("c2:", d["value"], d["ms_per_step"], d["roofline"].get("us_per_expansion")
 PY
   exit 0
 fi
-timeout 600 python bench.py --no-cpu-baseline --host-api-seconds 0 --regimes 8x1,8x2,4x3,8x3u > $O/s14_bench_default.json 2> $O/s14_bench_default.err; echo "default bench rc $?"
+timeout 600 python bench.py --full --no-cpu-baseline --host-api-seconds 0 --regimes 8x1,8x2,4x3,8x3u > $O/s14_bench_default.json 2> $O/s14_bench_default.err; echo "default bench rc $?"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $P/kt -o bench -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --ef 96 --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_under_rocprof.json 2> $P/kt.err; echo "rocprof rc $?"
+timeout 600 rocprofv3 --kernel-trace --stats -d $P/kt -o bench -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --ef 96 --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_under_rocprof.json 2> $P/kt.err; echo "rocprof rc $?"
 cd $R && python tools/rocprof_summarize.py $P r02c $P/summary > $P/summary.txt 2>&1
 tail -n 4 $P/summary.txt | cut -c1-600
 rm -rf $P/kt
-timeout 300 python bench.py --config c2 > $O/s14_bench_c2.json 2> $O/s14_bench_c2.err; echo "bench c2 rc $?"
+timeout 300 python bench.py --full --config c2 > $O/s14_bench_c2.json 2> $O/s14_bench_c2.err; echo "bench c2 rc $?"
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 cd $R
 timeout 120 python -m pytest tests/test_gpu_parity2.py -q -m gpu -x -p no:cacheprovider -k "several_batches" 2>&1 | tail -n 1
-timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --ef 96 --regimes 8x3 --no-cpu-baseline --host-api-seconds 0 > $O/s17_bench.json 2> $O/s17_bench.err; echo "bench rc $?"
+timeout 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --ef 96 --regimes 8x3 --no-cpu-baseline --host-api-seconds 0 > $O/s17_bench.json 2> $O/s17_bench.err; echo "bench rc $?"
 python - <<'PY'
 import json, os
 O = os.environ.get("GRAFT_REPO_ROOT", "/root/repo") + "/gpurun_out"

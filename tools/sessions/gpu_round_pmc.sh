@@ -6,7 +6,7 @@ P=$R/gpurun_out/prof_r02c
 mkdir -p $P/summary
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc8_$c -o pmc -- python3 $R/bench.py --steps 32 --warmup 8 --ef 96 --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_pmc8_$c.json 2> $P/pmc8_$c.err; echo "pmc $c rc $?"
+  timeout 500 rocprofv3 --kernel-trace --pmc $c --kernel-include-regex k_search -d $P/pmc8_$c -o pmc -- python3 $R/bench.py --full --steps 32 --warmup 8 --ef 96 --regimes none --no-cpu-baseline --host-api-seconds 0 > $P/bench_pmc8_$c.json 2> $P/pmc8_$c.err; echo "pmc $c rc $?"
 done
 cd $R && python - <<'PY'
 import json, os, sqlite3

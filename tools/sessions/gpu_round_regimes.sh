@@ -6,7 +6,7 @@ O=$R/gpurun_out
 cd $R
 timeout 600 python -m pytest tests/test_gpu_parity2.py tests/test_gpu_parity.py tests/test_host_harness.py -q -m gpu -x -k "several_batches or pipelined or two_rank or register_queue or load_validates or harness or fuzz or concurrent" > $O/s13_tests.txt 2>&1; echo "pytest rc $?"
 tail -n 6 $O/s13_tests.txt
-timeout 600 python bench.py --no-cpu-baseline --host-api-seconds 0 --coalesce 8 --pipeline 2 --regimes 8x2u,8x1,4x2,4x1,8x3,2x2,1x3 > $O/s13_bench.json 2> $O/s13_bench.err; echo "bench rc $?"
+timeout 600 python bench.py --full --no-cpu-baseline --host-api-seconds 0 --coalesce 8 --pipeline 2 --regimes 8x2u,8x1,4x2,4x1,8x3,2x2,1x3 > $O/s13_bench.json 2> $O/s13_bench.err; echo "bench rc $?"
 tail -n 3 $O/s13_bench.err
 python - <<'PY'
 import json, os
