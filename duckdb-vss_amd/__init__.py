@@ -83,6 +83,7 @@ SIGNATURES = {
     "vss_search_exact_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_exact_batch_device": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
+    "vss_last_search_shape": (_int, [_vp, _vp]),
     "vss_last_search_query_stats": (_int, [_vp, _vp, _u64]),
     "vss_timing": (_int, [_vp, _vp, _int]),
     "vss_build_work": (_int, [_vp, _vp]),
@@ -317,6 +318,13 @@ class GpuIndex:
     def last_search_stats(self):
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_search_stats(self.h, _p(out)))
+        return out
+
+    def last_search_shape(self):
+        """[threads, walkers, workgroups, LDS bytes, list placement (0 registers, 1 LDS, 2 HBM), visited-set placement
+        (0 LDS, 1 LDS compact, 2 HBM), solo, 0] of the last search call's launch."""
+        out = np.zeros(8, dtype=np.uint32)
+        self._check(self.lib.vss_last_search_shape(self.h, _p(out)))
         return out
 
     def timing(self, reset=False):

@@ -1495,6 +1495,7 @@ struct SearchArgs {
 	uint32_t *global_hash; // visited sets in HBM (grid x S x 2^hash_log2 words) or NULL = LDS
 	float *list_buf;      // MemList storage (E == 0): grid x S x 2 x list_cap words
 	uint32_t list_cap;
+	uint32_t list_lds;    // cells of the candidate list kept in every walker's slot of LDS (E == LDS_LIST_E: LdsList), 0 = none
 	float *cand_buf;      // CandQueue storage (tomb): grid x S x 2 x cand_cap words
 	uint32_t cand_cap;
 	uint32_t visited_compact; // workgroup engine, limits of 257-512: the FORM of the compact visited set laid over the 2^hash_log2
@@ -1565,14 +1566,17 @@ __device__ __forceinline__ void carve_lds(WaveLds &lds, unsigned char *base, uin
 // LDS of the search engine: a header {exit flag, walkers still running}, S mailboxes, then per walker
 // [visited set unless in HBM][staged query][ids][distances].
 // stage_cap: cells of the list-merge staging area (>= the search limit for register lists, 0 = none)
+// list_cells: cells of the candidate list kept in LDS (LdsList: two arrays of align16(4 x cells) bytes and the tile tops,
+// lds_list_index.h), 0 = no list here.  The slot stride is computed by the host, the walker, the scoring waves' loop and
+// crew_help: all four pass the same value.
 __host__ __device__ inline uint32_t engine_slot_bytes(uint32_t hash_log2, uint32_t V, uint32_t list_cap_max, bool hash_in_lds,
-                                                      uint32_t stage_cap) {
+                                                      uint32_t stage_cap, uint32_t list_cells = 0) {
 	return (hash_in_lds ? align16((1u << hash_log2) * 4) : 0) + align16(V * 16) + 4 * align16(list_cap_max * 4) +
-	       2 * align16(stage_cap * 4);
+	       2 * align16(stage_cap * 4) + lds_list::bytes(list_cells);
 }
 __host__ __device__ inline uint32_t engine_lds_bytes(uint32_t walkers, uint32_t hash_log2, uint32_t V, uint32_t list_cap_max,
-                                                     bool hash_in_lds, uint32_t stage_cap) {
-	return ENGINE_HEADER_BYTES + walkers * engine_slot_bytes(hash_log2, V, list_cap_max, hash_in_lds, stage_cap);
+                                                     bool hash_in_lds, uint32_t stage_cap, uint32_t list_cells = 0) {
+	return ENGINE_HEADER_BYTES + walkers * engine_slot_bytes(hash_log2, V, list_cap_max, hash_in_lds, stage_cap, list_cells);
 }
 
 struct EngineSlot {
@@ -1582,10 +1586,15 @@ struct EngineSlot {
 	uint32_t *hash; // LDS table, or nullptr when the visited sets live in HBM
 	float *stage_d; // list-merge staging (nullptr if stage_cap == 0)
 	uint32_t *stage_s;
+	float *list_d;  // the candidate list in LDS (nullptr if list_cells == 0): distances, slots, tile tops
+	uint32_t *list_s;
+	float *list_tops;
 };
 __device__ __forceinline__ EngineSlot engine_slot(unsigned char *smem, uint32_t s, uint32_t hash_log2, uint32_t V,
-                                                  uint32_t list_cap_max, bool hash_in_lds, uint32_t stage_cap) {
-	unsigned char *p = smem + ENGINE_HEADER_BYTES + s * engine_slot_bytes(hash_log2, V, list_cap_max, hash_in_lds, stage_cap);
+                                                  uint32_t list_cap_max, bool hash_in_lds, uint32_t stage_cap,
+                                                  uint32_t list_cells = 0) {
+	unsigned char *p =
+	    smem + ENGINE_HEADER_BYTES + s * engine_slot_bytes(hash_log2, V, list_cap_max, hash_in_lds, stage_cap, list_cells);
 	EngineSlot e;
 	e.hash = hash_in_lds ? reinterpret_cast<uint32_t *>(p) : nullptr;
 	if (hash_in_lds)
@@ -1603,6 +1612,12 @@ __device__ __forceinline__ EngineSlot engine_slot(unsigned char *smem, uint32_t 
 	e.stage_d = stage_cap ? reinterpret_cast<float *>(p) : nullptr;
 	p += align16(stage_cap * 4);
 	e.stage_s = stage_cap ? reinterpret_cast<uint32_t *>(p) : nullptr;
+	p += align16(stage_cap * 4);
+	e.list_d = list_cells ? reinterpret_cast<float *>(p) : nullptr;
+	p += align16(list_cells * 4);
+	e.list_s = list_cells ? reinterpret_cast<uint32_t *>(p) : nullptr;
+	p += align16(list_cells * 4);
+	e.list_tops = list_cells ? reinterpret_cast<float *>(p) : nullptr;
 	return e;
 }
 
@@ -1628,6 +1643,16 @@ __device__ __forceinline__ void emit_results(const GraphView &gv, int64_t *out_k
 	}
 }
 __device__ __forceinline__ void emit_results(const GraphView &gv, int64_t *out_keys, float *out_d, int k, const MemList &L,
+                                             int count) {
+	for (int pos = lane_id(); pos < k; pos += 64) {
+		const bool valid = pos < count;
+		out_keys[pos] = valid ? gv.keys[L.s[pos] & ~EXPANDED_BIT] : -1ll;
+		if (out_d)
+			out_d[pos] = valid ? L.d[pos] : __builtin_inff();
+	}
+}
+
+__device__ __forceinline__ void emit_results(const GraphView &gv, int64_t *out_keys, float *out_d, int k, const LdsList &L,
                                              int count) {
 	for (int pos = lane_id(); pos < k; pos += 64) {
 		const bool valid = pos < count;
@@ -1675,7 +1700,7 @@ struct CrewTouch {
 };
 template <int MT, int NCH, int R>
 __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs &a, const CrewBox *crew, int wave, int S,
-                                          int waves, bool hash_in_lds) {
+                                          int waves, bool hash_in_lds, uint32_t list_cells) {
 	const int RG = 64 >> a.gv.sp.logG;
 	const uint32_t touch_on = (a.crew & CREW_TOUCH) ? 1u : 0u; // (lists of at most 64 cells — one or two 128-byte lines: host)
 	uint32_t sink = 0;
@@ -1704,7 +1729,7 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 		const uint32_t where = where_level & 0xFFu, level = where_level >> 8;
 		if ((where >> 1) != slot) { // (once: a crew serves one walker until the launch is over)
 			slot = where >> 1;
-			const EngineSlot es = engine_slot(smem, slot, a.hash_log2, a.gv.sp.V, a.list_cap_max, hash_in_lds, a.stage_cap);
+			const EngineSlot es = engine_slot(smem, slot, a.hash_log2, a.gv.sp.V, a.list_cap_max, hash_in_lds, a.stage_cap, list_cells);
 			q = es.q, ids0 = es.ids, ids1 = es.ids2, dist0 = es.dist, dist1 = es.dist2;
 			// Which scoring waves take rows: all of them — or, when the walker works through its accept phase while they score
 			// (CREW_SPARE_SIMD), only those on the other SIMDs: at priority 2 the walker keeps its own SIMD to itself, the
@@ -1768,20 +1793,27 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 	asm volatile("" ::"v"(sink));
 }
 
-// E = registers of the candidate list (2, 4, 8), or 0 = MemList in HBM for limits beyond 64 * MAX_LIST_REGS
+// E = registers of the candidate list (2, 4, 8), or 0 = MemList in HBM for limits beyond 64 * MAX_LIST_REGS, or LDS_LIST_E =
+// LdsList in the walker's slot of LDS for capacities of 513-4096 (SearchArgs::list_lds cells; the host's placement rule:
+// host_logic.h).  Like E = 0 it keeps one neighbour list in flight, is never pipelined and has no register queue.
 // (Round 4 measured a 12-wave variant for 1536-dimensional rows — __launch_bounds__(768), 170 registers: 4 rows in flight per
 // scoring wave and the pipelined level search next to an 8-register list — at exactly the 16-wave kernel's rate while the visited
 // sets of these limits still lived in HBM (profiles/r04f_wide_rows_1536_workgroup_shapes.txt) and dropped it.  Round 5, with the
 // compact sets in LDS, brought it back for the 8-register list at every row width: profiles/r05c_*, r05j_*, r05m_*.)
 // THREADS = the largest workgroup the instantiation is launched with: 1024 (16 waves, 128 registers per lane), or
 // WIDE_LIST_THREADS for the pipelined 8-register list (round 5)
+constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS = 8)
 template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
+	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int lane = lane_id();
 	const uint32_t wave = (uint32_t)uniform((int)(threadIdx.x >> 6));
 	const uint32_t S = a.walkers;
 	const bool hash_in_lds = a.global_hash == nullptr;
+	// cells of the list in every walker's slot — part of the slot stride for walkers and scoring waves alike (a constant zero
+	// in every other instantiation: their code does not change)
+	const uint32_t list_cells = E == LDS_LIST_E ? a.list_lds : 0u;
 	uint32_t *exit_flag = reinterpret_cast<uint32_t *>(smem);
 	uint32_t *walkers_left = exit_flag + 1;
 	CrewBox *crew = reinterpret_cast<CrewBox *>(smem + ENGINE_CREW_OFFSET);
@@ -1812,7 +1844,8 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 			for (uint32_t s = 0; s < 2 * S; ++s) { // mailbox s = job buffer (s & 1) of walker (s >> 1)
 				const unsigned long long t = VSS_LDS_LOAD(lds_u64, &boxes[s].ticket);
 				if (uniform((int)((uint32_t)t < (uint32_t)(t >> 32)))) {
-					const EngineSlot es = engine_slot(smem, s >> 1, a.hash_log2, a.gv.sp.V, a.list_cap_max, hash_in_lds, a.stage_cap);
+					const EngineSlot es =
+					    engine_slot(smem, s >> 1, a.hash_log2, a.gv.sp.V, a.list_cap_max, hash_in_lds, a.stage_cap, list_cells);
 					worked |= pool_score<MT, NCH, R>(&boxes[s], scrap, a.gv.sp, es.q, (s & 1) ? es.ids2 : es.ids,
 					                                 (s & 1) ? es.dist2 : es.dist);
 				}
@@ -1820,7 +1853,7 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 			if (uniform((int)VSS_LDS_LOAD(lds_u32, exit_flag)))
 				return;
 			if (uniform((int)VSS_LDS_LOAD_ACQ(lds_u32, &crew->on))) { // one walker left: its crew, behind barriers, until it is done
-				crew_help<MT, NCH, R>(smem, a, crew, (int)wave, (int)S, (int)(blockDim.x >> 6), hash_in_lds);
+				crew_help<MT, NCH, R>(smem, a, crew, (int)wave, (int)S, (int)(blockDim.x >> 6), hash_in_lds, list_cells);
 				return;
 			}
 			if (!worked)
@@ -1830,7 +1863,7 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 
 	// -------------------------------------------------------------------------------- walking waves
 	__builtin_amdgcn_s_setprio(2); // the serial bookkeeping of a walker is the critical path of its query
-	const EngineSlot es = engine_slot(smem, wave, a.hash_log2, a.gv.sp.V, a.list_cap_max, hash_in_lds, a.stage_cap);
+	const EngineSlot es = engine_slot(smem, wave, a.hash_log2, a.gv.sp.V, a.list_cap_max, hash_in_lds, a.stage_cap, list_cells);
 	const size_t gslot = (size_t)blockIdx.x * S + wave; // this walker's scratch in HBM
 	WaveLds lds;
 	bind_visited(lds.visited, hash_in_lds ? es.hash : a.global_hash + (gslot << a.hash_log2), a.hash_log2);
@@ -1849,9 +1882,12 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 	CandQueue cq;
 	cq.bind(a.cand_buf + gslot * 2 * a.cand_cap, reinterpret_cast<uint32_t *>(a.cand_buf + gslot * 2 * a.cand_cap) + a.cand_cap,
 	        (int)a.cand_cap);
-	typename std::conditional<E == 0, MemList, WaveList<(E == 0 ? 1 : E)>>::type L;
+	typename std::conditional<E == LDS_LIST_E, LdsList,
+	                          typename std::conditional<E == 0, MemList, WaveList<(E == 0 || E == LDS_LIST_E ? 1 : E)>>::type>::type L;
 	if constexpr (E == 0)
 		L.bind(a.list_buf + gslot * 2 * a.list_cap, reinterpret_cast<uint32_t *>(a.list_buf + gslot * 2 * a.list_cap) + a.list_cap);
+	if constexpr (E == LDS_LIST_E)
+		L.bind(es.list_d, es.list_s, es.list_tops);
 	const int limit = a.ef > a.k ? a.ef : a.k; // expansion = max(ef, wanted), index.hpp:2908
 
 	// (the 8-register list's instantiations only — limits of 257-512, where the compact set's overflows are a per-cent matter:
@@ -1900,7 +1936,7 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 		// (round 6 measured two lists in flight next to the blocked 8-register list in its 12-wave instantiation, which has the
 		//  registers for it now: 262k -> 251k queries/s at 10M x 768, ef 512 — the second request and its bookkeeping cost the accept
 		//  phase more than the extra hits save the gather: profiles/r06c_wide_lists_phase_ticks_10m768_prof.txt.  One list stays.)
-		constexpr int PK = (NCH == 6 || NCH == 4 || E == 0 || E >= 8) ? 1 : 2;
+		constexpr int PK = (NCH == 6 || NCH == 4 || E == 0 || E == LDS_LIST_E || E >= 8) ? 1 : 2;
 		if (a.tomb == 1) { // few rejected rows expected: the pending candidates stay in registers (host: limits within the register lists only)
 			if constexpr (E == 2 || E == 4 || E == 8) {
 				// twice the result list (the queue fills up while the result list is still filling); as long as the list itself
@@ -1914,11 +1950,11 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 			rc = level_search_impl<MT, false, true, 1>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, cq, score, wc);
 		else if (a.spec_active)
 			rc = level_search_spec<MT>(a.gv, lds, sb, qa2, closest, limit, L, score, a.spec_active, wc);
-		else if (E > 0 && E <= pipelined_max_regs(THREADS) && a.pipelined) {
+		else if (E > 0 && E != LDS_LIST_E && E <= pipelined_max_regs(THREADS) && a.pipelined) {
 			// accept phase in the shadow of the successor's row loads (host: lists of at most 64 cells).  Limits beyond 256 — an
 			// 8-register list — keep the plain order in a 1024-thread workgroup: the pipeline's state next to it does not fit its
 			// 128 registers (112 bytes of scratch per lane measured); the 768-thread instantiation has room.
-			if constexpr (E > 0 && E <= pipelined_max_regs(THREADS))
+			if constexpr (E > 0 && E != LDS_LIST_E && E <= pipelined_max_regs(THREADS))
 				rc = level_search_pipelined<MT, PK>(a.gv, lds, sb, qa2, closest, limit, L, score, wc);
 			else
 				rc = LEVEL_INTERNAL;

@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "lds_list_index.h"
 #include "visited_compact.h"
 
 namespace vss {
@@ -250,6 +251,39 @@ inline uint32_t compact_visited_cells_log2(bool plain_table_fits_lds, bool solo_
 	const uint32_t form = nodes > (1ull << compact_visited::KEY_BITS) ? compact_visited::make_form(cells_log2, compact_visited::KEY_BITS_MAX)
 	                                                                  : cells_log2;
 	return compact_visited::form_ok(form) ? form : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Where the candidate list of a launch lives (no reference counterpart — results never depend on it):
+// registers up to 512 entries (WaveList), beyond that LDS (LdsList: capacities of 513-4096 in the workgroup engine) or HBM
+// (MemList: everything else — the solo shape, larger capacities, the builds).
+//   list_cap     capacity of the list in memory: min(limit, rows) for limits above 512, 0 = the list is in registers
+//   slot_bytes   LDS of one walker's slot WITHOUT the list (engine_slot_bytes, hnsw_kernels.h)
+//   walkers_hbm  walkers per workgroup the launch runs with the list in HBM (what it wants, bounded by what fits and by the cap)
+//   walkers_cap  the ceiling on walkers per workgroup that is not a matter of LDS (option / scoring waves that must remain)
+//   mode         search.list_lds: 0 never, 1 automatic — only when the workgroup keeps its walkers, so that no launch loses
+//                occupancy to the list —, 2 whenever one walker fits (A/B runs, tests)
+// *walkers_lds (may be null): the walkers that fit with the list in LDS when that is the answer, else 0.
+// ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t LIST_IN_REGISTERS = 0, LIST_IN_LDS = 1, LIST_IN_HBM = 2;
+constexpr uint32_t ENGINE_HEADER_BYTES_HOST = 1072; // = vss::ENGINE_HEADER_BYTES (hnsw_kernels.h; vss_engine.hip asserts it)
+inline uint32_t engine_walkers_that_fit(uint32_t slot_bytes, uint32_t walkers_cap) {
+	return std::min<uint32_t>(walkers_cap, (160u * 1024 - ENGINE_HEADER_BYTES_HOST) / std::max<uint32_t>(1, slot_bytes));
+}
+inline uint32_t candidate_list_placement(uint32_t mode, uint64_t list_cap, bool solo_shape, uint32_t slot_bytes, uint32_t walkers_hbm,
+                                         uint32_t walkers_cap, uint32_t *walkers_lds = nullptr) {
+	if (walkers_lds)
+		*walkers_lds = 0;
+	if (!list_cap)
+		return LIST_IN_REGISTERS;
+	if (mode == 0 || solo_shape || !lds_list::cells_ok(list_cap))
+		return LIST_IN_HBM;
+	const uint32_t fit = engine_walkers_that_fit(slot_bytes + lds_list::bytes((uint32_t)list_cap), walkers_cap);
+	if (fit < 1 || (mode == 1 && fit < walkers_hbm))
+		return LIST_IN_HBM;
+	if (walkers_lds)
+		*walkers_lds = fit;
+	return LIST_IN_LDS;
 }
 
 // ---------------------------------------------------------------------------------------------------------

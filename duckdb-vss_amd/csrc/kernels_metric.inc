@@ -35,7 +35,7 @@ static hipError_t allow_big_lds(K kernel) {
 
 // The search engine: c.threads / 64 waves per workgroup (walkers + scoring waves), 4 rows in flight per scoring pass
 // (<= 128 VGPRs, so that a 1024-thread workgroup fits a compute unit).  The candidate list takes 2, 4 or 8 registers per
-// lane, or lives in HBM (E = 0) for ef_search / k beyond 512.
+// lane, or lives in LDS (E = LDS_LIST_E: capacities of 513-4096) or in HBM (E = 0) for ef_search / k beyond 512.
 #ifndef VSS_SEARCH_R6
 #define VSS_SEARCH_R6 2 // 6 chunks per lane (dimension 1536): 4 rows in flight spill 72 bytes per lane beyond the 128 VGPRs
 #endif
@@ -45,6 +45,9 @@ static hipError_t search_e(const SearchArgs &a, const LaunchCfg &c) {
 	// limits of 257-512, pipelined: 12-wave workgroups (170 registers per lane; 4 rows in flight at every row width)
 	if (c.threads <= WIDE_LIST_THREADS && c.regs > PIPELINED_MAX_REGS && c.regs <= MAX_LIST_REGS && a.pipelined)
 		VSS_LAUNCH_T((k_search<MT, NCH, 4, MAX_LIST_REGS, WIDE_LIST_THREADS>), a, c.threads);
+	// capacities of 513-4096 with the list in the walkers' slots of LDS (the host's placement rule: host_logic.h)
+	if (a.list_lds)
+		VSS_LAUNCH_T((k_search<MT, NCH, RS, LDS_LIST_E>), a, c.threads);
 	if (c.regs <= 2)
 		VSS_LAUNCH_T((k_search<MT, NCH, RS, 2>), a, c.threads);
 	if (c.regs <= 4)

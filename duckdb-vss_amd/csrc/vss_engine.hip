@@ -32,6 +32,8 @@ using namespace vss::host;
 
 // the constants host_logic.h restates for the CPU tests are the kernels'
 static_assert(host::TOUCH_LISTS_BIT == TOUCH_LISTS, "ListTouch bit");
+static_assert(host::ENGINE_HEADER_BYTES_HOST == ENGINE_HEADER_BYTES, "LDS header of the search engine");
+static_assert(lds_list::MIN_CELLS == 64 * MAX_LIST_REGS + 1, "the LDS list starts where the register lists end");
 static_assert(host::SearchShapePolicy().team_box_bytes == TEAM_BOX_BYTES, "team box size");
 static_assert(team_touch_max_lines(0) == 8 && team_touch_max_lines(1) == 8 && team_touch_max_lines(3) == 24, "helper touch window");
 
@@ -199,6 +201,8 @@ struct vss_index {
 		uint64_t nq = 0, limit = 0, list_cap = 0;
 		uint32_t bump = 0;
 		uint32_t min_hash_log2 = 0; // after a visited-set overflow: the next pass's table is at least this large
+		uint32_t shape[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // vss_last_search_shape: this call's first launch
+		bool first_pass = true;
 		double kernel_ms = 0;
 		uint64_t stats[4] = {0, 0, 0, 0};
 	};
@@ -231,6 +235,7 @@ struct vss_index {
 
 	// search scratch
 	uint64_t last_stats[4] = {0, 0, 0, 0};
+	uint32_t last_shape[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	std::vector<uint32_t> last_query_stats;
 	// kernel timing (hipEvents on the index's stream): [0] last search kernel(s) ms, [1] build phase A ms,
 	// [2] build phase B (count/alloc/scatter/link) ms, [3] build host wall ms, [4] build batches, [5] build retries
@@ -933,16 +938,26 @@ struct vss_index {
 		//  LDS, WaveLds::spill_box)
 		a.stage_cap = (!solo && !c.list_cap && c.limit > 64u * PIPELINED_MAX_REGS) ? 4u : 0u;
 		const uint32_t slot_bytes = engine_slot_bytes(a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap);
-		uint32_t s_max = std::min<uint32_t>({search_walkers ? ENGINE_MAX_WALKERS : search_walkers_cap, waves - 1,
-		                                     (160u * 1024 - ENGINE_HEADER_BYTES) / slot_bytes});
+		const uint32_t walkers_cap = std::min<uint32_t>(search_walkers ? ENGINE_MAX_WALKERS : search_walkers_cap, waves - 1);
+		uint32_t s_max = host::engine_walkers_that_fit(slot_bytes, walkers_cap);
 		uint32_t S = search_walkers ? search_walkers : (n + n_cus - 1) / n_cus;
 		S = std::max<uint32_t>(1, std::min(S, s_max));
+		// Limits beyond the register lists: the candidate list in the walkers' slots of LDS (capacities of 513-4096; LdsList) where
+		// the workgroup keeps the walkers it has with the list in HBM — no launch loses occupancy to it —, else in HBM as before
+		// (the rule: host_logic.h, CPU-tested; search.list_lds = 0 is the path without it, exactly).  Retry passes come through
+		// here like every launch.
+		uint32_t walkers_lds = 0;
+		const uint32_t list_place = host::candidate_list_placement(search_list_lds, c.list_cap, solo, slot_bytes, S, walkers_cap, &walkers_lds);
+		const bool list_in_lds = list_place == host::LIST_IN_LDS;
+		a.list_lds = list_in_lds ? (uint32_t)c.list_cap : 0u;
+		if (list_in_lds)
+			S = std::min(S, walkers_lds); // (search.list_lds = 2 only: the automatic rule never takes a walker away)
 		// workgroups per compute unit: one 16-wave workgroup — or, with fewer waves per workgroup (vss_set_search_params), as
 		// many as the waves and the LDS admit, so that a workgroup of the NEXT launch can move in beside one that still drains
 		// (VSS_SEARCH_WGS_PER_CU caps it, default 1.  Measured: two 8-wave workgroups of 2 walkers + 6 scoring waves per compute
 		// unit run every regime at the rate of one 16-wave workgroup of 4 + 12 — profiles/r04_two_workgroups_per_compute_unit_no_gain.txt)
 		uint32_t wgs_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(16u / waves, (160u * 1024) /
-		                                             std::max<uint32_t>(1, engine_lds_bytes(S, a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap))));
+		                                             std::max<uint32_t>(1, engine_lds_bytes(S, a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap, a.list_lds))));
 		wgs_per_cu = std::min(wgs_per_cu, search_wgs_per_cu);
 		uint32_t grid = std::min<uint32_t>(n_cus * wgs_per_cu, (n + S - 1) / S);
 		const uint32_t solo_lds = wave_lds_bytes(a.hash_log2, V, a.list_cap_max, a.stage_cap, hash_in_lds);
@@ -962,7 +977,7 @@ struct vss_index {
 				retry_want_log2 = want_log2;
 		}
 		// (the retry tables count: ADVICE r05 — 512 MiB per context that runs such limits went unbudgeted)
-		const uint64_t per_walker = (hash_in_lds ? 0 : (4ull << a.hash_log2)) + 8ull * c.list_cap + (a.tomb == 2 ? 8ull * c.cand_cap : 0) +
+		const uint64_t per_walker = (hash_in_lds ? 0 : (4ull << a.hash_log2)) + (list_in_lds ? 0 : 8ull * c.list_cap) + (a.tomb == 2 ? 8ull * c.cand_cap : 0) +
 		                            (retry_want_log2 ? (4ull << retry_want_log2) : 0);
 		const uint64_t budget = 16ull << 30;
 		while (per_walker * grid * S > budget && (grid > 1 || S > 1)) {
@@ -997,7 +1012,7 @@ struct vss_index {
 			a.retry_hash = c.d_retry_hash.p, a.retry_log2 = retry_want_log2;
 		a.list_cap = (uint32_t)c.list_cap;
 		a.list_buf = nullptr;
-		if (c.list_cap) {
+		if (c.list_cap && !list_in_lds) {
 			c.d_list_buf.ensure((uint64_t)grid * S * 2 * c.list_cap, 0, c.stream);
 			a.list_buf = c.d_list_buf.p;
 		}
@@ -1033,7 +1048,7 @@ struct vss_index {
 			a.drain_flag = c.h_queue + 2;
 			a.done_count = nullptr;
 		}
-		LaunchCfg cfg = launch_cfg(grid, solo ? solo_lds : engine_lds_bytes(S, a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap),
+		LaunchCfg cfg = launch_cfg(grid, solo ? solo_lds : engine_lds_bytes(S, a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap, a.list_lds),
 		                           c.limit);
 		cfg.stream = c.stream;
 		// a team (helper waves on the compute unit's other SIMDs score a share of every expansion's rows) while every query
@@ -1042,6 +1057,12 @@ struct vss_index {
 		if (team)
 			cfg.lds += TEAM_BOX_BYTES;
 		cfg.threads = solo ? (team ? 64 * VSS_TEAM_WAVES : 64) : 64 * waves;
+		if (c.first_pass) { // vss_last_search_shape
+			const uint32_t shape[8] = {cfg.threads, S, grid, cfg.lds, list_place, hash_in_lds ? (a.visited_compact ? 1u : 0u) : 2u,
+			                           solo ? 1u : 0u, 0u};
+			std::memcpy(c.shape, shape, sizeof shape);
+			c.first_pass = false;
+		}
 		if (c.flag_wait)
 			c.flag_t0 = std::chrono::steady_clock::now();
 		else
@@ -1083,6 +1104,8 @@ struct vss_index {
 	bool search_pipelined = true;
 	// limits of 257-512 pipelined in 12-wave workgroups (vss_set_search_wide_lists, VSS_SEARCH_WIDE_LISTS=0 for A/B)
 	bool search_wide_lists = true;
+	// candidate lists of limits 513-4096 in LDS: 0 never, 1 automatic, 2 whenever a walker fits (search.list_lds, VSS_SEARCH_LIST_LDS)
+	uint32_t search_list_lds = 1;
 
 	// enqueue one batched probe on a context (asynchronous); search_end() completes it
 	int search_begin(int slot, const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, uint64_t ef,
@@ -1181,6 +1204,7 @@ struct vss_index {
 		c.limit = limit;
 		c.bump = 0;
 		c.min_hash_log2 = 0;
+		c.first_pass = true;
 		// beyond the register lists (ef_search or k above 512) the candidate list lives in HBM; no list outgrows the index
 		c.list_cap = limit > 64 * MAX_LIST_REGS ? std::min<uint64_t>(limit, count) : 0;
 		// accepted-but-unexpanded candidates of a search over tombstones / a predicate (the reference's unbounded `next` heap);
@@ -1316,6 +1340,7 @@ struct vss_index {
 		{
 			std::lock_guard<std::mutex> lk(stats_mu);
 			std::memcpy(last_stats, c.stats, sizeof last_stats);
+			std::memcpy(last_shape, c.shape, sizeof last_shape);
 			timing[0] = c.kernel_ms;
 			if (keep_query_stats)
 				last_query_stats.assign(c.h_stats, c.h_stats + 2 * c.nq);
@@ -2232,6 +2257,8 @@ const OptionRule OPTION_RULES[] = {
      "one expansion of look-ahead while at most this many walkers of a workgroup still run (0 = off)"},
     {"search.gating", 0, 1, [](vss_index *h, int64_t v) { h->search_gating = v != 0; },
      "a launch is issued when its predecessor on the device starts to drain"},
+    {"search.list_lds", 0, 2, [](vss_index *h, int64_t v) { h->search_list_lds = (uint32_t)v; },
+     "candidate lists of limits 513-4096 in LDS: 0 never (HBM), 1 when the workgroup keeps its walkers, 2 whenever one walker fits"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {
@@ -2310,6 +2337,7 @@ int vss_create(uint64_t dim, int metric, uint64_t M, uint64_t M0, uint64_t efc, 
 	    {"VSS_SEARCH_WIDE_LISTS", "search.wide_lists"}, {"VSS_VISITED_COMPACT", "search.visited_compact"},
 	    {"VSS_SEARCH_RETRY_IN_PLACE", "search.retry_in_place"}, {"VSS_HASH_LDS_MAX_LOG2", "search.visited_lds_log2_max"},
 	    {"VSS_VISITED_PER_LIMIT", "search.visited_cells_per_limit"}, {"VSS_PROBE_FLAG_WAIT", "search.probe_flag_wait"},
+	    {"VSS_SEARCH_LIST_LDS", "search.list_lds"},
 	};
 	for (const auto &e : ENV_OPTIONS)
 		if (const char *t = getenv(e.env)) {
@@ -2544,6 +2572,14 @@ int vss_last_search_stats(vss_index *h, uint64_t *out4) {
 	VSS_SHARED(h, {
 		std::lock_guard<std::mutex> lk(h->stats_mu);
 		std::memcpy(out4, h->last_stats, sizeof h->last_stats);
+		return VSS_OK;
+	})
+}
+
+int vss_last_search_shape(vss_index *h, uint32_t *out8) {
+	VSS_SHARED(h, {
+		std::lock_guard<std::mutex> lk(h->stats_mu);
+		std::memcpy(out8, h->last_shape, sizeof h->last_shape);
 		return VSS_OK;
 	})
 }

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "lds_list_index.h"
 #include "visited_compact.h"
 
 namespace vss {
@@ -548,6 +549,135 @@ struct MemList {
 		if (lane_id() == 0)
 			s[pos] |= EXPANDED_BIT;
 		wave_sync();
+	}
+};
+
+// ------------------------------------------------------------------------------------------------------
+// LdsList — MemList for capacities of 513-4096 entries, kept in the walker's slot of LDS and addressed as LDS (address space 3:
+// ds_read / ds_write, no flat instructions).  Same interface, same semantics, entry for entry: accepted candidates are
+// inserted one by one (nothing is batched or merged).  What changes is what an insert costs:
+//   lower_bound  two dependent LDS reads whatever the size — the compact array of tile tops (one cell per lane), then one
+//                ballot over the tile the new entry falls into — instead of a walk over the tiles from position 0
+//   shift        tile by tile, highest first, LDS to LDS; the lane that writes a tile's last position writes its top
+// Index arithmetic and the layout: lds_list_index.h (modelled on the CPU in tests/lds_list_probe.cpp).  Distances are taken
+// to be ordered (as MemList's own prefix count takes them to be).  The list is private to the walking wave: lds_sync() — a
+// wait for the wave's own LDS operations, which are performed in issue order — is all the ordering its lanes need, and the
+// wave's global loads (the neighbour list requested ahead) stay in flight across every operation.
+// ------------------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) uint32_t lds_u32; // (as hnsw_kernels.h declares them for the mailboxes)
+typedef __attribute__((address_space(3))) float lds_f32;
+#define VSS_LDS_PTR(type, ptr) ((type *)(uint32_t)(uintptr_t)(ptr))
+struct LdsList {
+	static constexpr bool can_merge = false;
+	static constexpr int regs = 0;
+	static constexpr int prefetch_slots = 1;
+	lds_f32 *d;    // [cells] ascending
+	lds_u32 *s;    // [cells] bit 31 = "already expanded"
+	lds_f32 *tops; // [lds_list::TOP_CELLS] tops[t] = d[64 t + 63] for every full tile
+	int size;      // wave-uniform
+	int limit;     // wave-uniform, <= cells
+	int cursor;    // every entry below `cursor` is expanded
+
+	__device__ __forceinline__ void bind(float *dd, uint32_t *ss, float *tt) {
+		d = VSS_LDS_PTR(lds_f32, dd), s = VSS_LDS_PTR(lds_u32, ss), tops = VSS_LDS_PTR(lds_f32, tt);
+	}
+	__device__ __forceinline__ void reset(int lim) {
+		limit = lim, size = 0, cursor = 0;
+	}
+	// number of entries with distance < nd (the list is sorted, so they form a prefix)
+	__device__ __forceinline__ int lower_bound(float nd) const {
+		const int lane = lane_id();
+		const unsigned long long below = __ballot(lane < lds_list::full_tiles(size) && tops[lane] < nd);
+		const int base = 64 * lds_list::tiles_below(below);
+		if (base >= size)
+			return base;
+		const int i = base + lane;
+		return base + __popcll(__ballot(i < size && d[i] < nd));
+	}
+	// move entries [p, end) one cell up (end < cells), highest tile first so that nothing is overwritten before it is read
+	__device__ __forceinline__ void shift_up(int p, int end) {
+		const int lane = lane_id();
+		for (int hi = end; hi > p;) {
+			const int lo = lds_list::shift_window_lo(p, hi);
+			const int i = lo + lane;
+			float vd = 0.f;
+			uint32_t vs = 0;
+			if (i < hi) {
+				vd = d[i];
+				vs = s[i];
+			}
+			lds_sync(); // every lane has its value before any lane stores
+			if (i < hi) {
+				d[i + 1] = vd;
+				s[i + 1] = vs;
+				if (lds_list::top_at(i + 1) >= 0)
+					tops[lds_list::top_at(i + 1)] = vd;
+			}
+			// (no wait here: the next tile's reads lie below everything written so far, and LDS performs them in order)
+			hi = lo;
+		}
+	}
+	template <bool SKIP = false> // (WaveList's flavour switch; nothing to choose here)
+	__device__ __forceinline__ bool insert(float nd, uint32_t ns) {
+		const int p = lower_bound(nd);
+		if (p == limit)
+			return false;
+		shift_up(p, size < limit ? size : limit - 1);
+		if (lane_id() == 0) {
+			d[p] = nd;
+			s[p] = ns;
+			if (lds_list::top_at(p) >= 0)
+				tops[lds_list::top_at(p)] = nd;
+		}
+		lds_sync();
+		if (size < limit)
+			size++;
+		if (p < cursor)
+			cursor = p;
+		return true;
+	}
+	__device__ __forceinline__ void get(int pos, float &od, uint32_t &os) const {
+		od = d[pos]; // same address in every lane: one broadcast read
+		os = s[pos];
+	}
+	__device__ __forceinline__ float last_distance() const {
+		return d[size - 1];
+	}
+	__device__ __forceinline__ int first_unexpanded() {
+		const int lane = lane_id();
+		for (int base = cursor; base < size; base += 64) {
+			const int i = base + lane;
+			const unsigned long long m = __ballot(i < size && !(s[i] & EXPANDED_BIT));
+			if (m) {
+				cursor = base + __builtin_ctzll(m);
+				return cursor;
+			}
+		}
+		cursor = size;
+		return -1;
+	}
+	__device__ __forceinline__ int first_unexpanded_entry(float &od, uint32_t &os) {
+		const int pos = first_unexpanded();
+		if (pos >= 0)
+			get(pos, od, os);
+		return pos;
+	}
+	// (WaveList::accept for the list in memory: the same sequence of inserts)
+	__device__ __forceinline__ void accept(float cd, uint32_t cs, unsigned long long pass, float &radius) {
+		while (pass) {
+			const int j = __builtin_ctzll(pass);
+			pass &= pass - 1;
+			const float dj = read_lane(cd, j);
+			if (size < limit || dj < radius) {
+				insert(dj, read_lane(cs, j));
+				radius = last_distance();
+			}
+		}
+	}
+	__device__ __forceinline__ void mark_expanded(int pos) {
+		if (lane_id() == 0)
+			s[pos] |= EXPANDED_BIT;
+		lds_sync();
 	}
 };
 

@@ -113,6 +113,8 @@ int vss_set_build_reorder(vss_index *index, int on);
  *   search.probe_flag_wait (0/1) host-pointer probes of <= 256 queries wait on a pinned flag instead of the stream
  *   search.lookahead (0..8)      one expansion of look-ahead (off: measured slower)
  *   search.gating (0/1)          a launch is issued when its predecessor on the device starts to drain
+ *   search.list_lds (0..2)       candidate lists of limits 513-4096 in LDS: 0 never (HBM), 1 automatic (when the workgroup keeps
+ *                                its walkers), 2 whenever one walker fits; vss_last_search_shape reports the placement
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -177,6 +179,14 @@ int vss_search_exact_batch_device(vss_index *index, const float *d_queries, uint
  * search_result_t::computed_distances / visited_members, index.hpp:2566-2571):
  * out[0] = computed distances, out[1] = expanded nodes, out[2] = queries, out[3] = retried queries. */
 int vss_last_search_stats(vss_index *index, uint64_t *out4);
+/* Shape of the search launch behind the last vss_search* call — the call's first launch; a pass that re-runs the few queries
+ * which outgrew their scratch is not reported — (diagnostics and tests; no reference counterpart, results never depend on it;
+ * the same context rule as vss_last_search_stats: written when the call completes):
+ * out[0] = threads per workgroup, out[1] = walkers per workgroup, out[2] = workgroups, out[3] = dynamic LDS bytes per workgroup,
+ * out[4] = where the candidate list lives: 0 registers, 1 LDS, 2 HBM,
+ * out[5] = where the visited set lives: 0 LDS (32-bit cells), 1 LDS (compact cells), 2 HBM,
+ * out[6] = 1 for the one-wave-per-query (solo) shape, out[7] = 0. */
+int vss_last_search_shape(vss_index *index, uint32_t *out8);
 /* Kernel timing measured with hipEvents on the index's stream (milliseconds): out[0] = search kernel(s) of the last
  * vss_search_batch* call, out[1] = build phase A kernels, out[2] = build phase B (link) kernels, out[3] = build host
  * wall time, out[4] = build batches, out[5] = build batches re-run with a larger visited set (cumulative since the
