@@ -84,6 +84,7 @@ SIGNATURES = {
     "vss_search_exact_batch_device": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
+    "vss_last_search_prescore": (_int, [_vp, _vp]),
     "vss_last_search_query_stats": (_int, [_vp, _vp, _u64]),
     "vss_timing": (_int, [_vp, _vp, _int]),
     "vss_build_work": (_int, [_vp, _vp]),
@@ -325,6 +326,13 @@ class GpuIndex:
         (0 LDS, 1 LDS compact, 2 HBM), solo, 0] of the last search call's launch."""
         out = np.zeros(8, dtype=np.uint32)
         self._check(self.lib.vss_last_search_shape(self.h, _p(out)))
+        return out
+
+    def last_search_prescore(self):
+        """[filter active in the last search call's first launch, rows pre-scored on their codes, rows rejected there, bytes of
+        row codes held] (search.prescore)."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.vss_last_search_prescore(self.h, _p(out)))
         return out
 
     def timing(self, reset=False):

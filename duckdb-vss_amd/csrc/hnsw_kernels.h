@@ -19,6 +19,7 @@
 //   keys      [capacity] i64               DuckDB row ids; VSS_FREE_KEY marks a tombstone
 #pragma once
 #include "wave_primitives.h"
+#include "prescore_bound.h"
 #include <type_traits>
 
 namespace vss {
@@ -475,9 +476,134 @@ struct Mailbox {
 	unsigned long long ticket;
 	uint32_t done;
 	uint32_t qa2_bits; // |query|^2 (cosine), as bits
-	uint32_t slots; // row slots per claim of the open job: 1, 2 or R (a claim covers slots x (64 / G) rows)
-	uint32_t pad[3];
+	uint32_t slots; // row slots per claim of the open job: 1, 2 or R (a claim covers slots x (64 / G) rows), or PRESCORE_SLOTS
+	uint32_t bound_bits; // pre-scoring (below): the job's bound as bits, +inf = score every row
+	uint32_t pad[2];
 };
+
+// ---------------------------------------------------------------------------------------------------------
+// Pre-scoring on 8-bit codes (row_codes.h, prescore_bound.h; DESIGN.md §4.2, "Pre-scoring").  THE CONTRACT: a scoring wave may write +inf
+// instead of a row's distance iff it has proved that the f32 distance the engine would compute for that row is >= the bound
+// handed over with the job.  The bound is the walker's radius if its list is full at hand-over, else +inf (filters nothing):
+// the radius only falls and a full list stays full, so such a row is rejected at accept time anyway — ids, distance bits, the
+// order of expansions and both work counters stay what they are (wc.distances counts every row handed over).
+// Only level_search_pipelined over the mailbox exchange hands a finite bound over, only for full-wave rows with NCH >= 2, and
+// only while the job would be claimed R rows at a time (scoring waves busy: the bandwidth regime).
+struct PrescoreView {
+	const uint32_t *codes;        // rows x V dwords (nullptr: no filter in this launch)
+	const RowCodeMeta *meta;      // rows
+	unsigned long long *counters; // {rows pre-scored, rows rejected}: added to once per scoring wave, when it leaves
+};
+constexpr uint32_t PRESCORE_SLOTS = 16; // Mailbox::slots of a job with a finite bound: claims of prescore_claim_rows(R) rows
+// rows of codes per claim: what costs the registers R rows of floats cost (a job of ~25 rows: one code pass and one row pass)
+__host__ __device__ constexpr int prescore_claim_rows(int R) {
+	return 4 * R;
+}
+__device__ __forceinline__ float code_to_float(uint32_t w, int k) {
+	return (float)(int)(int8_t)(w >> (8 * k));
+}
+// Phase 1: bounds of rows ids[0 .. n) (n <= CR) from their codes; writes +inf to out[j] for every row proved >= bound and
+// returns the others as a mask over LANES (row j = bit j x 64 / CR).  Loads are unconditional and clamped (wave_distances).
+template <int MT, int NCH, int CR>
+__device__ __forceinline__ unsigned long long prescore_codes(const RowSpace &sp, const PrescoreView &pv, uint32_t dim,
+                                                             const float4 *q_lds, float qa2, const uint32_t *ids, int n,
+                                                             float bound, float *out, uint32_t &rejected) {
+	static_assert(NCH >= 2, "full-wave rows only");
+	const uint32_t lane = lane_id();
+	constexpr int PER = 64 / CR;
+	uint32_t w[NCH][CR];
+	float sc[CR];
+#pragma unroll
+	for (int r = 0; r < CR; ++r) {
+		const uint32_t id = ids[r < n ? r : n - 1];
+		const uint32_t *crow = pv.codes + (size_t)id * sp.V;
+#pragma unroll
+		for (int ch = 0; ch < NCH; ++ch)
+			w[ch][r] = crow[lane + ch * 64];
+		sc[r] = MT == 0 ? pv.meta[id].scale : 0.f; // (l2sq: the difference needs the row's scale in every lane)
+	}
+	// transposed_reduce64 leaves row j's total in lane j x PER: that lane reads the row's record
+	const int jm = (int)(lane / PER) < n ? (int)(lane / PER) : n - 1;
+	const float4 mraw = *reinterpret_cast<const float4 *>(pv.meta + ids[jm]);
+	__builtin_amdgcn_sched_barrier(0); // every load is issued before the first use (see wave_distances)
+	float t[CR];
+#pragma unroll
+	for (int r = 0; r < CR; ++r)
+		t[r] = 0.f;
+#pragma unroll
+	for (int ch = 0; ch < NCH; ++ch) {
+		const float4 q = q_lds[lane + ch * 64];
+		const float qs[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+		for (int r = 0; r < CR; ++r)
+#pragma unroll
+			for (int k = 0; k < 4; ++k) {
+				const float c = code_to_float(w[ch][r], k);
+				if (MT == 0) {
+					const float v = __fmaf_rn(-sc[r], c, qs[k]);
+					t[r] = __fmaf_rn(v, v, t[r]);
+				} else {
+					t[r] = __fmaf_rn(qs[k], c, t[r]);
+				}
+			}
+	}
+	transposed_reduce64<CR>(t);
+	RowCodeMeta m;
+	m.scale = mraw.x, m.err = mraw.y, m.norm = mraw.z, m.spare = 0;
+	const float lb = prescore_bound(MT, t[0], t[0], m, MT == 0 ? 1.f : vss_sqrt(qa2), dim);
+	const bool mine = (lane % PER) == 0 && (int)(lane / PER) < n;
+	const bool rej = mine && lb >= bound;
+	if (rej)
+		out[lane / PER] = __builtin_inff();
+	rejected += (uint32_t)__popcll(__ballot(rej));
+	return __ballot(mine && !rej);
+}
+// Phase 2: the f32 distances of the next (up to) RR rows of `left` — a mask over lanes as prescore_codes returns it, the rows
+// taken are cleared — exactly as wave_distances computes them: the same lanes, the same order, the same bits.  Row addresses
+// come from ids[position of the r-th set bit], wave-uniform; a slot beyond the last survivor repeats it (same cache lines).
+template <int MT, int NCH, int RR>
+__device__ __forceinline__ void wave_distances_picked(const RowSpace &sp, const float4 *q_lds, float qa2, const uint32_t *ids,
+                                                      unsigned long long &left, int lane_shift, float *out) {
+	const uint32_t lane = lane_id();
+	int pos[RR], last = 0;
+	const float4 *row[RR];
+#pragma unroll
+	for (int r = 0; r < RR; ++r) {
+		if (left)
+			last = (int)(__builtin_ctzll(left) >> lane_shift);
+		pos[r] = last;
+		left &= left - 1ull;
+		row[r] = sp.vectors + (size_t)ids[pos[r]] * sp.V;
+	}
+	float4 x[NCH][RR];
+#pragma unroll
+	for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+		for (int r = 0; r < RR; ++r)
+			x[ch][r] = row[r][lane + ch * 64];
+	float ab[RR], b2[RR];
+#pragma unroll
+	for (int r = 0; r < RR; ++r)
+		ab[r] = 0.f, b2[r] = 0.f;
+#pragma unroll
+	for (int ch = 0; ch < NCH; ++ch) {
+		const float4 q = q_lds[lane + ch * 64];
+#pragma unroll
+		for (int r = 0; r < RR; ++r)
+			accumulate4<MT>(q, x[ch][r], ab[r], b2[r]);
+	}
+	transposed_reduce64<RR>(ab);
+	if (MT == 1)
+		transposed_reduce64<RR>(b2);
+	constexpr int PER = 64 / RR;
+	int j = pos[0];
+#pragma unroll
+	for (int r = 1; r < RR; ++r)
+		j = (int)(lane / PER) == r ? pos[r] : j;
+	if ((lane % PER) == 0)
+		out[j] = finish_distance<MT>(ab[0], qa2, b2[0]);
+}
+
 
 // The mailboxes are addressed as LDS (address space 3) explicitly: ds_* instructions instead of flat ones.
 typedef __attribute__((address_space(3))) unsigned long long lds_u64;
@@ -513,9 +639,11 @@ typedef __attribute__((address_space(3))) lds_u32x4 lds_u32x4_as3;
 // GPU with tools/microbench/mailbox_test).  Instead EVERY lane executes the atomic — lane 0 on the real word, lane i on
 // cell i of a scrap area nobody reads (distinct addresses: one LDS instruction, nothing for the compiler's wave-level
 // atomic combiner to rewrite) — and lane 0's return value is taken.
-template <int MT, int NCH, int R>
+// PRE: this instantiation carries the pre-scoring path (pv, dim, and the wave's two counters: rows pre-scored, rejected)
+template <int MT, int NCH, int R, bool PRE = false>
 __device__ __forceinline__ bool pool_score(Mailbox *mb, unsigned long long *scrap, const RowSpace &sp, const float4 *q,
-                                           const uint32_t *ids, float *dist) {
+                                           const uint32_t *ids, float *dist, const PrescoreView *pv = nullptr, uint32_t dim = 0,
+                                           uint32_t *pre_counts = nullptr) {
 	const int lane = lane_id();
 	unsigned long long *ticket_or_scrap = lane == 0 ? &mb->ticket : scrap + lane;
 	uint32_t *done_or_scrap = lane == 0 ? &mb->done : reinterpret_cast<uint32_t *>(scrap + lane);
@@ -524,8 +652,9 @@ __device__ __forceinline__ bool pool_score(Mailbox *mb, unsigned long long *scra
 		// rows per claim: the walker's choice for the open job (fewer rows per scoring wave when many of them are idle:
 		// a wave's latency grows by ~60 cycles per KiB it loads).  A stale value only changes how many rows this claim takes.
 		uint32_t slots = (uint32_t)uniform((int)VSS_LDS_LOAD(lds_u32, &mb->slots));
+		const bool wide_claim = PRE && slots == PRESCORE_SLOTS; // (stale like `slots`: decides the claim's size, nothing else)
 		slots = slots == 1 || slots == 2 ? slots : (uint32_t)R;
-		const uint32_t pass = slots * (64u >> sp.logG);
+		const uint32_t pass = wide_claim ? (uint32_t)prescore_claim_rows(R) : slots * (64u >> sp.logG);
 		const unsigned long long t = VSS_LDS_ADD_ACQ(lds_u64, ticket_or_scrap, (unsigned long long)pass); // claim: acquire
 		const uint32_t c = (uint32_t)uniform((int)(uint32_t)t), n = (uint32_t)uniform((int)(uint32_t)(t >> 32));
 		VSS_TRACE_INC(sp, 25);
@@ -553,6 +682,37 @@ __device__ __forceinline__ bool pool_score(Mailbox *mb, unsigned long long *scra
 		}
 #endif
 		const float qa2 = __uint_as_float(VSS_LDS_LOAD(lds_u32, &mb->qa2_bits));
+		// (a launch without codes — search.prescore = 0, no room for codes — reads no bound: pv->codes is a kernel argument)
+		if constexpr (PRE) {
+			if (pv->codes) {
+				// the bound of THIS job (read after the claim's acquire: the walker wrote it before the ticket that was claimed)
+				const float bound = __uint_as_float((uint32_t)uniform((int)VSS_LDS_LOAD(lds_u32, &mb->bound_bits)));
+				// (wave-uniform.  A finite bound implies a claim of <= CR rows, whatever `slots` said.  The other way round — a stale
+			//  PRESCORE_SLOTS read against a job whose bound is +inf — is an ordinary claim of up to CR rows: it falls through to
+			//  wave_distances below, which loops over any number of rows R at a time)
+			if (bound < __builtin_inff()) {
+					constexpr int CR = prescore_claim_rows(R);
+					constexpr int SHIFT = CR == 16 ? 2 : CR == 8 ? 3 : 4; // log2(64 / CR)
+					static_assert(CR == 16 || CR == 8 || CR == 4, "rows of codes per claim");
+					unsigned long long left = prescore_codes<MT, NCH, CR>(sp, *pv, dim, q, qa2, ids + c, (int)cnt, bound, dist + c, pre_counts[1]);
+					pre_counts[0] += cnt;
+					while (left) { // the survivors' rows ("no survivor": a wave-uniform skip)
+						const int have = __popcll(left);
+						if (have >= 3 && R >= 4)
+							wave_distances_picked<MT, NCH, (R >= 4 ? 4 : 1)>(sp, q, qa2, ids + c, left, SHIFT, dist + c);
+						else if (have >= 2)
+							wave_distances_picked<MT, NCH, 2>(sp, q, qa2, ids + c, left, SHIFT, dist + c);
+						else
+							wave_distances_picked<MT, NCH, 1>(sp, q, qa2, ids + c, left, SHIFT, dist + c);
+					}
+					wave_sync();
+					VSS_LDS_ADD_REL(lds_u32, done_or_scrap, cnt); // the distances (and the +inf) above are published with this add
+					VSS_TRACE_INC(sp, 29);
+					worked = true;
+					continue;
+				}
+			}
+		}
 		// (every variant reduces a row with the same lanes in the same order: same bits; all end with wave_sync)
 		if (slots == 1)
 			wave_distances<MT, NCH, 1>(sp, q, qa2, ids + c, (int)cnt, dist + c);
@@ -605,7 +765,7 @@ struct CrewBox {
 };
 static_assert(sizeof(CrewBox) == 16 && sizeof(Mailbox) == 32, "engine LDS header layout");
 
-template <int MT, int NCH, int R>
+template <int MT, int NCH, int R, bool PRE = false>
 struct PoolScorer {
 	static constexpr bool touches_rows = false, touches_lists = true, helpers_touch = false;
 	Mailbox *mb;            // this walker's two mailboxes (job buffers 0 and 1)
@@ -618,6 +778,7 @@ struct PoolScorer {
 	uint32_t crew_ok;       // the launch allows crew mode (host: SearchArgs::crew)
 	uint32_t no_requests;   // a walker running a crew asks for no lists ahead of time (CREW_NO_REQUESTS)
 	uint32_t touch_ok;      // the host allows list touches for this launch (CREW_TOUCH: vss_set_search_touch / list_cap <= 64)
+	uint32_t prescore_ok;   // PRE: the launch carries row codes (SearchArgs::prescore)
 	mutable uint32_t crew_on = 0; // wave-uniform: this walker is the last one and runs the crew
 	mutable uint32_t level = 0;   // wave-uniform: the graph level of the rows handed over next (descend; 0 = the base level)
 	__device__ __forceinline__ void at_level(int l) const {
@@ -639,7 +800,10 @@ struct PoolScorer {
 		return active ? active : 1u;
 	}
 	// offer the n ids of job buffer `buf` (already in LDS) to the scoring waves
-	__device__ __forceinline__ void post(int buf, const RowSpace &sp, int n) const {
+	// `bound` (PRE; level_search_pipelined only): the walker's radius if its list is full, else +inf.  It travels with the job
+	// only where the job is claimed R rows at a time — scoring waves busy, the bandwidth regime —, as claims of
+	// prescore_claim_rows(R) rows; a job spread thinly over idle scoring waves is scored as before (bound +inf).
+	__device__ __forceinline__ void post(int buf, const RowSpace &sp, int n, float bound = __builtin_inff()) const {
 		Mailbox *box = mb + buf;
 		// rows per claim: spread the job over the scoring waves this walker can count on (mine = scorers / active walkers: all
 		// of them once its neighbours have finished), never more than R row slots per wave.  Without the two run-time integer
@@ -649,7 +813,13 @@ struct PoolScorer {
 		const uint32_t x1 = ((uint32_t)n + (1u << lg) - 1u) >> lg, x2 = (x1 + 1u) >> 1;
 		const uint32_t a = active_walkers();
 		// (every lane stores the same values: no lane-0 branch, see pool_score)
-		VSS_LDS_STORE(lds_u32, &box->slots, a * x1 <= scorers ? 1u : a * x2 <= scorers ? 2u : (uint32_t)R);
+		if (PRE && prescore_ok) { // (a launch without codes stores no bound: the boxes hold +inf from the kernel's start; PRE is constexpr)
+			const bool filtered = bound < __builtin_inff() && a * x2 > scorers;
+			VSS_LDS_STORE(lds_u32, &box->slots, a * x1 <= scorers ? 1u : a * x2 <= scorers ? 2u : filtered ? PRESCORE_SLOTS : (uint32_t)R);
+			VSS_LDS_STORE(lds_u32, &box->bound_bits, __float_as_uint(filtered ? bound : __builtin_inff()));
+		} else {
+			VSS_LDS_STORE(lds_u32, &box->slots, a * x1 <= scorers ? 1u : a * x2 <= scorers ? 2u : (uint32_t)R);
+		}
 		VSS_LDS_STORE(lds_u32, &box->done, 0u);
 		// one 64-bit atomic store opens the job: {n rows, next row 0} — release: ids, query and the words above come first
 		VSS_LDS_STORE_REL(lds_u64, &box->ticket, (unsigned long long)(uint32_t)n << 32);
@@ -683,7 +853,7 @@ struct PoolScorer {
 	}
 	// Hand the n ids of job buffer `buf` (already in LDS) to the scoring waves — through the mailbox, or, for the last walker
 	// of the workgroup, behind the crew's first barrier.  The switch to crew mode happens here, between two jobs.
-	__device__ __forceinline__ void begin(int buf, const RowSpace &sp, float qa2, int n) const {
+	__device__ __forceinline__ void begin(int buf, const RowSpace &sp, float qa2, int n, float bound = __builtin_inff()) const {
 		if (crew_ok && !crew_on && uniform((int)VSS_LDS_LOAD(lds_u32, walkers_left)) == 1) {
 			crew_on = 1u; // (every lane stores the same value)
 #ifdef VSS_PHASE_TIMERS
@@ -701,7 +871,7 @@ struct PoolScorer {
 			lds_barrier(); // the ids (and, per query, the staged query) are in LDS: the crew starts
 			return;
 		}
-		post(buf, sp, n);
+		post(buf, sp, n, bound);
 	}
 	// block until the rows handed over by begin(buf, .., n) have their distances in LDS
 	__device__ __forceinline__ void end(int buf, const RowSpace &sp, int n) const {
@@ -1263,8 +1433,12 @@ __device__ __forceinline__ int level_search_pipelined(const GraphView &gv, WaveL
 		const int n = gather_neighbors<true>(gv, lds, cs, 0, have_first, first_cells);
 		VSS_TICK(tg1);
 		VSS_ACC(t_gather, tg0, tg1);
+		// The job's bound for pre-scoring: the radius if the list is full NOW — before the pending accept, which can only lower
+		// it: conservative —, else +inf.  INVARIANT: a finite bound implies a full list, and a full list stays full, so the +inf
+		// a scoring wave writes for a rejected row never passes `L.size < limit || d < radius`: it reaches neither L.accept's
+		// pass mask nor the pick's `m` (WaveList::accept mishandles +inf while a list is filling).
 		if (n > 0)
-			pool.begin(buf, gv.sp, qa2, n);
+			pool.begin(buf, gv.sp, qa2, n, L.size >= limit ? radius : __builtin_inff());
 		VSS_TICK(tg2);
 		VSS_ACC(t_solo_passes, tg1, tg2);
 		return n;
@@ -1502,6 +1676,7 @@ struct SearchArgs {
 	                          // words of LDS (visited_compact.h: log2 of its 16-bit cells | key bits << 8; 0 = the plain 32-bit
 	                          // set); host: slots < 2^25, first pass only
 	unsigned long long *phase_ticks; // debug (VSS_PHASE_TIMERS): n_queries x VSS_PHASE_STRIDE
+	PrescoreView prescore;    // row codes for the scoring waves of pipelined launches (codes == nullptr: off, the bound stays +inf)
 };
 
 __host__ __device__ inline uint32_t align16(uint32_t x) {
@@ -1834,10 +2009,22 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 		boxes[threadIdx.x].done = 0;
 		boxes[threadIdx.x].qa2_bits = 0;
 		boxes[threadIdx.x].slots = R;
+		boxes[threadIdx.x].bound_bits = 0x7F800000u; // +inf
 	}
 	__syncthreads();
+	// pre-scoring on row codes: full-wave rows of at least two chunks per lane, and the lists level_search_pipelined runs with
+	constexpr bool PRE = NCH >= 2 && E >= 1 && E != LDS_LIST_E && E <= pipelined_max_regs(THREADS);
 
 	if (wave >= S) { // ---------------------------------------------------------------- scoring waves
+		uint32_t pre_counts[2] = {0, 0}; // rows pre-scored / rejected by this wave: added to the launch's counters when it leaves
+		auto leave = [&] {
+			if constexpr (PRE) {
+				if (lane == 0 && pre_counts[0]) {
+					atomicAdd(a.prescore.counters, (unsigned long long)pre_counts[0]);
+					atomicAdd(a.prescore.counters + 1, (unsigned long long)pre_counts[1]);
+				}
+			}
+		};
 		for (;;) {
 			bool worked = false;
 			VSS_TRACE_INC(a.gv.sp, 24);
@@ -1846,13 +2033,16 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 				if (uniform((int)((uint32_t)t < (uint32_t)(t >> 32)))) {
 					const EngineSlot es =
 					    engine_slot(smem, s >> 1, a.hash_log2, a.gv.sp.V, a.list_cap_max, hash_in_lds, a.stage_cap, list_cells);
-					worked |= pool_score<MT, NCH, R>(&boxes[s], scrap, a.gv.sp, es.q, (s & 1) ? es.ids2 : es.ids,
-					                                 (s & 1) ? es.dist2 : es.dist);
+					worked |= pool_score<MT, NCH, R, PRE>(&boxes[s], scrap, a.gv.sp, es.q, (s & 1) ? es.ids2 : es.ids,
+					                                      (s & 1) ? es.dist2 : es.dist, &a.prescore, a.gv.dim, pre_counts);
 				}
 			}
-			if (uniform((int)VSS_LDS_LOAD(lds_u32, exit_flag)))
+			if (uniform((int)VSS_LDS_LOAD(lds_u32, exit_flag))) {
+				leave();
 				return;
+			}
 			if (uniform((int)VSS_LDS_LOAD_ACQ(lds_u32, &crew->on))) { // one walker left: its crew, behind barriers, until it is done
+				leave();
 				crew_help<MT, NCH, R>(smem, a, crew, (int)wave, (int)S, (int)(blockDim.x >> 6), hash_in_lds, list_cells);
 				return;
 			}
@@ -1875,9 +2065,9 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 	lds.q2 = nullptr, lds.kept_s = nullptr, lds.kept_d = nullptr;
 	lds.cand_d = nullptr, lds.cand_s = nullptr; // (rounds 2-5: staging of the batched list merge; the slot's few words are the spill box now)
 	lds.touch_lines = a.touch_lines & TOUCH_LISTS;   // latency-bound launches (host): ListTouch from the first expansion on
-	PoolScorer<MT, NCH, R> score {&boxes[2 * wave], exit_flag, a.engine_error, walkers_left, (blockDim.x >> 6) - S, crew, wave,
-	                              ((a.crew & CREW_ON) && !a.spec_active) ? 1u : 0u, (a.crew & CREW_NO_REQUESTS) ? 1u : 0u,
-	                              (a.crew & CREW_TOUCH) ? 1u : 0u};
+	PoolScorer<MT, NCH, R, PRE> score {&boxes[2 * wave], exit_flag, a.engine_error, walkers_left, (blockDim.x >> 6) - S, crew, wave,
+	                                   ((a.crew & CREW_ON) && !a.spec_active) ? 1u : 0u, (a.crew & CREW_NO_REQUESTS) ? 1u : 0u,
+	                                   (a.crew & CREW_TOUCH) ? 1u : 0u, (PRE && a.prescore.codes) ? 1u : 0u};
 	const SpecBuffers sb {es.ids, es.ids2, es.dist, es.dist2};
 	CandQueue cq;
 	cq.bind(a.cand_buf + gslot * 2 * a.cand_cap, reinterpret_cast<uint32_t *>(a.cand_buf + gslot * 2 * a.cand_cap) + a.cand_cap,
@@ -1918,7 +2108,8 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 		const uint32_t batch = qi / a.batch_size, row = qi - batch * a.batch_size;
 		stage_query(lds.q, a.queries[batch] + (size_t)row * a.q_stride, a.gv.dim, a.gv.sp.V);
 		VSS_TRACE(a.gv.sp, 19, 2u);
-		const float qa2 = MT == 1 ? wave_query_norm(a.gv.sp, lds.q) : 0.f;
+		// (ip with row codes: the bound needs |q| too; finish_distance<2> ignores it)
+		const float qa2 = (MT == 1 || (PRE && MT == 2 && a.prescore.codes)) ? wave_query_norm(a.gv.sp, lds.q) : 0.f;
 		VSS_LDS_STORE(lds_u32, &boxes[2 * wave].qa2_bits, __float_as_uint(qa2));
 		VSS_LDS_STORE(lds_u32, &boxes[2 * wave + 1].qa2_bits, __float_as_uint(qa2));
 		lds.ids = es.ids, lds.dist = es.dist;

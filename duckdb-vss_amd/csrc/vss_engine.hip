@@ -26,6 +26,7 @@
 #include "../../include/vssgpu.h"
 #include "launchers.h"
 #include "host_logic.h"
+#include "row_codes.h"
 
 using namespace vss;
 using namespace vss::host;
@@ -205,6 +206,11 @@ struct vss_index {
 		bool first_pass = true;
 		double kernel_ms = 0;
 		uint64_t stats[4] = {0, 0, 0, 0};
+		// pre-scoring: the kernels add to d_prescore {rows pre-scored, rejected} and never reset it; a call reports the difference
+		DevBuf<unsigned long long> d_prescore;
+		unsigned long long *h_prescore = nullptr; // pinned copy
+		unsigned long long prescore_base[2] = {0, 0};
+		bool prescore_first = false, prescore_used = false; // this call: its first launch filtered / any launch did
 	};
 	// contexts 0 .. EXPLICIT_CTX-1 belong to the caller (vss_search_batch_device_begin/_end; 0 is also the blocking
 	// device-pointer calls' context and runs on the index stream); the rest are leased by the host-pointer entry points
@@ -232,6 +238,75 @@ struct vss_index {
 	}
 	std::mutex ctx0_mu;  // blocking device-pointer searches share context 0
 	std::mutex exact_mu; // the exact path's scratch (score tiles, norms) is shared: exact searches take turns
+
+	// ---- row codes (row_codes.h): derived data of d_vectors for the scoring waves' pre-scoring (search.prescore, DESIGN.md §4.2, "Pre-scoring").
+	// ONE mechanism keeps them valid: every path that writes rows marks its slots in `codes_stale` (or everything), and
+	// ensure_codes() encodes what is marked — at the head of every search launch that would filter (nothing to do when clean)
+	// and at the end of the calls that change rows, so that the first search does not pay.  Not serialized.
+	// search.prescore, VSS_SEARCH_PRESCORE: 0 off (no codes held), 1 where it was measured to gain — limits of at most 256, the
+	// 16-wave kernels —, 2 every pipelined launch (the 12-wave kernels of limits 257-512 too: measured SLOWER there)
+	uint32_t search_prescore = 1;
+	DevBuf<uint32_t> d_codes;        // capacity x V dwords
+	DevBuf<RowCodeMeta> d_code_meta; // capacity
+	StaleSlots codes_stale;
+	std::mutex codes_mu;             // searches (shared index lock) encode stale slots one at a time
+	uint64_t codes_refused_capacity = 0; // the capacity at which the device had no room for codes: not tried again until it changes
+	uint64_t last_prescore[4] = {0, 0, 0, 0};
+	// rows the instantiations with a pre-scoring path run at: full-wave rows of 2, 3, 4 or 6 chunks per lane
+	bool codes_wanted() const {
+		const uint32_t nch = (G == 64 && V % 64 == 0 && !force_looping) ? V / 64 : 0;
+		return search_prescore && (nch == 2 || nch == 3 || nch == 4 || nch == 6);
+	}
+	void free_codes() {
+		d_codes.free(), d_code_meta.free();
+		codes_stale.clear();
+		codes_refused_capacity = 0;
+	}
+	// true: the codes of every linked row (slots below `count`) are valid once `s` has run what this call put on it (it has:
+	// the call waits).  may_allocate: only under the exclusive index lock — a search never replaces buffers another search
+	// may be reading; it finds them too small (a reserve() since) and runs unfiltered.  No room on the device: no filter, no error.
+	bool ensure_codes(hipStream_t s, bool may_allocate) {
+		if (!codes_wanted() || !capacity)
+			return false;
+		std::lock_guard<std::mutex> lk(codes_mu);
+		if (d_codes.n < capacity * V || d_code_meta.n < capacity) {
+			if (!may_allocate || codes_refused_capacity == capacity)
+				return false;
+			HIP_TRY(hipStreamSynchronize(s));
+			if (!d_codes.try_ensure(capacity * V) || !d_code_meta.try_ensure(capacity)) {
+				d_codes.free(), d_code_meta.free();
+				codes_refused_capacity = capacity;
+				return false;
+			}
+			codes_stale.mark_all(); // (fresh buffers: undefined contents)
+		}
+		const StaleSlots before = codes_stale;
+		uint64_t first = 0, end = 0;
+		// rows that are staged but not linked stay marked: no search reads them, and their copies may still be in flight
+		if (codes_stale.take(count, first, end)) {
+			const uint32_t grid = (uint32_t)std::min<uint64_t>((end - first + 3) / 4, (uint64_t)n_cus * 16);
+			hipLaunchKernelGGL(k_encode_rows, dim3(grid), dim3(256), 0, s, reinterpret_cast<const float4 *>(d_vectors.p), V, first, end,
+			                   d_codes.p, d_code_meta.p);
+			hipError_t status = hipGetLastError();
+			if (status == hipSuccess)
+				status = hipStreamSynchronize(s);
+			if (status != hipSuccess) {
+				codes_stale = before;
+				throw HipError {status, "k_encode_rows"};
+			}
+		}
+		return true;
+	}
+
+	// the same at the end of a call that changed rows (exclusive lock): codes are optional derived data, so a failure here
+	// never fails the call that has already succeeded — the slots stay marked and searches run unfiltered until an encode succeeds
+	void refresh_codes() noexcept {
+		try {
+			(void)ensure_codes(stream, true);
+		} catch (...) {
+			(void)hipGetLastError();
+		}
+	}
 
 	// search scratch
 	uint64_t last_stats[4] = {0, 0, 0, 0};
@@ -299,6 +374,7 @@ struct vss_index {
 	void release() {
 		d_vectors.free(), d_links0.free(), d_links_up.free(), d_upper_off.free(), d_list_owner.free();
 		d_levels.free(), d_keys.free();
+		free_codes();
 		d_req_list.free(), d_req_src.free(), d_req_rank.free(), d_sorted_src.free(), d_touched.free();
 		d_list_count.free(), d_list_offset.free(), d_counters.free(), d_req_d.free(), d_sorted_d.free();
 		d_node_status.free(), d_work_build.free(), d_work_stats.free(), d_build_list.free();
@@ -322,6 +398,9 @@ struct vss_index {
 			c.d_stats.free(), c.d_status.free(), c.d_work.free(), c.d_global_hash.free(), c.d_retry_hash.free(), c.d_phase.free();
 			c.d_queue.free(), c.d_list_buf.free(), c.d_cand_buf.free();
 			c.d_q.free(), c.d_out_d.free(), c.d_out_keys.free(), c.d_out_count.free(), c.d_filter.free();
+			c.d_prescore.free();
+			if (c.h_prescore)
+				(void)hipHostFree(c.h_prescore);
 			if (c.pinned_io)
 				(void)hipHostFree(c.pinned_io);
 			if (c.h_status)
@@ -517,6 +596,7 @@ struct vss_index {
 		int rc = VSS_OK;
 		if (nv > nr) {
 			copy_rows(nr, nv, d_vectors.p + first * stride);
+			codes_stale.mark(first, first + (nv - nr));
 			std::memcpy(keys_h.data() + first, kbuf.data() + nr, (nv - nr) * 8);
 			if (!st_slot.empty())
 				for (uint64_t i = 0; i != nv - nr; ++i)
@@ -817,6 +897,7 @@ struct vss_index {
 				const uint64_t stride = (uint64_t)V * 4;
 				HIP_TRY(hipMemcpyAsync(d_vectors.p + slot * stride, d_pending.p + src * stride, stride * 4,
 				                       hipMemcpyDeviceToDevice, stream));
+				codes_stale.mark(slot, (uint64_t)slot + 1);
 				HIP_TRY(hipMemcpyAsync(d_keys.p + slot, &pending_keys[src], 8, hipMemcpyHostToDevice, stream));
 			}
 			// a node above the current top level is always a singleton batch: it becomes the entry (index.hpp:2769-2772)
@@ -1000,6 +1081,30 @@ struct vss_index {
 		// the accept phase of an expansion in the shadow of the successor's row loads (level_search_pipelined): plain searches
 		// with a register list over neighbour lists of at most 64 cells
 		a.pipelined = (can_pipeline && (wide_list || c.limit <= 64u * PIPELINED_MAX_REGS)) ? 1u : 0u;
+		// pre-scoring on row codes (search.prescore): the pipelined level search over the mailbox exchange only; the pinned
+		// small-batch probe (latency-bound: crews) is left alone
+		a.prescore = PrescoreView {nullptr, nullptr, nullptr};
+		bool codes_ready = false;
+		const bool wide_limit = c.limit > 64u * PIPELINED_MAX_REGS; // (the 8-register list: walker-bound, two waves per walker)
+		if (a.pipelined && !solo && !c.direct_io && (search_prescore == 2 || !wide_limit)) {
+			try {
+				codes_ready = ensure_codes(c.stream, false);
+			} catch (const HipError &) { // (optional derived data: the search runs unfiltered, the slots stay marked)
+				(void)hipGetLastError();
+			}
+		}
+		if (codes_ready) {
+			if (!c.d_prescore.p) {
+				c.d_prescore.ensure(2, 0, c.stream, 0);
+				HIP_TRY(hipHostMalloc((void **)&c.h_prescore, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+				c.h_prescore[0] = c.h_prescore[1] = 0;
+				c.prescore_base[0] = c.prescore_base[1] = 0;
+			}
+			a.prescore = PrescoreView {d_codes.p, d_code_meta.p, c.d_prescore.p};
+			c.prescore_used = true;
+		}
+		if (c.first_pass)
+			c.prescore_first = a.prescore.codes != nullptr;
 		a.global_hash = nullptr;
 		if (!hash_in_lds) {
 			c.d_global_hash.ensure(((uint64_t)grid * S) << a.hash_log2, 0, c.stream);
@@ -1079,6 +1184,8 @@ struct vss_index {
 			HIP_TRY(hipMemcpyAsync(c.h_status, c.d_status.p, c.nq * 4, hipMemcpyDeviceToHost, c.stream));
 			HIP_TRY(hipMemcpyAsync(c.h_stats, c.d_stats.p, c.nq * 8, hipMemcpyDeviceToHost, c.stream));
 		}
+		if (a.prescore.codes)
+			HIP_TRY(hipMemcpyAsync(c.h_prescore, c.d_prescore.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
 	}
 
 	// Pipelined launches (explicit contexts): a launch of the engine occupies every compute unit, so a second one issued
@@ -1143,6 +1250,7 @@ struct vss_index {
 		c.stats[2] = nq;
 		c.kernel_ms = 0;
 		c.nq = nq;
+		c.prescore_first = c.prescore_used = false;
 		if (!nq || !k)
 			return VSS_OK;
 		if (!count) { // empty index: no results (index.hpp:2895-2896)
@@ -1341,6 +1449,14 @@ struct vss_index {
 			std::lock_guard<std::mutex> lk(stats_mu);
 			std::memcpy(last_stats, c.stats, sizeof last_stats);
 			std::memcpy(last_shape, c.shape, sizeof last_shape);
+			last_prescore[0] = c.prescore_first ? 1 : 0;
+			last_prescore[1] = last_prescore[2] = 0;
+			if (c.prescore_used) {
+				last_prescore[1] = c.h_prescore[0] - c.prescore_base[0];
+				last_prescore[2] = c.h_prescore[1] - c.prescore_base[1];
+				c.prescore_base[0] = c.h_prescore[0], c.prescore_base[1] = c.h_prescore[1];
+			}
+			last_prescore[3] = d_codes.n * sizeof(uint32_t) + d_code_meta.n * sizeof(RowCodeMeta);
 			timing[0] = c.kernel_ms;
 			if (keep_query_stats)
 				last_query_stats.assign(c.h_stats, c.h_stats + 2 * c.nq);
@@ -1848,6 +1964,7 @@ struct vss_index {
 		tombstones = t_tomb;
 		lists_may_repeat = t_repeat;
 		const uint64_t stride = (uint64_t)V * 4;
+		codes_stale.mark_all();
 		HIP_TRY(hipMemcpy2DAsync(d_vectors.p, stride * 4, vecs.data(), dim * 4, dim * 4, rows, hipMemcpyHostToDevice,
 		                         stream));
 		HIP_TRY(hipMemcpyAsync(d_links0.p, l0.data(), l0.size() * 4, hipMemcpyHostToDevice, stream));
@@ -1877,6 +1994,7 @@ struct vss_index {
 	void release_graph_only() {
 		d_vectors.free(), d_links0.free(), d_links_up.free(), d_upper_off.free(), d_list_owner.free();
 		d_levels.free(), d_keys.free(), d_list_count.free(), d_list_offset.free(), d_row_norm2.free();
+		free_codes();
 	}
 
 	void configure(uint64_t dim_, int metric_, uint64_t M_, uint64_t M0_) {
@@ -2014,6 +2132,7 @@ int vss_index::compact(bool reorder) {
 		}
 	}
 	const bool fresh_rows = n_vectors.p != nullptr;
+	codes_stale.mark_all(); // rows move (in place, or into the fresh buffer that is swapped in): every code is stale from here on
 	// ---- the order of the survivors: src_of[new slot] = old slot
 	std::vector<uint32_t> src_of;
 	src_of.reserve(live);
@@ -2259,6 +2378,16 @@ const OptionRule OPTION_RULES[] = {
      "a launch is issued when its predecessor on the device starts to drain"},
     {"search.list_lds", 0, 2, [](vss_index *h, int64_t v) { h->search_list_lds = (uint32_t)v; },
      "candidate lists of limits 513-4096 in LDS: 0 never (HBM), 1 when the workgroup keeps its walkers, 2 whenever one walker fits"},
+    {"search.prescore", 0, 2,
+     [](vss_index *h, int64_t v) {
+	     h->search_prescore = (uint32_t)v;
+	     if (!h->search_prescore)
+		     h->free_codes(); // 0: no codes are held, every job's bound is +inf — the path without the filter, exactly
+	     else if (h->stream)
+		     h->refresh_codes();
+     },
+     "scoring waves reject rows on exact bounds from 8-bit row codes before reading their f32 components: 0 never, 1 at limits of "
+     "at most 256, 2 in every pipelined launch"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {
@@ -2337,7 +2466,7 @@ int vss_create(uint64_t dim, int metric, uint64_t M, uint64_t M0, uint64_t efc, 
 	    {"VSS_SEARCH_WIDE_LISTS", "search.wide_lists"}, {"VSS_VISITED_COMPACT", "search.visited_compact"},
 	    {"VSS_SEARCH_RETRY_IN_PLACE", "search.retry_in_place"}, {"VSS_HASH_LDS_MAX_LOG2", "search.visited_lds_log2_max"},
 	    {"VSS_VISITED_PER_LIMIT", "search.visited_cells_per_limit"}, {"VSS_PROBE_FLAG_WAIT", "search.probe_flag_wait"},
-	    {"VSS_SEARCH_LIST_LDS", "search.list_lds"},
+	    {"VSS_SEARCH_LIST_LDS", "search.list_lds"}, {"VSS_SEARCH_PRESCORE", "search.prescore"},
 	};
 	for (const auto &e : ENV_OPTIONS)
 		if (const char *t = getenv(e.env)) {
@@ -2420,7 +2549,12 @@ int vss_synchronize(vss_index *h) {
 }
 
 int vss_reserve(vss_index *h, uint64_t members, uint64_t threads) {
-	VSS_GUARD(h, { return h->reserve(members, threads); })
+	VSS_GUARD(h, {
+		const int rc = h->reserve(members, threads);
+		if (rc == VSS_OK && h->count)
+			h->refresh_codes(); // (the rows moved to larger buffers: so do their codes)
+		return rc;
+	})
 }
 
 int vss_stage_batch(vss_index *h, const int64_t *rowids, const float *vecs, const uint64_t *validity, uint64_t n) {
@@ -2432,7 +2566,12 @@ int vss_stage_batch_device(vss_index *h, const int64_t *rowids, const float *vec
 }
 
 int vss_build_finalize(vss_index *h) {
-	VSS_GUARD(h, { return h->build_finalize(); })
+	VSS_GUARD(h, {
+		const int rc = h->build_finalize();
+		if (rc == VSS_OK)
+			h->refresh_codes();
+		return rc;
+	})
 }
 
 int vss_add_batch(vss_index *h, const int64_t *rowids, const float *vecs, const uint64_t *validity, uint64_t n) {
@@ -2440,7 +2579,10 @@ int vss_add_batch(vss_index *h, const int64_t *rowids, const float *vecs, const 
 		int rc = h->stage(rowids, vecs, validity, n, false);
 		if (rc != VSS_OK)
 			return rc;
-		return h->build_finalize();
+		rc = h->build_finalize();
+		if (rc == VSS_OK)
+			h->refresh_codes();
+		return rc;
 	})
 }
 
@@ -2576,6 +2718,14 @@ int vss_last_search_stats(vss_index *h, uint64_t *out4) {
 	})
 }
 
+int vss_last_search_prescore(vss_index *h, uint64_t *out4) {
+	VSS_SHARED(h, {
+		std::lock_guard<std::mutex> lk(h->stats_mu);
+		std::memcpy(out4, h->last_prescore, sizeof h->last_prescore);
+		return VSS_OK;
+	})
+}
+
 int vss_last_search_shape(vss_index *h, uint32_t *out8) {
 	VSS_SHARED(h, {
 		std::lock_guard<std::mutex> lk(h->stats_mu);
@@ -2636,12 +2786,19 @@ int vss_remove_batch(vss_index *h, const int64_t *rowids, uint64_t n, uint64_t *
 }
 
 int vss_compact(vss_index *h) {
-	VSS_GUARD(h, { return h->compact(true); })
+	VSS_GUARD(h, {
+		const int rc = h->compact(true);
+		if (rc == VSS_OK)
+			h->refresh_codes();
+		return rc;
+	})
 }
 
 int vss_compact_ex(vss_index *h, int reorder, int *out_reordered) {
 	VSS_GUARD(h, {
 		const int rc = h->compact(reorder != 0);
+		if (rc == VSS_OK)
+			h->refresh_codes();
 		if (out_reordered)
 			*out_reordered = rc == VSS_OK && h->last_compact_reordered ? 1 : 0;
 		return rc;
@@ -2681,7 +2838,7 @@ uint64_t vss_memory_usage(vss_index *h) {
 	if (!h)
 		return 0;
 	return h->d_vectors.n * 4 + h->d_links0.n * 4 + h->d_links_up.n * 4 + h->d_upper_off.n * 4 + h->d_levels.n +
-	       h->d_keys.n * 8 + h->d_list_owner.n * 4;
+	       h->d_keys.n * 8 + h->d_list_owner.n * 4 + h->d_codes.n * sizeof(uint32_t) + h->d_code_meta.n * sizeof(RowCodeMeta);
 }
 
 int vss_level_stats(vss_index *h, uint64_t level, uint64_t *out4) {
@@ -2703,7 +2860,12 @@ int vss_save(vss_index *h, vss_write_cb write, void *ctx) {
 }
 
 int vss_load(vss_index *h, vss_read_cb read, void *ctx) {
-	VSS_GUARD(h, { return h->load(read, ctx); })
+	VSS_GUARD(h, {
+		const int rc = h->load(read, ctx);
+		if (rc == VSS_OK)
+			h->refresh_codes();
+		return rc;
+	})
 }
 
 static int distance_launch(int fn, const float *a, const float *b, int b_const, uint64_t rows, uint64_t dim,

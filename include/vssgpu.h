@@ -115,6 +115,10 @@ int vss_set_build_reorder(vss_index *index, int on);
  *   search.gating (0/1)          a launch is issued when its predecessor on the device starts to drain
  *   search.list_lds (0..2)       candidate lists of limits 513-4096 in LDS: 0 never (HBM), 1 automatic (when the workgroup keeps
  *                                its walkers), 2 whenever one walker fits; vss_last_search_shape reports the placement
+ *   search.prescore (0..2)       scoring waves reject rows on exact lower bounds from 8-bit row codes before they read the rows'
+ *                                f32 components (rows of 512 / 768 / 1024 / 1536 dimensions, plain batched searches): 0 never (no
+ *                                codes held), 1 at limits of at most 256 (default: where it gains), 2 at limits of 257-512 as well;
+ *                                costs a quarter of the vectors' bytes again in device memory; vss_last_search_prescore reports it
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -187,6 +191,11 @@ int vss_last_search_stats(vss_index *index, uint64_t *out4);
  * out[5] = where the visited set lives: 0 LDS (32-bit cells), 1 LDS (compact cells), 2 HBM,
  * out[6] = 1 for the one-wave-per-query (solo) shape, out[7] = 0. */
 int vss_last_search_shape(vss_index *index, uint32_t *out8);
+/* Pre-scoring of the last vss_search* call (search.prescore; diagnostics and tests, results never depend on it; the same
+ * context rule as vss_last_search_stats): out[0] = 1 if the call's first launch ran with the filter, out[1] = rows whose bound
+ * was computed from their codes, out[2] = rows among them rejected without reading their f32 components (both summed over the
+ * call's launches), out[3] = bytes of device memory the index holds for row codes (counted by vss_memory_usage). */
+int vss_last_search_prescore(vss_index *index, uint64_t *out4);
 /* Kernel timing measured with hipEvents on the index's stream (milliseconds): out[0] = search kernel(s) of the last
  * vss_search_batch* call, out[1] = build phase A kernels, out[2] = build phase B (link) kernels, out[3] = build host
  * wall time, out[4] = build batches, out[5] = build batches re-run with a larger visited set (cumulative since the
