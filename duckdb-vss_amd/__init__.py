@@ -82,6 +82,7 @@ SIGNATURES = {
     "vss_search_batch_end": (_int, [_vp, _int]),
     "vss_search_exact_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_exact_batch_device": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
     "vss_last_search_prescore": (_int, [_vp, _vp]),
@@ -334,6 +335,11 @@ class GpuIndex:
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_search_prescore(self.h, _p(out)))
         return out
+
+    def last_exact_fallbacks(self):
+        """Queries of the last exact search that were answered again by brute force in the metric (their selection by ranking
+        score could not be certified, csrc/exact_certificate.h)."""
+        return int(self.lib.vss_last_exact_fallbacks(self.h))
 
     def timing(self, reset=False):
         out = np.zeros(6, dtype=np.float64)

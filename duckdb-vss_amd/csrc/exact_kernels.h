@@ -5,11 +5,15 @@
 //                      Replaces the distance loop of usearch search_exact_ (index.hpp:4004-4019) for a whole
 //                      batch of queries at once; scores are RANKING scores (|x|^2 - 2 q.x, -q.x/|x|, -q.x).
 //   k_exact_select     per query: fold one chunk of scores into a running top-K' (K' = k + slack)
-//   k_exact_rerank     per query: recompute the K' survivors with the exact wave-order metric, sort, emit k
+//   k_exact_rerank     per query: recompute the K' survivors with the exact wave-order metric, sort, emit k; decides whether
+//                      the selection by score provably kept the metric's top-k (exact_certificate.h)
+//   k_norm_extrema     largest / smallest |x|^2 over the live rows (cached with the norms; the certificate's E)
+//   k_exact_metric_scores  the redo of uncertified queries: the wave-order metric itself for every live row of a chunk
 //   k_array_distance   array_distance / array_cosine_distance / array_negative_inner_product over a column
 //   k_merge_topk       k-way merge of per-shard results after the RCCL all-gather
 #pragma once
 #include "hnsw_kernels.h"
+#include "exact_certificate.h"
 
 namespace vss {
 
@@ -1187,6 +1191,97 @@ __global__ __launch_bounds__(SEL_THREADS) void k_exact_select(SelectArgs a) {
 	}
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// out2[0] / out2[1] = the largest / smallest cached |x|^2 over the live rows, as bit patterns: sums of squares are never
+// negative, and non-negative floats order like their bits (a NaN sorts above +inf and so ends up in out2[0], where the
+// certificate refuses it).  The host presets out2 to {0, 0xFFFFFFFF}.
+__global__ __launch_bounds__(256) void k_norm_extrema(const float *norm2, const int64_t *keys, uint32_t rows, uint32_t *out2) {
+	uint32_t hi = 0u, lo = 0xFFFFFFFFu;
+	for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x)
+		if (keys[r] != FREE_KEY) {
+			const uint32_t b = __float_as_uint(norm2[r]);
+			hi = b > hi ? b : hi;
+			lo = b < lo ? b : lo;
+		}
+	for (int o = 32; o >= 1; o >>= 1) {
+		const uint32_t oh = __shfl_xor(hi, o), ol = __shfl_xor(lo, o);
+		hi = oh > hi ? oh : hi;
+		lo = ol < lo ? ol : lo;
+	}
+	if ((threadIdx.x & 63) == 0) {
+		atomicMax(&out2[0], hi);
+		atomicMin(&out2[1], lo);
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The redo of the queries whose selection by score could not be certified (exact_certificate.h): the score chunk is filled
+// with the engine's METRIC itself — the same lane-to-chunk partition, fma order and butterfly as wave_distance_one, hence the
+// bits k_exact_rerank computes — for every live row, +inf for tombstones; k_exact_select in plain mode then keeps the K'
+// smallest (distance, slot) pairs, which hold the answer by construction.  No matrix pipe here: a row is read once per
+// MS_QT queries (staged in LDS), 64 / G rows side by side per wave.  Score row t of the chunk belongs to query query_map[t].
+constexpr int MS_QT = 8;
+struct MetricScoreArgs {
+	RowSpace sp;
+	const int64_t *keys;
+	const float *queries; // n_queries x q_stride
+	uint32_t q_stride, dim;
+	const uint32_t *query_map;
+	uint32_t n_map;
+	uint32_t qt; // queries per workgroup, <= MS_QT (fewer where MS_QT of them do not fit the LDS)
+	uint32_t row_begin, row_end, chunk_stride;
+	float *scores; // n_map x chunk_stride
+};
+
+template <int MT>
+__global__ __launch_bounds__(256) void k_exact_metric_scores(MetricScoreArgs a) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char ms_smem[];
+	float4 *qs = reinterpret_cast<float4 *>(ms_smem); // [qt][V], zero padded
+	const uint32_t V = a.sp.V, G = a.sp.G;
+	const uint32_t t0 = blockIdx.y * a.qt;
+	const uint32_t nqt = a.n_map - t0 < a.qt ? a.n_map - t0 : a.qt;
+	for (uint32_t i = threadIdx.x; i < nqt * V * 4; i += blockDim.x) {
+		const uint32_t t = i / (V * 4), c = i - t * (V * 4);
+		reinterpret_cast<float *>(qs)[i] = c < a.dim ? a.queries[(size_t)a.query_map[t0 + t] * a.q_stride + c] : 0.f;
+	}
+	__syncthreads();
+	const uint32_t lane = threadIdx.x & 63, g = lane & (G - 1), sub = lane >> a.sp.logG, RG = 64u >> a.sp.logG;
+	float qa2[MS_QT];
+#pragma unroll
+	for (int t = 0; t < MS_QT; ++t)
+		qa2[t] = (MT == 1 && (uint32_t)t < nqt) ? wave_query_norm(a.sp, qs + (size_t)t * V) : 0.f;
+	const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = gridDim.x * (blockDim.x >> 6);
+	for (uint32_t base = a.row_begin + wave * RG; base < a.row_end; base += n_waves * RG) {
+		const uint32_t row = base + sub;
+		const float4 *rp = a.sp.vectors + (size_t)(row < a.row_end ? row : a.row_end - 1) * V;
+		float ab[MS_QT], b2 = 0.f, unused = 0.f;
+#pragma unroll
+		for (int t = 0; t < MS_QT; ++t)
+			ab[t] = 0.f;
+		for (uint32_t c = g; c < V; c += G) {
+			const float4 x = rp[c];
+#pragma unroll
+			for (int t = 0; t < MS_QT; ++t)
+				if ((uint32_t)t < nqt) {
+					if (MT == 1 && t > 0) // (the row's own sum of squares does not depend on the query: once is enough)
+						accumulate4<2>(qs[(size_t)t * V + c], x, ab[t], unused);
+					else
+						accumulate4<MT>(qs[(size_t)t * V + c], x, ab[t], b2);
+				}
+		}
+		if (MT == 1)
+			b2 = group_butterfly(b2, G);
+		const bool live = row < a.row_end && a.keys[row < a.row_end ? row : a.row_end - 1] != FREE_KEY;
+#pragma unroll
+		for (int t = 0; t < MS_QT; ++t)
+			if ((uint32_t)t < nqt) {
+				const float d = finish_distance<MT>(group_butterfly(ab[t], G), qa2[t], b2);
+				if (g == 0 && row < a.row_end)
+					a.scores[(size_t)(t0 + t) * a.chunk_stride + (row - a.row_begin)] = live ? d : __builtin_inff();
+			}
+	}
+}
+
 #endif // VSS_ENGINE_TU
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1201,22 +1296,30 @@ struct RerankArgs {
 	int64_t *out_keys;
 	float *out_d;
 	uint32_t *out_count;
+	// the certificate (exact_certificate.h; all NULL = none is asked for): certified[q] = 1 iff the kept set provably holds
+	// the k nearest rows of query q by (distance, slot)
+	const float *best_s;
+	const uint32_t *norm_ext; // bit patterns of the largest and the smallest |x|^2 over the live rows (k_norm_extrema)
+	uint32_t *certified;
+	// the redo: workgroup b answers query query_map[b] from row b of best_i (NULL = identity)
+	const uint32_t *query_map;
 };
 
 template <int MT, int NCH, int R>
 __global__ __launch_bounds__(64) void k_exact_rerank(RerankArgs a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int lane = lane_id();
-	const uint32_t qi = blockIdx.x;
+	const uint32_t bq = blockIdx.x; // row of best_s / best_i
+	const uint32_t qi = a.query_map ? a.query_map[bq] : bq;
 	float4 *q = reinterpret_cast<float4 *>(smem);
 	uint32_t *ids = reinterpret_cast<uint32_t *>(smem + align16(a.gv.sp.V * 16));
 	float *dist = reinterpret_cast<float *>(smem + align16(a.gv.sp.V * 16) + align16(a.KP * 4));
 	stage_query(q, a.queries + (size_t)qi * a.q_stride, a.gv.dim, a.gv.sp.V);
-	const float qa2 = MT == 1 ? wave_query_norm(a.gv.sp, q) : 0.f;
+	const float qa2 = (MT == 1 || a.certified) ? wave_query_norm(a.gv.sp, q) : 0.f;
 	// compact the valid candidates
 	int n = 0;
 	for (uint32_t off = 0; off < a.KP; off += 64) {
-		uint32_t id = (off + lane < a.KP) ? a.best_i[(size_t)qi * a.KP + off + lane] : EMPTY_SLOT;
+		uint32_t id = (off + lane < a.KP) ? a.best_i[(size_t)bq * a.KP + off + lane] : EMPTY_SLOT;
 		unsigned long long m = __ballot(id != EMPTY_SLOT);
 		if (id != EMPTY_SLOT)
 			ids[n + __popcll(m & lanes_below(lane))] = id;
@@ -1224,6 +1327,18 @@ __global__ __launch_bounds__(64) void k_exact_rerank(RerankArgs a) {
 	}
 	wave_sync();
 	wave_distances<MT, NCH, R>(a.gv.sp, q, qa2, ids, n, dist);
+	if (a.certified) {
+		// every live row outside the kept set has a distance >= floor; a kept set that is not full holds every live row (within
+		// the model's range of norms, where no score reaches the select's 3e38 cut)
+		const double E = exact_cert_error(MT, a.gv.sp.V * 4u, qa2, __uint_as_float(a.norm_ext[0]), __uint_as_float(a.norm_ext[1]));
+		const bool model = E < (double)__builtin_inff();
+		const double floor_d = exact_cert_floor_given(MT, a.best_s[(size_t)bq * a.KP + a.KP - 1], qa2, E);
+		int below = 0;
+		for (int off = 0; off < n; off += 64)
+			below += __popcll(__ballot(off + lane < n && (double)dist[off + lane] < floor_d));
+		if (lane == 0)
+			a.certified[qi] = (model && (n < (int)a.KP || below >= (int)a.k)) ? 1u : 0u;
+	}
 	// rank by (distance, slot) and emit the first k
 	const int count = n < (int)a.k ? n : (int)a.k;
 	for (int i = lane; i < n; i += 64) {

@@ -324,7 +324,12 @@ struct vss_index {
 
 	// exact-search scratch
 	DevBuf<float> d_row_norm2, d_q_norm2, d_scores, d_best_s, d_qpad, d_cand_s;
-	DevBuf<uint32_t> d_best_i, d_cand_cnt, d_cand_i;
+	DevBuf<uint32_t> d_best_i, d_cand_cnt, d_cand_i, d_norm_ext, d_certified, d_redo_map;
+	// 1 (default): a query whose selection by score is not certified (csrc/exact_certificate.h) is redone by brute force in the
+	// metric; 2: every query is redone (tests)  (VSS_EXACT_CERTIFY).  exact_redo_qt: queries per workgroup of the redo kernel
+	// (VSS_EXACT_REDO_QT; tests: the tiles it forms when fewer than MS_QT queries fit its LDS)
+	uint32_t exact_certify = 1, exact_redo_qt = MS_QT;
+	uint64_t last_exact_fallbacks = 0; // queries of the last exact call that were redone
 	bool exact_filter = true; // the select folded into the score tile's epilogue from the second chunk on (VSS_EXACT_FILTER=0: A/B)
 	uint64_t norms_valid_for = ~0ull; // value of `mutations` the norms were computed at
 	uint64_t mutations = 0;
@@ -384,6 +389,7 @@ struct vss_index {
 		d_pending.free(), d_row_slot.free(), d_row_src.free(), d_parked.free();
 		d_global_hash.free(), d_row_norm2.free(), d_q_norm2.free(), d_scores.free(), d_best_s.free(), d_qpad.free();
 		d_best_i.free(), d_cand_s.free(), d_cand_cnt.free(), d_cand_i.free();
+		d_norm_ext.free(), d_certified.free(), d_redo_map.free();
 		if (h_counters)
 			(void)hipHostFree(h_counters);
 		h_counters = nullptr;
@@ -1565,6 +1571,11 @@ struct vss_index {
 		if (!nq || !k)
 			return VSS_OK;
 		std::lock_guard<std::mutex> exact_lock(exact_mu); // score tiles, norms and the index stream are shared
+		last_exact_fallbacks = 0;
+		// Contract: for finite inputs the answer is the brute force of the wave-order metric over the live rows,
+		// ordered by (distance, slot).  Rows are SELECTED by an MFMA ranking score, the survivors re-scored with the metric; the
+		// re-rank certifies per query that the selection cannot have lost a row (csrc/exact_certificate.h), and the queries it
+		// cannot certify are redone with the metric itself as the score.
 		// running top-(k + 8) per query; exact search is not reachable from the reference's SQL surface (HNSWIndex never passes
 		// exact=true), its k is bounded by the select kernel's LDS
 		if (k + 8 > SEL_KP_MAX)
@@ -1584,9 +1595,16 @@ struct vss_index {
 		d_scores.ensure(nq * CH, 0, stream);
 		d_best_s.ensure(nq * KP, 0, stream);
 		d_best_i.ensure(nq * KP, 0, stream);
+		d_norm_ext.ensure(2, 0, stream);
+		d_certified.ensure(nq, 0, stream);
 		if (norms_valid_for != mutations) {
 			hipLaunchKernelGGL(k_row_norms, dim3(2048), dim3(256), 0, stream,
 			                   reinterpret_cast<const float4 *>(d_vectors.p), V, G, logG, (uint32_t)rows, d_row_norm2.p);
+			// the certificate's largest / smallest live |x|^2, cached with the norms
+			HIP_TRY(hipMemsetAsync(d_norm_ext.p, 0, 4, stream));
+			HIP_TRY(hipMemsetAsync(d_norm_ext.p + 1, 0xFF, 4, stream));
+			hipLaunchKernelGGL(k_norm_extrema, dim3((uint32_t)std::min<uint64_t>((rows + 255) / 256, 1024)), dim3(256), 0, stream,
+			                   d_row_norm2.p, d_keys.p, (uint32_t)rows, d_norm_ext.p);
 			norms_valid_for = mutations;
 		}
 		HIP_TRY(hipMemsetAsync(d_qpad.p, 0, nq * stride * 4, stream));
@@ -1703,9 +1721,75 @@ struct vss_index {
 		r.out_keys = d_keys_out;
 		r.out_d = d_dist_out;
 		r.out_count = d_count_out;
+		r.best_s = d_best_s.p;
+		r.norm_ext = d_norm_ext.p;
+		r.certified = d_certified.p;
+		r.query_map = nullptr;
 		const uint32_t lds = align16(V * 16) + 2 * align16((uint32_t)KP * 4);
 		launch_by_metric<RerankArgs>(launch_rerank<0>, launch_rerank<1>, launch_rerank<2>, r,
 		                             launch_cfg((uint32_t)nq, lds, 64));
+		// the queries the re-rank could not certify: redone with the metric itself as the score
+		std::vector<uint32_t> flags(nq), redo;
+		HIP_TRY(hipMemcpyAsync(flags.data(), d_certified.p, nq * 4, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		for (uint64_t i = 0; i != nq; ++i)
+			if (!flags[i] || exact_certify == 2)
+				redo.push_back((uint32_t)i);
+		last_exact_fallbacks = redo.size();
+		if (redo.empty())
+			return VSS_OK;
+		const uint64_t nb = redo.size();
+		d_redo_map.ensure(nb, 0, stream);
+		HIP_TRY(hipMemcpyAsync(d_redo_map.p, redo.data(), nb * 4, hipMemcpyHostToDevice, stream));
+		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, nb * KP * 4, stream));
+		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, nb * KP * 4, stream));
+		MetricScoreArgs m;
+		m.sp = r.gv.sp;
+		m.keys = d_keys.p;
+		m.queries = d_queries;
+		m.q_stride = q_stride, m.dim = (uint32_t)dim;
+		m.query_map = d_redo_map.p;
+		m.n_map = (uint32_t)nb;
+		m.qt = (uint32_t)std::min<uint64_t>(exact_redo_qt, (160 * 1024) / ((uint64_t)V * 16));
+		if (!m.qt)
+			return fail("exact search: a row of %llu dimensions does not fit the redo kernel's LDS", (unsigned long long)dim);
+		m.chunk_stride = (uint32_t)CH;
+		m.scores = d_scores.p;
+		const uint32_t m_lds = m.qt * V * 16;
+		const void *m_fn = metric == 0   ? reinterpret_cast<const void *>(k_exact_metric_scores<0>)
+		                   : metric == 1 ? reinterpret_cast<const void *>(k_exact_metric_scores<1>)
+		                                 : reinterpret_cast<const void *>(k_exact_metric_scores<2>);
+		HIP_TRY(hipFuncSetAttribute(m_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<uint32_t>(m_lds, 64 * 1024)));
+		for (uint64_t r0 = 0; r0 < rows; r0 += CH) {
+			const uint64_t r1 = std::min(rows, r0 + CH);
+			m.row_begin = (uint32_t)r0, m.row_end = (uint32_t)r1;
+			const uint32_t rows_per_wave_pass = 64u >> logG;
+			const uint64_t waves = (r1 - r0 + rows_per_wave_pass - 1) / rows_per_wave_pass;
+			dim3 grid((uint32_t)std::min<uint64_t>((waves + 3) / 4, 8ull * n_cus), (uint32_t)((nb + m.qt - 1) / m.qt));
+			if (metric == 0)
+				hipLaunchKernelGGL(k_exact_metric_scores<0>, grid, dim3(256), m_lds, stream, m);
+			else if (metric == 1)
+				hipLaunchKernelGGL(k_exact_metric_scores<1>, grid, dim3(256), m_lds, stream, m);
+			else
+				hipLaunchKernelGGL(k_exact_metric_scores<2>, grid, dim3(256), m_lds, stream, m);
+			SelectArgs s;
+			s.scores = d_scores.p;
+			s.chunk_stride = (uint32_t)CH;
+			s.chunk_cols = (uint32_t)(r1 - r0);
+			s.row_begin = (uint32_t)r0;
+			s.KP = (uint32_t)KP;
+			s.best_s = d_best_s.p;
+			s.best_i = d_best_i.p;
+			s.cand_cap = 0;
+			s.cand_cnt = nullptr, s.cand_s = nullptr, s.cand_i = nullptr;
+			s.overflow = nullptr;
+			hipLaunchKernelGGL(k_exact_select, dim3((uint32_t)nb), dim3(SEL_THREADS), 0, stream, s);
+		}
+		r.certified = nullptr; // (the kept set is the metric's own top-K': nothing left to prove)
+		r.query_map = d_redo_map.p;
+		launch_by_metric<RerankArgs>(launch_rerank<0>, launch_rerank<1>, launch_rerank<2>, r,
+		                             launch_cfg((uint32_t)nb, lds, 64));
+		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(stream));
 		return VSS_OK;
 	}
@@ -2490,6 +2574,10 @@ int vss_create(uint64_t dim, int metric, uint64_t M, uint64_t M0, uint64_t efc, 
 		h->search_walkers_cap = (uint32_t)std::max(1, std::min((int)ENGINE_MAX_WALKERS, atoi(t)));
 	if (const char *t = getenv("VSS_EXACT_FILTER"))
 		h->exact_filter = atoi(t) != 0;
+	if (const char *t = getenv("VSS_EXACT_CERTIFY"))
+		h->exact_certify = (uint32_t)std::max(1, std::min(2, atoi(t)));
+	if (const char *t = getenv("VSS_EXACT_REDO_QT"))
+		h->exact_redo_qt = (uint32_t)std::max(1, std::min(MS_QT, atoi(t)));
 	if (const char *t = getenv("VSS_SEARCH_CREW_TUNE"))
 		h->search_crew_tune = (uint32_t)atoi(t) & (CREW_SPARE_SIMD | CREW_NO_REQUESTS);
 	if (const char *t = getenv("VSS_SEARCH_TOUCH_LISTS"))
@@ -2724,6 +2812,13 @@ int vss_last_search_prescore(vss_index *h, uint64_t *out4) {
 		std::memcpy(out4, h->last_prescore, sizeof h->last_prescore);
 		return VSS_OK;
 	})
+}
+
+uint64_t vss_last_exact_fallbacks(vss_index *h) {
+	if (!h)
+		return 0;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	return h->last_exact_fallbacks;
 }
 
 int vss_last_search_shape(vss_index *h, uint32_t *out8) {

@@ -174,11 +174,20 @@ int vss_search_batch_end(vss_index *index, int context);
  * and a launch's measured duration is execution, not queueing.  vss_set_option(index, "search.gating", 0) = issue immediately
  * (round 1's behaviour). */
 /* index.ef_search(query, k, ef, thread, exact=true) — usearch search_exact_ index.hpp:4004-4019: brute force
- * over every live row (MFMA distance tiles + exact re-rank).  Same output layout as vss_search_batch. */
+ * over every live row.  Same output layout as vss_search_batch.  Contract, for finite inputs: the k live rows with the
+ * smallest (distance, slot) pairs, in that order, distance = the engine's f32 metric (the bits vss_search_batch reports).
+ * Rows are selected by MFMA ranking scores and the survivors re-scored; a query for which the engine cannot prove that this
+ * selection lost no row (csrc/exact_certificate.h) is answered again by brute force in the metric itself.
+ * Limits: k <= 4088; a live row whose distance is not below 3e38 (an f32 sum that overflowed: outside "finite inputs" in
+ * effect) is never returned; rows wider than 10 240 dimensions cannot be answered again and fail the call (VSS_ERROR). */
 int vss_search_exact_batch(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k,
                            int64_t *out_rowids, float *out_distances, uint32_t *out_counts);
 int vss_search_exact_batch_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k,
                                   int64_t *d_out_rowids, float *d_out_distances, uint32_t *d_out_counts);
+/* How many queries of the last vss_search_exact_batch* call on this index were answered again by brute force in the metric
+ * because their selection by score could not be certified (diagnostics and tests; results never depend on it; 0 on data
+ * whose nearest neighbours are further apart than the f32 scores' rounding error, e.g. the benchmark's). */
+uint64_t vss_last_exact_fallbacks(vss_index *index);
 /* Work counters of the last vss_search_batch* call, summed over its queries (usearch's
  * search_result_t::computed_distances / visited_members, index.hpp:2566-2571):
  * out[0] = computed distances, out[1] = expanded nodes, out[2] = queries, out[3] = retried queries. */

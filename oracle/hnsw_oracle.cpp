@@ -1529,6 +1529,11 @@ void orc_set_mode(orc_index *h, int order, int wave) {
 float orc_distance_wave(int metric, const float *a, const float *b, uint64_t dim) {
 	return dist_wave_order(metric, a, b, dim);
 }
+/* orc_distance_wave(metric, q, row r of x) for rows x dim floats: the brute-force reference of the exact-search contract */
+void orc_distance_wave_rows(int metric, const float *q, const float *x, uint64_t rows, uint64_t dim, float *out) {
+	for (uint64_t r = 0; r != rows; ++r)
+		out[r] = dist_wave_order(metric, q, x + r * dim, dim);
+}
 /* array_distance (fn 0) / array_cosine_distance (1) / array_negative_inner_product (2) over rows x dim floats, one
  * sequential f32 accumulation per row — SURVEY Appendix B's statement of DuckDB core's functions (named at reference
  * hnsw_index.cpp:659-673; their source is NOT in the reference tree: PARITY UNPINNED).  b = rows x dim, or one vector when

@@ -54,6 +54,8 @@ def _declare(lib, oracle_ext):
         lib.orc_compact_reordering.argtypes = [_vp]
         lib.orc_distance_wave.restype = C.c_float
         lib.orc_distance_wave.argtypes = [_int, _vp, _vp, _u64]
+        lib.orc_distance_wave_rows.restype = None
+        lib.orc_distance_wave_rows.argtypes = [_int, _vp, _vp, _u64, _u64, _vp]
         lib.orc_draw_levels.argtypes = [_u64, _u64, _vp]
         lib.orc_schedule.restype = _u64
         lib.orc_schedule.argtypes = [_u64, _int, _vp, _u64, _u64, _u64, _vp]
