@@ -86,6 +86,7 @@ SIGNATURES = {
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
     "vss_last_search_prescore": (_int, [_vp, _vp]),
+    "vss_last_search_prescore_descent": (_int, [_vp, _vp]),
     "vss_last_search_query_stats": (_int, [_vp, _vp, _u64]),
     "vss_timing": (_int, [_vp, _vp, _int]),
     "vss_build_work": (_int, [_vp, _vp]),
@@ -334,6 +335,13 @@ class GpuIndex:
         row codes held] (search.prescore)."""
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_search_prescore(self.h, _p(out)))
+        return out
+
+    def last_search_prescore_descent(self):
+        """[rows the greedy descent handed over with a finite bound, rows among them rejected on their codes] of the last
+        search call (search.prescore_descent)."""
+        out = np.zeros(2, dtype=np.uint64)
+        self._check(self.lib.vss_last_search_prescore_descent(self.h, _p(out)))
         return out
 
     def last_exact_fallbacks(self):

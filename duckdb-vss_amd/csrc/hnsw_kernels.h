@@ -300,7 +300,10 @@ struct SoloScorer {
 	// the one-wave search kernel touches ahead itself: the rows of the cached lists (RowTouch) and the lists of the rows it
 	// accepts (ListTouch)
 	static constexpr bool touches_rows = LATE, touches_lists = LATE, helpers_touch = false;
+	static constexpr bool bounds_descent = false; // (descend: only the engine's scoring waves filter on a hop's bound)
 	__device__ __forceinline__ void at_level(int) const { // (descend<.., AHEAD>: only a crew's scoring waves care)
+	}
+	__device__ __forceinline__ void at_bound(float) const {
 	}
 	__device__ __forceinline__ bool latency_mode() const { // (ListTouch is the host's decision alone: WaveLds::touch_lines)
 		return false;
@@ -354,7 +357,10 @@ struct TeamScorer {
 	__device__ __forceinline__ bool latency_mode() const {
 		return false;
 	}
+	static constexpr bool bounds_descent = false;
 	__device__ __forceinline__ void at_level(int) const {
+	}
+	__device__ __forceinline__ void at_bound(float) const {
 	}
 	TeamBox *box; // LDS
 	// `cache` (level search): the list cache whose freshly arrived lists name the rows to touch; `touch` = touching is on
@@ -489,10 +495,17 @@ struct Mailbox {
 // order of expansions and both work counters stay what they are (wc.distances counts every row handed over).
 // Only level_search_pipelined over the mailbox exchange hands a finite bound over, only for full-wave rows with NCH >= 2, and
 // only while the job would be claimed R rows at a time (scoring waves busy: the bandwidth regime).
+// THE CONTRACT, FOR THE DESCENT: descend() takes a row only if its distance is STRICTLY smaller than closest_dist (m < closest_dist,
+// first occurrence of the minimum), and closest_dist only falls.  A hop's job therefore carries closest_dist as its bound: a row
+// whose proved bound is >= it — equality included, the bound is <= the distance — can never be taken, so +inf in its place leaves
+// `changed`, `closest`, closest_dist and the order of hops what they are, and wc.distances / wc.cycles count every row handed
+// over as before.  A NaN or +inf closest_dist filters nothing (`bound < inf` is false), a row without a bound is never rejected,
+// a crew ignores the bound, and post()'s "scoring waves busy" rule applies to these jobs as to any other.
 struct PrescoreView {
 	const uint32_t *codes;        // rows x V dwords (nullptr: no filter in this launch)
 	const RowCodeMeta *meta;      // rows
-	unsigned long long *counters; // {rows pre-scored, rows rejected}: added to once per scoring wave, when it leaves
+	unsigned long long *counters; // {rows pre-scored, rows rejected}: added to once per scoring wave, when it leaves;
+	                              // [2], [3]: the descent's share of both, counted by the walkers, added to once per query
 };
 constexpr uint32_t PRESCORE_SLOTS = 16; // Mailbox::slots of a job with a finite bound: claims of prescore_claim_rows(R) rows
 // rows of codes per claim: what costs the registers R rows of floats cost (a job of ~25 rows: one code pass and one row pass)
@@ -779,10 +792,26 @@ struct PoolScorer {
 	uint32_t no_requests;   // a walker running a crew asks for no lists ahead of time (CREW_NO_REQUESTS)
 	uint32_t touch_ok;      // the host allows list touches for this launch (CREW_TOUCH: vss_set_search_touch / list_cap <= 64)
 	uint32_t prescore_ok;   // PRE: the launch carries row codes (SearchArgs::prescore)
+	unsigned long long *descent_counters; // PRE: the descent's jobs carry closest_dist as their bound (SearchArgs::prescore_descent);
+	                                      // {rows handed over with a finite bound, rows that came back +inf}.  nullptr: they carry +inf
 	mutable uint32_t crew_on = 0; // wave-uniform: this walker is the last one and runs the crew
 	mutable uint32_t level = 0;   // wave-uniform: the graph level of the rows handed over next (descend; 0 = the base level)
+	mutable float hop_bound = __builtin_inff(); // wave-uniform: the bound of the job operator() hands over next (descend)
+	mutable uint32_t hop_filtered = 0;          // wave-uniform: that job went out with a finite bound
+	static constexpr bool bounds_descent = PRE;
 	__device__ __forceinline__ void at_level(int l) const {
 		level = (uint32_t)l;
+	}
+	// descend, before each hop: its closest_dist (see THE CONTRACT, FOR THE DESCENT)
+	__device__ __forceinline__ void at_bound(float bound) const {
+		hop_bound = (PRE && descent_counters) ? bound : __builtin_inff();
+	}
+	// descend, once per query: rows of its hops handed over with a finite bound, and those that came back +inf
+	__device__ __forceinline__ void add_descent_counts(uint32_t rows, uint32_t rejected) const {
+		if (PRE && descent_counters && rows && lane_id() == 0) {
+			atomicAdd(descent_counters, (unsigned long long)rows);
+			atomicAdd(descent_counters + 1, (unsigned long long)rejected);
+		}
 	}
 
 	// look-ahead list requests: worth their instructions unless the crew's touches keep every candidate's list in L2 anyway
@@ -803,8 +832,10 @@ struct PoolScorer {
 	// `bound` (PRE; level_search_pipelined only): the walker's radius if its list is full, else +inf.  It travels with the job
 	// only where the job is claimed R rows at a time — scoring waves busy, the bandwidth regime —, as claims of
 	// prescore_claim_rows(R) rows; a job spread thinly over idle scoring waves is scored as before (bound +inf).
-	__device__ __forceinline__ void post(int buf, const RowSpace &sp, int n, float bound = __builtin_inff()) const {
+	// Returns whether the job went out with a finite bound.
+	__device__ __forceinline__ bool post(int buf, const RowSpace &sp, int n, float bound = __builtin_inff()) const {
 		Mailbox *box = mb + buf;
+		bool sent = false;
 		// rows per claim: spread the job over the scoring waves this walker can count on (mine = scorers / active walkers: all
 		// of them once its neighbours have finished), never more than R row slots per wave.  Without the two run-time integer
 		// divisions this used to cost on the walker's serial path (rounds 2-6): with x1 = the row slots the job needs,
@@ -817,6 +848,7 @@ struct PoolScorer {
 			const bool filtered = bound < __builtin_inff() && a * x2 > scorers;
 			VSS_LDS_STORE(lds_u32, &box->slots, a * x1 <= scorers ? 1u : a * x2 <= scorers ? 2u : filtered ? PRESCORE_SLOTS : (uint32_t)R);
 			VSS_LDS_STORE(lds_u32, &box->bound_bits, __float_as_uint(filtered ? bound : __builtin_inff()));
+			sent = filtered;
 		} else {
 			VSS_LDS_STORE(lds_u32, &box->slots, a * x1 <= scorers ? 1u : a * x2 <= scorers ? 2u : (uint32_t)R);
 		}
@@ -825,6 +857,7 @@ struct PoolScorer {
 		VSS_LDS_STORE_REL(lds_u64, &box->ticket, (unsigned long long)(uint32_t)n << 32);
 		VSS_TRACE_INC(sp, 16);
 		VSS_TRACE(sp, 17, (uint32_t)n);
+		return sent;
 	}
 	// block until the n rows of job buffer `buf` have been scored.  The walker does not score: it keeps the candidate
 	// list in registers, and a scoring pass on top of that would not fit the 128 registers a 1024-thread workgroup
@@ -853,7 +886,8 @@ struct PoolScorer {
 	}
 	// Hand the n ids of job buffer `buf` (already in LDS) to the scoring waves — through the mailbox, or, for the last walker
 	// of the workgroup, behind the crew's first barrier.  The switch to crew mode happens here, between two jobs.
-	__device__ __forceinline__ void begin(int buf, const RowSpace &sp, float qa2, int n, float bound = __builtin_inff()) const {
+	// Returns whether the job went out with a finite bound (never through a crew).
+	__device__ __forceinline__ bool begin(int buf, const RowSpace &sp, float qa2, int n, float bound = __builtin_inff()) const {
 		if (crew_ok && !crew_on && uniform((int)VSS_LDS_LOAD(lds_u32, walkers_left)) == 1) {
 			crew_on = 1u; // (every lane stores the same value)
 #ifdef VSS_PHASE_TIMERS
@@ -869,9 +903,9 @@ struct PoolScorer {
 				crew->walker = 2u * my_slot + (uint32_t)buf + (level << 8);
 			}
 			lds_barrier(); // the ids (and, per query, the staged query) are in LDS: the crew starts
-			return;
+			return false;
 		}
-		post(buf, sp, n, bound);
+		return post(buf, sp, n, bound);
 	}
 	// block until the rows handed over by begin(buf, .., n) have their distances in LDS
 	__device__ __forceinline__ void end(int buf, const RowSpace &sp, int n) const {
@@ -885,11 +919,12 @@ struct PoolScorer {
 	__device__ __forceinline__ void operator()(const WaveLds &lds, const RowSpace &sp, float qa2, int n, F before_loads
 	                                           VSS_WC_ARG) const {
 		if (n <= 0) {
+			hop_filtered = 0;
 			before_loads();
 			return;
 		}
 		VSS_TICK(tp0);
-		begin(0, sp, qa2, n);
+		hop_filtered = begin(0, sp, qa2, n, hop_bound) ? 1u : 0u; // (hop_bound: +inf unless descend has set it for this hop)
 		VSS_TICK(tpb);
 		VSS_ACC(t_solo_passes, tp0, tpb);
 		before_loads();
@@ -923,6 +958,7 @@ __device__ __forceinline__ uint32_t descend(const GraphView &gv, WaveLds &lds, f
 	ListPrefetch below; // AHEAD: the list of below.slot at below_level, one cell per lane (lists of at most 64 cells)
 	int below_level = -1;
 	const bool can_ahead = AHEAD && gv.M0 <= 64;
+	uint32_t pre_rows = 0, pre_rejected = 0; // Scorer::bounds_descent: rows handed over with a finite bound / that came back +inf
 	for (int level = begin_level; level > end_level; --level) {
 		bool changed;
 		do {
@@ -931,6 +967,7 @@ __device__ __forceinline__ uint32_t descend(const GraphView &gv, WaveLds &lds, f
 			const int n = gather_neighbors<false>(gv, lds, closest, level, have_first, have_first ? below.masked() : EMPTY_SLOT);
 			if constexpr (AHEAD)
 				score.at_level(level);
+			score.at_bound(closest_dist); // (the engine's scoring waves may write +inf for rows proved >= it; a no-op elsewhere)
 			score(lds, gv.sp, qa2, n, [&] {
 				if constexpr (AHEAD) {
 					if (can_ahead && !(below.slot == closest && below_level == level - 1)) {
@@ -942,9 +979,19 @@ __device__ __forceinline__ uint32_t descend(const GraphView &gv, WaveLds &lds, f
 			} VSS_WC_PASS);
 			wc.distances += n;
 			wc.cycles += 1;
+			bool counted = false;
+			if constexpr (Scorer::bounds_descent) {
+				counted = score.hop_filtered != 0;
+				if (counted)
+					pre_rows += (uint32_t)n;
+			}
 			// first occurrence of the minimum, taken only if strictly smaller (index.hpp:3835-3842)
 			for (int off = 0; off < n; off += 64) {
 				const float d = (off + lane < n) ? lds.dist[off + lane] : __builtin_inff();
+				if constexpr (Scorer::bounds_descent) {
+					if (counted) // one ballot per pass of 64
+						pre_rejected += (uint32_t)__popcll(__ballot(off + lane < n && d == __builtin_inff()));
+				}
 				float m = d;
 				m = fminf(m, lane_xor<32>(m));
 				m = fminf(m, lane_xor<16>(m));
@@ -964,6 +1011,10 @@ __device__ __forceinline__ uint32_t descend(const GraphView &gv, WaveLds &lds, f
 	}
 	if constexpr (AHEAD)
 		score.at_level(end_level);
+	if constexpr (Scorer::bounds_descent) {
+		score.at_bound(__builtin_inff()); // (the level search's operator() jobs, if any, carry no bound)
+		score.add_descent_counts(pre_rows, pre_rejected);
+	}
 	return closest;
 }
 
@@ -1677,6 +1728,7 @@ struct SearchArgs {
 	                          // set); host: slots < 2^25, first pass only
 	unsigned long long *phase_ticks; // debug (VSS_PHASE_TIMERS): n_queries x VSS_PHASE_STRIDE
 	PrescoreView prescore;    // row codes for the scoring waves of pipelined launches (codes == nullptr: off, the bound stays +inf)
+	uint32_t prescore_descent; // the descent's jobs carry closest_dist as their bound (search.prescore_descent; needs prescore.codes)
 };
 
 __host__ __device__ inline uint32_t align16(uint32_t x) {
@@ -2067,7 +2119,8 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 	lds.touch_lines = a.touch_lines & TOUCH_LISTS;   // latency-bound launches (host): ListTouch from the first expansion on
 	PoolScorer<MT, NCH, R, PRE> score {&boxes[2 * wave], exit_flag, a.engine_error, walkers_left, (blockDim.x >> 6) - S, crew, wave,
 	                                   ((a.crew & CREW_ON) && !a.spec_active) ? 1u : 0u, (a.crew & CREW_NO_REQUESTS) ? 1u : 0u,
-	                                   (a.crew & CREW_TOUCH) ? 1u : 0u, (PRE && a.prescore.codes) ? 1u : 0u};
+	                                   (a.crew & CREW_TOUCH) ? 1u : 0u, (PRE && a.prescore.codes) ? 1u : 0u,
+	                                   (PRE && a.prescore.codes && a.prescore_descent) ? a.prescore.counters + 2 : nullptr};
 	const SpecBuffers sb {es.ids, es.ids2, es.dist, es.dist2};
 	CandQueue cq;
 	cq.bind(a.cand_buf + gslot * 2 * a.cand_cap, reinterpret_cast<uint32_t *>(a.cand_buf + gslot * 2 * a.cand_cap) + a.cand_cap,

@@ -206,10 +206,11 @@ struct vss_index {
 		bool first_pass = true;
 		double kernel_ms = 0;
 		uint64_t stats[4] = {0, 0, 0, 0};
-		// pre-scoring: the kernels add to d_prescore {rows pre-scored, rejected} and never reset it; a call reports the difference
+		// pre-scoring: the kernels add to d_prescore {rows pre-scored, rejected; the descent's rows handed over with a bound, those
+		// that came back +inf} and never reset it; a call reports the difference
 		DevBuf<unsigned long long> d_prescore;
 		unsigned long long *h_prescore = nullptr; // pinned copy
-		unsigned long long prescore_base[2] = {0, 0};
+		unsigned long long prescore_base[4] = {0, 0, 0, 0};
 		bool prescore_first = false, prescore_used = false; // this call: its first launch filtered / any launch did
 	};
 	// contexts 0 .. EXPLICIT_CTX-1 belong to the caller (vss_search_batch_device_begin/_end; 0 is also the blocking
@@ -246,12 +247,16 @@ struct vss_index {
 	// search.prescore, VSS_SEARCH_PRESCORE: 0 off (no codes held), 1 where it was measured to gain — limits of at most 256, the
 	// 16-wave kernels —, 2 every pipelined launch (the 12-wave kernels of limits 257-512 too: measured SLOWER there)
 	uint32_t search_prescore = 1;
+	// search.prescore_descent, VSS_SEARCH_PRESCORE_DESCENT: the greedy descent's jobs carry closest_dist as their bound in the
+	// launches that filter at all (1, the default); 0: they carry +inf, as every job of the descent did before
+	bool search_prescore_descent = true;
 	DevBuf<uint32_t> d_codes;        // capacity x V dwords
 	DevBuf<RowCodeMeta> d_code_meta; // capacity
 	StaleSlots codes_stale;
 	std::mutex codes_mu;             // searches (shared index lock) encode stale slots one at a time
 	uint64_t codes_refused_capacity = 0; // the capacity at which the device had no room for codes: not tried again until it changes
 	uint64_t last_prescore[4] = {0, 0, 0, 0};
+	uint64_t last_prescore_descent[2] = {0, 0}; // vss_last_search_prescore_descent
 	// rows the instantiations with a pre-scoring path run at: full-wave rows of 2, 3, 4 or 6 chunks per lane
 	bool codes_wanted() const {
 		const uint32_t nch = (G == 64 && V % 64 == 0 && !force_looping) ? V / 64 : 0;
@@ -1101,14 +1106,16 @@ struct vss_index {
 		}
 		if (codes_ready) {
 			if (!c.d_prescore.p) {
-				c.d_prescore.ensure(2, 0, c.stream, 0);
-				HIP_TRY(hipHostMalloc((void **)&c.h_prescore, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-				c.h_prescore[0] = c.h_prescore[1] = 0;
-				c.prescore_base[0] = c.prescore_base[1] = 0;
+				c.d_prescore.ensure(4, 0, c.stream, 0);
+				HIP_TRY(hipHostMalloc((void **)&c.h_prescore, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+				for (int i = 0; i < 4; ++i)
+					c.h_prescore[i] = 0, c.prescore_base[i] = 0;
 			}
 			a.prescore = PrescoreView {d_codes.p, d_code_meta.p, c.d_prescore.p};
 			c.prescore_used = true;
 		}
+		// (the same launches, no others: without codes the kernel ignores it)
+		a.prescore_descent = (a.prescore.codes && search_prescore_descent) ? 1u : 0u;
 		if (c.first_pass)
 			c.prescore_first = a.prescore.codes != nullptr;
 		a.global_hash = nullptr;
@@ -1191,7 +1198,7 @@ struct vss_index {
 			HIP_TRY(hipMemcpyAsync(c.h_stats, c.d_stats.p, c.nq * 8, hipMemcpyDeviceToHost, c.stream));
 		}
 		if (a.prescore.codes)
-			HIP_TRY(hipMemcpyAsync(c.h_prescore, c.d_prescore.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
+			HIP_TRY(hipMemcpyAsync(c.h_prescore, c.d_prescore.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
 	}
 
 	// Pipelined launches (explicit contexts): a launch of the engine occupies every compute unit, so a second one issued
@@ -1461,6 +1468,12 @@ struct vss_index {
 				last_prescore[1] = c.h_prescore[0] - c.prescore_base[0];
 				last_prescore[2] = c.h_prescore[1] - c.prescore_base[1];
 				c.prescore_base[0] = c.h_prescore[0], c.prescore_base[1] = c.h_prescore[1];
+			}
+			last_prescore_descent[0] = last_prescore_descent[1] = 0;
+			if (c.prescore_used) {
+				last_prescore_descent[0] = c.h_prescore[2] - c.prescore_base[2];
+				last_prescore_descent[1] = c.h_prescore[3] - c.prescore_base[3];
+				c.prescore_base[2] = c.h_prescore[2], c.prescore_base[3] = c.h_prescore[3];
 			}
 			last_prescore[3] = d_codes.n * sizeof(uint32_t) + d_code_meta.n * sizeof(RowCodeMeta);
 			timing[0] = c.kernel_ms;
@@ -2472,6 +2485,8 @@ const OptionRule OPTION_RULES[] = {
      },
      "scoring waves reject rows on exact bounds from 8-bit row codes before reading their f32 components: 0 never, 1 at limits of "
      "at most 256, 2 in every pipelined launch"},
+    {"search.prescore_descent", 0, 1, [](vss_index *h, int64_t v) { h->search_prescore_descent = v != 0; },
+     "in launches that filter on row codes, the greedy descent's rows are bounded against its closest distance too"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {
@@ -2551,6 +2566,7 @@ int vss_create(uint64_t dim, int metric, uint64_t M, uint64_t M0, uint64_t efc, 
 	    {"VSS_SEARCH_RETRY_IN_PLACE", "search.retry_in_place"}, {"VSS_HASH_LDS_MAX_LOG2", "search.visited_lds_log2_max"},
 	    {"VSS_VISITED_PER_LIMIT", "search.visited_cells_per_limit"}, {"VSS_PROBE_FLAG_WAIT", "search.probe_flag_wait"},
 	    {"VSS_SEARCH_LIST_LDS", "search.list_lds"}, {"VSS_SEARCH_PRESCORE", "search.prescore"},
+	    {"VSS_SEARCH_PRESCORE_DESCENT", "search.prescore_descent"},
 	};
 	for (const auto &e : ENV_OPTIONS)
 		if (const char *t = getenv(e.env)) {
@@ -2810,6 +2826,14 @@ int vss_last_search_prescore(vss_index *h, uint64_t *out4) {
 	VSS_SHARED(h, {
 		std::lock_guard<std::mutex> lk(h->stats_mu);
 		std::memcpy(out4, h->last_prescore, sizeof h->last_prescore);
+		return VSS_OK;
+	})
+}
+
+int vss_last_search_prescore_descent(vss_index *h, uint64_t *out2) {
+	VSS_SHARED(h, {
+		std::lock_guard<std::mutex> lk(h->stats_mu);
+		std::memcpy(out2, h->last_prescore_descent, sizeof h->last_prescore_descent);
 		return VSS_OK;
 	})
 }

@@ -119,6 +119,9 @@ int vss_set_build_reorder(vss_index *index, int on);
  *                                f32 components (rows of 512 / 768 / 1024 / 1536 dimensions, plain batched searches): 0 never (no
  *                                codes held), 1 at limits of at most 256 (default: where it gains), 2 at limits of 257-512 as well;
  *                                costs a quarter of the vectors' bytes again in device memory; vss_last_search_prescore reports it
+ *   search.prescore_descent (0/1) in the launches that filter on row codes, the greedy descent's rows are bounded too, against the
+ *                                descent's closest distance (default 1; 0: the descent scores every row it gathers);
+ *                                vss_last_search_prescore_descent reports it
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -205,6 +208,10 @@ int vss_last_search_shape(vss_index *index, uint32_t *out8);
  * was computed from their codes, out[2] = rows among them rejected without reading their f32 components (both summed over the
  * call's launches), out[3] = bytes of device memory the index holds for row codes (counted by vss_memory_usage). */
 int vss_last_search_prescore(vss_index *index, uint64_t *out4);
+/* The greedy descent's share of the above (search.prescore_descent; the same rules): out[0] = rows the descent handed to the
+ * scoring waves with a finite bound (its closest distance at that hop), out[1] = rows among them that came back rejected.
+ * Counted by the walkers; both are part of out[1] / out[2] of vss_last_search_prescore as well. */
+int vss_last_search_prescore_descent(vss_index *index, uint64_t *out2);
 /* Kernel timing measured with hipEvents on the index's stream (milliseconds): out[0] = search kernel(s) of the last
  * vss_search_batch* call, out[1] = build phase A kernels, out[2] = build phase B (link) kernels, out[3] = build host
  * wall time, out[4] = build batches, out[5] = build batches re-run with a larger visited set (cumulative since the

@@ -1,10 +1,12 @@
 """Pre-scoring on 8-bit row codes (search.prescore) against the same launches without it.
 The benchmark's rows (1M x 768 cosine by default) under the given index options (the benchmark's M 32 / ef_construction 384 by
 default; pass 16 128 for the reference's defaults); one launch of 20 x 1024 queries per measurement at each ef, with
-search.prescore 0 and 1 (and 2 at limits above 256, which 1 leaves unfiltered), five repeats each: kernel milliseconds (vss_timing), the work counters, the algorithmic bytes over
+search.prescore 0 and 1 (and 2 at limits above 256, which 1 leaves unfiltered; each filtering setting with search.prescore_descent 0
+and 1: the greedy descent's rows unbounded / bounded), five repeats each: kernel milliseconds (vss_timing), the work counters, the algorithmic bytes over
 time as bench.py computes them (n_dist * (4 * dim + 4) + n_expand * (4 + 4 * M0) — no longer bounded by the HBM rate once rows
-are rejected on their codes), and the share of pre-scored rows that were rejected (vss_last_search_prescore).  Answers and
-work counters of the two settings must be identical.
+are rejected on their codes), the share of pre-scored rows that were rejected (vss_last_search_prescore), and the descent's rows
+handed over with a bound and rejected (vss_last_search_prescore_descent).  Answers and work counters of all settings must be
+identical.
     python tools/probe_prescore.py [rows [dim [metric [ef,ef,... [M [ef_construction]]]]]]"""
 import os
 import sys
@@ -51,8 +53,10 @@ torch.cuda.synchronize()
 bad = 0
 for ef in efs:
     ref = None
-    for mode in ((0, 1) if max(ef, K) <= 256 else (0, 1, 2)):  # (1 leaves limits of 257-512 alone, 2 filters there too)
+    # (1 leaves limits of 257-512 alone, 2 filters there too)
+    for mode, descent in ((0, 1), (1, 0), (1, 1)) if max(ef, K) <= 256 else ((0, 1), (1, 1), (2, 0), (2, 1)):
         idx.set_option("search.prescore", mode)
+        idx.set_option("search.prescore_descent", descent)
         ms_all = []
         for r in range(REPEATS + 1):  # (the first one warms up: scratch allocations)
             torch.cuda.synchronize()
@@ -63,6 +67,7 @@ for ef in efs:
         ms_all = ms_all[1:]
         st = idx.last_search_stats()
         pre = idx.last_search_prescore()
+        desc = idx.last_search_prescore_descent()
         gb = (float(st[0]) * (4 * dim + 4) + float(st[1]) * (4 + 4 * M0)) / 1e9
         ms = float(np.median(ms_all))
         ans = [o[j].cpu().numpy().view(np.uint32 if j == 1 else o[j].cpu().numpy().dtype).copy() for o in outs for j in range(3)]
@@ -71,12 +76,13 @@ for ef in efs:
             ref = ans
         same = all(np.array_equal(a, b) for a, b in zip(ref, ans))
         bad += not same
-        print("ef %4d  prescore %d active %d  kernel ms %s  median %8.2f spread %5.2f -> %7.0f queries/s, algorithmic %5.0f GB/s = "
+        print("ef %4d  prescore %d descent %d active %d  kernel ms %s  median %8.2f spread %5.2f -> %7.0f queries/s, algorithmic %5.0f GB/s = "
               "%.3f of 8 TB/s; distances %d expansions %d; pre-scored %d rejected %d = %.3f of pre-scored, %.3f of all rows; "
-              "code bytes %d; identical %s"
-              % (ef, mode, int(pre[0]), " ".join("%.2f" % v for v in ms_all), ms, max(ms_all) - min(ms_all), G * B / ms * 1e3,
+              "descent: %d rows with a bound (%.1f per query), %d rejected = %.3f; code bytes %d; identical %s"
+              % (ef, mode, descent, int(pre[0]), " ".join("%.2f" % v for v in ms_all), ms, max(ms_all) - min(ms_all), G * B / ms * 1e3,
                  gb / (ms / 1e3), gb / (ms / 1e3) / 8000, int(st[0]), int(st[1]), int(pre[1]), int(pre[2]),
-                 int(pre[2]) / max(1, int(pre[1])), int(pre[2]) / max(1, int(st[0])), int(pre[3]), same), flush=True)
+                 int(pre[2]) / max(1, int(pre[1])), int(pre[2]) / max(1, int(st[0])), int(desc[0]), int(desc[0]) / (G * B), int(desc[1]),
+                 int(desc[1]) / max(1, int(desc[0])), int(pre[3]), same), flush=True)
 # The regimes that run mostly in crew mode (one walker per workgroup) and must not get slower: ONE batch per launch, the
 # 204-query host chunk and the single vss_search — wall-clock medians through the blocking calls, option 0 against 1.
 ef0 = efs[0]
