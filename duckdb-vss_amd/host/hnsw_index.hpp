@@ -363,6 +363,9 @@ public:
 	void SetDirty() {
 		is_dirty = true;
 	}
+	void ClearDirty() { // for an owner that serialises Handle() itself (sharded_index.hpp writes G streams into one container)
+		is_dirty = false;
+	}
 	void SyncSize() {
 		index_size = vss_size(index);
 	}

@@ -14,6 +14,18 @@
 //     RCCL library can be loaded, the blocks travel by hipMemcpyPeerAsync instead and vss_merge_topk_device merges them
 //     (VSS_SHARDED_EXCHANGE=peer forces that path).
 //
+//   * Rows that arrive after the build (Construct = the reference's Append / Insert) have ids past the build's range and are
+//     dealt to the shards block-cyclically, 2048 ids at a time (shard_layout.hpp states the rule).  The rule is stateless, so
+//     Delete finds such a row by the same function and nothing but the build's row count has to survive a checkpoint.
+//   * PersistToBlocks writes one container — a 40-byte header (shard_layout.hpp), then every shard's usearch stream behind its
+//     length — through one linked-block writer; LoadFromBlocks checks the header against this index, loads all G streams into
+//     fresh shards built aside and swaps them in only when all G loaded.
+//   * GetStats sums the shards' statistics; SearchBatchFiltered and SearchExactBatch are SearchBatch with another per-shard call.
+//
+// Concurrency is the caller's, as for the reference under DuckDB's IndexLock: Construct, Delete, Compact, PersistToBlocks and
+// LoadFromBlocks are not to overlap each other or a probe, and the probes share one set of exchange buffers, so one probe
+// runs at a time.
+//
 // The multi-process flavour of the same exchange — one rank per GPU — is duckdb-vss_amd/sharded.py + `bench.py --gpus N`.
 // Nothing here computes anything: all arithmetic is behind `vss_*`.
 #pragma once
@@ -24,15 +36,16 @@
 #include <thread>
 
 #include "hnsw_index.hpp"
+#include "shard_layout.hpp"
 
 namespace vss_host {
 
 class ShardedHNSWIndex {
 public:
 	// `devices[g]` = HIP device ordinal of shard g (ordinals may repeat: several shards on one GPU is legal, and is how
-	// the logic is tested on a one-GPU box); `total_rows` fixes the row ranges.
+	// the logic is tested on a one-GPU box); `total_rows` fixes the row ranges (0: created empty, every row is inserted).
 	ShardedHNSWIndex(idx_t vector_size, const OptionMap &options, idx_t total_rows, const std::vector<int> &devices)
-	    : dim(vector_size), n_total(total_rows) {
+	    : dim(vector_size), n_total(total_rows), options(options) {
 		HNSWIndex::VerifyOptions(options);
 		for (size_t g = 0; g != devices.size(); ++g) {
 			auto range = ShardRange(g, devices.size(), total_rows);
@@ -40,6 +53,11 @@ public:
 			s.device = devices[g];
 			s.lo = range.first, s.hi = range.second;
 			s.index = std::make_unique<HNSWIndex>(vector_size, options, s.hi - s.lo, s.device);
+			// the row-id bitmap of a filtered probe is uploaded once per device: shards of one device share a slot
+			for (s.bitmap = 0; s.bitmap != bitmaps.size() && bitmaps[s.bitmap].device != s.device;)
+				s.bitmap++;
+			if (s.bitmap == bitmaps.size())
+				bitmaps.push_back({s.device, nullptr, 0});
 			shards.push_back(std::move(s));
 		}
 		if (shards.empty())
@@ -61,6 +79,11 @@ public:
 			(void)vss_exchange_destroy(c);
 		for (auto &s : shards)
 			s.Release();
+		for (auto &b : bitmaps)
+			if (b.words) {
+				(void)hipSetDevice(b.device);
+				(void)hipFree(b.words);
+			}
 		if (m_dist) {
 			(void)hipSetDevice(shards[0].device);
 			(void)hipFree(m_dist), (void)hipFree(m_keys), (void)hipFree(o_dist), (void)hipFree(o_keys), (void)hipFree(o_cnt);
@@ -68,18 +91,27 @@ public:
 	}
 
 	static std::pair<idx_t, idx_t> ShardRange(idx_t g, idx_t n_shards, idx_t n_total) {
-		return {g * n_total / n_shards, (g + 1) * n_total / n_shards};
+		return shard_layout::ShardRange(g, n_shards, n_total);
 	}
+	// shard_layout.hpp's rule: the row-range owner inside the build's range, block-cyclic past it, negative ids refused
 	idx_t OwnerOf(row_t rowid) const {
-		idx_t g = std::min<idx_t>(shards.size() - 1, (idx_t)rowid * shards.size() / std::max<idx_t>(1, n_total));
-		while (g > 0 && (idx_t)rowid < shards[g].lo)
-			g--;
-		while (g + 1 < shards.size() && (idx_t)rowid >= shards[g].hi)
-			g++;
-		return g;
+		if (rowid < 0)
+			throw InternalException("Row id " + std::to_string(rowid) + " is negative: no shard owns it");
+		return shard_layout::OwnerOf(rowid, shards.size(), n_total);
 	}
 	idx_t ShardCount() const {
 		return shards.size();
+	}
+	// the build's row count: the routing rule's n_total (adopted from the container by LoadFromBlocks)
+	idx_t BuildRows() const {
+		return n_total;
+	}
+	// live rows / statistics of one shard (the tests read how the inserts were dealt out)
+	idx_t ShardRowCount(idx_t g) {
+		return shards.at(g).index->Count();
+	}
+	std::unique_ptr<HNSWIndexStats> ShardStats(idx_t g) {
+		return shards.at(g).index->GetStats();
 	}
 	// "rccl": one all-gather per probe over one communicator per device; "peer": hipMemcpyPeerAsync to the merging device
 	const char *ExchangeKind() const {
@@ -100,22 +132,9 @@ public:
 	// one chunk of the collection: rows are cut into runs owned by the same shard (row ids of a scan chunk are ascending,
 	// so a chunk normally is one run, two at a shard boundary)
 	void BulkAppendChunk(const float *vec_child_data, const row_t *rowid_data, const uint64_t *validity, idx_t count) {
-		for (idx_t i = 0; i < count;) {
-			const idx_t g = OwnerOf(rowid_data[i]);
-			idx_t j = i + 1;
-			while (j < count && OwnerOf(rowid_data[j]) == g)
-				j++;
-			if (!validity) {
-				shards[g].index->BulkAppendChunk(vec_child_data + i * dim, rowid_data + i, nullptr, j - i);
-			} else { // re-base the validity words of the run
-				std::vector<uint64_t> v((j - i + 63) / 64, 0);
-				for (idx_t r = i; r != j; ++r)
-					if ((validity[r >> 6] >> (r & 63)) & 1)
-						v[(r - i) >> 6] |= 1ull << ((r - i) & 63);
-				shards[g].index->BulkAppendChunk(vec_child_data + i * dim, rowid_data + i, v.data(), j - i);
-			}
-			i = j;
-		}
+		for (auto &run : CutIntoRuns(rowid_data, validity, count))
+			shards[run.owner].index->BulkAppendChunk(vec_child_data + run.begin * dim, rowid_data + run.begin,
+			                                         validity ? run.validity.data() : nullptr, run.end - run.begin);
 	}
 	void BulkFinalize() { // the devices do not interact: every shard links its rows at the same time, one host thread each
 		std::vector<std::thread> pool;
@@ -128,6 +147,38 @@ public:
 					errors[g] = e.what();
 				}
 			});
+		for (auto &t : pool)
+			t.join();
+		for (auto &e : errors)
+			if (!e.empty())
+				throw InternalException(e);
+	}
+
+	// ---- HNSWIndex::Construct (Append / Insert) — hnsw_index.cpp:421-479, 519-530 — over the shards: the chunk is cut into
+	// runs with one owner exactly as BulkAppendChunk cuts it, every owner's HNSWIndex::Construct links its runs (it grows the
+	// shard's capacity by NextPowerOfTwo as the reference does), shards that received rows link at the same time, one host
+	// thread each.  Rows keep the chunk's order inside a shard; NULL rows (cleared validity bit) are skipped by the shard.
+	void Construct(const float *vec_child_data, const row_t *rowid_data, const uint64_t *validity, idx_t count) {
+		const auto runs = CutIntoRuns(rowid_data, validity, count); // (a negative id throws here, before any shard changes)
+		std::vector<std::thread> pool;
+		std::vector<std::string> errors(shards.size());
+		for (size_t g = 0; g != shards.size(); ++g) {
+			bool receives = false;
+			for (auto &run : runs)
+				receives = receives || run.owner == g;
+			if (!receives)
+				continue;
+			pool.emplace_back([this, g, &runs, &errors, vec_child_data, rowid_data, validity] {
+				try {
+					for (auto &run : runs)
+						if (run.owner == g)
+							shards[g].index->Construct(vec_child_data + run.begin * dim, rowid_data + run.begin,
+							                           validity ? run.validity.data() : nullptr, run.end - run.begin);
+				} catch (const std::exception &e) {
+					errors[g] = e.what();
+				}
+			});
+		}
 		for (auto &t : pool)
 			t.join();
 		for (auto &e : errors)
@@ -151,6 +202,114 @@ public:
 			s.index->Compact();
 	}
 
+	// ---- HNSWIndex::GetStats (hnsw_index.cpp:292-306) over the shards: count, capacity and approx_size are sums, max_level
+	// is the maximum, and the per-level statistics are summed level by level (a shard with fewer levels adds nothing above
+	// its top; every shard's list has the reference's `i < max_level` length).
+	std::unique_ptr<HNSWIndexStats> GetStats() {
+		auto result = std::make_unique<HNSWIndexStats>();
+		result->max_level = result->count = result->capacity = result->approx_size = 0;
+		for (auto &s : shards) {
+			const auto part = s.index->GetStats();
+			result->max_level = std::max(result->max_level, part->max_level);
+			result->count += part->count;
+			result->capacity += part->capacity;
+			result->approx_size += part->approx_size;
+			if (result->level_stats.size() < part->level_stats.size())
+				result->level_stats.resize(part->level_stats.size(), HNSWLevelStats {0, 0, 0, 0});
+			for (size_t l = 0; l != part->level_stats.size(); ++l) {
+				result->level_stats[l].nodes += part->level_stats[l].nodes;
+				result->level_stats[l].edges += part->level_stats[l].edges;
+				result->level_stats[l].max_edges += part->level_stats[l].max_edges;
+				result->level_stats[l].allocated_bytes += part->level_stats[l].allocated_bytes;
+			}
+		}
+		return result;
+	}
+
+	// ---- persistence (hnsw_index.cpp:532-554, 223-236): ONE container through one linked-block writer, split into blocks of
+	// `block_payload` bytes exactly as HNSWIndex::PersistToBlocks splits its stream — the header of shard_layout.hpp, then
+	// for every shard its stream's length and the stream vss_save writes.
+	bool IsDirty() const {
+		for (auto &s : shards)
+			if (s.index->IsDirty())
+				return true;
+		return false;
+	}
+	std::vector<std::vector<uint8_t>> PersistToBlocks(idx_t block_payload) {
+		if (!block_payload)
+			throw InternalException("Failed to serialize the HNSW index: blocks without payload");
+		BlockWriter w {{}, block_payload, 0};
+		shard_layout::ContainerHeader header;
+		header.n_shards = (uint32_t)shards.size();
+		header.n_total = n_total;
+		header.dim = dim;
+		uint8_t bytes[shard_layout::HEADER_BYTES];
+		shard_layout::Encode(header, bytes);
+		w.Write(bytes, sizeof bytes);
+		for (auto &s : shards) {
+			const uint64_t length = vss_serialized_length(s.index->Handle());
+			uint8_t le[8];
+			shard_layout::PutLE(le, length, 8);
+			w.Write(le, 8);
+			const uint64_t before = w.written;
+			if (vss_save(s.index->Handle(), &BlockWriter::Callback, &w) != VSS_OK)
+				throw InternalException(std::string("Failed to serialize the HNSW index: ") + vss_last_error(s.index->Handle()));
+			if (w.written - before != length)
+				throw InternalException("Failed to serialize the HNSW index: a shard wrote " +
+				                        std::to_string(w.written - before) + " bytes, " + std::to_string(length) + " announced");
+		}
+		for (auto &s : shards)
+			s.index->ClearDirty();
+		return std::move(w.blocks);
+	}
+	// Checks the header against this index before any shard is touched (G = ShardCount(), dim, route block 2048), loads every
+	// stream into a fresh HNSWIndex on its shard's device, and swaps all G in — adopting the container's n_total, hence its
+	// row ranges — only when all G loaded.  A refused or failed load throws and leaves the index exactly as it was.
+	void LoadFromBlocks(const std::vector<std::vector<uint8_t>> &blocks) {
+		BlockReader r {&blocks, 0, 0};
+		uint8_t bytes[shard_layout::HEADER_BYTES];
+		const size_t got = r.Read(bytes, sizeof bytes);
+		shard_layout::ContainerHeader header;
+		const std::string why = shard_layout::Decode(bytes, got, header);
+		if (!why.empty())
+			throw InternalException("Failed to load the sharded HNSW index: " + why);
+		if (header.n_shards != shards.size())
+			throw InternalException("Failed to load the sharded HNSW index: the container holds " +
+			                        std::to_string(header.n_shards) + " shards, this index has " + std::to_string(shards.size()));
+		if (header.dim != dim)
+			throw InternalException("Failed to load the sharded HNSW index: the container's vectors have " +
+			                        std::to_string(header.dim) + " dimensions, this index has " + std::to_string(dim));
+		if (header.route_block != shard_layout::ROUTE_BLOCK)
+			throw InternalException("Failed to load the sharded HNSW index: the container routes inserted rows in blocks of " +
+			                        std::to_string(header.route_block) + ", this code in blocks of " +
+			                        std::to_string(shard_layout::ROUTE_BLOCK));
+		std::vector<std::unique_ptr<HNSWIndex>> fresh;
+		for (size_t g = 0; g != shards.size(); ++g) {
+			const std::string shard_name = "shard " + std::to_string(g);
+			uint8_t le[8];
+			if (r.Read(le, 8) != 8)
+				throw InternalException("Failed to load the sharded HNSW index: the container ends before the stream of " + shard_name);
+			r.limit = shard_layout::GetLE(le, 8);
+			fresh.push_back(std::make_unique<HNSWIndex>(dim, options, 0, shards[g].device));
+			HNSWIndex &index = *fresh.back();
+			if (vss_load(index.Handle(), &BlockReader::Callback, &r) != VSS_OK)
+				throw InternalException("Failed to load the sharded HNSW index: " + shard_name + ": " + vss_last_error(index.Handle()));
+			if (r.limit)
+				throw InternalException("Failed to load the sharded HNSW index: " + shard_name + " left " + std::to_string(r.limit) +
+				                        " bytes of its stream unread");
+			if (index.GetVectorSize() != dim)
+				throw InternalException("Failed to load the sharded HNSW index: " + shard_name + " holds vectors of " +
+				                        std::to_string(index.GetVectorSize()) + " dimensions");
+			index.SyncSize();
+		}
+		n_total = header.n_total;
+		for (size_t g = 0; g != shards.size(); ++g) {
+			const auto range = ShardRange(g, shards.size(), n_total);
+			shards[g].lo = range.first, shards[g].hi = range.second;
+			shards[g].index = std::move(fresh[g]);
+		}
+	}
+
 	// ---- the batched probe (PhysicalHNSWIndexJoin::Execute, hnsw_optimize_join.cpp:111-168) over all shards.
 	// queries = n x dim host floats; out_rowids = n x k (unused cells -1), out_distances optional, out_counts optional.
 	void SearchBatch(const float *queries, idx_t n, idx_t k, idx_t ef, row_t *out_rowids, float *out_distances,
@@ -158,19 +317,79 @@ public:
 		if (!n || !k)
 			return;
 		Ensure(n, k);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_batch_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, keys, dist, s.d_cnt));
+		    },
+		    [&](Shard &s) { Vss(s, vss_search_batch_end(s.index->Handle(), 0)); });
+	}
+
+	// ---- the same probe with a predicate pushed into the traversal (vss_search_batch_filtered_device per shard): a row is
+	// admitted iff it is live and bit `rowid` of `allowed` is set.  The bitmap is over GLOBAL row ids, (n_bits + 63) / 64 host
+	// words; it is uploaded once per device that holds a shard, not once per shard.  Same exchange and merge as SearchBatch.
+	// (The filtered entry point of the engine returns when its shard has answered, so the shards answer one after the other.)
+	void SearchBatchFiltered(const float *queries, idx_t n, idx_t k, idx_t ef, const uint64_t *allowed, idx_t n_bits,
+	                         row_t *out_rowids, float *out_distances, uint32_t *out_counts) {
+		if (!n || !k)
+			return;
+		if (!allowed)
+			throw InternalException("Failed to search the HNSW index: filtered search needs a row-id bitmap");
+		Ensure(n, k);
+		const idx_t words = (n_bits + 63) / 64;
+		for (auto &b : bitmaps) {
+			Hip(hipSetDevice(b.device), "hipSetDevice");
+			if (b.capacity < std::max<idx_t>(words, 1)) {
+				(void)hipFree(b.words);
+				b.words = nullptr, b.capacity = 0;
+				Hip(hipMalloc((void **)&b.words, std::max<idx_t>(words, 1) * sizeof(uint64_t)), "hipMalloc");
+				b.capacity = std::max<idx_t>(words, 1);
+			}
+			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmap");
+		}
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_batch_filtered_device(s.index->Handle(), s.d_q, n, k, ef, bitmaps[s.bitmap].words, n_bits, keys,
+			                                            dist, s.d_cnt));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+	}
+
+	// ---- brute force over every live row of every shard (vss_search_exact_batch_device per shard, the same exchange and
+	// merge): the recall oracle of a sharded index.  Every shard returns its k best rows by (distance, slot); the merge orders
+	// the union by (distance, row id) — so rows at exactly equal distance come back in (distance, row id) order, and where
+	// more rows tie at the k-th distance than fit, which of them a shard hands over is its slot order's choice.
+	void SearchExactBatch(const float *queries, idx_t n, idx_t k, row_t *out_rowids, float *out_distances,
+	                      uint32_t *out_counts) {
+		if (!n || !k)
+			return;
+		Ensure(n, k);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_exact_batch_device(s.index->Handle(), s.d_q, n, k, keys, dist, s.d_cnt));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+	}
+
+private:
+	// One probe: `launch(shard, keys, dist)` starts (or runs) the shard's search of the uploaded batch into the given device
+	// cells, `finish(shard)` returns when they are valid; the answers are exchanged and merged, results to the host.
+	template <class Launch, class Finish>
+	void Probe(const float *queries, idx_t n, idx_t k, row_t *out_rowids, float *out_distances, uint32_t *out_counts,
+	           Launch launch, Finish finish) {
 		const size_t G = shards.size();
 		if (!comms.empty()) {
-			SearchBatchRccl(queries, n, k, ef, out_rowids, out_distances, out_counts);
+			ProbeRccl(queries, n, k, out_rowids, out_distances, out_counts, launch, finish);
 			return;
 		}
 		// 1. the batch goes to every device and every shard starts searching (asynchronous: own stream per shard)
-		UploadThenLaunch(queries, n, [&](Shard &s) {
-			Vss(s, vss_search_batch_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, s.d_keys, s.d_dist, s.d_cnt));
-		});
+		UploadThenLaunch(queries, n, [&](Shard &s) { launch(s, s.d_keys, s.d_dist); });
 		// 2. as each shard finishes, its block travels to the merging device (shard 0's)
 		for (size_t g = 0; g != G; ++g) {
 			Shard &s = shards[g];
-			Vss(s, vss_search_batch_end(s.index->Handle(), 0));
+			finish(s);
 			Hip(hipSetDevice(shards[0].device), "hipSetDevice");
 			Hip(hipMemcpyPeerAsync(m_dist + g * n * k, shards[0].device, s.d_dist, s.device, n * k * sizeof(float),
 			                       shards[0].stream),
@@ -192,21 +411,21 @@ public:
 		Hip(hipStreamSynchronize(shards[0].stream), "sync");
 	}
 
-private:
 	// The probe with every shard on a device of its own: the engine writes a shard's answers straight into its block of
 	// the packed exchange (row ids, then distances), one grouped RCCL all-gather leaves all G blocks on every device, the
 	// merging device (shard 0's) runs the packed k-way merge.
-	void SearchBatchRccl(const float *queries, idx_t n, idx_t k, idx_t ef, row_t *out_rowids, float *out_distances,
-	                     uint32_t *out_counts) {
+	template <class Launch, class Finish>
+	void ProbeRccl(const float *queries, idx_t n, idx_t k, row_t *out_rowids, float *out_distances, uint32_t *out_counts,
+	               Launch launch, Finish finish) {
 		const size_t G = shards.size();
 		const uint64_t block = vss_packed_block_bytes(n, k);
 		UploadThenLaunch(queries, n, [&](Shard &s) {
 			row_t *keys = reinterpret_cast<row_t *>(s.d_block);
 			float *dist = reinterpret_cast<float *>(s.d_block + n * k * sizeof(row_t));
-			Vss(s, vss_search_batch_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, keys, dist, s.d_cnt));
+			launch(s, keys, dist);
 		});
 		for (auto &s : shards)
-			Vss(s, vss_search_batch_end(s.index->Handle(), 0));
+			finish(s);
 		// ONE grouped all-gather (not G gathers to the merging device): the blocks are small — 12 bytes x n x k per shard, 120 KiB
 		// at n = 1024, k = 10 — so the exchange is bound by the latency of its ring steps, which a gather to one root over
 		// point-to-point xGMI links does not have fewer of; and every device ends up able to merge, which is what the
@@ -267,9 +486,89 @@ private:
 			throw InternalException(std::string("Failed to exchange the shard results: ") + vss_exchange_last_error());
 	}
 
+	// rows [begin, end) of a chunk owned by one shard, with the validity words of the run re-based to bit 0 (when the chunk
+	// has a validity mask).  Row ids of a scan chunk are ascending, so a chunk normally is one run, two at a boundary.
+	struct Run {
+		idx_t owner, begin, end;
+		std::vector<uint64_t> validity;
+	};
+	std::vector<Run> CutIntoRuns(const row_t *rowid_data, const uint64_t *validity, idx_t count) const {
+		std::vector<Run> runs;
+		for (idx_t i = 0; i < count;) {
+			const idx_t g = OwnerOf(rowid_data[i]);
+			idx_t j = i + 1;
+			while (j < count && OwnerOf(rowid_data[j]) == g)
+				j++;
+			Run run {g, i, j, {}};
+			if (validity) {
+				run.validity.assign((j - i + 63) / 64, 0);
+				for (idx_t r = i; r != j; ++r)
+					if ((validity[r >> 6] >> (r & 63)) & 1)
+						run.validity[(r - i) >> 6] |= 1ull << ((r - i) & 63);
+			}
+			runs.push_back(std::move(run));
+			i = j;
+		}
+		return runs;
+	}
+
+	// the linked-block writer / reader of HNSWIndex::PersistToBlocks / LoadFromBlocks, shared by the header and all G streams
+	struct BlockWriter {
+		std::vector<std::vector<uint8_t>> blocks;
+		idx_t payload;
+		uint64_t written;
+		void Write(const uint8_t *p, uint64_t size) {
+			written += size;
+			while (size) {
+				if (blocks.empty() || blocks.back().size() == payload)
+					blocks.emplace_back();
+				const idx_t take = std::min<idx_t>(size, payload - blocks.back().size());
+				blocks.back().insert(blocks.back().end(), p, p + take);
+				p += take;
+				size -= take;
+			}
+		}
+		static int Callback(void *ctx, const void *data, uint64_t size) {
+			static_cast<BlockWriter *>(ctx)->Write(static_cast<const uint8_t *>(data), size);
+			return 1;
+		}
+	};
+	struct BlockReader {
+		const std::vector<std::vector<uint8_t>> *blocks;
+		size_t block, off;
+		uint64_t limit = 0; // bytes left of the stream a shard is loading: vss_load may not read past them
+		size_t Read(uint8_t *p, size_t size) { // returns the bytes copied: fewer than `size` where the blocks end
+			size_t done = 0;
+			while (done != size && block < blocks->size()) {
+				const auto &b = (*blocks)[block];
+				const size_t take = std::min<size_t>(size - done, b.size() - off);
+				if (take)
+					std::memcpy(p + done, b.data() + off, take);
+				done += take, off += take;
+				if (off == b.size())
+					block++, off = 0;
+			}
+			return done;
+		}
+		static int Callback(void *ctx, void *data, uint64_t size) {
+			auto &r = *static_cast<BlockReader *>(ctx);
+			if (size > r.limit || r.Read(static_cast<uint8_t *>(data), size) != size)
+				return 0;
+			r.limit -= size;
+			return 1;
+		}
+	};
+
+	struct DeviceBitmap { // the row-id bitmap of a filtered probe on one device
+		int device;
+		uint64_t *words;
+		idx_t capacity;
+	};
+
 	struct Shard {
 		int device = 0;
 		idx_t lo = 0, hi = 0;
+		size_t bitmap = 0; // slot of this shard's device in `bitmaps`
 		std::unique_ptr<HNSWIndex> index;
 		hipStream_t stream = nullptr;
 		float *d_q = nullptr, *d_dist = nullptr;
@@ -328,7 +627,9 @@ private:
 	}
 
 	idx_t dim, n_total;
+	OptionMap options; // what a reload creates its fresh shards with
 	std::vector<Shard> shards;
+	std::vector<DeviceBitmap> bitmaps; // one per distinct device
 	std::vector<vss_comm *> comms; // one per shard when every shard has its own device and RCCL is available, else empty
 	idx_t cap_n = 0, cap_k = 0;
 	float *m_dist = nullptr, *o_dist = nullptr; // on shards[0].device

@@ -26,6 +26,20 @@ def owner_of(rowid, world, n_total):
     return r
 
 
+def route_row(rowid, world, n_total, block=2048):
+    """Rank that holds `rowid`, rows inserted after the build included (host/shard_layout.hpp states the same rule):
+    inside the build's range [0, n_total) the row-range owner, exactly owner_of; past it ((rowid - n_total) // block) %
+    world — block-cyclic in chunks of STANDARD_VECTOR_SIZE ids, so consecutive appended chunks go round the ranks.
+    Stateless: deletes are routed by the same function.  n_total == 0 (created empty) is legal; negative ids are refused."""
+    if rowid < 0:
+        raise ValueError("negative row id %d has no shard" % rowid)
+    if world < 1 or block < 1:
+        raise ValueError("routing needs at least one rank and a route block of at least one row")
+    if rowid < n_total:
+        return owner_of(rowid, world, n_total)
+    return ((rowid - n_total) // block) % world
+
+
 class ShardedTopK:
     """all-gather + merge of per-shard top-k.  `merge(gathered_d, gathered_ids, out_d, out_ids)` is the k-way merge:
     on the GPU it is vss_merge_topk_device (see bench.py); the tests pass a torch reference."""
