@@ -19,6 +19,7 @@
 //   keys      [capacity] i64               DuckDB row ids; VSS_FREE_KEY marks a tombstone
 #pragma once
 #include "wave_primitives.h"
+#include "engine_layout.h"
 #include "prescore_bound.h"
 #include <type_traits>
 
@@ -332,16 +333,6 @@ struct SoloScorer {
 // the engine's mailbox polling (that exchange has to serve several walkers; here there is one).  A row is still reduced
 // by one lane group in wave order, so distances keep their bits whichever wave scores them.
 // ---------------------------------------------------------------------------------------------------------
-constexpr uint32_t CREW_ON = 1u, CREW_TOUCH = 2u, CREW_SPARE_SIMD = 4u, CREW_NO_REQUESTS = 8u; // SearchArgs::crew
-constexpr uint32_t TOUCH_LISTS = 0x100u; // WaveLds::touch_lines / SearchArgs::touch_lines: bits 0-7 row lines, bit 8 ListTouch
-struct TeamBox {
-	int n;     // rows on offer (lds.ids[0..n)), < 0 = the walk is over
-	float qa2; // the query's squared norm (cosine)
-	uint32_t touch_n; // neighbour lists in `cells` whose rows the helpers pull into L2 after the second barrier (RowTouch)
-	uint32_t pad;
-	uint32_t cells[2][64];
-};
-constexpr uint32_t TEAM_BOX_BYTES = (uint32_t)sizeof(TeamBox); // the first bytes of a team's LDS (multiple of 16)
 __device__ __forceinline__ void team_share(const RowSpace &sp, int n, int T, int wave, int &lo, int &hi) {
 	const int RG = 64 >> sp.logG; // rows side by side in one register slot (a power of two): shares are multiples of it
 	const int per = ((n + T - 1) / T + RG - 1) & ~(RG - 1); // (a mask, not `/ RG * RG`: RG is a run-time value — an integer division)
@@ -739,16 +730,6 @@ __device__ __forceinline__ bool pool_score(Mailbox *mb, unsigned long long *scra
 	}
 	return worked;
 }
-
-// LDS header of the search engine (k_search)
-constexpr uint32_t ENGINE_MAX_WALKERS = 8; // (the host keeps to 4 unless told otherwise: vss_engine.hip search_walkers_cap)
-// {exit flag, walkers left, pad} + crew box + mailboxes + 64 scrap cells (the dummy targets of pool_score's all-lane atomics)
-constexpr uint32_t ENGINE_BOXES = 2 * ENGINE_MAX_WALKERS; // two job buffers (and mailboxes) per walker
-constexpr uint32_t ENGINE_CREW_OFFSET = 16;                       // the crew box (16 bytes) follows {exit flag, walkers left, pad}
-constexpr uint32_t ENGINE_SIMD_OFFSET = 32;                       // which SIMD each of the (at most 16) waves runs on, one byte each
-constexpr uint32_t ENGINE_BOX_OFFSET = 48;                        // the mailboxes
-constexpr uint32_t ENGINE_SCRAP_OFFSET = ENGINE_BOX_OFFSET + ENGINE_BOXES * 32;
-constexpr uint32_t ENGINE_HEADER_BYTES = ENGINE_SCRAP_OFFSET + 64 * 8;
 
 constexpr uint32_t POOL_SPIN_LIMIT = 1u << 26; // polls before a waiting wave gives up and traps (never hang the GPU)
 
@@ -1663,14 +1644,6 @@ __device__ __forceinline__ int refine_candidates(const GraphView &gv, WaveLds &l
 // One launch may carry several probe batches (vss_search_multi_device_begin): the queries of batch b are numbered
 // b * batch_size .. and read / answered through the b-th entry of these tables; a plain probe is a launch of one batch.
 constexpr int MAX_COALESCED = 32; // (round 5: 16 -> 32: the drain of a launch is paid once per launch, whatever it carries)
-constexpr int PIPELINED_MAX_REGS = 4; // level_search_pipelined: candidate lists of at most this many registers (limit <= 256) ...
-// ... in a 1024-thread workgroup (128 registers per lane).  Round 5: limits of 257-512 — the 8-register list — run as
-// 768-thread workgroups (12 waves: 170 registers per lane), where the pipeline's state fits next to the list; four walkers
-// and eight scoring waves, which is plenty for expansions that bring four to eight new rows.
-constexpr int WIDE_LIST_THREADS = 768;
-__host__ __device__ constexpr int pipelined_max_regs(int workgroup_threads) {
-	return workgroup_threads <= WIDE_LIST_THREADS ? MAX_LIST_REGS : PIPELINED_MAX_REGS;
-}
 struct SearchArgs {
 	GraphView gv;
 	const float *queries[MAX_COALESCED]; // per batch: batch_size x q_stride floats
@@ -1731,23 +1704,6 @@ struct SearchArgs {
 	uint32_t prescore_descent; // the descent's jobs carry closest_dist as their bound (search.prescore_descent; needs prescore.codes)
 };
 
-__host__ __device__ inline uint32_t align16(uint32_t x) {
-	return (x + 15u) & ~15u;
-}
-
-// dynamic LDS bytes of one wave of the BUILD kernels (shared by host launch code and the kernels)
-__host__ __device__ inline uint32_t wave_lds_bytes(uint32_t hash_log2, uint32_t V, uint32_t list_cap_max,
-                                                   uint32_t cand_cap, bool hash_in_lds = true) {
-	uint32_t b = 0;
-	if (hash_in_lds)
-		b += align16((1u << hash_log2) * 4);
-	b += align16(V * 16) * 2;
-	b += align16(list_cap_max * 4) * 2;
-	b += align16(cand_cap * 4) * 2;
-	b += align16((list_cap_max + 1) * 4) * 2;
-	return b;
-}
-
 __device__ __forceinline__ void bind_visited(VisitedSet &v, uint32_t *table, uint32_t hash_log2) {
 	v.table = table;
 	v.mask = (1u << hash_log2) - 1;
@@ -1788,22 +1744,6 @@ __device__ __forceinline__ void carve_lds(WaveLds &lds, unsigned char *base, uin
 	lds.kept_s = reinterpret_cast<uint32_t *>(p);
 	p += align16((list_cap_max + 1) * 4);
 	lds.kept_d = reinterpret_cast<float *>(p);
-}
-
-// LDS of the search engine: a header {exit flag, walkers still running}, S mailboxes, then per walker
-// [visited set unless in HBM][staged query][ids][distances].
-// stage_cap: cells of the list-merge staging area (>= the search limit for register lists, 0 = none)
-// list_cells: cells of the candidate list kept in LDS (LdsList: two arrays of align16(4 x cells) bytes and the tile tops,
-// lds_list_index.h), 0 = no list here.  The slot stride is computed by the host, the walker, the scoring waves' loop and
-// crew_help: all four pass the same value.
-__host__ __device__ inline uint32_t engine_slot_bytes(uint32_t hash_log2, uint32_t V, uint32_t list_cap_max, bool hash_in_lds,
-                                                      uint32_t stage_cap, uint32_t list_cells = 0) {
-	return (hash_in_lds ? align16((1u << hash_log2) * 4) : 0) + align16(V * 16) + 4 * align16(list_cap_max * 4) +
-	       2 * align16(stage_cap * 4) + lds_list::bytes(list_cells);
-}
-__host__ __device__ inline uint32_t engine_lds_bytes(uint32_t walkers, uint32_t hash_log2, uint32_t V, uint32_t list_cap_max,
-                                                     bool hash_in_lds, uint32_t stage_cap, uint32_t list_cells = 0) {
-	return ENGINE_HEADER_BYTES + walkers * engine_slot_bytes(hash_log2, V, list_cap_max, hash_in_lds, stage_cap, list_cells);
 }
 
 struct EngineSlot {

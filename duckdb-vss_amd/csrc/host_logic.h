@@ -5,6 +5,9 @@
 //   FreeRing        usearch's ring_gt as index_dense uses it for freed slots, wrap quirk included
 //   KeyMap          rowid -> slot (lazy; deletes and duplicate checks)
 //   batch_schedule  how a bulk build is cut into batch-synchronous steps
+//   plan_search_launch  THE one place where a launch of the search engine is decided (shape, visited set, candidate list,
+//                   scoring options, HBM scratch), over the rules before it (visited_set_log2, compact_visited_cells_log2,
+//                   candidate_list_placement, the search shape) and the kernels' own LDS formulas (engine_layout.h)
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -12,6 +15,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "engine_layout.h"
 #include "lds_list_index.h"
 #include "visited_compact.h"
 
@@ -258,7 +262,7 @@ inline uint32_t compact_visited_cells_log2(bool plain_table_fits_lds, bool solo_
 // registers up to 512 entries (WaveList), beyond that LDS (LdsList: capacities of 513-4096 in the workgroup engine) or HBM
 // (MemList: everything else — the solo shape, larger capacities, the builds).
 //   list_cap     capacity of the list in memory: min(limit, rows) for limits above 512, 0 = the list is in registers
-//   slot_bytes   LDS of one walker's slot WITHOUT the list (engine_slot_bytes, hnsw_kernels.h)
+//   slot_bytes   LDS of one walker's slot WITHOUT the list (engine_slot_bytes, engine_layout.h)
 //   walkers_hbm  walkers per workgroup the launch runs with the list in HBM (what it wants, bounded by what fits and by the cap)
 //   walkers_cap  the ceiling on walkers per workgroup that is not a matter of LDS (option / scoring waves that must remain)
 //   mode         search.list_lds: 0 never, 1 automatic — only when the workgroup keeps its walkers, so that no launch loses
@@ -266,9 +270,9 @@ inline uint32_t compact_visited_cells_log2(bool plain_table_fits_lds, bool solo_
 // *walkers_lds (may be null): the walkers that fit with the list in LDS when that is the answer, else 0.
 // ---------------------------------------------------------------------------------------------------------
 constexpr uint32_t LIST_IN_REGISTERS = 0, LIST_IN_LDS = 1, LIST_IN_HBM = 2;
-constexpr uint32_t ENGINE_HEADER_BYTES_HOST = 1072; // = vss::ENGINE_HEADER_BYTES (hnsw_kernels.h; vss_engine.hip asserts it)
+constexpr uint32_t ENGINE_HEADER_BYTES_HOST = ENGINE_HEADER_BYTES; // (the name tests/lds_list_probe.cpp reads it by: the kernels' own now)
 inline uint32_t engine_walkers_that_fit(uint32_t slot_bytes, uint32_t walkers_cap) {
-	return std::min<uint32_t>(walkers_cap, (160u * 1024 - ENGINE_HEADER_BYTES_HOST) / std::max<uint32_t>(1, slot_bytes));
+	return std::min<uint32_t>(walkers_cap, (160u * 1024 - ENGINE_HEADER_BYTES) / std::max<uint32_t>(1, slot_bytes));
 }
 inline uint32_t candidate_list_placement(uint32_t mode, uint64_t list_cap, bool solo_shape, uint32_t slot_bytes, uint32_t walkers_hbm,
                                          uint32_t walkers_cap, uint32_t *walkers_lds = nullptr) {
@@ -296,9 +300,8 @@ inline uint32_t candidate_list_placement(uint32_t mode, uint64_t list_cap, bool 
 //               behind two workgroup barriers instead of the mailboxes — from the first expansion on when a launch has
 //               at most one query per compute unit (wide rows: the one-query probe and the join chunks at 768 dims),
 //               and in the drain of every larger launch
-// and what the latency-bound launches touch ahead (RowTouch: lines per row in bits 0-7; ListTouch: TOUCH_LISTS_BIT).
+// and what the latency-bound launches touch ahead (RowTouch: lines per row in bits 0-7; ListTouch: TOUCH_LISTS).
 // ---------------------------------------------------------------------------------------------------------
-constexpr uint32_t TOUCH_LISTS_BIT = 0x100u;    // = vss::TOUCH_LISTS (hnsw_kernels.h)
 constexpr uint32_t LDS_BYTES_PER_CU = 160u * 1024;
 struct SearchShapePolicy {
 	uint32_t solo_mode = 1;           // 0 never, 1 automatic, 2 always (vss_set_search_solo)
@@ -309,7 +312,6 @@ struct SearchShapePolicy {
 	bool touch_rows = true, touch_lists = true;
 	uint32_t touch_max_queries = 256; // touches cost bandwidth: only launches that cannot be bound by it
 	bool force_looping = false;
-	uint32_t team_box_bytes = 528;    // = vss::TEAM_BOX_BYTES
 	bool crew = true;                 // vss_set_search_crew
 	uint32_t engine_walkers = 0;      // vss_set_search_params: walkers per workgroup forced (0 = from the launch size)
 };
@@ -344,14 +346,10 @@ inline bool wants_solo(const SearchShapePolicy &p, uint32_t n, uint64_t M0, uint
 inline bool one_walker_launch(const SearchShapePolicy &p, uint32_t n) {
 	return p.engine_walkers ? p.engine_walkers == 1 : n <= p.n_cus;
 }
-// one walker per compute unit — the solo shape, or a one-walker launch of the workgroup engine — has the unit's LDS to itself:
-// the visited set may take up to 64 KiB (the rule the engine's launch path and choose_search_shape share)
-inline bool roomy_visited_set(const SearchShapePolicy &p, bool solo, uint32_t n) {
-	return solo || one_walker_launch(p, n);
-}
-// solo_lds_bytes: the dynamic LDS of one solo workgroup for this launch (visited set, staged query, id / distance buffers)
-inline SearchShape choose_search_shape(const SearchShapePolicy &p, uint32_t n, uint64_t M0, uint64_t V, uint64_t G,
-                                       uint32_t solo_lds_bytes) {
+// The shape is settled in two steps, because the LDS of a solo workgroup depends on the visited set and the visited set's size
+// on the shape: first everything that needs no LDS figure — solo or not (the ONE question put to wants_solo per launch), the
+// roomy visited set, and for the workgroup engine the crew and its ListTouch ...
+inline SearchShape search_shape_before_lds(const SearchShapePolicy &p, uint32_t n, uint64_t M0, uint64_t V, uint64_t G) {
 	SearchShape s;
 	s.solo = wants_solo(p, n, M0, V, G);
 	if (!s.solo) {
@@ -359,24 +357,225 @@ inline SearchShape choose_search_shape(const SearchShapePolicy &p, uint32_t n, u
 		// a launch of at most one query per compute unit runs one walker per workgroup: alone from the first expansion on,
 		// i.e. a latency chain — ListTouch as in the solo shape (a 128-byte line per accepted row; RowTouch never: the rows
 		// the engine serves are wide, and pulling 64 of them ahead would swamp the compute unit's fill rate)
-		const bool one_walker = one_walker_launch(p, n);
-		s.roomy = roomy_visited_set(p, false, n);
+		const bool one_walker = s.roomy = one_walker_launch(p, n);
 		if (s.crew && one_walker && n <= p.n_cus && n <= p.touch_max_queries && p.touch_lists)
-			s.touch_lines = TOUCH_LISTS_BIT;
+			s.touch_lines = TOUCH_LISTS;
 		return s;
 	}
-	s.roomy = true;
+	s.roomy = true; // (one walker per compute unit, like a one-walker launch of the engine: the unit's LDS to itself)
+	return s;
+}
+// ... then, for the solo shape only, whether it runs as a team and what it touches ahead.
+// solo_lds_bytes: the dynamic LDS of one solo workgroup for this launch (visited set, staged query, id / distance buffers)
+inline void settle_solo_shape(const SearchShapePolicy &p, SearchShape &s, uint32_t n, uint64_t V, uint64_t G, uint32_t solo_lds_bytes) {
+	if (!s.solo)
+		return;
 	const uint32_t nch = chunks_per_lane(V, G, p.force_looping);
-	s.team = p.team && team_variant_exists(nch) && n <= p.n_cus && solo_lds_bytes + p.team_box_bytes <= LDS_BYTES_PER_CU;
+	s.team = p.team && team_variant_exists(nch) && n <= p.n_cus && solo_lds_bytes + TEAM_BOX_BYTES <= LDS_BYTES_PER_CU;
 	if (n <= p.touch_max_queries) {
 		const uint32_t row_lines = (uint32_t)((V * 16 + 127) / 128);
 		const uint32_t max_lines = s.team ? team_touch_lines_max(nch) : 4u; // (the lone wave: RowTouch<.., 4>)
 		if (p.touch_rows && row_lines <= max_lines)
 			s.touch_lines = row_lines;
 		if (p.touch_lists)
-			s.touch_lines |= TOUCH_LISTS_BIT;
+			s.touch_lines |= TOUCH_LISTS;
 	}
+}
+inline SearchShape choose_search_shape(const SearchShapePolicy &p, uint32_t n, uint64_t M0, uint64_t V, uint64_t G,
+                                       uint32_t solo_lds_bytes) {
+	SearchShape s = search_shape_before_lds(p, n, M0, V, G);
+	settle_solo_shape(p, s, n, V, G, solo_lds_bytes);
 	return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// plan_search_launch — THE one place where a launch of the search engine is decided (no reference counterpart —
+// results never depend on any of it): shape, visited set, candidate list, scoring options and HBM scratch, from what the index
+// and its options contribute (SearchEngineConfig) and what varies per launch (SearchLaunchInput).  Pure: the engine's
+// launch_search_kernel only carries the plan out (allocations, row codes, queue words, events, the launch itself), and the CPU
+// tests replay launches recorded on a GPU through it (tests/test_search_plan.py).
+// ---------------------------------------------------------------------------------------------------------
+struct SearchEngineConfig {
+	SearchShapePolicy policy; // with it: n_cus, search.walkers (engine_walkers) and search.touch_lists (touch_lists)
+	uint64_t M0 = 32, V = 1, G = 1, list_cap_max = 64;
+	uint64_t nodes = 0;          // slots in use (the compact visited set's keys must cover them)
+	uint32_t hash_max_log2 = 10; // a visited set of this size cannot overflow: every node fits below the 7/8 fill limit
+	uint32_t search_waves = 16, search_walkers_cap = 4, search_wgs_per_cu = 1;
+	uint32_t search_spec_active = 0;
+	bool search_pipelined = true, search_wide_lists = true;
+	uint32_t search_list_lds = 1, search_prescore = 1;
+	bool search_prescore_descent = true;
+	bool retry_in_place = true;
+	uint64_t visited_per_limit = 0;                                 // 0 = the sizing rule's own
+	uint32_t hash_lds_max_log2 = 13, hash_lds_max_override = 0;     // the LDS table ceiling with several walkers (0 = no override)
+	bool visited_compact_on = true;
+	uint32_t search_crew_tune = 0;
+};
+struct SearchLaunchInput {
+	uint32_t n = 0;             // queries of this launch (all of the batch, or a retry pass's)
+	uint64_t limit = 0;         // max(k, ef)
+	uint32_t bump = 0, min_hash_log2 = 0; // retry passes: a larger visited set, strictly larger than the one that overflowed
+	uint64_t list_cap = 0;      // capacity of the candidate list in memory, 0 = the list is in registers
+	uint32_t cand_cap = 0;      // cells of the unbounded candidate queue (tomb == 2)
+	uint32_t tomb = 0;          // SearchArgs::tomb
+	bool direct_io = false;     // the host-pointer probe: answers straight into pinned memory
+};
+struct SearchLaunchPlan {
+	// shape
+	bool solo = false, team = false;
+	uint32_t threads = 0, walkers = 0, grid = 0, lds_bytes = 0, regs = 0, nch = 0;
+	// visited set
+	uint32_t hash_log2 = 0;
+	bool hash_in_lds = false;
+	uint32_t visited_compact = 0, stage_cap = 0;
+	uint32_t retry_log2 = 0; // wanted: the engine drops it when the tables cannot be allocated
+	bool roomy = false;
+	// candidate list
+	uint32_t list_place = LIST_IN_REGISTERS, list_lds = 0;
+	// scoring
+	uint32_t pipelined = 0, crew = 0, touch_lines = 0, spec_active = 0;
+	bool wants_prescore = false; // the engine filters where the row codes can be had
+	uint32_t prescore_descent = 0; // (with the filter only)
+	// scratch in HBM, in words (0 = none)
+	uint64_t global_hash = 0, retry_hash = 0, list_buf = 0, cand_buf = 0;
+	uint32_t shape[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // vss_last_search_shape
+};
+inline SearchLaunchPlan plan_search_launch(const SearchEngineConfig &e, const SearchLaunchInput &in) {
+	SearchLaunchPlan a;
+	const SearchShapePolicy &policy = e.policy;
+	const uint32_t n = in.n, n_cus = policy.n_cus, V = (uint32_t)e.V, list_cap_max = (uint32_t)e.list_cap_max;
+	SearchShape shape = search_shape_before_lds(policy, n, e.M0, e.V, e.G);
+	const bool solo = a.solo = shape.solo;
+	// One walker per compute unit — the solo shape, or the workgroup engine on a launch of at most one query per compute
+	// unit — has the unit's LDS to itself: a visited set four times roomier (at most 64 KiB) keeps the probe sequences of
+	// a chunk of 64 ids short — the gather phase is dominated by them
+	const bool roomy = a.roomy = shape.roomy;
+	a.hash_log2 = visited_set_log2(in.limit, in.bump, e.M0, e.list_cap_max,
+	                               e.visited_per_limit ? e.visited_per_limit : search_cells_per_limit(in.limit), e.hash_max_log2);
+	if (roomy && a.hash_log2 <= e.hash_lds_max_log2)
+		a.hash_log2 = std::min<uint32_t>({a.hash_log2 + 2, 14u, std::max(a.hash_log2, e.hash_max_log2)});
+	// a retry after a visited-set overflow must get a LARGER table than the one that overflowed, whatever shape and
+	// enlargement the pass before had (min_hash_log2 = that table's size + 1; nothing exceeds "every node fits")
+	a.hash_log2 = std::max(a.hash_log2, std::min(in.min_hash_log2, e.hash_max_log2));
+	// LDS or HBM: tables up to 32 KiB stay in LDS (four walkers per workgroup).  (Measured and not kept: 64-KiB tables in LDS
+	// with two walkers — 0.77 against 0.60 of the HBM peak at 12.5M x 1536 / ef 192, but 0.45 against 0.56 at 768 dims and
+	// 0.51 against 0.63 on the configs[4] shard at ef 480: two walkers do not feed a compute unit once expansions are thin.)
+	const uint32_t lds_table_log2 = roomy ? 14u : (e.hash_lds_max_override ? e.hash_lds_max_override : e.hash_lds_max_log2);
+	bool hash_in_lds = a.hash_log2 <= lds_table_log2;
+	// Limits of 257-512 — the 8-register list's instantiation — whose 32-bit table would go to HBM take the COMPACT exact
+	// form instead (16-bit cells: tag + displacement, wave_primitives.h) over the largest table LDS admits: twice the cells
+	// in the same bytes, every probe an LDS round trip instead of an L2 / memory one (2M x 1536 at ef 480 / 320: 0.52 -> 0.60
+	// / 0.59 -> 0.68 of the HBM peak, answers and work counters identical: profiles/r04_compact_visited_set_*.txt).  Slots
+	// must fit 24 bits; first pass only — a query that overflows it (too many visits, or a displacement beyond its bits)
+	// is re-run with the plain table like any other overflow.  vss_set_search_visited_set(index, 0, ..) turns it off for A/B.
+	// (the rule: compact_visited_cells_log2 above)
+	a.visited_compact = e.visited_compact_on ? compact_visited_cells_log2(hash_in_lds, solo, !in.list_cap, in.limit, e.nodes,
+	                                                                      !in.bump && !in.min_hash_log2, lds_table_log2)
+	                                         : 0u;
+	if (a.visited_compact) {
+		a.hash_log2 = lds_table_log2;
+		hash_in_lds = true;
+	}
+	a.hash_in_lds = hash_in_lds;
+	// walkers per workgroup: as many as the batch needs to cover every compute unit once, as many as LDS admits
+	uint32_t waves = std::max<uint32_t>(2, std::min<uint32_t>(e.search_waves, 16));
+	// the accept phase of an expansion in the shadow of the successor's row loads (level_search_pipelined): plain searches
+	// with a register list over neighbour lists of at most 64 cells.  Limits of 257-512 (the 8-register list) are pipelined
+	// in 12-wave workgroups only (170 registers per lane: k_search<.., WIDE_LIST_THREADS>, round 5) — four walkers and eight
+	// scoring waves; vss_set_search_wide_lists(0) keeps them in 16 waves and the plain order (round 4; A/B)
+	const bool wide_limit = in.limit > 64u * PIPELINED_MAX_REGS; // (beyond the 4-register list: walker-bound, two waves per walker)
+	const bool can_pipeline = e.search_pipelined && !solo && !in.tomb && !in.list_cap && list_cap_max <= 64;
+	const bool wide_list = can_pipeline && e.search_wide_lists && wide_limit;
+	if (wide_list)
+		waves = std::min<uint32_t>(waves, WIDE_LIST_THREADS / 64);
+	a.pipelined = (can_pipeline && (wide_list || !wide_limit)) ? 1u : 0u;
+	// (rounds 2-5 staged the batched list merge here — `limit` cells per walker; the blocked list of round 6 merges nothing.
+	//  What is left is four words per walker of the 8-register list's kernels: where its visited set moves when it outgrows
+	//  LDS, WaveLds::spill_box)
+	const bool wide_register_list = !solo && !in.list_cap && wide_limit; // (k_search<.., 8, ..>)
+	a.stage_cap = wide_register_list ? 4u : 0u;
+	const uint32_t slot_bytes = engine_slot_bytes(a.hash_log2, V, list_cap_max, hash_in_lds, a.stage_cap);
+	const uint32_t walkers_cap = std::min<uint32_t>(policy.engine_walkers ? ENGINE_MAX_WALKERS : e.search_walkers_cap, waves - 1);
+	uint32_t S = policy.engine_walkers ? policy.engine_walkers : (n + n_cus - 1) / n_cus;
+	S = std::max<uint32_t>(1, std::min(S, engine_walkers_that_fit(slot_bytes, walkers_cap)));
+	// Limits beyond the register lists: the candidate list in the walkers' slots of LDS (capacities of 513-4096; LdsList) where
+	// the workgroup keeps the walkers it has with the list in HBM — no launch loses occupancy to it —, else in HBM as before
+	// (the rule: candidate_list_placement above; search.list_lds = 0 is the path without it, exactly).  Retry passes come
+	// through here like every launch.
+	uint32_t walkers_lds = 0;
+	a.list_place = candidate_list_placement(e.search_list_lds, in.list_cap, solo, slot_bytes, S, walkers_cap, &walkers_lds);
+	const bool list_in_lds = a.list_place == LIST_IN_LDS;
+	a.list_lds = list_in_lds ? (uint32_t)in.list_cap : 0u;
+	if (list_in_lds)
+		S = std::min(S, walkers_lds); // (search.list_lds = 2 only: the automatic rule never takes a walker away)
+	const auto engine_lds = [&](uint32_t walkers) {
+		return engine_lds_bytes(walkers, a.hash_log2, V, list_cap_max, hash_in_lds, a.stage_cap, a.list_lds);
+	};
+	// workgroups per compute unit: one 16-wave workgroup — or, with fewer waves per workgroup (vss_set_search_params), as
+	// many as the waves and the LDS admit, so that a workgroup of the NEXT launch can move in beside one that still drains
+	// (VSS_SEARCH_WGS_PER_CU caps it, default 1.  Measured: two 8-wave workgroups of 2 walkers + 6 scoring waves per compute
+	// unit run every regime at the rate of one 16-wave workgroup of 4 + 12 — profiles/r04_two_workgroups_per_compute_unit_no_gain.txt)
+	uint32_t wgs_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(16u / waves, LDS_BYTES_PER_CU / std::max<uint32_t>(1, engine_lds(S))));
+	wgs_per_cu = std::min(wgs_per_cu, e.search_wgs_per_cu);
+	uint32_t grid = std::min<uint32_t>(n_cus * wgs_per_cu, (n + S - 1) / S);
+	const uint32_t solo_lds = wave_lds_bytes(a.hash_log2, V, list_cap_max, a.stage_cap, hash_in_lds);
+	if (solo) { // one single-wave workgroup per query in flight, as many per compute unit as LDS admits (at most 8)
+		S = 1;
+		grid = std::min<uint32_t>(n, n_cus * std::max<uint32_t>(1, std::min<uint32_t>(8, LDS_BYTES_PER_CU / solo_lds)));
+	}
+	// a query that outgrows its LDS-resident set is repeated by its walker, in the same launch, over a table in HBM (2^17
+	// cells = 512 KiB per walker, or what holds the whole index if that is less) — where overflows are a per-cent matter:
+	// limits of 257-512, the compact form (the only instantiations that carry the code: k_search<.., 8, ..>)
+	if (e.retry_in_place && wide_register_list && hash_in_lds) {
+		const uint32_t have_log2 = a.visited_compact ? compact_visited::cells_log2_of(a.visited_compact) : a.hash_log2;
+		const uint32_t want_log2 = std::min<uint32_t>(17u, e.hash_max_log2);
+		if (want_log2 > have_log2)
+			a.retry_log2 = want_log2;
+	}
+	// scratch in HBM scales with the resident walkers: bound it (retry passes with very large tables run fewer at a time)
+	// (the retry tables count: ADVICE r05 — 512 MiB per context that runs such limits went unbudgeted)
+	const uint64_t per_walker = (hash_in_lds ? 0 : (4ull << a.hash_log2)) + (list_in_lds ? 0 : 8ull * in.list_cap) +
+	                            (in.tomb == 2 ? 8ull * in.cand_cap : 0) + (a.retry_log2 ? (4ull << a.retry_log2) : 0);
+	const uint64_t budget = 16ull << 30;
+	while (per_walker * grid * S > budget && (grid > 1 || S > 1)) {
+		if (S > 1)
+			S--;
+		else
+			grid = (grid + 1) / 2;
+	}
+	a.walkers = S;
+	a.grid = grid;
+	const uint64_t resident = (uint64_t)grid * S;
+	a.global_hash = hash_in_lds ? 0 : resident << a.hash_log2;
+	a.retry_hash = a.retry_log2 ? resident << a.retry_log2 : 0;
+	a.list_buf = (in.list_cap && !list_in_lds) ? resident * 2 * in.list_cap : 0;
+	a.cand_buf = in.tomb == 2 ? resident * 2 * in.cand_cap : 0;
+	// one expansion of look-ahead while scoring waves are idle (lists of at most 64 cells: one cell per lane)
+	a.spec_active = (!in.tomb && !solo && list_cap_max <= 64) ? e.search_spec_active : 0;
+	// latency-bound launches of the solo shape (at most one query per compute unit): pull the rows the cached lists name
+	// (RowTouch: by the team's helpers, or by the lone wave for rows of at most four 128-byte lines) and the lists of the
+	// rows being accepted (ListTouch) into L2 ahead of time.  Costs bandwidth, so never for launches that could be bound by it.
+	// A team (helper waves on the compute unit's other SIMDs score a share of every expansion's rows) while every query
+	// of the launch still gets a compute unit of its own; its job box takes the first bytes of the workgroup's LDS
+	settle_solo_shape(policy, shape, n, e.V, e.G, solo_lds);
+	a.team = shape.team;
+	a.touch_lines = shape.touch_lines;
+	// the last walker of a workgroup runs its scoring waves as a crew (two barriers per expansion instead of the mailbox
+	// exchange): from the start when S = 1, in the drain of a larger launch otherwise
+	a.crew = shape.crew ? (CREW_ON | ((policy.touch_lists && list_cap_max <= 64) ? CREW_TOUCH : 0u) | e.search_crew_tune) : 0u;
+	// pre-scoring on row codes (search.prescore): the pipelined level search over the mailbox exchange only; the pinned
+	// small-batch probe (latency-bound: crews) is left alone.  Limits above 256 only when asked for (search.prescore = 2)
+	a.wants_prescore = a.pipelined && !in.direct_io && (e.search_prescore == 2 || !wide_limit);
+	// (the same launches, no others: without codes the kernel ignores it)
+	a.prescore_descent = (a.wants_prescore && e.search_prescore_descent) ? 1u : 0u;
+	a.nch = chunks_per_lane(e.V, e.G, policy.force_looping);
+	a.regs = (uint32_t)((in.limit + 63) / 64);
+	a.lds_bytes = solo ? solo_lds + (a.team ? TEAM_BOX_BYTES : 0u) : engine_lds(S);
+	a.threads = solo ? (a.team ? 64 * VSS_TEAM_WAVES : 64) : 64 * waves;
+	const uint32_t words[8] = {a.threads, S, grid, a.lds_bytes, a.list_place, hash_in_lds ? (a.visited_compact ? 1u : 0u) : 2u,
+	                           solo ? 1u : 0u, 0u};
+	std::copy(words, words + 8, a.shape);
+	return a;
 }
 
 } // namespace host

@@ -1,5 +1,5 @@
 // lds_list_index.h — the index arithmetic of the candidate list kept in LDS (wave_primitives.h: LdsList), shared by the device
-// code, the host (hnsw_kernels.h: the bytes a walker's slot sets aside for it; host_logic.h: when a launch takes it) and
+// code, the host (engine_layout.h: the bytes a walker's slot sets aside for it; host_logic.h: when a launch takes it) and
 // tests/lds_list_probe.cpp: a lane-by-lane model of the list checked against std::vector on the CPU.  No reference counterpart:
 // usearch's sorted_buffer_gt (index.hpp:783-917) is one array searched by bisection.
 //

@@ -31,11 +31,7 @@
 using namespace vss;
 using namespace vss::host;
 
-// the constants host_logic.h restates for the CPU tests are the kernels'
-static_assert(host::TOUCH_LISTS_BIT == TOUCH_LISTS, "ListTouch bit");
-static_assert(host::ENGINE_HEADER_BYTES_HOST == ENGINE_HEADER_BYTES, "LDS header of the search engine");
-static_assert(lds_list::MIN_CELLS == 64 * MAX_LIST_REGS + 1, "the LDS list starts where the register lists end");
-static_assert(host::SearchShapePolicy().team_box_bytes == TEAM_BOX_BYTES, "team box size");
+// the one rule host_logic.h still restates for the CPU tests (team_touch_lines_max) is the kernels'
 static_assert(team_touch_max_lines(0) == 8 && team_touch_max_lines(1) == 8 && team_touch_max_lines(3) == 24, "helper touch window");
 
 namespace {
@@ -658,18 +654,23 @@ struct vss_index {
 	// wave pulls a whole level-0 list about as fast as it could be spread over scoring waves; as teams (helper waves behind
 	// workgroup barriers) the shape wins while every query gets a compute unit of its own (1M x 128: 404 against 737 us for
 	// 256 queries, profiles/r03t_engine_shapes_by_batch_1m128_touch_threshold.txt).
-	host::SearchShapePolicy shape_policy() const {
-		host::SearchShapePolicy p;
+	// This is everything the index and its options contribute to a launch's plan (host_logic.h: plan_search_launch decides).
+	host::SearchEngineConfig search_engine_config() const {
+		host::SearchEngineConfig e;
+		host::SearchShapePolicy &p = e.policy;
 		p.solo_mode = search_solo, p.solo_max_queries = solo_max_queries, p.solo_max_bytes = solo_max_bytes;
 		p.team = search_team, p.n_cus = n_cus;
 		p.touch_rows = search_touch_rows, p.touch_lists = search_touch_lists, p.touch_max_queries = search_touch_max_queries;
 		p.force_looping = force_looping;
-		p.team_box_bytes = TEAM_BOX_BYTES;
 		p.crew = search_crew, p.engine_walkers = search_walkers;
-		return p;
-	}
-	bool use_solo(uint32_t n) const {
-		return host::wants_solo(shape_policy(), n, M0, V, G);
+		e.M0 = M0, e.V = V, e.G = G, e.list_cap_max = list_cap_max(), e.nodes = count, e.hash_max_log2 = hash_max_log2();
+		e.search_waves = search_waves, e.search_walkers_cap = search_walkers_cap, e.search_wgs_per_cu = search_wgs_per_cu;
+		e.search_spec_active = search_spec_active, e.search_pipelined = search_pipelined, e.search_wide_lists = search_wide_lists;
+		e.search_list_lds = search_list_lds, e.search_prescore = search_prescore, e.search_prescore_descent = search_prescore_descent;
+		e.retry_in_place = retry_in_place, e.visited_per_limit = visited_per_limit;
+		e.hash_lds_max_log2 = HASH_LDS_MAX_LOG2, e.hash_lds_max_override = hash_lds_max_override;
+		e.visited_compact_on = visited_compact_on, e.search_crew_tune = search_crew_tune;
+		return e;
 	}
 	// searches over tombstones / a predicate start with the register queue (VSS_SEARCH_REG_QUEUE=0: always the unbounded one)
 	bool search_reg_queue = true;
@@ -979,125 +980,17 @@ struct vss_index {
 	void launch_search_kernel(SearchCtx &c, uint32_t n) {
 		SearchArgs &a = c.args;
 		a.n_queries = n;
-		const host::SearchShapePolicy policy = shape_policy();
-		const bool solo = host::wants_solo(policy, n, M0, V, G);
-		// One walker per compute unit — the solo shape, or the workgroup engine on a launch of at most one query per compute
-		// unit — has the unit's LDS to itself: a visited set four times roomier (at most 64 KiB) keeps the probe sequences of
-		// a chunk of 64 ids short — the gather phase is dominated by them
-		const bool roomy = host::roomy_visited_set(policy, solo, n); // (host_logic.h: the rule choose_search_shape reports)
-		a.hash_log2 = hash_log2_for(c.limit, c.bump, host::search_cells_per_limit(c.limit));
-		if (roomy && a.hash_log2 <= HASH_LDS_MAX_LOG2)
-			a.hash_log2 = std::min<uint32_t>({a.hash_log2 + 2, 14u, std::max(a.hash_log2, hash_max_log2())});
-		// a retry after a visited-set overflow must get a LARGER table than the one that overflowed, whatever shape and
-		// enlargement the pass before had (c.min_hash_log2 = that table's size + 1; nothing exceeds "every node fits")
-		a.hash_log2 = std::max(a.hash_log2, std::min(c.min_hash_log2, hash_max_log2()));
-		// LDS or HBM: tables up to 32 KiB stay in LDS (four walkers per workgroup).  (Measured and not kept: 64-KiB tables in LDS
-		// with two walkers — 0.77 against 0.60 of the HBM peak at 12.5M x 1536 / ef 192, but 0.45 against 0.56 at 768 dims and
-		// 0.51 against 0.63 on the configs[4] shard at ef 480: two walkers do not feed a compute unit once expansions are thin.)
-		const uint32_t hash_lds_max = hash_lds_max_override ? hash_lds_max_override : HASH_LDS_MAX_LOG2;
-		bool hash_in_lds = a.hash_log2 <= (roomy ? 14u : hash_lds_max);
-		// Limits of 257-512 — the 8-register list's instantiation — whose 32-bit table would go to HBM take the COMPACT exact
-		// form instead (16-bit cells: tag + displacement, wave_primitives.h) over the largest table LDS admits: twice the cells
-		// in the same bytes, every probe an LDS round trip instead of an L2 / memory one (2M x 1536 at ef 480 / 320: 0.52 -> 0.60
-		// / 0.59 -> 0.68 of the HBM peak, answers and work counters identical: profiles/r04_compact_visited_set_*.txt).  Slots
-		// must fit 24 bits; first pass only — a query that overflows it (too many visits, or a displacement beyond its bits)
-		// is re-run with the plain table like any other overflow.  vss_set_search_visited_set(index, 0, ..) turns it off for A/B.
-		// (the rule: host_logic.h, CPU-tested)
-		a.visited_compact = 0;
-		{
-			const uint32_t lds_table_log2 = roomy ? 14u : hash_lds_max;
-			const uint32_t cells_log2 = visited_compact_on ? host::compact_visited_cells_log2(hash_in_lds, solo, !c.list_cap, c.limit, count,
-			                                                                                  !c.bump && !c.min_hash_log2, lds_table_log2)
-			                                                : 0u;
-			if (cells_log2) {
-				a.hash_log2 = lds_table_log2;
-				a.visited_compact = cells_log2;
-				hash_in_lds = true;
-			}
-		}
-		// walkers per workgroup: as many as the batch needs to cover every compute unit once, as many as LDS admits
-		uint32_t waves = std::max<uint32_t>(2, std::min<uint32_t>(search_waves, 16));
-		// the accept phase of an expansion in the shadow of the successor's row loads (level_search_pipelined): plain searches
-		// with a register list over neighbour lists of at most 64 cells.  Limits of 257-512 (the 8-register list) are pipelined
-		// in 12-wave workgroups only (170 registers per lane: k_search<.., WIDE_LIST_THREADS>, round 5) — four walkers and eight
-		// scoring waves; vss_set_search_wide_lists(0) keeps them in 16 waves and the plain order (round 4; A/B)
-		const bool can_pipeline = search_pipelined && !solo && !a.tomb && !c.list_cap && list_cap_max() <= 64;
-		const bool wide_list = can_pipeline && search_wide_lists && c.limit > 64u * PIPELINED_MAX_REGS;
-		if (wide_list)
-			waves = std::min<uint32_t>(waves, WIDE_LIST_THREADS / 64);
-		// (rounds 2-5 staged the batched list merge here — `limit` cells per walker; the blocked list of round 6 merges nothing.
-		//  What is left is four words per walker of the 8-register list's kernels: where its visited set moves when it outgrows
-		//  LDS, WaveLds::spill_box)
-		a.stage_cap = (!solo && !c.list_cap && c.limit > 64u * PIPELINED_MAX_REGS) ? 4u : 0u;
-		const uint32_t slot_bytes = engine_slot_bytes(a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap);
-		const uint32_t walkers_cap = std::min<uint32_t>(search_walkers ? ENGINE_MAX_WALKERS : search_walkers_cap, waves - 1);
-		uint32_t s_max = host::engine_walkers_that_fit(slot_bytes, walkers_cap);
-		uint32_t S = search_walkers ? search_walkers : (n + n_cus - 1) / n_cus;
-		S = std::max<uint32_t>(1, std::min(S, s_max));
-		// Limits beyond the register lists: the candidate list in the walkers' slots of LDS (capacities of 513-4096; LdsList) where
-		// the workgroup keeps the walkers it has with the list in HBM — no launch loses occupancy to it —, else in HBM as before
-		// (the rule: host_logic.h, CPU-tested; search.list_lds = 0 is the path without it, exactly).  Retry passes come through
-		// here like every launch.
-		uint32_t walkers_lds = 0;
-		const uint32_t list_place = host::candidate_list_placement(search_list_lds, c.list_cap, solo, slot_bytes, S, walkers_cap, &walkers_lds);
-		const bool list_in_lds = list_place == host::LIST_IN_LDS;
-		a.list_lds = list_in_lds ? (uint32_t)c.list_cap : 0u;
-		if (list_in_lds)
-			S = std::min(S, walkers_lds); // (search.list_lds = 2 only: the automatic rule never takes a walker away)
-		// workgroups per compute unit: one 16-wave workgroup — or, with fewer waves per workgroup (vss_set_search_params), as
-		// many as the waves and the LDS admit, so that a workgroup of the NEXT launch can move in beside one that still drains
-		// (VSS_SEARCH_WGS_PER_CU caps it, default 1.  Measured: two 8-wave workgroups of 2 walkers + 6 scoring waves per compute
-		// unit run every regime at the rate of one 16-wave workgroup of 4 + 12 — profiles/r04_two_workgroups_per_compute_unit_no_gain.txt)
-		uint32_t wgs_per_cu = std::max<uint32_t>(1, std::min<uint32_t>(16u / waves, (160u * 1024) /
-		                                             std::max<uint32_t>(1, engine_lds_bytes(S, a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap, a.list_lds))));
-		wgs_per_cu = std::min(wgs_per_cu, search_wgs_per_cu);
-		uint32_t grid = std::min<uint32_t>(n_cus * wgs_per_cu, (n + S - 1) / S);
-		const uint32_t solo_lds = wave_lds_bytes(a.hash_log2, V, a.list_cap_max, a.stage_cap, hash_in_lds);
-		if (solo) { // one single-wave workgroup per query in flight, as many per compute unit as LDS admits (at most 8)
-			S = 1;
-			grid = std::min<uint32_t>(n, n_cus * std::max<uint32_t>(1, std::min<uint32_t>(8, 160u * 1024 / solo_lds)));
-		}
-		// scratch in HBM scales with the resident walkers: bound it (retry passes with very large tables run fewer at a time)
-		// a query that outgrows its LDS-resident set is repeated by its walker, in the same launch, over a table in HBM (2^17
-		// cells = 512 KiB per walker, or what holds the whole index if that is less) — where overflows are a per-cent matter:
-		// limits of 257-512, the compact form (the only instantiations that carry the code: k_search<.., 8, ..>)
-		uint32_t retry_want_log2 = 0;
-		if (retry_in_place && !solo && hash_in_lds && !c.list_cap && c.limit > 64u * PIPELINED_MAX_REGS) { // (the 8-register list's kernels)
-			const uint32_t have_log2 = a.visited_compact ? compact_visited::cells_log2_of(a.visited_compact) : a.hash_log2;
-			const uint32_t want_log2 = std::min<uint32_t>(17u, hash_max_log2());
-			if (want_log2 > have_log2)
-				retry_want_log2 = want_log2;
-		}
-		// (the retry tables count: ADVICE r05 — 512 MiB per context that runs such limits went unbudgeted)
-		const uint64_t per_walker = (hash_in_lds ? 0 : (4ull << a.hash_log2)) + (list_in_lds ? 0 : 8ull * c.list_cap) + (a.tomb == 2 ? 8ull * c.cand_cap : 0) +
-		                            (retry_want_log2 ? (4ull << retry_want_log2) : 0);
-		const uint64_t budget = 16ull << 30;
-		while (per_walker * grid * S > budget && (grid > 1 || S > 1)) {
-			if (S > 1)
-				S--;
-			else
-				grid = (grid + 1) / 2;
-		}
-		a.walkers = S;
-		// one expansion of look-ahead while scoring waves are idle (lists of at most 64 cells: one cell per lane)
-		a.spec_active = (!a.tomb && !solo && list_cap_max() <= 64) ? search_spec_active : 0;
-		// latency-bound launches of the solo shape (at most one query per compute unit): pull the rows the cached lists name
-		// (RowTouch: by the team's helpers, or by the lone wave for rows of at most four 128-byte lines) and the lists of the
-		// rows being accepted (ListTouch) into L2 ahead of time.  Costs bandwidth, so never for launches that could be bound by it.
-		const host::SearchShape shape = host::choose_search_shape(policy, n, M0, V, G, solo_lds);
-		a.touch_lines = shape.touch_lines;
-		// the last walker of a workgroup runs its scoring waves as a crew (two barriers per expansion instead of the mailbox
-		// exchange): from the start when S = 1, in the drain of a larger launch otherwise
-		a.crew = shape.crew ? (CREW_ON | ((search_touch_lists && list_cap_max() <= 64) ? CREW_TOUCH : 0u) | search_crew_tune) : 0u;
-		// the accept phase of an expansion in the shadow of the successor's row loads (level_search_pipelined): plain searches
-		// with a register list over neighbour lists of at most 64 cells
-		a.pipelined = (can_pipeline && (wide_list || c.limit <= 64u * PIPELINED_MAX_REGS)) ? 1u : 0u;
-		// pre-scoring on row codes (search.prescore): the pipelined level search over the mailbox exchange only; the pinned
-		// small-batch probe (latency-bound: crews) is left alone
+		host::SearchLaunchInput in;
+		in.n = n, in.limit = c.limit, in.bump = c.bump, in.min_hash_log2 = c.min_hash_log2;
+		in.list_cap = c.list_cap, in.cand_cap = c.cand_cap, in.tomb = a.tomb, in.direct_io = c.direct_io;
+		const host::SearchLaunchPlan plan = host::plan_search_launch(search_engine_config(), in);
+		a.hash_log2 = plan.hash_log2, a.visited_compact = plan.visited_compact, a.stage_cap = plan.stage_cap;
+		a.list_lds = plan.list_lds, a.walkers = plan.walkers;
+		a.spec_active = plan.spec_active, a.touch_lines = plan.touch_lines, a.crew = plan.crew, a.pipelined = plan.pipelined;
+		// pre-scoring on row codes (search.prescore), where the plan wants it and the codes can be had
 		a.prescore = PrescoreView {nullptr, nullptr, nullptr};
 		bool codes_ready = false;
-		const bool wide_limit = c.limit > 64u * PIPELINED_MAX_REGS; // (the 8-register list: walker-bound, two waves per walker)
-		if (a.pipelined && !solo && !c.direct_io && (search_prescore == 2 || !wide_limit)) {
+		if (plan.wants_prescore) {
 			try {
 				codes_ready = ensure_codes(c.stream, false);
 			} catch (const HipError &) { // (optional derived data: the search runs unfiltered, the slots stay marked)
@@ -1115,29 +1008,30 @@ struct vss_index {
 			c.prescore_used = true;
 		}
 		// (the same launches, no others: without codes the kernel ignores it)
-		a.prescore_descent = (a.prescore.codes && search_prescore_descent) ? 1u : 0u;
+		a.prescore_descent = a.prescore.codes ? plan.prescore_descent : 0u;
 		if (c.first_pass)
 			c.prescore_first = a.prescore.codes != nullptr;
+		// the scratch in HBM, to the plan's word counts
 		a.global_hash = nullptr;
-		if (!hash_in_lds) {
-			c.d_global_hash.ensure(((uint64_t)grid * S) << a.hash_log2, 0, c.stream);
+		if (plan.global_hash) {
+			c.d_global_hash.ensure(plan.global_hash, 0, c.stream);
 			a.global_hash = c.d_global_hash.p;
 		}
 		// the retry tables: no memory for them is no reason to fail a search that would have succeeded without — such queries
 		// then go back to the host's re-run launch, as before round 5
 		a.retry_hash = nullptr, a.retry_log2 = 0;
-		if (retry_want_log2 && c.d_retry_hash.try_ensure(((uint64_t)grid * S) << retry_want_log2))
-			a.retry_hash = c.d_retry_hash.p, a.retry_log2 = retry_want_log2;
+		if (plan.retry_hash && c.d_retry_hash.try_ensure(plan.retry_hash))
+			a.retry_hash = c.d_retry_hash.p, a.retry_log2 = plan.retry_log2;
 		a.list_cap = (uint32_t)c.list_cap;
 		a.list_buf = nullptr;
-		if (c.list_cap && !list_in_lds) {
-			c.d_list_buf.ensure((uint64_t)grid * S * 2 * c.list_cap, 0, c.stream);
+		if (plan.list_buf) {
+			c.d_list_buf.ensure(plan.list_buf, 0, c.stream);
 			a.list_buf = c.d_list_buf.p;
 		}
 		a.cand_cap = c.cand_cap;
 		a.cand_buf = nullptr;
-		if (a.tomb == 2) {
-			c.d_cand_buf.ensure((uint64_t)grid * S * 2 * c.cand_cap, 0, c.stream);
+		if (plan.cand_buf) {
+			c.d_cand_buf.ensure(plan.cand_buf, 0, c.stream);
 			a.cand_buf = c.d_cand_buf.p;
 		}
 		if (!c.d_queue.p) { // first launch on this context: both query counters start at zero
@@ -1166,26 +1060,18 @@ struct vss_index {
 			a.drain_flag = c.h_queue + 2;
 			a.done_count = nullptr;
 		}
-		LaunchCfg cfg = launch_cfg(grid, solo ? solo_lds : engine_lds_bytes(S, a.hash_log2, V, a.list_cap_max, hash_in_lds, a.stage_cap, a.list_lds),
-		                           c.limit);
+		LaunchCfg cfg;
+		cfg.nch = plan.nch, cfg.regs = plan.regs, cfg.grid = plan.grid, cfg.lds = plan.lds_bytes, cfg.threads = plan.threads;
 		cfg.stream = c.stream;
-		// a team (helper waves on the compute unit's other SIMDs score a share of every expansion's rows) while every query
-		// of the launch still gets a compute unit of its own; its job box takes the first bytes of the workgroup's LDS
-		const bool team = shape.team;
-		if (team)
-			cfg.lds += TEAM_BOX_BYTES;
-		cfg.threads = solo ? (team ? 64 * VSS_TEAM_WAVES : 64) : 64 * waves;
 		if (c.first_pass) { // vss_last_search_shape
-			const uint32_t shape[8] = {cfg.threads, S, grid, cfg.lds, list_place, hash_in_lds ? (a.visited_compact ? 1u : 0u) : 2u,
-			                           solo ? 1u : 0u, 0u};
-			std::memcpy(c.shape, shape, sizeof shape);
+			std::memcpy(c.shape, plan.shape, sizeof c.shape);
 			c.first_pass = false;
 		}
 		if (c.flag_wait)
 			c.flag_t0 = std::chrono::steady_clock::now();
 		else
 			HIP_TRY(hipEventRecord(c.ev0, c.stream));
-		if (solo)
+		if (plan.solo)
 			launch_by_metric<SearchArgs>(launch_search_solo<0>, launch_search_solo<1>, launch_search_solo<2>, a, cfg);
 		else
 			launch_by_metric<SearchArgs>(launch_search<0>, launch_search<1>, launch_search<2>, a, cfg);

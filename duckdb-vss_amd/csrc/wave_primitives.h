@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "engine_layout.h"
 #include "lds_list_index.h"
 #include "visited_compact.h"
 
@@ -32,7 +33,6 @@ namespace vss {
 
 constexpr uint32_t EMPTY_SLOT = 0xFFFFFFFFu;
 constexpr uint32_t EXPANDED_BIT = 0x80000000u;
-constexpr int MAX_LIST_REGS = 8; // 64 * 8 = 512 entries: the largest ef / ef_construction a register list holds
 
 // Correctly rounded f32 square root (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt applies to sqrtf; the
 // __fsqrt_rn intrinsic of ROCm 7.2 maps to the NATIVE, ~1 ulp, square root and made cosine distances of vectors with

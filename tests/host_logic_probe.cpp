@@ -76,6 +76,43 @@ void hl_search_shape(uint32_t n, uint64_t M0, uint64_t V, uint64_t G, uint32_t s
 	out[4] = s.crew, out[5] = s.roomy;
 }
 
+// plan_search_launch over flat arrays (tests/test_search_plan.py names the cells in this order):
+//   cfg  solo_mode, solo_max_queries, solo_max_bytes, team, n_cus, touch_rows, touch_lists, touch_max_queries, force_looping, crew,
+//        engine_walkers, M0, V, G, list_cap_max, nodes, hash_max_log2, search_waves, search_walkers_cap, search_wgs_per_cu,
+//        search_spec_active, search_pipelined, search_wide_lists, search_list_lds, search_prescore, search_prescore_descent,
+//        retry_in_place, visited_per_limit, hash_lds_max_log2, hash_lds_max_override, visited_compact_on, search_crew_tune
+//   in   n, limit, bump, min_hash_log2, list_cap, cand_cap, tomb, direct_io
+//   out  solo, team, threads, walkers, grid, lds_bytes, regs, nch, hash_log2, hash_in_lds, visited_compact, stage_cap, retry_log2,
+//        roomy, list_place, list_lds, pipelined, crew, touch_lines, spec_active, wants_prescore, prescore_descent, global_hash,
+//        retry_hash, list_buf, cand_buf, shape[0..8)
+void hl_plan_search_launch(const uint64_t *cfg, const uint64_t *in, uint64_t *out) {
+	SearchEngineConfig e;
+	SearchShapePolicy &p = e.policy;
+	int i = 0;
+	p.solo_mode = (uint32_t)cfg[i++], p.solo_max_queries = (uint32_t)cfg[i++], p.solo_max_bytes = (uint32_t)cfg[i++];
+	p.team = cfg[i++] != 0, p.n_cus = (uint32_t)cfg[i++], p.touch_rows = cfg[i++] != 0, p.touch_lists = cfg[i++] != 0;
+	p.touch_max_queries = (uint32_t)cfg[i++], p.force_looping = cfg[i++] != 0, p.crew = cfg[i++] != 0;
+	p.engine_walkers = (uint32_t)cfg[i++];
+	e.M0 = cfg[i++], e.V = cfg[i++], e.G = cfg[i++], e.list_cap_max = cfg[i++], e.nodes = cfg[i++];
+	e.hash_max_log2 = (uint32_t)cfg[i++], e.search_waves = (uint32_t)cfg[i++], e.search_walkers_cap = (uint32_t)cfg[i++];
+	e.search_wgs_per_cu = (uint32_t)cfg[i++], e.search_spec_active = (uint32_t)cfg[i++], e.search_pipelined = cfg[i++] != 0;
+	e.search_wide_lists = cfg[i++] != 0, e.search_list_lds = (uint32_t)cfg[i++], e.search_prescore = (uint32_t)cfg[i++];
+	e.search_prescore_descent = cfg[i++] != 0, e.retry_in_place = cfg[i++] != 0, e.visited_per_limit = cfg[i++];
+	e.hash_lds_max_log2 = (uint32_t)cfg[i++], e.hash_lds_max_override = (uint32_t)cfg[i++], e.visited_compact_on = cfg[i++] != 0;
+	e.search_crew_tune = (uint32_t)cfg[i++];
+	SearchLaunchInput l;
+	l.n = (uint32_t)in[0], l.limit = in[1], l.bump = (uint32_t)in[2], l.min_hash_log2 = (uint32_t)in[3], l.list_cap = in[4];
+	l.cand_cap = (uint32_t)in[5], l.tomb = (uint32_t)in[6], l.direct_io = in[7] != 0;
+	const SearchLaunchPlan a = plan_search_launch(e, l);
+	const uint64_t flat[] = {a.solo, a.team, a.threads, a.walkers, a.grid, a.lds_bytes, a.regs, a.nch, a.hash_log2, a.hash_in_lds,
+	                         a.visited_compact, a.stage_cap, a.retry_log2, a.roomy, a.list_place, a.list_lds, a.pipelined, a.crew,
+	                         a.touch_lines, a.spec_active, a.wants_prescore, a.prescore_descent, a.global_hash, a.retry_hash,
+	                         a.list_buf, a.cand_buf};
+	std::memcpy(out, flat, sizeof flat);
+	for (int w = 0; w != 8; ++w)
+		out[sizeof flat / sizeof flat[0] + w] = a.shape[w];
+}
+
 // visited-set sizing of a SEARCH with this limit (cells per limit entry chosen by search_cells_per_limit)
 uint32_t hl_search_visited_log2(uint64_t limit, uint32_t bump, uint64_t M0, uint64_t list_cap_max, uint32_t max_log2) {
 	return visited_set_log2(limit, bump, M0, list_cap_max, search_cells_per_limit(limit), max_log2);

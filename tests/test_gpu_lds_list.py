@@ -83,7 +83,7 @@ HEADER = 48 + 16 * 32 + 64 * 8  # ENGINE_HEADER_BYTES
 
 
 def _slot_bytes(dim):
-    """A walker's slot for this file's index (engine_slot_bytes, hnsw_kernels.h): M0 16 and a visited set of 2^13 cells in
+    """A walker's slot for this file's index (engine_slot_bytes, engine_layout.h): M0 16 and a visited set of 2^13 cells in
     LDS — what holds every row of the index."""
     return (4 << 13) + _align16(16 * ((dim + 3) // 4)) + 4 * _align16(4 * 16)
 

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 @pytest.fixture(scope="module")
 def hl():
     src = os.path.join(HERE, "host_logic_probe.cpp")
-    hdrs = [os.path.join(ROOT, "duckdb-vss_amd", "csrc", h) for h in ("host_logic.h", "visited_compact.h")]
+    hdrs = [os.path.join(ROOT, "duckdb-vss_amd", "csrc", h) for h in ("host_logic.h", "engine_layout.h", "lds_list_index.h", "visited_compact.h")]
     out = os.path.join(HERE, "host_logic_probe.so")
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in [src] + hdrs):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", src, "-o", out])
@@ -148,7 +148,7 @@ def _shape(hl, n, dim, M0, solo_lds=70 * 1024, solo_mode=1, team=True, touch_row
     hl.hl_search_shape(C.c_uint32(n), C.c_uint64(M0), C.c_uint64(V), C.c_uint64(G), C.c_uint32(solo_lds), C.c_uint32(solo_mode),
                        int(team), int(touch_rows), int(touch_lists), C.c_uint32(n_cus), int(force_looping), int(crew),
                        C.c_uint32(engine_walkers), out)
-    assert out[0] == out[3]  # the engine asks wants_solo() first (to size the visited set), then choose_search_shape()
+    assert out[0] == out[3]  # wants_solo() is asked once per launch, inside choose_search_shape(): the shape reports its answer
     if full:  # (solo, team, touches, crew, roomy visited set)
         return bool(out[0]), bool(out[1]), int(out[2]), bool(out[4]), bool(out[5])
     return bool(out[0]), bool(out[1]), int(out[2])

@@ -19,7 +19,7 @@ LDS_LIST_E = 64  # the value of k_search's template parameter E that selects Lds
 @pytest.fixture(scope="module")
 def ll():
     src = os.path.join(HERE, "lds_list_probe.cpp")
-    hdrs = [os.path.join(ROOT, "duckdb-vss_amd", "csrc", h) for h in ("host_logic.h", "visited_compact.h", "lds_list_index.h")]
+    hdrs = [os.path.join(ROOT, "duckdb-vss_amd", "csrc", h) for h in ("host_logic.h", "engine_layout.h", "visited_compact.h", "lds_list_index.h")]
     out = os.path.join(HERE, "lds_list_probe.so")
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in [src] + hdrs):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", src, "-o", out])
@@ -35,7 +35,7 @@ def align16(x):
 
 
 def slot_bytes(dim, visited_in_lds, M0=32):
-    """engine_slot_bytes (hnsw_kernels.h) without a list: [visited set of 2^13 cells][staged query][2 x (ids, distances)]"""
+    """engine_slot_bytes (engine_layout.h) without a list: [visited set of 2^13 cells][staged query][2 x (ids, distances)]"""
     V = (dim + 3) // 4
     return (4 << 13 if visited_in_lds else 0) + align16(16 * V) + 4 * align16(4 * M0)
 
@@ -46,7 +46,7 @@ def list_bytes(cells):
 
 
 def test_list_bytes_and_header(ll):
-    assert ll.ll_header_bytes() == 48 + 16 * 32 + 64 * 8  # = ENGINE_HEADER_BYTES (vss_engine.hip asserts the same)
+    assert ll.ll_header_bytes() == 48 + 16 * 32 + 64 * 8  # = ENGINE_HEADER_BYTES (engine_layout.h: the kernels' own)
     assert ll.ll_list_bytes(0) == 0
     for cells in (513, 514, 1536, 4095, 4096):
         assert ll.ll_list_bytes(cells) == list_bytes(cells)
