@@ -77,6 +77,8 @@ SIGNATURES = {
     "vss_search_batch_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_batch_filtered": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp]),
     "vss_search_batch_filtered_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "vss_search_batch_filtered_groups": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_filtered_groups_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_device_begin": (_int, [_vp, _int, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_multi_device_begin": (_int, [_vp, _int, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_batch_end": (_int, [_vp, _int]),
@@ -295,6 +297,32 @@ class GpuIndex:
         self._check(self.lib.vss_search_batch_filtered(self.h, _p(Q), nq, k, ef, _p(allowed_bitmap), n_bits, _p(keys), _p(d),
                                                        _p(cnt)))
         return keys, d, cnt
+
+    def search_batch_filtered_groups(self, Q, k, ef, bitmaps, n_bits, group_of):
+        """vss_search_batch_filtered_groups: query q is filtered by row `group_of[q]` of `bitmaps`, an
+        n_groups x ((n_bits + 63) // 64) uint64 array of row-id bitmaps — one launch for a chunk of per-query predicates."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        bitmaps = np.ascontiguousarray(bitmaps, dtype=np.uint64)
+        words = (n_bits + 63) // 64
+        if bitmaps.ndim != 2 or bitmaps.shape[1] != words:
+            raise ValueError("bitmaps must be n_groups x %d uint64 words for %d bits, got shape %r"
+                             % (words, n_bits, bitmaps.shape))
+        group_of = np.ascontiguousarray(group_of, dtype=np.uint32)
+        nq = len(Q)
+        if group_of.shape != (nq,):
+            raise ValueError("group_of must name one group per query: %d queries, shape %r" % (nq, group_of.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        self._check(self.lib.vss_search_batch_filtered_groups(self.h, _p(Q), nq, k, ef, _p(bitmaps), len(bitmaps), n_bits,
+                                                              _p(group_of), _p(keys), _p(d), _p(cnt)))
+        return keys, d, cnt
+
+    def search_batch_filtered_groups_device(self, d_Q, nq, k, ef, d_bitmaps, n_groups, n_bits, d_group_of, d_keys, d_dist,
+                                            d_counts):
+        """The same over raw device pointers (the caller keeps the tensors alive); blocking."""
+        self._check(self.lib.vss_search_batch_filtered_groups_device(self.h, d_Q, nq, k, ef, d_bitmaps, n_groups, n_bits,
+                                                                     d_group_of, d_keys, d_dist, d_counts))
 
     def search_batch_device(self, d_Q, nq, k, ef, d_keys, d_dist, d_counts, exact=False):
         if exact:

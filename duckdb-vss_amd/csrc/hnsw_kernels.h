@@ -27,6 +27,13 @@ namespace vss {
 
 constexpr int64_t FREE_KEY = 0x7FFFFFFFFFFFFFFFll;
 
+// One predicate per query (vss_search_batch_filtered_groups): GraphView::filter_bits carries FILTER_PER_QUERY (row ids are
+// below 2^63: the bit is free) and GraphView::filter is then no bitmap but a table of one bitmap ADDRESS per query of the
+// launch, written by k_resolve_filter_groups — nullptr for a query whose group is not in the caller's table.  Such launches
+// run the k_search_groups / k_search_solo_groups kernels (below): the lookup costs the walker a vector register wherever it
+// is compiled in, so the kernels of every other launch do not contain it.
+constexpr uint64_t FILTER_PER_QUERY = 1ull << 63;
+
 struct GraphView {
 	RowSpace sp;
 	uint32_t dim;
@@ -50,6 +57,19 @@ struct GraphView {
 		if (!filter)
 			return true;
 		return key >= 0 && (uint64_t)key < filter_bits && ((filter[key >> 6] >> (key & 63)) & 1ull);
+	}
+	// The same with one predicate PER QUERY (the k_search_groups / k_search_solo_groups kernels only): `filter` is the table of
+	// bitmap addresses k_resolve_filter_groups has written, `query` (wave-uniform) the number of the query the walker is
+	// answering as the launch numbers it — NOT its position in the work queue of a re-run round.  A query without a bitmap (its
+	// group is not in the caller's table) admits nothing.
+	__device__ __forceinline__ bool admitted_for(uint32_t slot, uint32_t query) const {
+		const int64_t key = keys[slot];
+		if (key == 0x7FFFFFFFFFFFFFFFll)
+			return false;
+		const unsigned long long *mine = reinterpret_cast<const unsigned long long *const *>(filter)[query];
+		if (!mine)
+			return false;
+		return key >= 0 && (uint64_t)key < (filter_bits & ~FILTER_PER_QUERY) && ((mine[key >> 6] >> (key & 63)) & 1ull);
 	}
 
 	__device__ __forceinline__ uint32_t *list_ptr(uint32_t slot, int level) const {
@@ -76,6 +96,9 @@ struct WaveLds {
 	// (64 bits), log2 of its cells, "this query's set has moved there"} — or nullptr.  In LDS, not in this struct: the walker's
 	// kernel sits at its scalar-register limit, and the words are read on the rare path only (gather_neighbors).
 	uint32_t *spill_box = nullptr;
+	// the *_groups search kernels: the number of the query being answered (what GraphView::admitted_for looks its predicate up
+	// by); the walker holds it anyway, for the query's status and counters
+	uint32_t query = 0;
 };
 
 struct WorkCounters {
@@ -1081,7 +1104,9 @@ struct RowTouch {
 
 // PK: neighbour lists kept in flight (0 = the list type's default); MERGE_REGS: widest register list whose accepted
 // candidates are merged in batches (the 1024-thread search engine cannot afford the temporaries of an 8-register merge)
-template <int MT, bool INSERT, bool TOMB, int PK = 0, int MERGE_REGS = MAX_LIST_REGS, class List, class Queue, class Scorer>
+// PER_QUERY (TOMB, the *_groups kernels): the predicate is the one of the query being answered, GraphView::admitted_for
+template <int MT, bool INSERT, bool TOMB, int PK = 0, int MERGE_REGS = MAX_LIST_REGS, bool PER_QUERY = false, class List, class Queue,
+          class Scorer>
 __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &lds, float qa2, uint32_t start,
                                                  uint32_t new_slot, int level, int limit, List &L, Queue &cq,
                                                  const Scorer &score, WorkCounters &wc) {
@@ -1098,7 +1123,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 	if (TOMB) {
 		cq.restart();
 		cq.push(d0, start, 0.f, false);
-		if (gv.admitted(start))
+		if (PER_QUERY ? gv.admitted_for(start, lds.query) : gv.admitted(start))
 			L.template insert<INSERT>(d0, start);
 	} else {
 		L.template insert<INSERT>(d0, start);
@@ -1195,7 +1220,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 			const bool have = off + lane < n;
 			const float d = have ? lds.dist[off + lane] : 0.f;
 			const uint32_t id = have ? lds.ids[off + lane] : 0;
-			const uint32_t live = (TOMB && have) ? (gv.admitted(id) ? 1u : 0u) : 0u;
+			const uint32_t live = (TOMB && have) ? ((PER_QUERY ? gv.admitted_for(id, lds.query) : gv.admitted(id)) ? 1u : 0u) : 0u;
 			unsigned long long pass = __ballot(have && (L.size < limit || d < radius));
 			if constexpr (TOUCH_L) {
 				// ListTouch: a row about to enter the candidate list will be asked for its neighbour list by the look-ahead of one
@@ -1970,8 +1995,10 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 // THREADS = the largest workgroup the instantiation is launched with: 1024 (16 waves, 128 registers per lane), or
 // WIDE_LIST_THREADS for the pipelined 8-register list (round 5)
 constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS = 8)
-template <int MT, int NCH, int R, int E, int THREADS = 1024>
-__global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
+// GROUPS: the body of k_search_groups — a launch with one predicate per query (always a TOMB launch): the level search looks
+// the query's own bitmap up, and the paths such a launch never takes are not compiled.
+template <int MT, int NCH, int R, int E, int THREADS, bool GROUPS>
+__device__ __forceinline__ void search_engine(SearchArgs &a) {
 	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	const int lane = lane_id();
@@ -2095,6 +2122,8 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 		if (idx + 1 == a.n_queries && a.drain_flag)
 			__hip_atomic_store(a.drain_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 		const uint32_t qi = a.work ? a.work[idx] : idx;
+		if constexpr (GROUPS)
+			lds.query = qi;
 		VSS_TRACE(a.gv.sp, 19, 1u);
 		// which batch of the launch, and which of its queries (the tables are read with wave-uniform indices: scalar loads
 		// from the kernel arguments)
@@ -2126,12 +2155,14 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 				// twice the result list (the queue fills up while the result list is still filling); as long as the list itself
 				// where that is all the registers there are
 				RegQueue<(E == 8 ? E : 2 * E)> rq;
-				rc = level_search_impl<MT, false, true, 1>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, rq, score, wc);
+				rc = level_search_impl<MT, false, true, 1, MAX_LIST_REGS, GROUPS>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, rq, score, wc);
 			} else {
 				rc = LEVEL_QUEUE_OVERFLOW;
 			}
 		} else if (a.tomb)
-			rc = level_search_impl<MT, false, true, 1>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, cq, score, wc);
+			rc = level_search_impl<MT, false, true, 1, MAX_LIST_REGS, GROUPS>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, cq, score, wc);
+		else if (GROUPS) // (a constant: a launch with predicates is a TOMB launch, the paths below are not compiled for it)
+			rc = LEVEL_INTERNAL;
 		else if (a.spec_active)
 			rc = level_search_spec<MT>(a.gv, lds, sb, qa2, closest, limit, L, score, a.spec_active, wc);
 		else if (E > 0 && E != LDS_LIST_E && E <= pipelined_max_regs(THREADS) && a.pipelined) {
@@ -2204,6 +2235,16 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 	VSS_TRACE(a.gv.sp, 19, 6u);
 }
 
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, false>(a);
+}
+// the same engine for launches with one predicate per query (vss_search_batch_filtered_groups)
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search_groups(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, true>(a);
+}
+
 // =========================================================================================================
 // k_search_solo — the search engine's shape for FEW queries (the single-query probe of HNSW_INDEX_SCAN, reference
 // hnsw_index_scan.cpp:43-90 / hnsw_index.cpp:315-341, and small batches): one 64-thread workgroup = one wave per query,
@@ -2219,8 +2260,8 @@ __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
 // scheduler from trading the row window's registers for an occupancy nobody can use)
 // T > 1: a team — T - 1 helper waves score a share of every expansion's rows (TeamScorer above); R is then the row window
 // of EACH wave.
-template <int MT, int NCH, int R, int E, int T = 1>
-__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo(SearchArgs a) {
+template <int MT, int NCH, int R, int E, int T, bool GROUPS>
+__device__ __forceinline__ void search_solo(SearchArgs &a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	TeamBox &team_box = *reinterpret_cast<TeamBox *>(smem); // teams: the first bytes of the workgroup's LDS (host: + TEAM_BOX_BYTES)
 	const int lane = lane_id();
@@ -2256,6 +2297,8 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 		if (idx + 1 == a.n_queries && a.drain_flag)
 			__hip_atomic_store(a.drain_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 		const uint32_t qi = a.work ? a.work[idx] : idx;
+		if constexpr (GROUPS)
+			lds.query = qi;
 		const uint32_t batch = qi / a.batch_size, row = qi - batch * a.batch_size;
 		stage_query(lds.q, a.queries[batch] + (size_t)row * a.q_stride, a.gv.dim, a.gv.sp.V);
 		const float qa2 = MT == 1 ? wave_query_norm(a.gv.sp, lds.q) : 0.f;
@@ -2268,12 +2311,14 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 		if (a.tomb == 1) { // few rejected rows expected: the pending candidates stay in registers (host: limits within the register lists only)
 			if constexpr (E == 1 || E == 2 || E == 4 || E == 8) {
 				RegQueue<2 * E> rq;
-				rc = level_search_impl<MT, false, true>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, rq, score, wc);
+				rc = level_search_impl<MT, false, true, 0, MAX_LIST_REGS, GROUPS>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, rq, score, wc);
 			} else {
 				rc = LEVEL_QUEUE_OVERFLOW;
 			}
 		} else if (a.tomb)
-			rc = level_search_impl<MT, false, true>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, cq, score, wc);
+			rc = level_search_impl<MT, false, true, 0, MAX_LIST_REGS, GROUPS>(a.gv, lds, qa2, closest, EMPTY_SLOT, 0, limit, L, cq, score, wc);
+		else if (GROUPS) // (a constant: a launch with predicates is a TOMB launch)
+			rc = LEVEL_INTERNAL;
 		else
 			// (round 6 measured the team running level_search_pipelined — the helpers score, the walker accepts meanwhile — and dropped
 			//  it: 222 against 196 us per query at 1M x 128; what the hidden accept phase saves, the pipeline's heavier pick and its
@@ -2311,6 +2356,15 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 			team_box.n = -1;
 		__syncthreads();
 	}
+}
+
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, false>(a);
+}
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_groups(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, true>(a);
 }
 
 // =========================================================================================================
@@ -2466,6 +2520,20 @@ struct LinkArgs {
 };
 
 #ifdef VSS_ENGINE_TU // plain kernels are defined once, in the engine's translation unit
+
+// Ahead of a launch with one predicate per query: the address of every query's bitmap — `allowed` holds n_groups bitmaps of
+// `words` 64-bit words each, laid end to end, query q names bitmap group_of[q].  A group beyond the table gets no bitmap
+// (nullptr: GraphView::admitted rejects every row), so nothing outside the n_groups * words words is ever addressed.
+__global__ __launch_bounds__(256) void k_resolve_filter_groups(const unsigned long long *allowed, const uint32_t *group_of,
+                                                               uint32_t n_groups, uint64_t words, uint32_t n_queries,
+                                                               const unsigned long long **bitmap_of) {
+	const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+	if (q >= n_queries)
+		return;
+	const uint32_t group = group_of[q];
+	bitmap_of[q] = group < n_groups ? allowed + (size_t)group * (size_t)words : nullptr;
+}
+
 // Reused slots, before phase A: blank every list of the node (update() zeroes the node tape, index.hpp:2837-2840).
 // After phase A: move the parked new lists in.  One wave per batch node; appended nodes are skipped.
 __global__ __launch_bounds__(64) void k_reuse_lists(BuildArgs a, int commit) {

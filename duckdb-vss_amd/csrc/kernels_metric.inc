@@ -39,9 +39,26 @@ static hipError_t allow_big_lds(K kernel) {
 #ifndef VSS_SEARCH_R6
 #define VSS_SEARCH_R6 2 // 6 chunks per lane (dimension 1536): 4 rows in flight spill 72 bytes per lane beyond the 128 VGPRs
 #endif
+// launches with one predicate per query (GraphView::filter_bits carries FILTER_PER_QUERY): the *_groups kernels, same ladders
+// (such a launch is never pipelined: no 12-wave variant)
+template <int MT, int NCH, int R>
+static hipError_t search_groups_e(const SearchArgs &a, const LaunchCfg &c) {
+	constexpr int RS = NCH == 6 ? VSS_SEARCH_R6 : 4;
+	if (a.list_lds)
+		VSS_LAUNCH_T((k_search_groups<MT, NCH, RS, LDS_LIST_E>), a, c.threads);
+	if (c.regs <= 2)
+		VSS_LAUNCH_T((k_search_groups<MT, NCH, RS, 2>), a, c.threads);
+	if (c.regs <= 4)
+		VSS_LAUNCH_T((k_search_groups<MT, NCH, RS, 4>), a, c.threads);
+	if (c.regs <= MAX_LIST_REGS)
+		VSS_LAUNCH_T((k_search_groups<MT, NCH, RS, MAX_LIST_REGS>), a, c.threads);
+	VSS_LAUNCH_T((k_search_groups<MT, NCH, RS, 0>), a, c.threads);
+}
 template <int MT, int NCH, int R>
 static hipError_t search_e(const SearchArgs &a, const LaunchCfg &c) {
 	constexpr int RS = NCH == 6 ? VSS_SEARCH_R6 : 4;
+	if (a.gv.filter_bits & FILTER_PER_QUERY)
+		return search_groups_e<MT, NCH, R>(a, c);
 	// limits of 257-512, pipelined: 12-wave workgroups (170 registers per lane; 4 rows in flight at every row width)
 	if (c.threads <= WIDE_LIST_THREADS && c.regs > PIPELINED_MAX_REGS && c.regs <= MAX_LIST_REGS && a.pipelined)
 		VSS_LAUNCH_T((k_search<MT, NCH, 4, MAX_LIST_REGS, WIDE_LIST_THREADS>), a, c.threads);
@@ -69,6 +86,17 @@ static hipError_t search_team_e(const SearchArgs &a, const LaunchCfg &c) {
 #define VSS_TEAM_R (VSS_TEAM_WAVES <= 4 ? 4 : 2) // (a level-0 list of 32 rows at 128 dims: 4 rows per wave; A/B builds)
 #endif
 	constexpr int T = VSS_TEAM_WAVES, RT = VSS_TEAM_R;
+	if (a.gv.filter_bits & FILTER_PER_QUERY) {
+		if (c.regs <= 1)
+			VSS_LAUNCH_W((k_search_solo_groups<MT, NCH, RT, 1, T>), a, T);
+		if (c.regs <= 2)
+			VSS_LAUNCH_W((k_search_solo_groups<MT, NCH, RT, 2, T>), a, T);
+		if (c.regs <= 4)
+			VSS_LAUNCH_W((k_search_solo_groups<MT, NCH, RT, 4, T>), a, T);
+		if (c.regs <= MAX_LIST_REGS)
+			VSS_LAUNCH_W((k_search_solo_groups<MT, NCH, RT, MAX_LIST_REGS, T>), a, T);
+		VSS_LAUNCH_W((k_search_solo_groups<MT, NCH, RT, 0, T>), a, T);
+	}
 	if (c.regs <= 1)
 		VSS_LAUNCH_W((k_search_solo<MT, NCH, RT, 1, T>), a, T);
 	if (c.regs <= 2)
@@ -86,6 +114,17 @@ static hipError_t search_solo_e(const SearchArgs &a, const LaunchCfg &c) {
 			return search_team_e<MT, NCH>(a, c);
 	}
 	constexpr int RS = NCH == 1 ? 16 : (NCH == 6 || NCH == 4) ? 4 : 8;
+	if (a.gv.filter_bits & FILTER_PER_QUERY) {
+		if (c.regs <= 1)
+			VSS_LAUNCH((k_search_solo_groups<MT, NCH, RS, 1>), a);
+		if (c.regs <= 2)
+			VSS_LAUNCH((k_search_solo_groups<MT, NCH, RS, 2>), a);
+		if (c.regs <= 4)
+			VSS_LAUNCH((k_search_solo_groups<MT, NCH, RS, 4>), a);
+		if (c.regs <= MAX_LIST_REGS)
+			VSS_LAUNCH((k_search_solo_groups<MT, NCH, RS, MAX_LIST_REGS>), a);
+		VSS_LAUNCH((k_search_solo_groups<MT, NCH, RS, 0>), a);
+	}
 	if (c.regs <= 1)
 		VSS_LAUNCH((k_search_solo<MT, NCH, RS, 1>), a);
 	if (c.regs <= 2)

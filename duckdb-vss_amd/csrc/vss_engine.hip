@@ -26,6 +26,7 @@
 #include "../../include/vssgpu.h"
 #include "launchers.h"
 #include "host_logic.h"
+#include "filter_groups.h"
 #include "row_codes.h"
 
 using namespace vss;
@@ -77,7 +78,9 @@ struct DevBuf {
 		p = np;
 		n = want;
 	}
-	// grow to at least `want` elements, contents undefined; false (nothing changed but a freed buffer) when the device has no room
+	// grow to at least `want` elements, contents undefined; false (nothing changed but a freed buffer) when the device has no room.
+	// Frees FIRST: for the large optional buffers (row codes, retry tables) whose old and new sizes may not fit side by side and
+	// whose loss only turns an optimisation off.  A buffer a call cannot do without takes try_grow.
 	bool try_ensure(size_t want) {
 		if (want <= n)
 			return true;
@@ -87,6 +90,22 @@ struct DevBuf {
 			(void)hipGetLastError();
 			return false;
 		}
+		p = np;
+		n = want;
+		return true;
+	}
+	// the same, but the new buffer is allocated BEFORE the old one is freed (the order ADVICE.md asks for): on failure the buffer
+	// stays exactly as it was and the call that needed it fails alone.  For the small per-call tables of the search contexts.
+	bool try_grow(size_t want) {
+		if (want <= n)
+			return true;
+		T *np = nullptr;
+		if (hipMalloc(&np, want * sizeof(T)) != hipSuccess) {
+			(void)hipGetLastError();
+			return false;
+		}
+		if (p)
+			(void)hipFree(p);
 		p = np;
 		n = want;
 		return true;
@@ -137,6 +156,7 @@ struct vss_index {
 	KeyMap keymap;
 	FreeRing free_slots;
 	std::atomic<uint64_t> progress_linked {0}, progress_total {0}; // vss_build_progress (read without the index lock)
+	std::atomic<uint64_t> group_table_bytes {0}; // device bytes of the contexts' group tables (vss_memory_usage, read without a lock)
 
 	// Staged rows that take over a tombstoned slot (the reference's update() path, index_dense.hpp:1766-1793): their
 	// new vectors wait in d_pending until the node has been re-linked, because every distance to the slot taken during
@@ -178,6 +198,10 @@ struct vss_index {
 		DevBuf<int64_t> d_out_keys;
 		DevBuf<uint32_t> d_out_count;
 		DevBuf<uint64_t> d_filter;
+		DevBuf<uint64_t> d_group_filter; // vss_search_batch_filtered_groups: n_groups bitmaps end to end ...
+		DevBuf<uint32_t> d_group_of;     // ... and the group of every query of the call
+		DevBuf<const unsigned long long *> d_group_bitmap; // the address of every query's bitmap (either form of the call)
+		uint64_t group_bytes = 0; // of these three, as counted in vss_index::group_table_bytes
 		unsigned char *pinned_io = nullptr;
 		size_t pinned_cap = 0;
 		bool leased = false;
@@ -215,6 +239,12 @@ struct vss_index {
 	SearchCtx ctx[MAX_CTX];
 	std::mutex lease_mu;
 	std::condition_variable lease_cv;
+	// after a context's group tables grew: keep the sum vss_memory_usage reports
+	void count_group_tables(SearchCtx &c) {
+		const uint64_t now = c.d_group_filter.n * 8 + c.d_group_of.n * 4 + c.d_group_bitmap.n * 8;
+		group_table_bytes.fetch_add(now - c.group_bytes, std::memory_order_relaxed);
+		c.group_bytes = now;
+	}
 	int lease_context() {
 		std::unique_lock<std::mutex> lk(lease_mu);
 		for (;;) {
@@ -405,6 +435,7 @@ struct vss_index {
 			c.d_stats.free(), c.d_status.free(), c.d_work.free(), c.d_global_hash.free(), c.d_retry_hash.free(), c.d_phase.free();
 			c.d_queue.free(), c.d_list_buf.free(), c.d_cand_buf.free();
 			c.d_q.free(), c.d_out_d.free(), c.d_out_keys.free(), c.d_out_count.free(), c.d_filter.free();
+			c.d_group_filter.free(), c.d_group_of.free(), c.d_group_bitmap.free();
 			c.d_prescore.free();
 			if (c.h_prescore)
 				(void)hipHostFree(c.h_prescore);
@@ -1116,9 +1147,10 @@ struct vss_index {
 	// enqueue one batched probe on a context (asynchronous); search_end() completes it
 	int search_begin(int slot, const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, uint64_t ef,
 	                 int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out,
-	                 const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0, bool direct_io = false) {
+	                 const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0, bool direct_io = false,
+	                 const uint32_t *d_group_of = nullptr, uint64_t n_groups = 0) {
 		return search_begin_multi(slot, 1, &d_queries, q_stride, nq, k, ef, &d_keys_out, &d_dist_out, &d_count_out, d_filter,
-		                          filter_bits, direct_io);
+		                          filter_bits, direct_io, false, d_group_of, n_groups);
 	}
 
 	// The same for `n_batches` probe batches of `per_batch` queries each, answered by ONE launch of the search engine:
@@ -1127,7 +1159,8 @@ struct vss_index {
 	int search_begin_multi(int slot, uint64_t n_batches, const float *const *d_queries, uint32_t q_stride, uint64_t per_batch,
 	                       uint64_t k, uint64_t ef, int64_t *const *d_keys_out, float *const *d_dist_out,
 	                       uint32_t *const *d_count_out, const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0,
-	                       bool direct_io = false, bool gate = false) {
+	                       bool direct_io = false, bool gate = false, const uint32_t *d_group_of = nullptr,
+	                       uint64_t n_groups = 0) {
 		if (slot < 0 || slot >= MAX_CTX)
 			return fail("search context %d out of range (0..%d)", slot, MAX_CTX - 1);
 		if (n_batches < 1 || n_batches > MAX_COALESCED)
@@ -1180,7 +1213,22 @@ struct vss_index {
 		SearchArgs &a = c.args;
 		a.gv = view();
 		a.gv.filter = reinterpret_cast<const unsigned long long *>(d_filter);
-		a.gv.filter_bits = filter_bits;
+		// (row ids are below 2^63 — 2^63 - 1 is the free key — so a wider bitmap admits nothing more; the top bit is the kernels'
+		//  FILTER_PER_QUERY)
+		a.gv.filter_bits = std::min<uint64_t>(filter_bits, FILTER_PER_QUERY - 1);
+		if (d_filter && d_group_of) {
+			// per-query predicates: d_filter holds n_groups bitmaps end to end, query q takes bitmap d_group_of[q].  A small kernel
+			// ahead of the launch resolves every query's bitmap address; the walkers of the *_groups kernels read that (GraphView::admitted_for).
+			if (!c.d_group_bitmap.try_grow(nq))
+				return fail("filtered search: no device memory for the bitmap addresses of %llu queries", (unsigned long long)nq);
+			count_group_tables(c);
+			hipLaunchKernelGGL(k_resolve_filter_groups, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, c.stream,
+			                   reinterpret_cast<const unsigned long long *>(d_filter), d_group_of, (uint32_t)n_groups,
+			                   filter_group_words(filter_bits), (uint32_t)nq, c.d_group_bitmap.p);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits |= FILTER_PER_QUERY;
+		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
 			a.queries[b] = used ? d_queries[b] : nullptr;
@@ -1372,12 +1420,13 @@ struct vss_index {
 	// blocking search on context `slot` (0 = the index stream, shared by the blocking device-pointer calls)
 	int search_launch(int slot, const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, uint64_t ef,
 	                  int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out, bool keep_query_stats,
-	                  const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0, bool direct_io = false) {
+	                  const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0, bool direct_io = false,
+	                  const uint32_t *d_group_of = nullptr, uint64_t n_groups = 0) {
 		std::unique_lock<std::mutex> lk0(ctx0_mu, std::defer_lock);
 		if (slot == 0)
 			lk0.lock();
 		int rc = search_begin(slot, d_queries, q_stride, nq, k, ef, d_keys_out, d_dist_out, d_count_out, d_filter,
-		                      filter_bits, direct_io);
+		                      filter_bits, direct_io, d_group_of, n_groups);
 		if (rc != VSS_OK)
 			return rc;
 		return search_end(slot, keep_query_stats);
@@ -1396,7 +1445,8 @@ struct vss_index {
 
 	static constexpr uint64_t DIRECT_IO_MAX_QUERIES = 256;
 	int search_host(const float *queries, uint64_t nq, uint64_t k, uint64_t ef, int64_t *out_keys, float *out_d,
-	                uint32_t *out_counts, bool exact, const uint64_t *filter = nullptr, uint64_t filter_bits = 0) {
+	                uint32_t *out_counts, bool exact, const uint64_t *filter = nullptr, uint64_t filter_bits = 0,
+	                const uint32_t *group_of = nullptr, uint64_t n_groups = 0) {
 		if (!nq || !k)
 			return VSS_OK;
 		Lease lease(this);
@@ -1433,7 +1483,20 @@ struct vss_index {
 			return VSS_OK;
 		}
 		const uint64_t *d_filter = nullptr;
-		if (filter) {
+		const uint32_t *d_group_of = nullptr;
+		if (filter && group_of) {
+			// per-query predicates: the n_groups bitmaps and the group of every query, in buffers of the context that grow and
+			// are reused.  No room on the device is an error of this call, and the context keeps what it had.
+			const uint64_t words = filter_group_words(filter_bits);
+			if (!c.d_group_filter.try_grow(std::max<uint64_t>(n_groups * words, 1)) || !c.d_group_of.try_grow(nq))
+				return fail("filtered search: no device memory for %llu bitmaps of %llu bits and %llu group numbers",
+				            (unsigned long long)n_groups, (unsigned long long)filter_bits, (unsigned long long)nq);
+			count_group_tables(c);
+			if (n_groups * words)
+				HIP_TRY(hipMemcpyAsync(c.d_group_filter.p, filter, n_groups * words * 8, hipMemcpyHostToDevice, c.stream));
+			HIP_TRY(hipMemcpyAsync(c.d_group_of.p, group_of, nq * 4, hipMemcpyHostToDevice, c.stream));
+			d_filter = c.d_group_filter.p, d_group_of = c.d_group_of.p;
+		} else if (filter) {
 			const uint64_t words = (filter_bits + 63) / 64;
 			c.d_filter.ensure(std::max<uint64_t>(words, 1), 0, c.stream);
 			HIP_TRY(hipMemcpyAsync(c.d_filter.p, filter, words * 8, hipMemcpyHostToDevice, c.stream));
@@ -1450,7 +1513,7 @@ struct vss_index {
 			rc = exact_launch(c.d_q.p, (uint32_t)dim, nq, k, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p);
 		} else {
 			rc = search_launch(lease.slot, c.d_q.p, (uint32_t)dim, nq, k, ef, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p, true,
-			                   d_filter, filter_bits);
+			                   d_filter, filter_bits, false, d_group_of, n_groups);
 		}
 		if (rc != VSS_OK)
 			return rc;
@@ -2649,6 +2712,46 @@ int vss_search_batch_filtered_device(vss_index *h, const float *Q, uint64_t nq, 
 	})
 }
 
+// Per-query predicates: ONE launch for a join chunk whose outer rows each carry their own WHERE (hnsw_optimize_join.cpp:111-168
+// with a correlated predicate; the predicate itself is usearch's filtered_search, index_dense.hpp:625-629).
+#define VSS_CHECK_FILTER_GROUPS(h, what)                                                                               \
+	if (nq && k) {                                                                                                     \
+		if (!allowed)                                                                                                  \
+			return (h)->fail(what ": grouped filtered search needs the groups' row-id bitmaps");                        \
+		if (!group_of)                                                                                                 \
+			return (h)->fail(what ": grouped filtered search needs the group of every query");                         \
+		if (!n_groups)                                                                                                 \
+			return (h)->fail(what ": grouped filtered search needs at least one group");                               \
+		if (n_groups > 0xFFFFFFFFull || !filter_group_table_fits(n_groups, n_bits))                                    \
+			return (h)->fail(what ": %llu groups of %llu bits are more than a table can hold",                          \
+			                 (unsigned long long)n_groups, (unsigned long long)n_bits);                                \
+	}
+
+int vss_search_batch_filtered_groups(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef,
+                                     const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
+                                     int64_t *out, float *out_d, uint32_t *out_counts) {
+	VSS_SHARED(h, {
+		VSS_CHECK_FILTER_GROUPS(h, "vss_search_batch_filtered_groups")
+		if (nq && k) { // refused before anything is uploaded or launched
+			const uint64_t bad = first_unknown_group(group_of, nq, n_groups);
+			if (bad != NO_BAD_GROUP)
+				return h->fail("vss_search_batch_filtered_groups: query %llu names group %u, the table holds %llu",
+				               (unsigned long long)bad, group_of[bad], (unsigned long long)n_groups);
+		}
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, allowed, n_bits, group_of, n_groups);
+	})
+}
+
+int vss_search_batch_filtered_groups_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef,
+                                            const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits,
+                                            const uint32_t *group_of, int64_t *out, float *out_d, uint32_t *out_counts) {
+	VSS_SHARED(h, {
+		VSS_CHECK_FILTER_GROUPS(h, "vss_search_batch_filtered_groups_device")
+		return h->search_launch(0, Q, (uint32_t)h->dim, nq, k, ef, out, out_d, out_counts, false, allowed, n_bits, false,
+		                        group_of, n_groups);
+	})
+}
+
 // the caller's contexts are 0 .. EXPLICIT_CTX-1; the others are leased internally by the host-pointer entry points
 #define VSS_CHECK_CALLER_CONTEXT(h, context)                                                                           \
 	if ((context) < 0 || (context) >= vss_index::EXPLICIT_CTX)                                                         \
@@ -2842,8 +2945,12 @@ int vss_metric(vss_index *h) {
 uint64_t vss_memory_usage(vss_index *h) {
 	if (!h)
 		return 0;
+	// what the contexts keep for vss_search_batch_filtered_groups (they grow and are reused): searches on other threads grow
+	// them, so the sum is kept in an atomic and not read off the buffers
+	const uint64_t group_tables = h->group_table_bytes.load(std::memory_order_relaxed);
 	return h->d_vectors.n * 4 + h->d_links0.n * 4 + h->d_links_up.n * 4 + h->d_upper_off.n * 4 + h->d_levels.n +
-	       h->d_keys.n * 8 + h->d_list_owner.n * 4 + h->d_codes.n * sizeof(uint32_t) + h->d_code_meta.n * sizeof(RowCodeMeta);
+	       h->d_keys.n * 8 + h->d_list_owner.n * 4 + h->d_codes.n * sizeof(uint32_t) + h->d_code_meta.n * sizeof(RowCodeMeta) +
+	       group_tables;
 }
 
 int vss_level_stats(vss_index *h, uint64_t level, uint64_t *out4) {

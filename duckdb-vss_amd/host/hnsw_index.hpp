@@ -235,6 +235,31 @@ public:
 			*counts_out = counts;
 		return total;
 	}
+	// The chunk form of ExecuteMultiScanBatch for a join whose LATERAL subquery is correlated (`WHERE items.tenant = q.tenant`,
+	// hnsw_optimize_join.cpp:111-168 with the predicate pushed into the traversal): outer row q is answered under bitmap
+	// group_of[q] of `allowed` — n_groups bitmaps over row ids laid end to end, (n_bits + 63) / 64 words each — in ONE launch
+	// instead of one ExecuteMultiScanBatch per distinct predicate.  Row ids are appended query after query.
+	idx_t ExecuteMultiScanBatchGrouped(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit,
+	                                   const uint64_t *allowed, idx_t n_groups, idx_t n_bits, const uint32_t *group_of,
+	                                   std::vector<uint32_t> *counts_out) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::vector<row_t> ids(n_queries * limit);
+		std::vector<uint32_t> counts(n_queries);
+		{
+			std::shared_lock<std::shared_mutex> lock(rwlock);
+			Check(vss_search_batch_filtered_groups(index, queries, n_queries, limit, state.ef_search, allowed, n_groups, n_bits,
+			                                       group_of, ids.data(), nullptr, counts.data()),
+			      "search");
+		}
+		idx_t total = 0;
+		for (idx_t q = 0; q != n_queries; ++q) {
+			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
+			total += counts[q];
+		}
+		if (counts_out)
+			*counts_out = counts;
+		return total;
+	}
 	const std::vector<row_t> &GetMultiScanResult(IndexScanState &state) {
 		return static_cast<MultiScanState &>(state).row_ids;
 	}

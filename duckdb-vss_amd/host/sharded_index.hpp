@@ -35,6 +35,7 @@
 #include <cstring>
 #include <thread>
 
+#include "../csrc/filter_groups.h"
 #include "hnsw_index.hpp"
 #include "shard_layout.hpp"
 
@@ -83,6 +84,11 @@ public:
 			if (b.words) {
 				(void)hipSetDevice(b.device);
 				(void)hipFree(b.words);
+			}
+		for (auto &b : bitmaps)
+			if (b.group_of) {
+				(void)hipSetDevice(b.device);
+				(void)hipFree(b.group_of);
 			}
 		if (m_dist) {
 			(void)hipSetDevice(shards[0].device);
@@ -356,6 +362,53 @@ public:
 		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
 	}
 
+	// ---- the same probe with a predicate PER QUERY (vss_search_batch_filtered_groups_device per shard): the chunk of a join whose
+	// subquery is correlated.  `allowed` = n_groups bitmaps over GLOBAL row ids laid end to end, (n_bits + 63) / 64 host words
+	// each; query q is filtered by bitmap group_of[q] < n_groups (checked here, before any device is touched).  Table and group
+	// numbers are uploaded once per device that holds a shard, not once per shard.  Exchange and merge are SearchBatchFiltered's.
+	void SearchBatchFilteredGroups(const float *queries, idx_t n, idx_t k, idx_t ef, const uint64_t *allowed, idx_t n_groups,
+	                               idx_t n_bits, const uint32_t *group_of, row_t *out_rowids, float *out_distances,
+	                               uint32_t *out_counts) {
+		if (!n || !k)
+			return;
+		if (!allowed || !group_of || !n_groups)
+			throw InternalException("Failed to search the HNSW index: grouped filtered search needs the groups' row-id bitmaps "
+			                        "and the group of every query");
+		for (idx_t q = 0; q != n; ++q)
+			if (group_of[q] >= n_groups)
+				throw InternalException("Failed to search the HNSW index: query " + std::to_string(q) + " names group " +
+				                        std::to_string(group_of[q]) + ", the table holds " + std::to_string(n_groups));
+		if (n_groups > 0xFFFFFFFFull || !vss::host::filter_group_table_fits(n_groups, n_bits))
+			throw InternalException("Failed to search the HNSW index: " + std::to_string(n_groups) + " groups of " +
+			                        std::to_string(n_bits) + " bits are more than a table can hold");
+		Ensure(n, k);
+		const idx_t words = vss::host::filter_group_words(n_bits) * n_groups; // (the engine's own arithmetic: no wrap)
+		for (auto &b : bitmaps) {
+			Hip(hipSetDevice(b.device), "hipSetDevice");
+			if (b.capacity < std::max<idx_t>(words, 1)) { // (allocate, then free: a failed allocation leaves the slot as it was)
+				uint64_t *grown = nullptr;
+				Hip(hipMalloc((void **)&grown, std::max<idx_t>(words, 1) * sizeof(uint64_t)), "hipMalloc");
+				(void)hipFree(b.words);
+				b.words = grown, b.capacity = std::max<idx_t>(words, 1);
+			}
+			if (b.group_capacity < n) {
+				uint32_t *grown = nullptr;
+				Hip(hipMalloc((void **)&grown, n * sizeof(uint32_t)), "hipMalloc");
+				(void)hipFree(b.group_of);
+				b.group_of = grown, b.group_capacity = n;
+			}
+			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
+			Hip(hipMemcpy(b.group_of, group_of, n * sizeof(uint32_t), hipMemcpyHostToDevice), "copy groups");
+		}
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_batch_filtered_groups_device(s.index->Handle(), s.d_q, n, k, ef, bitmaps[s.bitmap].words, n_groups,
+			                                                   n_bits, bitmaps[s.bitmap].group_of, keys, dist, s.d_cnt));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+	}
+
 	// ---- brute force over every live row of every shard (vss_search_exact_batch_device per shard, the same exchange and
 	// merge): the recall oracle of a sharded index.  Every shard returns its k best rows by (distance, slot); the merge orders
 	// the union by (distance, row id) — so rows at exactly equal distance come back in (distance, row id) order, and where
@@ -563,6 +616,8 @@ private:
 		int device;
 		uint64_t *words;
 		idx_t capacity;
+		uint32_t *group_of = nullptr; // SearchBatchFilteredGroups: the group of every query of the batch
+		idx_t group_capacity = 0;
 	};
 
 	struct Shard {

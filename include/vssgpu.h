@@ -150,6 +150,27 @@ int vss_search_batch_filtered(vss_index *index, const float *queries, uint64_t n
 int vss_search_batch_filtered_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
                                      const uint64_t *d_allowed, uint64_t n_bits, int64_t *d_out_rowids,
                                      float *d_out_distances, uint32_t *d_out_counts);
+/* The same with ONE PREDICATE PER QUERY, in one launch: the chunk of PhysicalHNSWIndexJoin::Execute
+ * (hnsw_optimize_join.cpp:111-168) whose LATERAL subquery is correlated — `WHERE items.tenant = q.tenant` — so that every
+ * outer row has its own filtered_search predicate (index_dense.hpp:625-629).  `allowed` = n_groups bitmaps laid end to end, each
+ * words = (n_bits + 63) / 64 words, group g at allowed + g * words; group_of[q] < n_groups names the bitmap of query q.
+ * Query q gets exactly what vss_search_batch_filtered returns for it alone with bitmap allowed + group_of[q] * words and the
+ * same n_bits — row ids, distance bits, count; tombstones excluded, rejected rows traversed, row ids >= n_bits rejected (a
+ * set padding bit after n_bits admits nothing, whatever group follows it).  There is no "no predicate" group number: pass a
+ * group of all ones.  Outputs are laid out as vss_search_batch_filtered's; after the host-pointer form vss_last_search_stats /
+ * vss_last_search_query_stats describe the call as they do there.
+ * VSS_ERROR: allowed or group_of NULL, or n_groups == 0, with n_queries > 0; no device memory for the table.  Host-pointer
+ * form: a group_of[q] >= n_groups is refused before anything is launched (the message names the first such query).  Device
+ * form: the engine does not copy group_of back to look; such a query is answered as if its predicate admitted nothing —
+ * count 0, cells -1 / +inf — and nothing outside the n_groups * words words is read.
+ * Blocking calls only: the pipelined _begin form and the multi-batch launch below take no predicate per query. */
+int vss_search_batch_filtered_groups(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                     const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
+                                     int64_t *out_rowids, float *out_distances, uint32_t *out_counts);
+int vss_search_batch_filtered_groups_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k,
+                                            uint64_t ef, const uint64_t *d_allowed, uint64_t n_groups, uint64_t n_bits,
+                                            const uint32_t *d_group_of, int64_t *d_out_rowids, float *d_out_distances,
+                                            uint32_t *d_out_counts);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
