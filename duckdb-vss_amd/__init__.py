@@ -81,6 +81,11 @@ SIGNATURES = {
     "vss_search_batch_filtered_groups_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_device_begin": (_int, [_vp, _int, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_multi_device_begin": (_int, [_vp, _int, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "vss_search_batch_filtered_device_begin": (_int, [_vp, _int, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "vss_search_batch_filtered_groups_device_begin": (_int, [_vp, _int, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp,
+                                                             _vp]),
+    "vss_search_multi_filtered_device_begin": (_int, [_vp, _int, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp,
+                                                      _vp]),
     "vss_search_batch_end": (_int, [_vp, _int]),
     "vss_search_exact_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_exact_batch_device": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
@@ -339,6 +344,28 @@ class GpuIndex:
         tables = [(C.c_void_p * n)(*[int(p) if p else None for p in t]) for t in (d_Qs, d_keys, d_dists, d_counts)]
         self._check(self.lib.vss_search_multi_device_begin(self.h, context, n, tables[0], per_batch, k, ef, tables[1], tables[2],
                                                            tables[3]))
+
+    def search_filtered_begin(self, context, d_Q, nq, k, ef, d_bitmap, n_bits, d_keys, d_dist, d_counts):
+        """search_begin under one row-id bitmap (a device address); the bitmap stays untouched until search_end returns."""
+        self._check(self.lib.vss_search_batch_filtered_device_begin(self.h, context, d_Q, nq, k, ef, d_bitmap, n_bits, d_keys,
+                                                                    d_dist, d_counts))
+
+    def search_filtered_groups_begin(self, context, d_Q, nq, k, ef, d_bitmaps, n_groups, n_bits, d_group_of, d_keys, d_dist,
+                                     d_counts):
+        """search_begin with one predicate per query: query q takes bitmap d_group_of[q] of the table d_bitmaps."""
+        self._check(self.lib.vss_search_batch_filtered_groups_device_begin(self.h, context, d_Q, nq, k, ef, d_bitmaps, n_groups,
+                                                                           n_bits, d_group_of, d_keys, d_dist, d_counts))
+
+    def search_multi_filtered_begin(self, context, d_Qs, per_batch, k, ef, d_bitmaps, n_groups, n_bits, d_group_ofs, d_keys,
+                                    d_dists, d_counts):
+        """search_multi_begin where batch b has its own table d_bitmaps[b] of n_groups[b] bitmaps and its own group numbers
+        d_group_ofs[b] (None: every query of the batch takes bitmap 0).  Lists of device addresses, one entry per batch."""
+        n = len(d_Qs)
+        tables = [(C.c_void_p * n)(*[int(p) if p else None for p in t]) if t is not None else None
+                  for t in (d_Qs, d_bitmaps, d_group_ofs, d_keys, d_dists, d_counts)]
+        groups = (C.c_uint64 * n)(*[int(g) for g in n_groups]) if n_groups is not None else None
+        self._check(self.lib.vss_search_multi_filtered_device_begin(self.h, context, n, tables[0], per_batch, k, ef, tables[1],
+                                                                    groups, n_bits, tables[2], tables[3], tables[4], tables[5]))
 
     def set_search_gating(self, on):
         self.set_option("search.gating", 1 if on else 0)

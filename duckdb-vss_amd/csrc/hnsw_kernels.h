@@ -21,6 +21,7 @@
 #include "wave_primitives.h"
 #include "engine_layout.h"
 #include "prescore_bound.h"
+#include "filter_groups.h"
 #include <type_traits>
 
 namespace vss {
@@ -29,7 +30,8 @@ constexpr int64_t FREE_KEY = 0x7FFFFFFFFFFFFFFFll;
 
 // One predicate per query (vss_search_batch_filtered_groups): GraphView::filter_bits carries FILTER_PER_QUERY (row ids are
 // below 2^63: the bit is free) and GraphView::filter is then no bitmap but a table of one bitmap ADDRESS per query of the
-// launch, written by k_resolve_filter_groups — nullptr for a query whose group is not in the caller's table.  Such launches
+// launch, written by k_resolve_filter_groups (one table) or k_resolve_filter_group_batches (a table per batch of the launch) —
+// nullptr for a query whose group is not in the caller's table.  Such launches
 // run the k_search_groups / k_search_solo_groups kernels (below): the lookup costs the walker a vector register wherever it
 // is compiled in, so the kernels of every other launch do not contain it.
 constexpr uint64_t FILTER_PER_QUERY = 1ull << 63;
@@ -2532,6 +2534,27 @@ __global__ __launch_bounds__(256) void k_resolve_filter_groups(const unsigned lo
 		return;
 	const uint32_t group = group_of[q];
 	bitmap_of[q] = group < n_groups ? allowed + (size_t)group * (size_t)words : nullptr;
+}
+
+// The same ahead of a launch that answers several batches, each under its own table (vss_search_multi_filtered_device_begin):
+// the launch numbers its queries q = batch * n_per_batch + row, and query q takes the bitmap its OWN batch's table holds for
+// it (host::filter_group_word_offset — the arithmetic the CPU check runs).  The descriptors travel by value in the kernel
+// arguments (32 x 24 bytes): nothing is allocated, copied or waited for on the launch path.
+struct ResolveBatchesArgs {
+	host::FilterGroupBatch batch[host::MAX_FILTER_GROUP_BATCHES];
+	uint64_t words;
+	uint32_t n_per_batch;
+	uint32_t n_queries;
+	const unsigned long long **bitmap_of;
+};
+
+__global__ __launch_bounds__(256) void k_resolve_filter_group_batches(ResolveBatchesArgs a) {
+	const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+	if (q >= a.n_queries)
+		return;
+	const host::FilterGroupBatch &d = a.batch[host::filter_group_batch_of(a.n_per_batch, q)];
+	const uint64_t at = host::filter_group_word_offset(d, a.n_per_batch, a.words, q);
+	a.bitmap_of[q] = at != host::NO_GROUP_BITMAP ? reinterpret_cast<const unsigned long long *>(d.allowed) + at : nullptr;
 }
 
 // Reused slots, before phase A: blank every list of the node (update() zeroes the node tape, index.hpp:2837-2840).

@@ -1160,7 +1160,7 @@ struct vss_index {
 	                       uint64_t k, uint64_t ef, int64_t *const *d_keys_out, float *const *d_dist_out,
 	                       uint32_t *const *d_count_out, const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0,
 	                       bool direct_io = false, bool gate = false, const uint32_t *d_group_of = nullptr,
-	                       uint64_t n_groups = 0) {
+	                       uint64_t n_groups = 0, const FilterGroupBatch *group_batches = nullptr) {
 		if (slot < 0 || slot >= MAX_CTX)
 			return fail("search context %d out of range (0..%d)", slot, MAX_CTX - 1);
 		if (n_batches < 1 || n_batches > MAX_COALESCED)
@@ -1228,6 +1228,24 @@ struct vss_index {
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits |= FILTER_PER_QUERY;
+		} else if (group_batches) {
+			// the same with one table PER BATCH of the launch (descriptor b = batch b's table, group numbers and group count): the
+			// descriptors go to the resolve kernel by value, so the launch path allocates, copies and waits for nothing once the
+			// address table has its size — cap_q, like the context's other per-query words
+			if (!c.d_group_bitmap.try_grow(cap_q))
+				return fail("filtered search: no device memory for the bitmap addresses of %llu queries", (unsigned long long)cap_q);
+			count_group_tables(c);
+			ResolveBatchesArgs r = {};
+			for (uint64_t b = 0; b != n_batches; ++b)
+				r.batch[b] = group_batches[b];
+			r.words = filter_group_words(filter_bits);
+			r.n_per_batch = (uint32_t)per_batch;
+			r.n_queries = (uint32_t)nq;
+			r.bitmap_of = c.d_group_bitmap.p;
+			hipLaunchKernelGGL(k_resolve_filter_group_batches, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, c.stream, r);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits |= FILTER_PER_QUERY;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
@@ -1245,7 +1263,7 @@ struct vss_index {
 		a.max_level = max_level;
 		// rejected rows (tombstones, predicate) are traversed but not returned: the pending candidates wait in a register
 		// queue while the limit allows (RegQueue), in the unbounded queue in HBM otherwise or once a query outgrew the former
-		a.tomb = (tombstones || d_filter) ? (limit <= reg_queue_max_limit && search_reg_queue ? 1u : 2u) : 0u;
+		a.tomb = (tombstones || d_filter || group_batches) ? (limit <= reg_queue_max_limit && search_reg_queue ? 1u : 2u) : 0u;
 		a.list_cap_max = list_cap_max();
 		a.work = nullptr;
 		c.direct_io = direct_io;
@@ -2783,6 +2801,72 @@ int vss_search_multi_device_begin(vss_index *h, int context, uint64_t n_batches,
 				               (unsigned long long)b);
 		return h->search_begin_multi(context, n_batches, Q, (uint32_t)h->dim, per_batch, k, ef, out, out_d, out_counts, nullptr,
 		                             0, false, true);
+	})
+}
+
+// The filtered forms of the two calls above.  The caller's bitmaps, tables and group numbers are read by the launch AND by the
+// re-run rounds of vss_search_batch_end: they stay the caller's, valid and unchanged, until that returns.
+int vss_search_batch_filtered_device_begin(vss_index *h, int context, const float *Q, uint64_t nq, uint64_t k, uint64_t ef,
+                                           const uint64_t *d_allowed, uint64_t n_bits, int64_t *out, float *out_d,
+                                           uint32_t *out_counts) {
+	VSS_SHARED(h, {
+		VSS_CHECK_CALLER_CONTEXT(h, context)
+		if (nq && k && (!Q || !out || !out_counts))
+			return h->fail("vss_search_batch_filtered_device_begin: null query / row-id / count pointer");
+		if (nq && k && !d_allowed)
+			return h->fail("vss_search_batch_filtered_device_begin: filtered search needs a row-id bitmap");
+		return h->search_begin_multi(context, 1, &Q, (uint32_t)h->dim, nq, k, ef, &out, &out_d, &out_counts, d_allowed, n_bits,
+		                             false, true);
+	})
+}
+
+int vss_search_batch_filtered_groups_device_begin(vss_index *h, int context, const float *Q, uint64_t nq, uint64_t k,
+                                                  uint64_t ef, const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits,
+                                                  const uint32_t *group_of, int64_t *out, float *out_d,
+                                                  uint32_t *out_counts) {
+	VSS_SHARED(h, {
+		VSS_CHECK_CALLER_CONTEXT(h, context)
+		if (nq && k && (!Q || !out || !out_counts))
+			return h->fail("vss_search_batch_filtered_groups_device_begin: null query / row-id / count pointer");
+		VSS_CHECK_FILTER_GROUPS(h, "vss_search_batch_filtered_groups_device_begin")
+		return h->search_begin_multi(context, 1, &Q, (uint32_t)h->dim, nq, k, ef, &out, &out_d, &out_counts, allowed, n_bits,
+		                             false, true, group_of, n_groups);
+	})
+}
+
+int vss_search_multi_filtered_device_begin(vss_index *h, int context, uint64_t n_batches, const float *const *Q,
+                                           uint64_t per_batch, uint64_t k, uint64_t ef, const uint64_t *const *d_allowed,
+                                           const uint64_t *n_groups, uint64_t n_bits, const uint32_t *const *d_group_of,
+                                           int64_t *const *out, float *const *out_d, uint32_t *const *out_counts) {
+	VSS_SHARED(h, {
+		VSS_CHECK_CALLER_CONTEXT(h, context)
+		if (!Q || !out || !out_d || !out_counts || !d_allowed || !n_groups || !d_group_of)
+			return h->fail("vss_search_multi_filtered_device_begin: null table");
+		if (n_batches < 1 || n_batches > MAX_COALESCED)
+			return h->fail("1 to %d batches per launch", MAX_COALESCED);
+		static_assert((uint32_t)MAX_COALESCED == MAX_FILTER_GROUP_BATCHES, "one descriptor per batch of a launch");
+		FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES];
+		bool one_bitmap = true; // every batch filtered by the same single bitmap: a plain filtered launch
+		for (uint64_t b = 0; per_batch && k && b != n_batches; ++b) {
+			if (!Q[b] || !out[b] || !out_counts[b]) // only d_out_distances[b] may be NULL
+				return h->fail("vss_search_multi_filtered_device_begin: null query / row-id / count pointer for batch %llu",
+				               (unsigned long long)b);
+			if (!d_allowed[b])
+				return h->fail("vss_search_multi_filtered_device_begin: batch %llu needs its groups' row-id bitmaps",
+				               (unsigned long long)b);
+			if (!n_groups[b])
+				return h->fail("vss_search_multi_filtered_device_begin: batch %llu needs at least one group", (unsigned long long)b);
+			if (n_groups[b] > 0xFFFFFFFFull || !filter_group_table_fits(n_groups[b], n_bits))
+				return h->fail("vss_search_multi_filtered_device_begin: batch %llu: %llu groups of %llu bits are more than a table "
+				               "can hold", (unsigned long long)b, (unsigned long long)n_groups[b], (unsigned long long)n_bits);
+			batches[b] = FilterGroupBatch {d_allowed[b], d_group_of[b], n_groups[b]};
+			one_bitmap &= !d_group_of[b] && d_allowed[b] == d_allowed[0];
+		}
+		if (!per_batch || !k || one_bitmap)
+			return h->search_begin_multi(context, n_batches, Q, (uint32_t)h->dim, per_batch, k, ef, out, out_d, out_counts,
+			                             per_batch && k ? d_allowed[0] : nullptr, n_bits, false, true);
+		return h->search_begin_multi(context, n_batches, Q, (uint32_t)h->dim, per_batch, k, ef, out, out_d, out_counts, nullptr,
+		                             n_bits, false, true, nullptr, 0, batches);
 	})
 }
 

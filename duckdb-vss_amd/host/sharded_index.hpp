@@ -119,6 +119,10 @@ public:
 	std::unique_ptr<HNSWIndexStats> ShardStats(idx_t g) {
 		return shards.at(g).index->GetStats();
 	}
+	// the engine's handle of one shard (filter_probe_harness.cpp asks every shard on its own and merges the answers itself)
+	vss_index *ShardHandle(idx_t g) {
+		return shards.at(g).index->Handle();
+	}
 	// "rccl": one all-gather per probe over one communicator per device; "peer": hipMemcpyPeerAsync to the merging device
 	const char *ExchangeKind() const {
 		return comms.empty() ? "peer" : "rccl";
@@ -333,8 +337,10 @@ public:
 
 	// ---- the same probe with a predicate pushed into the traversal (vss_search_batch_filtered_device per shard): a row is
 	// admitted iff it is live and bit `rowid` of `allowed` is set.  The bitmap is over GLOBAL row ids, (n_bits + 63) / 64 host
-	// words; it is uploaded once per device that holds a shard, not once per shard.  Same exchange and merge as SearchBatch.
-	// (The filtered entry point of the engine returns when its shard has answered, so the shards answer one after the other.)
+	// words; it is uploaded once per device that holds a shard, not once per shard.  Same exchange and merge as SearchBatch, and
+	// like it every shard is started through the engine's _begin form before the first is waited for: all G search at once.
+	// The uploaded bitmap stays in bitmaps[] until every shard's vss_search_batch_end has returned (the engine reads it again when
+	// it re-runs a query), on the error path too: DrainProbes.
 	void SearchBatchFiltered(const float *queries, idx_t n, idx_t k, idx_t ef, const uint64_t *allowed, idx_t n_bits,
 	                         row_t *out_rowids, float *out_distances, uint32_t *out_counts) {
 		if (!n || !k)
@@ -353,13 +359,18 @@ public:
 			}
 			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmap");
 		}
-		Probe(
-		    queries, n, k, out_rowids, out_distances, out_counts,
-		    [&](Shard &s, row_t *keys, float *dist) {
-			    Vss(s, vss_search_batch_filtered_device(s.index->Handle(), s.d_q, n, k, ef, bitmaps[s.bitmap].words, n_bits, keys,
-			                                            dist, s.d_cnt));
-		    },
-		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		try {
+			Probe(
+			    queries, n, k, out_rowids, out_distances, out_counts,
+			    [&](Shard &s, row_t *keys, float *dist) {
+				    Vss(s, vss_search_batch_filtered_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, bitmaps[s.bitmap].words,
+				                                                  n_bits, keys, dist, s.d_cnt));
+			    },
+			    [&](Shard &s) { Vss(s, vss_search_batch_end(s.index->Handle(), 0)); });
+		} catch (...) {
+			DrainProbes();
+			throw;
+		}
 	}
 
 	// ---- the same probe with a predicate PER QUERY (vss_search_batch_filtered_groups_device per shard): the chunk of a join whose
@@ -400,13 +411,19 @@ public:
 			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
 			Hip(hipMemcpy(b.group_of, group_of, n * sizeof(uint32_t), hipMemcpyHostToDevice), "copy groups");
 		}
-		Probe(
-		    queries, n, k, out_rowids, out_distances, out_counts,
-		    [&](Shard &s, row_t *keys, float *dist) {
-			    Vss(s, vss_search_batch_filtered_groups_device(s.index->Handle(), s.d_q, n, k, ef, bitmaps[s.bitmap].words, n_groups,
-			                                                   n_bits, bitmaps[s.bitmap].group_of, keys, dist, s.d_cnt));
-		    },
-		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		try {
+			Probe(
+			    queries, n, k, out_rowids, out_distances, out_counts,
+			    [&](Shard &s, row_t *keys, float *dist) {
+				    Vss(s, vss_search_batch_filtered_groups_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, bitmaps[s.bitmap].words,
+				                                                         n_groups, n_bits, bitmaps[s.bitmap].group_of, keys, dist,
+				                                                         s.d_cnt));
+			    },
+			    [&](Shard &s) { Vss(s, vss_search_batch_end(s.index->Handle(), 0)); });
+		} catch (...) {
+			DrainProbes();
+			throw;
+		}
 	}
 
 	// ---- brute force over every live row of every shard (vss_search_exact_batch_device per shard, the same exchange and
@@ -427,6 +444,17 @@ public:
 	}
 
 private:
+	// An error between launch and finish of a filtered probe: every shard's probe is completed and its stream drained before the
+	// error leaves the call, so that no kernel (and no re-run round of vss_search_batch_end) still reads the tables in bitmaps[]
+	// when a later call grows or frees them, and context 0 of every shard is free again.
+	void DrainProbes() noexcept {
+		for (auto &s : shards) {
+			(void)hipSetDevice(s.device);
+			(void)vss_search_batch_end(s.index->Handle(), 0);
+			(void)hipStreamSynchronize(s.stream);
+		}
+	}
+
 	// One probe: `launch(shard, keys, dist)` starts (or runs) the shard's search of the uploaded batch into the given device
 	// cells, `finish(shard)` returns when they are valid; the answers are exchanged and merged, results to the host.
 	template <class Launch, class Finish>

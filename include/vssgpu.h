@@ -163,7 +163,8 @@ int vss_search_batch_filtered_device(vss_index *index, const float *d_queries, u
  * form: a group_of[q] >= n_groups is refused before anything is launched (the message names the first such query).  Device
  * form: the engine does not copy group_of back to look; such a query is answered as if its predicate admitted nothing —
  * count 0, cells -1 / +inf — and nothing outside the n_groups * words words is read.
- * Blocking calls only: the pipelined _begin form and the multi-batch launch below take no predicate per query. */
+ * The pipelined and multi-batch forms are vss_search_batch_filtered_groups_device_begin and
+ * vss_search_multi_filtered_device_begin, below. */
 int vss_search_batch_filtered_groups(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
                                      const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
                                      int64_t *out_rowids, float *out_distances, uint32_t *out_counts);
@@ -189,8 +190,48 @@ int vss_search_batch_device_begin(vss_index *index, int context, const float *d_
 int vss_search_multi_device_begin(vss_index *index, int context, uint64_t n_batches, const float *const *d_queries,
                                   uint64_t n_per_batch, uint64_t k, uint64_t ef, int64_t *const *d_out_rowids,
                                   float *const *d_out_distances, uint32_t *const *d_out_counts);
+/* Pipelined forms of vss_search_batch_filtered_device and vss_search_batch_filtered_groups_device: a pipeline thread of a
+ * join with a WHERE keeps its own context, as vss_search_batch_device_begin gives an unfiltered one.  Each query gets, bit for
+ * bit (row ids, f32 distance bits, count), what vss_search_batch_filtered_device returns for it alone under its own bitmap and
+ * the same n_bits: tombstones excluded, rejected rows traversed, row ids >= n_bits rejected, set padding bits after n_bits
+ * admit nothing, whatever follows them in memory.  Groups form: a d_group_of[q] >= n_groups is answered as the blocking
+ * device form answers it — count 0, cells -1 / +inf, nothing outside the n_groups * words words read.
+ * THE ONE NEW OBLIGATION: the bitmap, the table and the group numbers stay the caller's.  They must remain valid and unchanged
+ * until vss_search_batch_end(context) returns — the rounds of _end that re-run a query which outgrew its scratch read them
+ * again.
+ * VSS_ERROR before anything is enqueued: context out of range or already in flight; a NULL query / row-id / count / bitmap
+ * pointer, d_group_of NULL, n_groups == 0 or a table no size_t can hold (with n_queries and k > 0); no device memory for the
+ * queries' bitmap addresses.  n_queries == 0 or k == 0: VSS_OK, nothing pending.  An empty index answers as the unfiltered
+ * forms do.  A mutating call while such a probe is in flight is refused. */
+int vss_search_batch_filtered_device_begin(vss_index *index, int context, const float *d_queries, uint64_t n_queries,
+                                           uint64_t k, uint64_t ef, const uint64_t *d_allowed, uint64_t n_bits,
+                                           int64_t *d_out_rowids, float *d_out_distances, uint32_t *d_out_counts);
+int vss_search_batch_filtered_groups_device_begin(vss_index *index, int context, const float *d_queries, uint64_t n_queries,
+                                                  uint64_t k, uint64_t ef, const uint64_t *d_allowed, uint64_t n_groups,
+                                                  uint64_t n_bits, const uint32_t *d_group_of, int64_t *d_out_rowids,
+                                                  float *d_out_distances, uint32_t *d_out_counts);
+/* vss_search_multi_device_begin with predicates: every batch is one join chunk with its OWN table.  The four tables
+ * d_queries / d_allowed / n_groups / d_group_of and the three output tables are host arrays of n_batches entries, read before
+ * the call returns; what d_allowed[b] and d_group_of[b] point AT is device memory under the obligation above.
+ *   d_allowed[b]   batch b's n_groups[b] (>= 1) bitmaps end to end, each (n_bits + 63) / 64 words; one n_bits for the launch
+ *   d_group_of[b]  n_per_batch group numbers (a correlated predicate), or NULL: every query of batch b takes bitmap 0 of its
+ *                  table (an uncorrelated predicate: a one-bitmap table).  Tables of different batches may be one address.
+ * Every query gets what vss_search_batch_filtered_device returns for it alone under its own bitmap (the contract above); a
+ * group number >= n_groups[b] gives count 0, cells -1 / +inf, and nothing outside batch b's n_groups[b] * words words is
+ * read.  d_out_distances[b] may be NULL.  A launch whose batches all have d_group_of[b] == NULL and the same d_allowed[b]
+ * runs as a plain one-bitmap launch.  After vss_search_batch_end, vss_last_search_stats / vss_last_search_shape / vss_timing
+ * describe the launch as they do for vss_search_multi_device_begin: the counters cover all the batches.
+ * VSS_ERROR before anything is enqueued, naming the batch where there is one: context out of range or already in flight;
+ * n_batches outside 1..32; a NULL table array; a NULL query, row-id, count or bitmap pointer of a batch; n_groups[b] == 0; a
+ * table no size_t can hold; no device memory for the queries' bitmap addresses.  n_per_batch == 0 or k == 0: VSS_OK, nothing
+ * pending. */
+int vss_search_multi_filtered_device_begin(vss_index *index, int context, uint64_t n_batches, const float *const *d_queries,
+                                           uint64_t n_per_batch, uint64_t k, uint64_t ef, const uint64_t *const *d_allowed,
+                                           const uint64_t *n_groups, uint64_t n_bits, const uint32_t *const *d_group_of,
+                                           int64_t *const *d_out_rowids, float *const *d_out_distances,
+                                           uint32_t *const *d_out_counts);
 int vss_search_batch_end(vss_index *index, int context);
-/* Pipelining policy of the two _begin calls above (default on; tuning, no reference counterpart, results never depend on it).  A launch of the search engine occupies every compute
+/* Pipelining policy of the _begin calls above (default on; tuning, no reference counterpart, results never depend on it).  A launch of the search engine occupies every compute
  * unit, so a second one issued immediately would wait in its hardware queue with its clock running.  With gating on, _begin
  * returns only once the launch begun before it (on another context of this index, or by another index on the same device —
  * e.g. row-range shards sharing one GPU) has handed out its last query — the

@@ -7,6 +7,12 @@ The benchmark's mixture (1M x 128 l2sq by default), the reference's default inde
   2. tenants: 1024 queries in 16 equal groups whose bitmaps admit 1/16 of the rows each, and 204 queries in 4 such groups — one
      grouped call against one filtered call per group over that group's queries (what a caller had to do before), both as
      host-pointer wall time and as summed kernel ms, median of five; the answers of both must be identical.
+  3. eight join chunks of 204 queries, each with its own table of 4 tenants: ONE vss_search_multi_filtered_device_begin + _end
+     against eight blocking vss_search_batch_filtered_groups_device calls.
+  4. three 1024-query batches under one bitmap each: three contexts in flight (vss_search_batch_filtered_device_begin) against
+     three blocking vss_search_batch_filtered_device calls.
+     Legs 3 and 4 alternate their two sides in this process, five repetitions after a warm-up, host clock between
+     synchronisations; identical answers required.  A library without these calls stops after leg 2.
     python tools/probe_filter_groups.py [rows [dim [metric [ef]]]]"""
 import os
 import sys
@@ -119,5 +125,113 @@ for nq, n_groups in ((1024, 16), (204, 4)):
     print("  wall: grouped / per-group = %.3f; kernel: %.3f; re-run queries of the grouped call %d; full answers %d of %d; identical %s"
           % (np.median(gw[1:]) / np.median(pw[1:]), np.median(gk[1:]) / np.median(pk[1:]), reruns,
              int((grouped[2] == K).sum()), nq, same), flush=True)
+if not hasattr(idx, "search_multi_filtered_begin"):
+    print("this library has no pipelined filtered calls: done\nDIFFERENCES: %d" % bad)
+    sys.exit(1 if bad else 0)
+
+# ---- 3. / 4. the pipelined and multi-batch forms against the sequence of blocking device calls they replace.  Device pointers on
+# both sides, the two sides alternating in this process; every timed call returns with the device idle (vss_search_batch_end and
+# the blocking calls synchronise), so the host clock around it, taken after a torch.cuda.synchronize(), measures it whole.
+
+
+def to_dev(a):
+    a = np.ascontiguousarray(a)
+    signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32}.get(a.dtype)
+    return torch.from_numpy(a.view(signed) if signed else a).to(dev)
+
+
+def cells(nq):
+    return (torch.empty((nq, K), dtype=torch.int64, device=dev), torch.empty((nq, K), dtype=torch.float32, device=dev),
+            torch.empty(nq, dtype=torch.int32, device=dev))
+
+
+def alternate(new_side, old_side):
+    """[(wall ms, kernel ms)] of both sides, REPEATS each after one warm-up, new / old / new / old ..."""
+    new, old = [], []
+    for r in range(REPEATS + 1):
+        for side, into in ((new_side, new), (old_side, old)):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            k_ms = side()
+            into.append(((time.perf_counter() - t) * 1e3, k_ms))
+    return new[1:], old[1:]
+
+
+def report(what, new_name, old_name, new, old, same):
+    line("%s: %s" % (what, new_name), [w for w, _ in new], [k for _, k in new])
+    line("%s: %s" % (what, old_name), [w for w, _ in old], [k for _, k in old])
+    print("  wall: new / blocking = %.3f; kernel: %.3f; identical %s" % (
+        np.median([w for w, _ in new]) / np.median([w for w, _ in old]),
+        np.median([k for _, k in new]) / np.median([k for _, k in old]), same), flush=True)
+
+
+def equal(a, b):
+    return all(bool(torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y))
+               for x, y in zip(a, b))
+
+
+# 3. eight join chunks of 204 queries, each chunk with its own table of 4 tenants (of 16): one launch against eight
+CHUNKS, PER = 8, 204
+Q3 = gen.rows(bench.QUERY_SEED, 1, CHUNKS * PER).contiguous()
+d_q3 = [Q3[c * PER:(c + 1) * PER].contiguous() for c in range(CHUNKS)]
+d_tables = [to_dev(np.stack([bitmap_of(tenant == (2 * c + j) % 16) for j in range(4)])) for c in range(CHUNKS)]
+d_groups = [to_dev(((np.arange(PER) + c) % 4).astype(np.uint32)) for c in range(CHUNKS)]
+out_new, out_old = [cells(PER) for _ in range(CHUNKS)], [cells(PER) for _ in range(CHUNKS)]
+torch.cuda.synchronize()
+
+
+def multi_launch():
+    idx.search_multi_filtered_begin(1, [t.data_ptr() for t in d_q3], PER, K, EF, [t.data_ptr() for t in d_tables], [4] * CHUNKS, rows,
+                                    [t.data_ptr() for t in d_groups], [o[0].data_ptr() for o in out_new],
+                                    [o[1].data_ptr() for o in out_new], [o[2].data_ptr() for o in out_new])
+    idx.search_end(1)
+    return idx.timing()["search_kernel_ms"]
+
+
+def eight_blocking():
+    total = 0.0
+    for c in range(CHUNKS):
+        idx.search_batch_filtered_groups_device(d_q3[c].data_ptr(), PER, K, EF, d_tables[c].data_ptr(), 4, rows, d_groups[c].data_ptr(),
+                                                *[t.data_ptr() for t in out_old[c]])
+        total += idx.timing()["search_kernel_ms"]
+    return total
+
+
+new, old = alternate(multi_launch, eight_blocking)
+same = all(equal(a, b) for a, b in zip(out_new, out_old))
+bad += not same
+report("8 chunks x 204 queries, 4 tenants each", "ONE multi-batch launch", "8 blocking grouped calls", new, old, same)
+
+# 4. three 1024-query batches, one bitmap each: three contexts in flight against three blocking calls
+d_q4 = [to_dev(Q) for _ in range(3)]
+d_bitmaps = [to_dev(half), to_dev(~half), to_dev(bitmap_of(rng.random(rows) < 0.1))]
+out_new, out_old = [cells(1024) for _ in range(3)], [cells(1024) for _ in range(3)]
+torch.cuda.synchronize()
+
+
+def three_in_flight():
+    for c in range(3):
+        idx.search_filtered_begin(c, d_q4[c].data_ptr(), 1024, K, EF, d_bitmaps[c].data_ptr(), rows, *[t.data_ptr() for t in out_new[c]])
+    total = 0.0
+    for c in range(3):
+        idx.search_end(c)
+        total += idx.timing()["search_kernel_ms"]
+    return total
+
+
+def three_blocking():
+    total = 0.0
+    for c in range(3):
+        idx._check(idx.lib.vss_search_batch_filtered_device(idx.h, d_q4[c].data_ptr(), 1024, K, EF, d_bitmaps[c].data_ptr(), rows,
+                                                            *[t.data_ptr() for t in out_old[c]]))
+        total += idx.timing()["search_kernel_ms"]
+    return total
+
+
+new, old = alternate(three_in_flight, three_blocking)
+same = all(equal(a, b) for a, b in zip(out_new, out_old))
+bad += not same
+report("3 batches x 1024 queries, one bitmap each", "three contexts in flight", "3 blocking filtered calls", new, old, same)
+print("  (kernel ms of launches in flight together overlap: their sum is not the elapsed time; compare the wall times)")
 print("DIFFERENCES: %d" % bad)
 sys.exit(1 if bad else 0)
