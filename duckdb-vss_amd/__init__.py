@@ -89,6 +89,9 @@ SIGNATURES = {
     "vss_search_batch_end": (_int, [_vp, _int]),
     "vss_search_exact_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_exact_batch_device": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "vss_search_exact_batch_filtered_groups": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_exact_batch_filtered_groups_device": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "vss_last_exact_filtered": (_int, [_vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -328,6 +331,40 @@ class GpuIndex:
         """The same over raw device pointers (the caller keeps the tensors alive); blocking."""
         self._check(self.lib.vss_search_batch_filtered_groups_device(self.h, d_Q, nq, k, ef, d_bitmaps, n_groups, n_bits,
                                                                      d_group_of, d_keys, d_dist, d_counts))
+
+    def search_exact_batch_filtered_groups(self, Q, k, bitmaps, n_bits, group_of=None):
+        """vss_search_exact_batch_filtered_groups: the exact top-k of query q among the live rows that row `group_of[q]` of
+        `bitmaps` admits (group_of=None: every query takes row 0), scoring the admitted rows only."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        bitmaps = np.ascontiguousarray(bitmaps, dtype=np.uint64)
+        words = (n_bits + 63) // 64
+        if bitmaps.ndim != 2 or bitmaps.shape[1] != words:
+            raise ValueError("bitmaps must be n_groups x %d uint64 words for %d bits, got shape %r"
+                             % (words, n_bits, bitmaps.shape))
+        nq = len(Q)
+        if group_of is not None:
+            group_of = np.ascontiguousarray(group_of, dtype=np.uint32)
+            if group_of.shape != (nq,):
+                raise ValueError("group_of must name one group per query: %d queries, shape %r" % (nq, group_of.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        self._check(self.lib.vss_search_exact_batch_filtered_groups(self.h, _p(Q), nq, k, _p(bitmaps), len(bitmaps), n_bits,
+                                                                    _p(group_of), _p(keys), _p(d), _p(cnt)))
+        return keys, d, cnt
+
+    def search_exact_batch_filtered_groups_device(self, d_Q, nq, k, d_bitmaps, n_groups, n_bits, d_group_of, d_keys, d_dist,
+                                                  d_counts):
+        """The same over raw device pointers (d_group_of may be None); blocking."""
+        self._check(self.lib.vss_search_exact_batch_filtered_groups_device(self.h, d_Q, nq, k, d_bitmaps, n_groups, n_bits,
+                                                                           d_group_of, d_keys, d_dist, d_counts))
+
+    def last_exact_filtered(self):
+        """[admitted rows listed over the groups that had queries, (query, row) distances computed, passes, bytes of list
+        scratch held] of the last search_exact_batch_filtered_groups call."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.vss_last_exact_filtered(self.h, _p(out)))
+        return out
 
     def search_batch_device(self, d_Q, nq, k, ef, d_keys, d_dist, d_counts, exact=False):
         if exact:

@@ -1,0 +1,273 @@
+// exact_filtered_kernels.h — the kernels of vss_search_exact_batch_filtered_groups: exact top-k under per-query predicates that
+// scores only the rows a query's group admits.  The host plan is exact_filtered_plan.h.
+//
+//   listing    k_filter_list_count -> k_filter_list_scan -> k_filter_list_scatter: for every group IN USE, the ASCENDING list of
+//              the live slots its bitmap admits.  A wave owns FL_WAVE_SLOTS consecutive slots and keeps their keys in registers:
+//              keys[slot] is read once per launch, however many groups the launch lists.  Ascending, so that position order in a
+//              list is slot order and ties come back by slot.
+//   scoring    k_exact_filtered_scores: k_exact_metric_scores with the rows gathered through a list — the same lane-to-component
+//              partition, accumulate4 / group_butterfly / finish_distance order, hence the bits k_exact_rerank computes.  One
+//              launch covers every group of a pass through the plan's tile table.
+//   selection  k_exact_select_lists: k_exact_select's plain mode with one column count per query; it keeps (distance, SLOT)
+//              pairs, looked up through the list, so the running lists go to k_exact_rerank as they are.
+//
+// Scratch: the lists of one pass hold at most max(B, rows) entries (exact_filtered_plan.h); the block counts take one word per
+// (group in use, FL_WAVE_SLOTS slots).
+#pragma once
+#include "exact_filtered_plan.h"
+#include "exact_kernels.h"
+
+namespace vss {
+
+#ifdef VSS_ENGINE_TU
+
+constexpr uint32_t FL_KEYS_PER_LANE = 8, FL_WAVE_SLOTS = 64 * FL_KEYS_PER_LANE;
+
+struct FilterListArgs {
+	const int64_t *keys;
+	uint32_t rows, n_blocks;  // n_blocks = ceil(rows / FL_WAVE_SLOTS): one wave each
+	const uint64_t *table;    // the caller's bitmaps, `words` words each
+	uint64_t words, n_bits;
+	const uint32_t *groups;   // table group of used group u
+	uint32_t u_begin, u_end;  // the used groups this launch lists
+	uint32_t *counts;         // [u][n_blocks]: admitted rows per block (count), then where the block's rows start (scan)
+	uint32_t *totals;         // [u]: the list's length (scan)
+	const uint32_t *list_base; // [u]: where the list starts in `lists` (scatter)
+	uint32_t *lists;
+};
+
+// keys of slots block * FL_WAVE_SLOTS + s * 64 + lane, s = 0 .. FL_KEYS_PER_LANE - 1: ascending in (s, lane)
+__device__ __forceinline__ void filter_list_keys(const FilterListArgs &a, uint32_t block, int64_t (&key)[FL_KEYS_PER_LANE]) {
+#pragma unroll
+	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+		const uint32_t slot = block * FL_WAVE_SLOTS + s * 64 + lane_id();
+		key[s] = slot < a.rows ? a.keys[slot] : host::EXACT_FILTER_FREE_KEY;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_filter_list_count(FilterListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks) // (wave-uniform; no barrier below)
+		return;
+	int64_t key[FL_KEYS_PER_LANE];
+	filter_list_keys(a, block, key);
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint64_t *bitmap = a.table + (size_t)a.groups[u] * a.words;
+		uint32_t n = 0;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			n += __popcll(__ballot(host::exact_filter_admits(key[s], bitmap, a.n_bits)));
+		if (lane_id() == 0)
+			a.counts[(size_t)u * a.n_blocks + block] = n;
+	}
+}
+
+// one workgroup per used group: counts[u][*] becomes its exclusive prefix sum, totals[u] the sum
+__global__ __launch_bounds__(256) void k_filter_list_scan(FilterListArgs a) {
+	__shared__ uint32_t wave_sum[4];
+	uint32_t *row = a.counts + (size_t)(a.u_begin + blockIdx.x) * a.n_blocks;
+	const int lane = lane_id(), wave = threadIdx.x >> 6;
+	uint32_t running = 0;
+	for (uint32_t base = 0; base < a.n_blocks; base += 256) {
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t v = i < a.n_blocks ? row[i] : 0u;
+		uint32_t incl = v;
+		for (int o = 1; o < 64; o <<= 1) {
+			const uint32_t up = __shfl_up(incl, o);
+			if (lane >= o)
+				incl += up;
+		}
+		if (lane == 63)
+			wave_sum[wave] = incl;
+		__syncthreads();
+		uint32_t before = running;
+		for (int w = 0; w < wave; ++w)
+			before += wave_sum[w];
+		if (i < a.n_blocks)
+			row[i] = before + incl - v;
+		running += wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0)
+		a.totals[a.u_begin + blockIdx.x] = running;
+}
+
+__global__ __launch_bounds__(256) void k_filter_list_scatter(FilterListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks)
+		return;
+	int64_t key[FL_KEYS_PER_LANE];
+	filter_list_keys(a, block, key);
+	const int lane = lane_id();
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint64_t *bitmap = a.table + (size_t)a.groups[u] * a.words;
+		// the rows this block found in the count pass (the index is read-locked in between: the same rows now)
+		uint32_t at = a.list_base[u] + a.counts[(size_t)u * a.n_blocks + block];
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+			const bool in = host::exact_filter_admits(key[s], bitmap, a.n_bits);
+			const unsigned long long m = __ballot(in);
+			if (in)
+				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;
+			at += __popcll(m);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Score rows t of `scores` are positions of the plan's group order (query order[t]); column c of a launch is list position
+// pos_begin + c of that query's list.  blockIdx.y = tile of the pass, blockIdx.x strides over the list positions.
+struct FilteredScoreArgs {
+	RowSpace sp;
+	const float *queries; // n_queries x q_stride
+	uint32_t q_stride, dim;
+	const uint32_t *order;
+	const host::ExactFilterTile *tiles; // of this pass
+	const uint32_t *lists;
+	uint32_t pos_begin, chunk_stride;
+	float *scores;
+};
+
+template <int MT>
+__global__ __launch_bounds__(256) void k_exact_filtered_scores(FilteredScoreArgs a) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char fs_smem[];
+	float4 *qs = reinterpret_cast<float4 *>(fs_smem); // [tile.n_queries][V], zero padded
+	const host::ExactFilterTile tile = a.tiles[blockIdx.y];
+	if (tile.list_length <= a.pos_begin) // (workgroup-uniform) this list ended in an earlier chunk
+		return;
+	const uint32_t pos_end = tile.list_length - a.pos_begin < a.chunk_stride ? tile.list_length : a.pos_begin + a.chunk_stride;
+	const uint32_t V = a.sp.V, G = a.sp.G;
+	const uint32_t nqt = tile.n_queries; // <= MS_QT
+	for (uint32_t i = threadIdx.x; i < nqt * V * 4; i += blockDim.x) {
+		const uint32_t t = i / (V * 4), c = i - t * (V * 4);
+		reinterpret_cast<float *>(qs)[i] = c < a.dim ? a.queries[(size_t)a.order[tile.first_query + t] * a.q_stride + c] : 0.f;
+	}
+	__syncthreads();
+	const uint32_t lane = threadIdx.x & 63, g = lane & (G - 1), sub = lane >> a.sp.logG, RG = 64u >> a.sp.logG;
+	float qa2[MS_QT];
+#pragma unroll
+	for (int t = 0; t < MS_QT; ++t)
+		qa2[t] = (MT == 1 && (uint32_t)t < nqt) ? wave_query_norm(a.sp, qs + (size_t)t * V) : 0.f;
+	const uint32_t *list = a.lists + tile.list_offset;
+	const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = gridDim.x * (blockDim.x >> 6);
+	// (64-bit position: pos_begin + wave * RG may pass 2^32 on the last stride of a list of nearly 2^32 entries)
+	for (uint64_t base = (uint64_t)a.pos_begin + (uint64_t)wave * RG; base < pos_end; base += (uint64_t)n_waves * RG) {
+		const uint64_t pos = base + sub;
+		const bool valid = pos < pos_end;
+		const uint32_t row = list[valid ? (uint32_t)pos : pos_end - 1]; // 64 / G entries side by side
+		const float4 *rp = a.sp.vectors + (size_t)row * V;
+		float ab[MS_QT], b2 = 0.f, unused = 0.f;
+#pragma unroll
+		for (int t = 0; t < MS_QT; ++t)
+			ab[t] = 0.f;
+		for (uint32_t c = g; c < V; c += G) {
+			const float4 x = rp[c];
+#pragma unroll
+			for (int t = 0; t < MS_QT; ++t)
+				if ((uint32_t)t < nqt) {
+					if (MT == 1 && t > 0) // (the row's own sum of squares does not depend on the query: once is enough)
+						accumulate4<2>(qs[(size_t)t * V + c], x, ab[t], unused);
+					else
+						accumulate4<MT>(qs[(size_t)t * V + c], x, ab[t], b2);
+				}
+		}
+		if (MT == 1)
+			b2 = group_butterfly(b2, G);
+#pragma unroll
+		for (int t = 0; t < MS_QT; ++t)
+			if ((uint32_t)t < nqt) {
+				const float d = finish_distance<MT>(group_butterfly(ab[t], G), qa2[t], b2);
+				if (g == 0 && valid)
+					a.scores[(size_t)(tile.first_query + t) * a.chunk_stride + ((uint32_t)pos - a.pos_begin)] = d;
+			}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_exact_select's plain mode where every query has its own column count: workgroup b serves position query_begin + b of the
+// group order, whose list is lists[offset[t] .. offset[t] + length[t]); this launch's columns are its positions from pos_begin
+// on.  Candidates are (distance, slot): lists ascend, so that order is the order by (distance, position).
+struct SelectListsArgs {
+	const float *scores;
+	uint32_t chunk_stride, pos_begin, query_begin, KP;
+	const uint32_t *offset, *length, *lists;
+	float *best_s;
+	uint32_t *best_i;
+};
+
+__global__ __launch_bounds__(SEL_THREADS) void k_exact_select_lists(SelectListsArgs a) {
+	__shared__ float buf_s[SEL_CAP];
+	__shared__ uint32_t buf_i[SEL_CAP];
+	__shared__ float old_s[SEL_KP_MAX];
+	__shared__ uint32_t old_i[SEL_KP_MAX];
+	__shared__ float red_s[SEL_THREADS / 64];
+	__shared__ uint32_t red_i[SEL_THREADS / 64];
+	__shared__ uint32_t cnt;
+	const uint32_t t = a.query_begin + blockIdx.x;
+	const int tid = threadIdx.x;
+	const uint32_t length = a.length[t];
+	if (length <= a.pos_begin) // (workgroup-uniform) nothing of this query's list in this chunk
+		return;
+	const uint32_t cols = length - a.pos_begin < a.chunk_stride ? length - a.pos_begin : a.chunk_stride;
+	const uint32_t *slots = a.lists + a.offset[t] + a.pos_begin;
+	const float *row = a.scores + (size_t)t * a.chunk_stride;
+	float *bs = a.best_s + (size_t)t * a.KP;
+	uint32_t *bi = a.best_i + (size_t)t * a.KP;
+	for (uint32_t i = tid; i < a.KP; i += SEL_THREADS)
+		old_s[i] = bs[i], old_i[i] = bi[i];
+	if (tid == 0)
+		cnt = 0;
+	__syncthreads();
+	const float tau_s = old_s[a.KP - 1];
+	const uint32_t tau_i = old_i[a.KP - 1];
+	for (uint32_t c = tid; c < cols; c += SEL_THREADS) {
+		const float s = row[c];
+		if (s < 3.0e38f && !(tau_s < s)) { // (the slot is looked up only for what may enter)
+			const uint32_t idx = slots[c];
+			if (lex_less(s, idx, tau_s, tau_i)) {
+				const uint32_t p = atomicAdd(&cnt, 1u);
+				if (p < SEL_CAP)
+					buf_s[p] = s, buf_i[p] = idx;
+			}
+		}
+	}
+	__syncthreads();
+	const uint32_t n = cnt;
+	if (n == 0)
+		return;
+	const bool overflow = n > SEL_CAP;
+	// successive minima over (old top-K') U (buffer | whole chunk), strictly above the last one taken
+	float last_s = -__builtin_inff();
+	uint32_t last_i = 0;
+	bool first = true;
+	for (uint32_t out = 0; out < a.KP; ++out) {
+		float s = __builtin_inff();
+		uint32_t i = EMPTY_SLOT;
+		auto consider = [&](float cs, uint32_t ci) {
+			if ((first || lex_less(last_s, last_i, cs, ci)) && lex_less(cs, ci, s, i))
+				s = cs, i = ci;
+		};
+		for (uint32_t j = tid; j < a.KP; j += SEL_THREADS)
+			consider(old_s[j], old_i[j]);
+		if (!overflow) {
+			for (uint32_t j = tid; j < n; j += SEL_THREADS)
+				consider(buf_s[j], buf_i[j]);
+		} else {
+			for (uint32_t c = tid; c < cols; c += SEL_THREADS)
+				consider(row[c], slots[c]);
+		}
+		block_argmin(s, i, red_s, red_i);
+		if (tid == 0)
+			bs[out] = s, bi[out] = i;
+		if (i == EMPTY_SLOT) { // nothing left: the rest stays (+inf, EMPTY)
+			for (uint32_t j = out + 1 + tid; j < a.KP; j += SEL_THREADS)
+				bs[j] = __builtin_inff(), bi[j] = EMPTY_SLOT;
+			break;
+		}
+		last_s = s, last_i = i, first = false;
+	}
+}
+
+#endif // VSS_ENGINE_TU
+
+} // namespace vss

@@ -27,6 +27,7 @@
 #include "launchers.h"
 #include "host_logic.h"
 #include "filter_groups.h"
+#include "exact_filtered_kernels.h"
 #include "row_codes.h"
 
 using namespace vss;
@@ -363,6 +364,13 @@ struct vss_index {
 	uint64_t last_exact_fallbacks = 0; // queries of the last exact call that were redone
 	bool exact_filter = true; // the select folded into the score tile's epilogue from the second chunk on (VSS_EXACT_FILTER=0: A/B)
 	uint64_t norms_valid_for = ~0ull; // value of `mutations` the norms were computed at
+	// vss_search_exact_batch_filtered_groups (exact_filtered_kernels.h), under exact_mu like the rest: the lists of one pass, the
+	// block counts of the groups in use, and the small tables of the plan.  exact_filter_budget = B, the entries the lists of
+	// one pass may hold where that is more than the index has rows (VSS_EXACT_FILTER_LIST_ENTRIES).
+	DevBuf<uint32_t> d_xf_lists, d_xf_counts, d_xf_tables;
+	uint64_t exact_filter_budget = EXACT_FILTER_LIST_ENTRIES;
+	uint64_t last_exact_filtered[4] = {0, 0, 0, 0}; // vss_last_exact_filtered
+	std::atomic<uint64_t> exact_filter_bytes {0};   // of the three buffers (vss_memory_usage, read without a lock)
 	uint64_t mutations = 0;
 
 	int fail(const char *fmt, ...) {
@@ -421,6 +429,8 @@ struct vss_index {
 		d_global_hash.free(), d_row_norm2.free(), d_q_norm2.free(), d_scores.free(), d_best_s.free(), d_qpad.free();
 		d_best_i.free(), d_cand_s.free(), d_cand_cnt.free(), d_cand_i.free();
 		d_norm_ext.free(), d_certified.free(), d_redo_map.free();
+		d_xf_lists.free(), d_xf_counts.free(), d_xf_tables.free();
+		exact_filter_bytes.store(0, std::memory_order_relaxed);
 		if (h_counters)
 			(void)hipHostFree(h_counters);
 		h_counters = nullptr;
@@ -1774,6 +1784,181 @@ struct vss_index {
 		return VSS_OK;
 	}
 
+	// ------------------------------------------------------------------ exact search under per-query predicates
+	// Carries out the plan of exact_filtered_plan.h: list the live admitted slots of every group in use, score each query
+	// against its group's list only, keep the K' smallest (distance, slot) pairs per query, re-rank.  Distances are the metric's
+	// own from the start, so nothing is certified and nothing redone.  group_of: HOST memory, or nullptr (all take bitmap 0).
+	int exact_filtered_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, const uint64_t *d_table,
+	                          uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, int64_t *d_keys_out, float *d_dist_out,
+	                          uint32_t *d_count_out) {
+		std::lock_guard<std::mutex> exact_lock(exact_mu); // scores, running lists and the index stream are shared
+		last_exact_fallbacks = 0;
+		std::fill(last_exact_filtered, last_exact_filtered + 4, 0);
+		if (k + 8 > SEL_KP_MAX)
+			return fail("exact filtered search supports k <= %d", SEL_KP_MAX - 8);
+		const uint32_t qt = (uint32_t)std::min<uint64_t>(MS_QT, (160 * 1024) / ((uint64_t)V * 16));
+		if (!qt)
+			return fail("exact filtered search: a row of %llu dimensions does not fit the scoring kernel's LDS", (unsigned long long)dim);
+		const uint64_t KP = k + 8, CH = 32768, rows = count;
+		ExactFilterPlan plan;
+		exact_filter_order(group_of, nq, n_groups, plan);
+		const uint64_t nu = plan.groups.size();
+		const uint64_t n_blocks = (rows + FL_WAVE_SLOTS - 1) / FL_WAVE_SLOTS;
+		// d_xf_tables: [groups nu][totals nu] | [list_base nu][order nq][offset nq][length nq][tiles 5 x (<= nq)]
+		const uint64_t at_totals = nu, at_base = 2 * nu, at_order = 3 * nu, at_offset = at_order + nq, at_length = at_offset + nq,
+		               at_tiles = at_length + nq;
+		static_assert(sizeof(ExactFilterTile) == 20, "five words per tile");
+		if (!d_xf_tables.try_grow(at_tiles + 5 * nq) || !d_xf_counts.try_grow(std::max<uint64_t>(nu * n_blocks, 1)) ||
+		    !d_scores.try_grow(nq * CH) || !d_best_s.try_grow(nq * KP) || !d_best_i.try_grow(nq * KP))
+			return fail("exact filtered search: no device memory for %llu queries over %llu groups in use", (unsigned long long)nq,
+			            (unsigned long long)nu);
+		auto count_scratch = [&] {
+			last_exact_filtered[3] = (d_xf_lists.n + d_xf_counts.n + d_xf_tables.n) * 4;
+			exact_filter_bytes.store(last_exact_filtered[3], std::memory_order_relaxed);
+		};
+		count_scratch();
+		ensure_events();
+		HIP_TRY(hipEventRecord(ev[0], stream));
+		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, nq * KP * 4, stream)); // 0x7F7F7F7F = 3.39e38 (acts as +inf)
+		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, nq * KP * 4, stream));
+		FilterListArgs l;
+		l.keys = d_keys.p, l.rows = (uint32_t)rows, l.n_blocks = (uint32_t)n_blocks;
+		l.table = d_table, l.words = filter_group_words(n_bits), l.n_bits = n_bits;
+		l.groups = d_xf_tables.p, l.totals = d_xf_tables.p + at_totals, l.list_base = d_xf_tables.p + at_base;
+		l.u_begin = 0, l.u_end = (uint32_t)nu;
+		l.counts = d_xf_counts.p, l.lists = nullptr;
+		const dim3 list_grid((uint32_t)((n_blocks + 3) / 4));
+		std::vector<uint32_t> lengths(nu);
+		if (nu && rows) { // (an empty index lists nothing: every length stays 0)
+			HIP_TRY(hipMemcpyAsync(d_xf_tables.p, plan.groups.data(), nu * 4, hipMemcpyHostToDevice, stream));
+			hipLaunchKernelGGL(k_filter_list_count, list_grid, dim3(256), 0, stream, l);
+			hipLaunchKernelGGL(k_filter_list_scan, dim3((uint32_t)nu), dim3(256), 0, stream, l);
+			HIP_TRY(hipMemcpyAsync(lengths.data(), l.totals, nu * 4, hipMemcpyDeviceToHost, stream));
+			HIP_TRY(hipStreamSynchronize(stream));
+		}
+		exact_filter_pack(lengths.data(), std::max<uint64_t>(exact_filter_budget, rows), qt, plan);
+		uint64_t entries_max = 0;
+		for (const ExactFilterPass &pass : plan.passes)
+			entries_max = std::max(entries_max, pass.entries);
+		if (!d_xf_lists.try_grow(std::max<uint64_t>(entries_max, 1)))
+			return fail("exact filtered search: no device memory for lists of %llu rows", (unsigned long long)entries_max);
+		count_scratch();
+		last_exact_filtered[0] = plan.listed, last_exact_filtered[1] = plan.distances, last_exact_filtered[2] = plan.passes.size();
+		{
+			std::vector<uint32_t> up(at_tiles - at_base + 5 * plan.tiles.size());
+			std::copy(plan.list_base.begin(), plan.list_base.begin() + nu, up.begin());
+			std::copy(plan.order.begin(), plan.order.end(), up.begin() + (at_order - at_base));
+			std::copy(plan.query_offset.begin(), plan.query_offset.end(), up.begin() + (at_offset - at_base));
+			std::copy(plan.query_length.begin(), plan.query_length.end(), up.begin() + (at_length - at_base));
+			if (!plan.tiles.empty())
+				std::memcpy(up.data() + (at_tiles - at_base), plan.tiles.data(), plan.tiles.size() * sizeof(ExactFilterTile));
+			HIP_TRY(hipMemcpyAsync(d_xf_tables.p + at_base, up.data(), up.size() * 4, hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipStreamSynchronize(stream)); // (`up` is pageable: the copy has left it before it goes)
+		}
+		l.lists = d_xf_lists.p;
+		FilteredScoreArgs m;
+		m.sp = view().sp;
+		m.queries = d_queries;
+		m.q_stride = q_stride, m.dim = (uint32_t)dim;
+		m.order = d_xf_tables.p + at_order;
+		m.lists = d_xf_lists.p;
+		m.chunk_stride = (uint32_t)CH;
+		m.scores = d_scores.p;
+		const uint32_t m_lds = qt * V * 16;
+		const void *m_fn = metric == 0   ? reinterpret_cast<const void *>(k_exact_filtered_scores<0>)
+		                   : metric == 1 ? reinterpret_cast<const void *>(k_exact_filtered_scores<1>)
+		                                 : reinterpret_cast<const void *>(k_exact_filtered_scores<2>);
+		HIP_TRY(hipFuncSetAttribute(m_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<uint32_t>(m_lds, 64 * 1024)));
+		SelectListsArgs s;
+		s.scores = d_scores.p;
+		s.chunk_stride = (uint32_t)CH;
+		s.KP = (uint32_t)KP;
+		s.offset = d_xf_tables.p + at_offset, s.length = d_xf_tables.p + at_length, s.lists = d_xf_lists.p;
+		s.best_s = d_best_s.p, s.best_i = d_best_i.p;
+		for (const ExactFilterPass &pass : plan.passes) {
+			const uint32_t n_tiles = pass.tile_end - pass.tile_begin;
+			if (!n_tiles)
+				continue; // (none of its groups admits a row)
+			l.u_begin = pass.group_begin, l.u_end = pass.group_end;
+			hipLaunchKernelGGL(k_filter_list_scatter, list_grid, dim3(256), 0, stream, l);
+			m.tiles = reinterpret_cast<const ExactFilterTile *>(d_xf_tables.p + at_tiles) + pass.tile_begin;
+			s.query_begin = pass.query_begin;
+			for (uint64_t p0 = 0; p0 < pass.longest; p0 += CH) {
+				// the launches per pass follow the longest list, never the number of groups: a workgroup column per tile
+				const uint64_t cols = std::min<uint64_t>(CH, pass.longest - p0), rows_per_wave_pass = 64u >> logG;
+				const uint64_t waves = (cols + rows_per_wave_pass - 1) / rows_per_wave_pass;
+				const uint64_t per_tile = std::max<uint64_t>(1, (16ull * n_cus + n_tiles - 1) / n_tiles);
+				const dim3 grid((uint32_t)std::min<uint64_t>((waves + 3) / 4, per_tile), n_tiles);
+				m.pos_begin = s.pos_begin = (uint32_t)p0;
+				if (metric == 0)
+					hipLaunchKernelGGL(k_exact_filtered_scores<0>, grid, dim3(256), m_lds, stream, m);
+				else if (metric == 1)
+					hipLaunchKernelGGL(k_exact_filtered_scores<1>, grid, dim3(256), m_lds, stream, m);
+				else
+					hipLaunchKernelGGL(k_exact_filtered_scores<2>, grid, dim3(256), m_lds, stream, m);
+				hipLaunchKernelGGL(k_exact_select_lists, dim3(pass.query_end - pass.query_begin), dim3(SEL_THREADS), 0, stream, s);
+			}
+		}
+		// the running lists hold slots; row t of them answers query order[t].  A query of an unknown group, of a group that
+		// admits nothing, or of an empty index still has its empty list: count 0, cells -1 / +inf.
+		RerankArgs r;
+		r.gv = view();
+		r.queries = d_queries;
+		r.q_stride = q_stride;
+		r.n_queries = (uint32_t)nq;
+		r.k = (uint32_t)k;
+		r.KP = (uint32_t)KP;
+		r.best_i = d_best_i.p;
+		r.out_keys = d_keys_out;
+		r.out_d = d_dist_out;
+		r.out_count = d_count_out;
+		r.best_s = nullptr, r.norm_ext = nullptr, r.certified = nullptr;
+		r.query_map = d_xf_tables.p + at_order;
+		const uint32_t lds = align16(V * 16) + 2 * align16((uint32_t)KP * 4);
+		launch_by_metric<RerankArgs>(launch_rerank<0>, launch_rerank<1>, launch_rerank<2>, r, launch_cfg((uint32_t)nq, lds, 64));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(ev[1], stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+		{
+			std::lock_guard<std::mutex> lk(stats_mu);
+			timing[0] = ms;
+		}
+		return VSS_OK;
+	}
+
+	// the host-pointer form: queries, table and answers staged through a leased context, as search_host does
+	int exact_filtered_host(const float *queries, uint64_t nq, uint64_t k, const uint64_t *allowed, uint64_t n_groups,
+	                        uint64_t n_bits, const uint32_t *group_of, int64_t *out_keys, float *out_d, uint32_t *out_counts) {
+		Lease lease(this);
+		SearchCtx &c = context(lease.slot);
+		const uint64_t words = filter_group_words(n_bits);
+		if (!c.d_group_filter.try_grow(std::max<uint64_t>(n_groups * words, 1)))
+			return fail("exact filtered search: no device memory for %llu bitmaps of %llu bits", (unsigned long long)n_groups,
+			            (unsigned long long)n_bits);
+		count_group_tables(c);
+		if (n_groups * words)
+			HIP_TRY(hipMemcpyAsync(c.d_group_filter.p, allowed, n_groups * words * 8, hipMemcpyHostToDevice, c.stream));
+		c.d_q.ensure(nq * dim, 0, c.stream);
+		c.d_out_keys.ensure(nq * k, 0, c.stream);
+		c.d_out_d.ensure(nq * k, 0, c.stream);
+		c.d_out_count.ensure(nq, 0, c.stream);
+		HIP_TRY(hipMemcpyAsync(c.d_q.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c.stream));
+		HIP_TRY(hipStreamSynchronize(c.stream)); // the exact kernels run on the index stream
+		const int rc = exact_filtered_launch(c.d_q.p, (uint32_t)dim, nq, k, c.d_group_filter.p, n_groups, n_bits, group_of,
+		                                     c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p);
+		if (rc != VSS_OK)
+			return rc;
+		HIP_TRY(hipMemcpyAsync(out_keys, c.d_out_keys.p, nq * k * 8, hipMemcpyDeviceToHost, c.stream));
+		if (out_d)
+			HIP_TRY(hipMemcpyAsync(out_d, c.d_out_d.p, nq * k * 4, hipMemcpyDeviceToHost, c.stream));
+		if (out_counts)
+			HIP_TRY(hipMemcpyAsync(out_counts, c.d_out_count.p, nq * 4, hipMemcpyDeviceToHost, c.stream));
+		HIP_TRY(hipStreamSynchronize(c.stream));
+		return VSS_OK;
+	}
+
 	// ------------------------------------------------------------------ remove
 	void ensure_keymap() {
 		if (keymap.ready)
@@ -2561,6 +2746,14 @@ int vss_create(uint64_t dim, int metric, uint64_t M, uint64_t M0, uint64_t efc, 
 		h->exact_certify = (uint32_t)std::max(1, std::min(2, atoi(t)));
 	if (const char *t = getenv("VSS_EXACT_REDO_QT"))
 		h->exact_redo_qt = (uint32_t)std::max(1, std::min(MS_QT, atoi(t)));
+	if (const char *t = getenv("VSS_EXACT_FILTER_LIST_ENTRIES")) {
+		const long long v = atoll(t);
+		if (v < (long long)EXACT_FILTER_LIST_ENTRIES_MIN || v > (long long)EXACT_FILTER_LIST_ENTRIES_MAX)
+			fprintf(stderr, "vssgpu: VSS_EXACT_FILTER_LIST_ENTRIES=%s ignored (%llu .. %llu list entries per pass)\n", t,
+			        (unsigned long long)EXACT_FILTER_LIST_ENTRIES_MIN, (unsigned long long)EXACT_FILTER_LIST_ENTRIES_MAX);
+		else
+			h->exact_filter_budget = (uint64_t)v;
+	}
 	if (const char *t = getenv("VSS_SEARCH_CREW_TUNE"))
 		h->search_crew_tune = (uint32_t)atoi(t) & (CREW_SPARE_SIMD | CREW_NO_REQUESTS);
 	if (const char *t = getenv("VSS_SEARCH_TOUCH_LISTS"))
@@ -2887,6 +3080,64 @@ int vss_search_exact_batch_device(vss_index *h, const float *Q, uint64_t nq, uin
 	VSS_SHARED(h, { return h->exact_launch(Q, (uint32_t)h->dim, nq, k, out, out_d, out_counts); })
 }
 
+// Exact top-k under per-query predicates: only the rows a query's group admits are scored (exact_filtered_kernels.h).  The table
+// and the admission rule are vss_search_batch_filtered_groups'; group_of == NULL gives every query bitmap 0.
+#define VSS_CHECK_EXACT_FILTER_GROUPS(h, what)                                                                         \
+	if (nq && k) {                                                                                                     \
+		if (!Q || !out || !out_counts)                                                                                 \
+			return (h)->fail(what ": null query / row-id / count pointer");                                            \
+		if (!allowed)                                                                                                  \
+			return (h)->fail(what ": exact filtered search needs the groups' row-id bitmaps");                         \
+		if (!n_groups)                                                                                                 \
+			return (h)->fail(what ": exact filtered search needs at least one group");                                 \
+		if (n_groups > 0xFFFFFFFFull || !filter_group_table_fits(n_groups, n_bits))                                    \
+			return (h)->fail(what ": %llu groups of %llu bits are more than a table can hold",                          \
+			                 (unsigned long long)n_groups, (unsigned long long)n_bits);                                \
+		if (nq > 0xFFFFFFFFull)                                                                                        \
+			return (h)->fail(what ": at most 2^32 - 1 queries per call");                                              \
+	} else                                                                                                             \
+		return VSS_OK;
+
+int vss_search_exact_batch_filtered_groups(vss_index *h, const float *Q, uint64_t nq, uint64_t k, const uint64_t *allowed,
+                                           uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, int64_t *out,
+                                           float *out_d, uint32_t *out_counts) {
+	VSS_SHARED(h, {
+		VSS_CHECK_EXACT_FILTER_GROUPS(h, "vss_search_exact_batch_filtered_groups")
+		if (group_of) { // refused before anything is uploaded or launched
+			const uint64_t bad = first_unknown_group(group_of, nq, n_groups);
+			if (bad != NO_BAD_GROUP)
+				return h->fail("vss_search_exact_batch_filtered_groups: query %llu names group %u, the table holds %llu",
+				               (unsigned long long)bad, group_of[bad], (unsigned long long)n_groups);
+		}
+		return h->exact_filtered_host(Q, nq, k, allowed, n_groups, n_bits, group_of, out, out_d, out_counts);
+	})
+}
+
+int vss_search_exact_batch_filtered_groups_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k,
+                                                  const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits,
+                                                  const uint32_t *group_of, int64_t *out, float *out_d, uint32_t *out_counts) {
+	VSS_SHARED(h, {
+		VSS_CHECK_EXACT_FILTER_GROUPS(h, "vss_search_exact_batch_filtered_groups_device")
+		// the plan needs every group's queries on the host: 4 bytes per query come back
+		std::vector<uint32_t> groups_h;
+		if (group_of) {
+			groups_h.resize(nq);
+			HIP_TRY(hipMemcpyAsync(groups_h.data(), group_of, nq * 4, hipMemcpyDeviceToHost, h->stream));
+			HIP_TRY(hipStreamSynchronize(h->stream));
+		}
+		return h->exact_filtered_launch(Q, (uint32_t)h->dim, nq, k, allowed, n_groups, n_bits, group_of ? groups_h.data() : nullptr,
+		                                out, out_d, out_counts);
+	})
+}
+
+int vss_last_exact_filtered(vss_index *h, uint64_t *out4) {
+	if (!h || !out4)
+		return VSS_ERROR;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	std::memcpy(out4, h->last_exact_filtered, sizeof h->last_exact_filtered);
+	return VSS_OK;
+}
+
 int vss_last_search_stats(vss_index *h, uint64_t *out4) {
 	VSS_SHARED(h, {
 		std::lock_guard<std::mutex> lk(h->stats_mu);
@@ -3034,7 +3285,7 @@ uint64_t vss_memory_usage(vss_index *h) {
 	const uint64_t group_tables = h->group_table_bytes.load(std::memory_order_relaxed);
 	return h->d_vectors.n * 4 + h->d_links0.n * 4 + h->d_links_up.n * 4 + h->d_upper_off.n * 4 + h->d_levels.n +
 	       h->d_keys.n * 8 + h->d_list_owner.n * 4 + h->d_codes.n * sizeof(uint32_t) + h->d_code_meta.n * sizeof(RowCodeMeta) +
-	       group_tables;
+	       group_tables + h->exact_filter_bytes.load(std::memory_order_relaxed);
 }
 
 int vss_level_stats(vss_index *h, uint64_t level, uint64_t *out4) {

@@ -260,6 +260,30 @@ public:
 			*counts_out = counts;
 		return total;
 	}
+	// The same chunk answered EXACTLY, scoring only the rows each outer row's predicate admits (vss_search_exact_batch_filtered_groups):
+	// the call for selective predicates — tenants of a sixteenth of the table and less —, where the graph
+	// call above traverses every rejected row.  group_of may be nullptr: every outer row takes bitmap 0.  No ef_search here.
+	idx_t ExecuteMultiScanBatchGroupedExact(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit,
+	                                        const uint64_t *allowed, idx_t n_groups, idx_t n_bits, const uint32_t *group_of,
+	                                        std::vector<uint32_t> *counts_out) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::vector<row_t> ids(n_queries * limit);
+		std::vector<uint32_t> counts(n_queries);
+		{
+			std::shared_lock<std::shared_mutex> lock(rwlock);
+			Check(vss_search_exact_batch_filtered_groups(index, queries, n_queries, limit, allowed, n_groups, n_bits, group_of,
+			                                             ids.data(), nullptr, counts.data()),
+			      "search");
+		}
+		idx_t total = 0;
+		for (idx_t q = 0; q != n_queries; ++q) {
+			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
+			total += counts[q];
+		}
+		if (counts_out)
+			*counts_out = counts;
+		return total;
+	}
 	const std::vector<row_t> &GetMultiScanResult(IndexScanState &state) {
 		return static_cast<MultiScanState &>(state).row_ids;
 	}

@@ -443,6 +443,53 @@ public:
 		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
 	}
 
+	// ---- the exact answer under a predicate PER QUERY, scoring only the admitted rows (vss_search_exact_batch_filtered_groups_device
+	// per shard): every shard answers under the same table over GLOBAL row ids, uploaded as SearchBatchFilteredGroups uploads it
+	// (group_of may be nullptr here: every query takes bitmap 0).  Exchange and merge are SearchExactBatch's, and so is the order
+	// of rows at exactly equal distance: (distance, row id).
+	void SearchExactBatchFilteredGroups(const float *queries, idx_t n, idx_t k, const uint64_t *allowed, idx_t n_groups, idx_t n_bits,
+	                                    const uint32_t *group_of, row_t *out_rowids, float *out_distances, uint32_t *out_counts) {
+		if (!n || !k)
+			return;
+		if (!allowed || !n_groups)
+			throw InternalException("Failed to search the HNSW index: exact filtered search needs the groups' row-id bitmaps");
+		for (idx_t q = 0; group_of && q != n; ++q)
+			if (group_of[q] >= n_groups)
+				throw InternalException("Failed to search the HNSW index: query " + std::to_string(q) + " names group " +
+				                        std::to_string(group_of[q]) + ", the table holds " + std::to_string(n_groups));
+		if (n_groups > 0xFFFFFFFFull || !vss::host::filter_group_table_fits(n_groups, n_bits))
+			throw InternalException("Failed to search the HNSW index: " + std::to_string(n_groups) + " groups of " +
+			                        std::to_string(n_bits) + " bits are more than a table can hold");
+		Ensure(n, k);
+		const idx_t words = vss::host::filter_group_words(n_bits) * n_groups;
+		for (auto &b : bitmaps) {
+			Hip(hipSetDevice(b.device), "hipSetDevice");
+			if (b.capacity < std::max<idx_t>(words, 1)) { // (allocate, then free: a failed allocation leaves the slot as it was)
+				uint64_t *grown = nullptr;
+				Hip(hipMalloc((void **)&grown, std::max<idx_t>(words, 1) * sizeof(uint64_t)), "hipMalloc");
+				(void)hipFree(b.words);
+				b.words = grown, b.capacity = std::max<idx_t>(words, 1);
+			}
+			if (group_of && b.group_capacity < n) {
+				uint32_t *grown = nullptr;
+				Hip(hipMalloc((void **)&grown, n * sizeof(uint32_t)), "hipMalloc");
+				(void)hipFree(b.group_of);
+				b.group_of = grown, b.group_capacity = n;
+			}
+			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
+			if (group_of)
+				Hip(hipMemcpy(b.group_of, group_of, n * sizeof(uint32_t), hipMemcpyHostToDevice), "copy groups");
+		}
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_exact_batch_filtered_groups_device(s.index->Handle(), s.d_q, n, k, bitmaps[s.bitmap].words, n_groups,
+			                                                         n_bits, group_of ? bitmaps[s.bitmap].group_of : nullptr, keys,
+			                                                         dist, s.d_cnt));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+	}
+
 private:
 	// An error between launch and finish of a filtered probe: every shard's probe is completed and its stream drained before the
 	// error leaves the call, so that no kernel (and no re-run round of vss_search_batch_end) still reads the tables in bitmaps[]

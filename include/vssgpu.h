@@ -172,6 +172,37 @@ int vss_search_batch_filtered_groups_device(vss_index *index, const float *d_que
                                             uint64_t ef, const uint64_t *d_allowed, uint64_t n_groups, uint64_t n_bits,
                                             const uint32_t *d_group_of, int64_t *d_out_rowids, float *d_out_distances,
                                             uint32_t *d_out_counts);
+/* Exact top-k under per-query predicates, scanning only the admitted rows: the call for a SELECTIVE predicate (a tenant join),
+ * where the graph calls above traverse every rejected row like a tombstone.  Table layout and admission rule are those of
+ * vss_search_batch_filtered_groups: n_groups bitmaps of (n_bits + 63) / 64 words end to end, query q filtered by bitmap
+ * group_of[q]; a row is admitted iff it is live, 0 <= rowid < n_bits and bit rowid is set (a set padding bit after n_bits
+ * admits nothing, whatever group follows it).  group_of == NULL is legal HERE: every query takes bitmap 0.
+ * For finite inputs query q gets the min(k, admitted live rows) admitted rows with the smallest (distance, slot) pairs, in
+ * that order; `distance` is the engine's f32 metric, the bits vss_search_batch reports for that pair.  Outputs are laid out as
+ * vss_search_exact_batch's (unused cells -1 / +inf; out_distances may be NULL).  Distances are the metric's own throughout — no
+ * ranking score, no certificate, no fallback: vss_last_exact_fallbacks is 0 after the call, and answers depend on no option.
+ * Mechanism (csrc/exact_filtered_kernels.h): for every group that has a query, the ascending list of its live admitted
+ * slots; rows are scored through the lists, MS_QT queries of one group per workgroup; the k + 8 best (distance, slot) pairs
+ * per query are re-ranked as vss_search_exact_batch re-ranks.  Scratch: the lists of one pass hold at most max(B, rows)
+ * entries of 4 bytes, B = 2^23 or VSS_EXACT_FILTER_LIST_ENTRIES (read in vss_create); groups are packed into passes in group
+ * order.  The scratch is counted in vss_memory_usage while it is held.
+ * k <= 4088.  VSS_ERROR with a message: allowed NULL or n_groups == 0 (with n_queries > 0 and k > 0); a table no size_t can
+ * hold; a row that does not fit the scoring kernel's LDS; no device memory.  Host form: a group_of[q] >= n_groups is refused
+ * before anything runs (the message names the first such query).  Device form: such a query gets count 0, cells -1 / +inf;
+ * the engine copies d_group_of back (4 bytes per query) for its plan.  n_queries == 0 or k == 0: VSS_OK.  An empty index
+ * answers count 0 everywhere.  Takes the reader lock and the exact path's mutex, as vss_search_exact_batch does; the device
+ * form runs on the index stream and its results are valid when it returns. */
+int vss_search_exact_batch_filtered_groups(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k,
+                                           const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits,
+                                           const uint32_t *group_of, int64_t *out_rowids, float *out_distances,
+                                           uint32_t *out_counts);
+int vss_search_exact_batch_filtered_groups_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k,
+                                                  const uint64_t *d_allowed, uint64_t n_groups, uint64_t n_bits,
+                                                  const uint32_t *d_group_of, int64_t *d_out_rowids, float *d_out_distances,
+                                                  uint32_t *d_out_counts);
+/* The last such call: out4[0] = admitted rows listed, summed over the groups that had queries; [1] = (query, row) distances
+ * computed; [2] = passes; [3] = bytes of list scratch held.  Results never depend on it. */
+int vss_last_exact_filtered(vss_index *index, uint64_t *out4);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
