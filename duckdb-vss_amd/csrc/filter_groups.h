@@ -22,6 +22,20 @@ inline bool filter_group_table_fits(uint64_t n_groups, uint64_t n_bits) {
 	return !words || n_groups <= (SIZE_MAX / 8) / words;
 }
 
+// What a caller's description of one table violates: the first rule, in this order, or none.  Every layer that takes a table
+// (the engine's entry points, host/sharded_index.hpp) asks this and words the answer itself.
+enum class FilterTableFault { NONE, NO_BITMAPS, NO_GROUP_NUMBERS, NO_GROUPS, TOO_LARGE };
+
+inline FilterTableFault check_filter_table(const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
+                                           bool group_of_required) {
+	const bool too_large = n_groups > 0xFFFFFFFFull || !filter_group_table_fits(n_groups, n_bits); // (group numbers have 32 bits)
+	return !allowed                         ? FilterTableFault::NO_BITMAPS
+	       : group_of_required && !group_of ? FilterTableFault::NO_GROUP_NUMBERS
+	       : !n_groups                      ? FilterTableFault::NO_GROUPS
+	       : too_large                      ? FilterTableFault::TOO_LARGE
+	                                        : FilterTableFault::NONE;
+}
+
 // the first query whose group is not in the table, or NO_BAD_GROUP
 inline uint64_t first_unknown_group(const uint32_t *group_of, uint64_t n_queries, uint64_t n_groups) {
 	for (uint64_t q = 0; q != n_queries; ++q)

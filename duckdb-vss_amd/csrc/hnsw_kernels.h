@@ -30,10 +30,9 @@ constexpr int64_t FREE_KEY = 0x7FFFFFFFFFFFFFFFll;
 
 // One predicate per query (vss_search_batch_filtered_groups): GraphView::filter_bits carries FILTER_PER_QUERY (row ids are
 // below 2^63: the bit is free) and GraphView::filter is then no bitmap but a table of one bitmap ADDRESS per query of the
-// launch, written by k_resolve_filter_groups (one table) or k_resolve_filter_group_batches (a table per batch of the launch) —
-// nullptr for a query whose group is not in the caller's table.  Such launches
-// run the k_search_groups / k_search_solo_groups kernels (below): the lookup costs the walker a vector register wherever it
-// is compiled in, so the kernels of every other launch do not contain it.
+// launch, written by k_resolve_filter_group_batches — nullptr for a query whose group is not in the caller's table.  Such
+// launches run the k_search_groups / k_search_solo_groups kernels (below): the lookup costs the walker a vector register
+// wherever it is compiled in, so the kernels of every other launch do not contain it.
 constexpr uint64_t FILTER_PER_QUERY = 1ull << 63;
 
 struct GraphView {
@@ -61,7 +60,7 @@ struct GraphView {
 		return key >= 0 && (uint64_t)key < filter_bits && ((filter[key >> 6] >> (key & 63)) & 1ull);
 	}
 	// The same with one predicate PER QUERY (the k_search_groups / k_search_solo_groups kernels only): `filter` is the table of
-	// bitmap addresses k_resolve_filter_groups has written, `query` (wave-uniform) the number of the query the walker is
+	// bitmap addresses k_resolve_filter_group_batches has written, `query` (wave-uniform) the number of the query the walker is
 	// answering as the launch numbers it — NOT its position in the work queue of a re-run round.  A query without a bitmap (its
 	// group is not in the caller's table) admits nothing.
 	__device__ __forceinline__ bool admitted_for(uint32_t slot, uint32_t query) const {
@@ -2523,23 +2522,12 @@ struct LinkArgs {
 
 #ifdef VSS_ENGINE_TU // plain kernels are defined once, in the engine's translation unit
 
-// Ahead of a launch with one predicate per query: the address of every query's bitmap — `allowed` holds n_groups bitmaps of
-// `words` 64-bit words each, laid end to end, query q names bitmap group_of[q].  A group beyond the table gets no bitmap
-// (nullptr: GraphView::admitted rejects every row), so nothing outside the n_groups * words words is ever addressed.
-__global__ __launch_bounds__(256) void k_resolve_filter_groups(const unsigned long long *allowed, const uint32_t *group_of,
-                                                               uint32_t n_groups, uint64_t words, uint32_t n_queries,
-                                                               const unsigned long long **bitmap_of) {
-	const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-	if (q >= n_queries)
-		return;
-	const uint32_t group = group_of[q];
-	bitmap_of[q] = group < n_groups ? allowed + (size_t)group * (size_t)words : nullptr;
-}
-
-// The same ahead of a launch that answers several batches, each under its own table (vss_search_multi_filtered_device_begin):
-// the launch numbers its queries q = batch * n_per_batch + row, and query q takes the bitmap its OWN batch's table holds for
-// it (host::filter_group_word_offset — the arithmetic the CPU check runs).  The descriptors travel by value in the kernel
-// arguments (32 x 24 bytes): nothing is allocated, copied or waited for on the launch path.
+// Ahead of a launch with one predicate per query: the address of every query's bitmap.  Every batch of the launch brings its own
+// table — n_groups bitmaps of `words` 64-bit words each, end to end, the batch's query `row` names bitmap group_of[row] — and a
+// call with one table is a launch of one batch.  Query q = batch * n_per_batch + row takes the bitmap its OWN batch's table holds
+// for it (host::filter_group_word_offset, which the CPU check runs too), or none where its group is beyond that table (nullptr:
+// GraphView::admitted_for rejects every row), so nothing outside a table's n_groups * words words is ever addressed.  The
+// descriptors travel by value in the kernel arguments (32 x 24 bytes): the launch path allocates, copies and waits for nothing.
 struct ResolveBatchesArgs {
 	host::FilterGroupBatch batch[host::MAX_FILTER_GROUP_BATCHES];
 	uint64_t words;

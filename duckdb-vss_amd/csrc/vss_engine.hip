@@ -121,6 +121,41 @@ struct DevBuf {
 // result.error.what() of the calling thread's last failed call (searches run concurrently: one string per thread)
 static thread_local std::string tls_error;
 
+// What a search launch filters its results by.  The pointers are device memory for search_begin / search_launch and host
+// memory for search_host, which stages what they name and hands search_launch the staged copy.
+struct SearchPredicate {
+	enum Kind { NONE, ONE_BITMAP, PER_QUERY } kind = NONE;
+	const uint64_t *bitmap = nullptr;                        // ONE_BITMAP: the whole launch's; bit set = row id admitted
+	FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES] = {}; // PER_QUERY: the table of every batch of the launch
+	uint64_t n_bits = 0;
+
+	static SearchPredicate one_bitmap(const uint64_t *bitmap, uint64_t n_bits) {
+		return {ONE_BITMAP, bitmap, {}, n_bits};
+	}
+	// a launch of one batch under one table: query q takes bitmap group_of[q]
+	static SearchPredicate one_table(const uint64_t *allowed, const uint32_t *group_of, uint64_t n_groups, uint64_t n_bits) {
+		return {PER_QUERY, nullptr, {{allowed, group_of, n_groups}}, n_bits};
+	}
+};
+static_assert((uint32_t)MAX_COALESCED == MAX_FILTER_GROUP_BATCHES, "one descriptor per batch of a launch");
+
+// One launch of the search engine: n_batches probe batches of per_batch queries each, batch b read from queries[b] and answered
+// into out_keys[b] / out_d[b] (may be NULL) / out_count[b].  vss_index::request fills everything but the named options.
+struct SearchRequest {
+	int slot = 0; // the context that carries the launch
+	uint64_t n_batches = 1, per_batch = 0;
+	const float *const *queries = nullptr;
+	int64_t *const *out_keys = nullptr;
+	float *const *out_d = nullptr;
+	uint32_t *const *out_count = nullptr;
+	uint32_t q_stride = 0;
+	uint64_t k = 0, ef = 0;
+	SearchPredicate predicate;
+	bool direct_io = false;        // queries and answers live in pinned host memory (the small-batch probe)
+	bool gate = false;             // issue the launch when the previous one starts to drain (the pipelined calls)
+	bool keep_query_stats = false; // search_launch: keep every query's counters for vss_last_query_stats
+};
+
 struct vss_index {
 	// Reader/writer discipline of the reference (SURVEY §8b "Threading"): any number of concurrent searches (shared), every
 	// call that changes the graph or its buffers exclusive.  Searches lease one of the pooled contexts below.
@@ -1154,23 +1189,19 @@ struct vss_index {
 	// candidate lists of limits 513-4096 in LDS: 0 never, 1 automatic, 2 whenever a walker fits (search.list_lds, VSS_SEARCH_LIST_LDS)
 	uint32_t search_list_lds = 1;
 
-	// enqueue one batched probe on a context (asynchronous); search_end() completes it
-	int search_begin(int slot, const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, uint64_t ef,
-	                 int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out,
-	                 const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0, bool direct_io = false,
-	                 const uint32_t *d_group_of = nullptr, uint64_t n_groups = 0) {
-		return search_begin_multi(slot, 1, &d_queries, q_stride, nq, k, ef, &d_keys_out, &d_dist_out, &d_count_out, d_filter,
-		                          filter_bits, direct_io, false, d_group_of, n_groups);
+	// a request over rows of `dim` floats with no predicate and no option set: the callers name those field by field
+	SearchRequest request(int slot, const float *const *d_queries, uint64_t n_batches, uint64_t per_batch, uint64_t k, uint64_t ef,
+	                      int64_t *const *d_keys_out, float *const *d_dist_out, uint32_t *const *d_count_out) const {
+		return {slot, n_batches, per_batch, d_queries, d_keys_out, d_dist_out, d_count_out, (uint32_t)dim, k, ef};
 	}
 
-	// The same for `n_batches` probe batches of `per_batch` queries each, answered by ONE launch of the search engine:
-	// its walkers take queries from all of them until none is left, so compute units that drew short queries in one batch
-	// go on with the next instead of idling until the slowest query of the batch is done.
-	int search_begin_multi(int slot, uint64_t n_batches, const float *const *d_queries, uint32_t q_stride, uint64_t per_batch,
-	                       uint64_t k, uint64_t ef, int64_t *const *d_keys_out, float *const *d_dist_out,
-	                       uint32_t *const *d_count_out, const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0,
-	                       bool direct_io = false, bool gate = false, const uint32_t *d_group_of = nullptr,
-	                       uint64_t n_groups = 0, const FilterGroupBatch *group_batches = nullptr) {
+	// Enqueue the probe batches of a request on its context (asynchronous); search_end() completes them.  ONE launch of the
+	// search engine answers all of them: its walkers take queries from every batch until none is left, so compute units that
+	// drew short queries in one batch go on with the next instead of idling until the slowest query of the batch is done.
+	int search_begin(const SearchRequest &r) {
+		const int slot = r.slot;
+		const uint64_t n_batches = r.n_batches, per_batch = r.per_batch, k = r.k;
+		uint64_t ef = r.ef;
 		if (slot < 0 || slot >= MAX_CTX)
 			return fail("search context %d out of range (0..%d)", slot, MAX_CTX - 1);
 		if (n_batches < 1 || n_batches > MAX_COALESCED)
@@ -1178,7 +1209,7 @@ struct vss_index {
 		SearchCtx &c = context(slot);
 		if (c.pending)
 			return fail("search context %d already has a batch in flight", slot);
-		if (gate)
+		if (r.gate)
 			wait_for_drain_of_previous_launch(slot);
 		if (!ef)
 			ef = efs ? efs : 64;
@@ -1197,10 +1228,10 @@ struct vss_index {
 			return VSS_OK;
 		if (!count) { // empty index: no results (index.hpp:2895-2896)
 			for (uint64_t b = 0; b != n_batches; ++b) {
-				HIP_TRY(hipMemsetAsync(d_keys_out[b], 0xFF, per_batch * k * 8, c.stream));
-				if (d_dist_out[b])
-					HIP_TRY(hipMemsetAsync(d_dist_out[b], 0x7F, per_batch * k * 4, c.stream));
-				HIP_TRY(hipMemsetAsync(d_count_out[b], 0, per_batch * 4, c.stream));
+				HIP_TRY(hipMemsetAsync(r.out_keys[b], 0xFF, per_batch * k * 8, c.stream));
+				if (r.out_d[b])
+					HIP_TRY(hipMemsetAsync(r.out_d[b], 0x7F, per_batch * k * 4, c.stream));
+				HIP_TRY(hipMemsetAsync(r.out_count[b], 0, per_batch * 4, c.stream));
 			}
 			c.nq = 0;
 			c.pending = true;
@@ -1222,50 +1253,34 @@ struct vss_index {
 		}
 		SearchArgs &a = c.args;
 		a.gv = view();
-		a.gv.filter = reinterpret_cast<const unsigned long long *>(d_filter);
-		// (row ids are below 2^63 — 2^63 - 1 is the free key — so a wider bitmap admits nothing more; the top bit is the kernels'
-		//  FILTER_PER_QUERY)
-		a.gv.filter_bits = std::min<uint64_t>(filter_bits, FILTER_PER_QUERY - 1);
-		if (d_filter && d_group_of) {
-			// per-query predicates: d_filter holds n_groups bitmaps end to end, query q takes bitmap d_group_of[q].  A small kernel
-			// ahead of the launch resolves every query's bitmap address; the walkers of the *_groups kernels read that (GraphView::admitted_for).
-			if (!c.d_group_bitmap.try_grow(nq))
-				return fail("filtered search: no device memory for the bitmap addresses of %llu queries", (unsigned long long)nq);
-			count_group_tables(c);
-			hipLaunchKernelGGL(k_resolve_filter_groups, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, c.stream,
-			                   reinterpret_cast<const unsigned long long *>(d_filter), d_group_of, (uint32_t)n_groups,
-			                   filter_group_words(filter_bits), (uint32_t)nq, c.d_group_bitmap.p);
-			HIP_TRY(hipGetLastError());
-			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
-			a.gv.filter_bits |= FILTER_PER_QUERY;
-		} else if (group_batches) {
-			// the same with one table PER BATCH of the launch (descriptor b = batch b's table, group numbers and group count): the
-			// descriptors go to the resolve kernel by value, so the launch path allocates, copies and waits for nothing once the
-			// address table has its size — cap_q, like the context's other per-query words
+		// The launch's predicate becomes the kernels' view of it HERE and nowhere else.  (Row ids are below 2^63 — 2^63 - 1 is the
+		// free key — so a wider bitmap admits nothing more; the top bit is the kernels' FILTER_PER_QUERY.)
+		const SearchPredicate &p = r.predicate;
+		a.gv.filter = p.kind == SearchPredicate::ONE_BITMAP ? reinterpret_cast<const unsigned long long *>(p.bitmap) : nullptr;
+		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_PER_QUERY - 1);
+		if (p.kind == SearchPredicate::PER_QUERY) {
+			// Descriptor b = batch b's table.  A small kernel ahead of the launch resolves every query's bitmap address; the walkers
+			// of the *_groups kernels read that (GraphView::admitted_for).  The descriptors go to it by value, so the launch path
+			// allocates, copies and waits for nothing once the address table has its size — cap_q, like the other per-query words.
 			if (!c.d_group_bitmap.try_grow(cap_q))
 				return fail("filtered search: no device memory for the bitmap addresses of %llu queries", (unsigned long long)cap_q);
 			count_group_tables(c);
-			ResolveBatchesArgs r = {};
-			for (uint64_t b = 0; b != n_batches; ++b)
-				r.batch[b] = group_batches[b];
-			r.words = filter_group_words(filter_bits);
-			r.n_per_batch = (uint32_t)per_batch;
-			r.n_queries = (uint32_t)nq;
-			r.bitmap_of = c.d_group_bitmap.p;
-			hipLaunchKernelGGL(k_resolve_filter_group_batches, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, c.stream, r);
+			ResolveBatchesArgs res = {{}, filter_group_words(p.n_bits), (uint32_t)per_batch, (uint32_t)nq, c.d_group_bitmap.p};
+			std::copy(p.batches, p.batches + n_batches, res.batch);
+			hipLaunchKernelGGL(k_resolve_filter_group_batches, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, c.stream, res);
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits |= FILTER_PER_QUERY;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
-			a.queries[b] = used ? d_queries[b] : nullptr;
-			a.out_keys[b] = used ? d_keys_out[b] : nullptr;
-			a.out_d[b] = used ? d_dist_out[b] : nullptr;
-			a.out_count[b] = used ? d_count_out[b] : nullptr;
+			a.queries[b] = used ? r.queries[b] : nullptr;
+			a.out_keys[b] = used ? r.out_keys[b] : nullptr;
+			a.out_d[b] = used ? r.out_d[b] : nullptr;
+			a.out_count[b] = used ? r.out_count[b] : nullptr;
 		}
 		a.batch_size = (uint32_t)per_batch;
-		a.q_stride = q_stride;
+		a.q_stride = r.q_stride;
 		a.n_queries = (uint32_t)nq;
 		a.k = (uint32_t)k;
 		a.ef = (uint32_t)ef;
@@ -1273,12 +1288,12 @@ struct vss_index {
 		a.max_level = max_level;
 		// rejected rows (tombstones, predicate) are traversed but not returned: the pending candidates wait in a register
 		// queue while the limit allows (RegQueue), in the unbounded queue in HBM otherwise or once a query outgrew the former
-		a.tomb = (tombstones || d_filter || group_batches) ? (limit <= reg_queue_max_limit && search_reg_queue ? 1u : 2u) : 0u;
+		a.tomb = (tombstones || a.gv.filter) ? (limit <= reg_queue_max_limit && search_reg_queue ? 1u : 2u) : 0u;
 		a.list_cap_max = list_cap_max();
 		a.work = nullptr;
-		c.direct_io = direct_io;
-		a.out_stats = direct_io ? c.h_stats : c.d_stats.p;
-		a.status = direct_io ? c.h_status : c.d_status.p;
+		c.direct_io = r.direct_io;
+		a.out_stats = r.direct_io ? c.h_stats : c.d_stats.p;
+		a.status = r.direct_io ? c.h_status : c.d_status.p;
 		a.phase_ticks = nullptr;
 #ifdef VSS_PHASE_TIMERS
 		c.d_phase.ensure(nq * VSS_PHASE_STRIDE, 0, c.stream);
@@ -1293,7 +1308,7 @@ struct vss_index {
 		// accepted-but-unexpanded candidates of a search over tombstones / a predicate (the reference's unbounded `next` heap);
 		// a query that outgrows the queue is re-run with a larger one
 		c.cand_cap = (uint32_t)std::min<uint64_t>(count + 1, std::max<uint64_t>(1024, 4 * limit));
-		if (direct_io)
+		if (r.direct_io)
 			std::memset(c.h_status, 0xFF, nq * 4); // "not processed" until the engine says otherwise
 		else
 			HIP_TRY(hipMemsetAsync(c.d_status.p, 0xFF, nq * 4, c.stream));
@@ -1445,19 +1460,15 @@ struct vss_index {
 		return VSS_OK;
 	}
 
-	// blocking search on context `slot` (0 = the index stream, shared by the blocking device-pointer calls)
-	int search_launch(int slot, const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, uint64_t ef,
-	                  int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out, bool keep_query_stats,
-	                  const uint64_t *d_filter = nullptr, uint64_t filter_bits = 0, bool direct_io = false,
-	                  const uint32_t *d_group_of = nullptr, uint64_t n_groups = 0) {
+	// blocking search on the request's context (0 = the index stream, shared by the blocking device-pointer calls)
+	int search_launch(const SearchRequest &r) {
 		std::unique_lock<std::mutex> lk0(ctx0_mu, std::defer_lock);
-		if (slot == 0)
+		if (r.slot == 0)
 			lk0.lock();
-		int rc = search_begin(slot, d_queries, q_stride, nq, k, ef, d_keys_out, d_dist_out, d_count_out, d_filter,
-		                      filter_bits, direct_io, d_group_of, n_groups);
+		int rc = search_begin(r);
 		if (rc != VSS_OK)
 			return rc;
-		return search_end(slot, keep_query_stats);
+		return search_end(r.slot, r.keep_query_stats);
 	}
 
 	struct Lease { // a pooled context for the duration of one host-pointer call
@@ -1471,10 +1482,40 @@ struct vss_index {
 		}
 	};
 
+	// ---- staging of the host-pointer calls.  A table in HOST memory (group_of may be nullptr: none is staged) into buffers of the
+	// leased context that grow and are reused.  No room on the device is an error of this call; the context keeps what it had.
+	int stage_group_table(SearchCtx &c, const FilterGroupBatch &table, uint64_t n_bits, uint64_t nq) {
+		const uint64_t words = table.n_groups * filter_group_words(n_bits);
+		if (!c.d_group_filter.try_grow(std::max<uint64_t>(words, 1)) || (table.group_of && !c.d_group_of.try_grow(nq)))
+			return fail("filtered search: no device memory for %llu bitmaps of %llu bits and the groups of %llu queries",
+			            (unsigned long long)table.n_groups, (unsigned long long)n_bits, (unsigned long long)nq);
+		count_group_tables(c);
+		if (words)
+			HIP_TRY(hipMemcpyAsync(c.d_group_filter.p, table.allowed, words * 8, hipMemcpyHostToDevice, c.stream));
+		if (table.group_of)
+			HIP_TRY(hipMemcpyAsync(c.d_group_of.p, table.group_of, nq * 4, hipMemcpyHostToDevice, c.stream));
+		return VSS_OK;
+	}
+	// queries in, result buffers ensured ...
+	void stage_queries(SearchCtx &c, const float *queries, uint64_t nq, uint64_t k) {
+		c.d_q.ensure(nq * dim, 0, c.stream), c.d_out_count.ensure(nq, 0, c.stream);
+		c.d_out_keys.ensure(nq * k, 0, c.stream), c.d_out_d.ensure(nq * k, 0, c.stream);
+		HIP_TRY(hipMemcpyAsync(c.d_q.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c.stream));
+	}
+	// ... results out, synchronised
+	void fetch_results(SearchCtx &c, uint64_t nq, uint64_t k, int64_t *out_keys, float *out_d, uint32_t *out_counts) {
+		HIP_TRY(hipMemcpyAsync(out_keys, c.d_out_keys.p, nq * k * 8, hipMemcpyDeviceToHost, c.stream));
+		if (out_d)
+			HIP_TRY(hipMemcpyAsync(out_d, c.d_out_d.p, nq * k * 4, hipMemcpyDeviceToHost, c.stream));
+		if (out_counts)
+			HIP_TRY(hipMemcpyAsync(out_counts, c.d_out_count.p, nq * 4, hipMemcpyDeviceToHost, c.stream));
+		HIP_TRY(hipStreamSynchronize(c.stream));
+	}
+
+	// `filter`: the predicate in HOST memory (of one batch: batches[0] where it has tables); exact search takes none
 	static constexpr uint64_t DIRECT_IO_MAX_QUERIES = 256;
 	int search_host(const float *queries, uint64_t nq, uint64_t k, uint64_t ef, int64_t *out_keys, float *out_d,
-	                uint32_t *out_counts, bool exact, const uint64_t *filter = nullptr, uint64_t filter_bits = 0,
-	                const uint32_t *group_of = nullptr, uint64_t n_groups = 0) {
+	                uint32_t *out_counts, bool exact, const SearchPredicate &filter) {
 		if (!nq || !k)
 			return VSS_OK;
 		Lease lease(this);
@@ -1484,7 +1525,7 @@ struct vss_index {
 		// distances / counts / status straight into, one pinned host block.  No staging copies; the only host-device
 		// interaction is the launch and one synchronisation.  (Up to DIRECT_IO_MAX_QUERIES — a query per compute unit: such a
 		// launch is bound by its longest query, and a walker reads its 3 KiB over PCIe once per ~0.4 ms of work.)
-		if (!exact && !filter && nq <= DIRECT_IO_MAX_QUERIES && count) {
+		if (!exact && filter.kind == SearchPredicate::NONE && nq <= DIRECT_IO_MAX_QUERIES && count) {
 			const size_t q_bytes = (nq * dim * 4 + 15) & ~size_t(15), key_bytes = nq * k * 8;
 			const size_t d_bytes = (nq * k * 4 + 15) & ~size_t(15), c_bytes = (nq * 4 + 15) & ~size_t(15);
 			const size_t need = q_bytes + key_bytes + d_bytes + c_bytes;
@@ -1500,8 +1541,9 @@ struct vss_index {
 			float *pd = reinterpret_cast<float *>(c.pinned_io + q_bytes + key_bytes);
 			uint32_t *pc = reinterpret_cast<uint32_t *>(c.pinned_io + q_bytes + key_bytes + d_bytes);
 			std::memcpy(pq, queries, nq * dim * 4);
-			int rc = search_launch(lease.slot, pq, (uint32_t)dim, nq, k, ef, pk, pd, pc, true, nullptr, 0, true);
-			if (rc != VSS_OK)
+			SearchRequest r = request(lease.slot, &pq, 1, nq, k, ef, &pk, &pd, &pc);
+			r.direct_io = r.keep_query_stats = true;
+			if (const int rc = search_launch(r))
 				return rc;
 			std::memcpy(out_keys, pk, nq * k * 8);
 			if (out_d)
@@ -1510,47 +1552,30 @@ struct vss_index {
 				std::memcpy(out_counts, pc, nq * 4);
 			return VSS_OK;
 		}
-		const uint64_t *d_filter = nullptr;
-		const uint32_t *d_group_of = nullptr;
-		if (filter && group_of) {
-			// per-query predicates: the n_groups bitmaps and the group of every query, in buffers of the context that grow and
-			// are reused.  No room on the device is an error of this call, and the context keeps what it had.
-			const uint64_t words = filter_group_words(filter_bits);
-			if (!c.d_group_filter.try_grow(std::max<uint64_t>(n_groups * words, 1)) || !c.d_group_of.try_grow(nq))
-				return fail("filtered search: no device memory for %llu bitmaps of %llu bits and %llu group numbers",
-				            (unsigned long long)n_groups, (unsigned long long)filter_bits, (unsigned long long)nq);
-			count_group_tables(c);
-			if (n_groups * words)
-				HIP_TRY(hipMemcpyAsync(c.d_group_filter.p, filter, n_groups * words * 8, hipMemcpyHostToDevice, c.stream));
-			HIP_TRY(hipMemcpyAsync(c.d_group_of.p, group_of, nq * 4, hipMemcpyHostToDevice, c.stream));
-			d_filter = c.d_group_filter.p, d_group_of = c.d_group_of.p;
-		} else if (filter) {
-			const uint64_t words = (filter_bits + 63) / 64;
+		SearchRequest r = request(lease.slot, &c.d_q.p, 1, nq, k, ef, &c.d_out_keys.p, &c.d_out_d.p, &c.d_out_count.p);
+		r.keep_query_stats = true;
+		if (filter.kind == SearchPredicate::PER_QUERY) {
+			const FilterGroupBatch &table = filter.batches[0];
+			if (const int rc = stage_group_table(c, table, filter.n_bits, nq))
+				return rc;
+			r.predicate = SearchPredicate::one_table(c.d_group_filter.p, c.d_group_of.p, table.n_groups, filter.n_bits);
+		} else if (filter.kind == SearchPredicate::ONE_BITMAP) {
+			const uint64_t words = filter_group_words(filter.n_bits);
 			c.d_filter.ensure(std::max<uint64_t>(words, 1), 0, c.stream);
-			HIP_TRY(hipMemcpyAsync(c.d_filter.p, filter, words * 8, hipMemcpyHostToDevice, c.stream));
-			d_filter = c.d_filter.p;
+			HIP_TRY(hipMemcpyAsync(c.d_filter.p, filter.bitmap, words * 8, hipMemcpyHostToDevice, c.stream));
+			r.predicate = SearchPredicate::one_bitmap(c.d_filter.p, filter.n_bits);
 		}
-		c.d_q.ensure(nq * dim, 0, c.stream);
-		c.d_out_keys.ensure(nq * k, 0, c.stream);
-		c.d_out_d.ensure(nq * k, 0, c.stream);
-		c.d_out_count.ensure(nq, 0, c.stream);
-		HIP_TRY(hipMemcpyAsync(c.d_q.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c.stream));
+		stage_queries(c, queries, nq, k);
 		int rc;
 		if (exact) {
 			HIP_TRY(hipStreamSynchronize(c.stream)); // the exact kernels run on the index stream
 			rc = exact_launch(c.d_q.p, (uint32_t)dim, nq, k, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p);
 		} else {
-			rc = search_launch(lease.slot, c.d_q.p, (uint32_t)dim, nq, k, ef, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p, true,
-			                   d_filter, filter_bits, false, d_group_of, n_groups);
+			rc = search_launch(r);
 		}
 		if (rc != VSS_OK)
 			return rc;
-		HIP_TRY(hipMemcpyAsync(out_keys, c.d_out_keys.p, nq * k * 8, hipMemcpyDeviceToHost, c.stream));
-		if (out_d)
-			HIP_TRY(hipMemcpyAsync(out_d, c.d_out_d.p, nq * k * 4, hipMemcpyDeviceToHost, c.stream));
-		if (out_counts)
-			HIP_TRY(hipMemcpyAsync(out_counts, c.d_out_count.p, nq * 4, hipMemcpyDeviceToHost, c.stream));
-		HIP_TRY(hipStreamSynchronize(c.stream));
+		fetch_results(c, nq, k, out_keys, out_d, out_counts);
 		return VSS_OK;
 	}
 
@@ -1933,29 +1958,15 @@ struct vss_index {
 	                        uint64_t n_bits, const uint32_t *group_of, int64_t *out_keys, float *out_d, uint32_t *out_counts) {
 		Lease lease(this);
 		SearchCtx &c = context(lease.slot);
-		const uint64_t words = filter_group_words(n_bits);
-		if (!c.d_group_filter.try_grow(std::max<uint64_t>(n_groups * words, 1)))
-			return fail("exact filtered search: no device memory for %llu bitmaps of %llu bits", (unsigned long long)n_groups,
-			            (unsigned long long)n_bits);
-		count_group_tables(c);
-		if (n_groups * words)
-			HIP_TRY(hipMemcpyAsync(c.d_group_filter.p, allowed, n_groups * words * 8, hipMemcpyHostToDevice, c.stream));
-		c.d_q.ensure(nq * dim, 0, c.stream);
-		c.d_out_keys.ensure(nq * k, 0, c.stream);
-		c.d_out_d.ensure(nq * k, 0, c.stream);
-		c.d_out_count.ensure(nq, 0, c.stream);
-		HIP_TRY(hipMemcpyAsync(c.d_q.p, queries, nq * dim * 4, hipMemcpyHostToDevice, c.stream));
-		HIP_TRY(hipStreamSynchronize(c.stream)); // the exact kernels run on the index stream
-		const int rc = exact_filtered_launch(c.d_q.p, (uint32_t)dim, nq, k, c.d_group_filter.p, n_groups, n_bits, group_of,
-		                                     c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p);
-		if (rc != VSS_OK)
+		// (the plan reads the group numbers on the host: only the bitmaps are staged)
+		if (const int rc = stage_group_table(c, FilterGroupBatch {allowed, nullptr, n_groups}, n_bits, nq))
 			return rc;
-		HIP_TRY(hipMemcpyAsync(out_keys, c.d_out_keys.p, nq * k * 8, hipMemcpyDeviceToHost, c.stream));
-		if (out_d)
-			HIP_TRY(hipMemcpyAsync(out_d, c.d_out_d.p, nq * k * 4, hipMemcpyDeviceToHost, c.stream));
-		if (out_counts)
-			HIP_TRY(hipMemcpyAsync(out_counts, c.d_out_count.p, nq * 4, hipMemcpyDeviceToHost, c.stream));
-		HIP_TRY(hipStreamSynchronize(c.stream));
+		stage_queries(c, queries, nq, k);
+		HIP_TRY(hipStreamSynchronize(c.stream)); // the exact kernels run on the index stream
+		if (const int rc = exact_filtered_launch(c.d_q.p, (uint32_t)dim, nq, k, c.d_group_filter.p, n_groups, n_bits, group_of,
+		                                         c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p))
+			return rc;
+		fetch_results(c, nq, k, out_keys, out_d, out_counts);
 		return VSS_OK;
 	}
 
@@ -2887,7 +2898,7 @@ int vss_set_option(vss_index *h, const char *name, int64_t value) {
 int vss_search(vss_index *h, const float *q, uint64_t k, uint64_t ef, int64_t *out, uint64_t *out_count) {
 	VSS_SHARED(h, {
 		uint32_t cnt = 0;
-		int rc = h->search_host(q, 1, k, ef, out, nullptr, &cnt, false);
+		int rc = h->search_host(q, 1, k, ef, out, nullptr, &cnt, false, SearchPredicate());
 		if (out_count)
 			*out_count = cnt;
 		return rc;
@@ -2896,12 +2907,12 @@ int vss_search(vss_index *h, const float *q, uint64_t k, uint64_t ef, int64_t *o
 
 int vss_search_batch(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, int64_t *out, float *out_d,
                      uint32_t *out_counts) {
-	VSS_SHARED(h, { return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false); })
+	VSS_SHARED(h, { return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, SearchPredicate()); })
 }
 
 int vss_search_batch_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, int64_t *out,
                             float *out_d, uint32_t *out_counts) {
-	VSS_SHARED(h, { return h->search_launch(0, Q, (uint32_t)h->dim, nq, k, ef, out, out_d, out_counts, false); })
+	VSS_SHARED(h, { return h->search_launch(h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts)); })
 }
 
 int vss_search_batch_filtered(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint64_t *allowed,
@@ -2909,7 +2920,7 @@ int vss_search_batch_filtered(vss_index *h, const float *Q, uint64_t nq, uint64_
 	VSS_SHARED(h, {
 		if (!allowed)
 			return h->fail("filtered search needs a row-id bitmap");
-		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, allowed, n_bits);
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, SearchPredicate::one_bitmap(allowed, n_bits));
 	})
 }
 
@@ -2919,37 +2930,52 @@ int vss_search_batch_filtered_device(vss_index *h, const float *Q, uint64_t nq, 
 	VSS_SHARED(h, {
 		if (!d_allowed)
 			return h->fail("filtered search needs a row-id bitmap");
-		return h->search_launch(0, Q, (uint32_t)h->dim, nq, k, ef, out, out_d, out_counts, false, d_allowed, n_bits);
+		SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+		r.predicate = SearchPredicate::one_bitmap(d_allowed, n_bits);
+		return h->search_launch(r);
 	})
+}
+
+// VSS_OK, or the rule of csrc/filter_groups.h that table `t` of `n_bits` bits per group breaks, in the engine's words: `what` is
+// the entry point, `batch` the batch of a multi-batch launch the table belongs to, or -1 where the call has one table.
+static int check_table(vss_index *h, const char *what, int64_t batch, const FilterGroupBatch &t, uint64_t n_bits,
+                       bool group_of_required) {
+	char who[40] = "filtered search";
+	if (batch >= 0)
+		std::snprintf(who, sizeof who, "batch %lld", (long long)batch);
+	const FilterTableFault fault = check_filter_table(t.allowed, t.n_groups, n_bits, t.group_of, group_of_required);
+	if (fault == FilterTableFault::NONE)
+		return VSS_OK;
+	if (fault == FilterTableFault::TOO_LARGE)
+		return h->fail("%s: %s: %llu groups of %llu bits are more than a table can hold", what, who, (unsigned long long)t.n_groups,
+		               (unsigned long long)n_bits);
+	return h->fail("%s: %s needs %s", what, who,
+	               fault == FilterTableFault::NO_GROUPS          ? "at least one group"
+	               : fault == FilterTableFault::NO_GROUP_NUMBERS ? "the group of every query"
+	               : batch < 0                                   ? "the groups' row-id bitmaps"
+	                                                             : "its groups' row-id bitmaps");
+}
+// ... and the group numbers of a table, in HOST memory: refused before anything is uploaded or launched
+static int check_group_numbers(vss_index *h, const char *what, const FilterGroupBatch &t, uint64_t nq) {
+	const uint64_t bad = first_unknown_group(t.group_of, nq, t.n_groups);
+	if (bad == NO_BAD_GROUP)
+		return VSS_OK;
+	return h->fail("%s: query %llu names group %u, the table holds %llu", what, (unsigned long long)bad, t.group_of[bad],
+	               (unsigned long long)t.n_groups);
 }
 
 // Per-query predicates: ONE launch for a join chunk whose outer rows each carry their own WHERE (hnsw_optimize_join.cpp:111-168
 // with a correlated predicate; the predicate itself is usearch's filtered_search, index_dense.hpp:625-629).
-#define VSS_CHECK_FILTER_GROUPS(h, what)                                                                               \
-	if (nq && k) {                                                                                                     \
-		if (!allowed)                                                                                                  \
-			return (h)->fail(what ": grouped filtered search needs the groups' row-id bitmaps");                        \
-		if (!group_of)                                                                                                 \
-			return (h)->fail(what ": grouped filtered search needs the group of every query");                         \
-		if (!n_groups)                                                                                                 \
-			return (h)->fail(what ": grouped filtered search needs at least one group");                               \
-		if (n_groups > 0xFFFFFFFFull || !filter_group_table_fits(n_groups, n_bits))                                    \
-			return (h)->fail(what ": %llu groups of %llu bits are more than a table can hold",                          \
-			                 (unsigned long long)n_groups, (unsigned long long)n_bits);                                \
-	}
-
 int vss_search_batch_filtered_groups(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef,
                                      const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
                                      int64_t *out, float *out_d, uint32_t *out_counts) {
 	VSS_SHARED(h, {
-		VSS_CHECK_FILTER_GROUPS(h, "vss_search_batch_filtered_groups")
-		if (nq && k) { // refused before anything is uploaded or launched
-			const uint64_t bad = first_unknown_group(group_of, nq, n_groups);
-			if (bad != NO_BAD_GROUP)
-				return h->fail("vss_search_batch_filtered_groups: query %llu names group %u, the table holds %llu",
-				               (unsigned long long)bad, group_of[bad], (unsigned long long)n_groups);
-		}
-		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, allowed, n_bits, group_of, n_groups);
+		const char *what = "vss_search_batch_filtered_groups";
+		const SearchPredicate filter = SearchPredicate::one_table(allowed, group_of, n_groups, n_bits);
+		const FilterGroupBatch &table = filter.batches[0];
+		if (nq && k && (check_table(h, what, -1, table, n_bits, true) != VSS_OK || check_group_numbers(h, what, table, nq) != VSS_OK))
+			return VSS_ERROR;
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, filter);
 	})
 }
 
@@ -2957,9 +2983,11 @@ int vss_search_batch_filtered_groups_device(vss_index *h, const float *Q, uint64
                                             const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits,
                                             const uint32_t *group_of, int64_t *out, float *out_d, uint32_t *out_counts) {
 	VSS_SHARED(h, {
-		VSS_CHECK_FILTER_GROUPS(h, "vss_search_batch_filtered_groups_device")
-		return h->search_launch(0, Q, (uint32_t)h->dim, nq, k, ef, out, out_d, out_counts, false, allowed, n_bits, false,
-		                        group_of, n_groups);
+		SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+		r.predicate = SearchPredicate::one_table(allowed, group_of, n_groups, n_bits);
+		if (nq && k && check_table(h, "vss_search_batch_filtered_groups_device", -1, r.predicate.batches[0], n_bits, true) != VSS_OK)
+			return VSS_ERROR;
+		return h->search_launch(r);
 	})
 }
 
@@ -2974,8 +3002,9 @@ int vss_search_batch_device_begin(vss_index *h, int context, const float *Q, uin
 		VSS_CHECK_CALLER_CONTEXT(h, context)
 		if (nq && k && (!Q || !out || !out_counts))
 			return h->fail("vss_search_batch_device_begin: null query / row-id / count pointer");
-		return h->search_begin_multi(context, 1, &Q, (uint32_t)h->dim, nq, k, ef, &out, &out_d, &out_counts, nullptr, 0, false,
-		                             true);
+		SearchRequest r = h->request(context, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+		r.gate = true;
+		return h->search_begin(r);
 	})
 }
 
@@ -2992,8 +3021,9 @@ int vss_search_multi_device_begin(vss_index *h, int context, uint64_t n_batches,
 			if (!Q[b] || !out[b] || !out_counts[b])
 				return h->fail("vss_search_multi_device_begin: null query / row-id / count pointer for batch %llu",
 				               (unsigned long long)b);
-		return h->search_begin_multi(context, n_batches, Q, (uint32_t)h->dim, per_batch, k, ef, out, out_d, out_counts, nullptr,
-		                             0, false, true);
+		SearchRequest r = h->request(context, Q, n_batches, per_batch, k, ef, out, out_d, out_counts);
+		r.gate = true;
+		return h->search_begin(r);
 	})
 }
 
@@ -3008,8 +3038,10 @@ int vss_search_batch_filtered_device_begin(vss_index *h, int context, const floa
 			return h->fail("vss_search_batch_filtered_device_begin: null query / row-id / count pointer");
 		if (nq && k && !d_allowed)
 			return h->fail("vss_search_batch_filtered_device_begin: filtered search needs a row-id bitmap");
-		return h->search_begin_multi(context, 1, &Q, (uint32_t)h->dim, nq, k, ef, &out, &out_d, &out_counts, d_allowed, n_bits,
-		                             false, true);
+		SearchRequest r = h->request(context, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+		r.gate = true;
+		r.predicate = SearchPredicate::one_bitmap(d_allowed, n_bits);
+		return h->search_begin(r);
 	})
 }
 
@@ -3021,9 +3053,12 @@ int vss_search_batch_filtered_groups_device_begin(vss_index *h, int context, con
 		VSS_CHECK_CALLER_CONTEXT(h, context)
 		if (nq && k && (!Q || !out || !out_counts))
 			return h->fail("vss_search_batch_filtered_groups_device_begin: null query / row-id / count pointer");
-		VSS_CHECK_FILTER_GROUPS(h, "vss_search_batch_filtered_groups_device_begin")
-		return h->search_begin_multi(context, 1, &Q, (uint32_t)h->dim, nq, k, ef, &out, &out_d, &out_counts, allowed, n_bits,
-		                             false, true, group_of, n_groups);
+		SearchRequest r = h->request(context, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+		r.gate = true;
+		r.predicate = SearchPredicate::one_table(allowed, group_of, n_groups, n_bits);
+		if (nq && k && check_table(h, "vss_search_batch_filtered_groups_device_begin", -1, r.predicate.batches[0], n_bits, true) != VSS_OK)
+			return VSS_ERROR;
+		return h->search_begin(r);
 	})
 }
 
@@ -3037,29 +3072,23 @@ int vss_search_multi_filtered_device_begin(vss_index *h, int context, uint64_t n
 			return h->fail("vss_search_multi_filtered_device_begin: null table");
 		if (n_batches < 1 || n_batches > MAX_COALESCED)
 			return h->fail("1 to %d batches per launch", MAX_COALESCED);
-		static_assert((uint32_t)MAX_COALESCED == MAX_FILTER_GROUP_BATCHES, "one descriptor per batch of a launch");
-		FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES];
-		bool one_bitmap = true; // every batch filtered by the same single bitmap: a plain filtered launch
+		SearchRequest r = h->request(context, Q, n_batches, per_batch, k, ef, out, out_d, out_counts);
+		r.gate = true;
+		r.predicate.kind = SearchPredicate::PER_QUERY, r.predicate.n_bits = n_bits;
+		bool one_bitmap = per_batch && k; // every batch filtered by the same single bitmap: a plain filtered launch
 		for (uint64_t b = 0; per_batch && k && b != n_batches; ++b) {
 			if (!Q[b] || !out[b] || !out_counts[b]) // only d_out_distances[b] may be NULL
 				return h->fail("vss_search_multi_filtered_device_begin: null query / row-id / count pointer for batch %llu",
 				               (unsigned long long)b);
-			if (!d_allowed[b])
-				return h->fail("vss_search_multi_filtered_device_begin: batch %llu needs its groups' row-id bitmaps",
-				               (unsigned long long)b);
-			if (!n_groups[b])
-				return h->fail("vss_search_multi_filtered_device_begin: batch %llu needs at least one group", (unsigned long long)b);
-			if (n_groups[b] > 0xFFFFFFFFull || !filter_group_table_fits(n_groups[b], n_bits))
-				return h->fail("vss_search_multi_filtered_device_begin: batch %llu: %llu groups of %llu bits are more than a table "
-				               "can hold", (unsigned long long)b, (unsigned long long)n_groups[b], (unsigned long long)n_bits);
-			batches[b] = FilterGroupBatch {d_allowed[b], d_group_of[b], n_groups[b]};
+			const FilterGroupBatch table = {d_allowed[b], d_group_of[b], n_groups[b]};
+			if (check_table(h, "vss_search_multi_filtered_device_begin", (int64_t)b, table, n_bits, false) != VSS_OK)
+				return VSS_ERROR;
+			r.predicate.batches[b] = table;
 			one_bitmap &= !d_group_of[b] && d_allowed[b] == d_allowed[0];
 		}
-		if (!per_batch || !k || one_bitmap)
-			return h->search_begin_multi(context, n_batches, Q, (uint32_t)h->dim, per_batch, k, ef, out, out_d, out_counts,
-			                             per_batch && k ? d_allowed[0] : nullptr, n_bits, false, true);
-		return h->search_begin_multi(context, n_batches, Q, (uint32_t)h->dim, per_batch, k, ef, out, out_d, out_counts, nullptr,
-		                             n_bits, false, true, nullptr, 0, batches);
+		if (one_bitmap)
+			r.predicate = SearchPredicate::one_bitmap(d_allowed[0], n_bits);
+		return h->search_begin(r);
 	})
 }
 
@@ -3072,7 +3101,7 @@ int vss_search_batch_end(vss_index *h, int context) {
 
 int vss_search_exact_batch(vss_index *h, const float *Q, uint64_t nq, uint64_t k, int64_t *out, float *out_d,
                            uint32_t *out_counts) {
-	VSS_SHARED(h, { return h->search_host(Q, nq, k, 0, out, out_d, out_counts, true); })
+	VSS_SHARED(h, { return h->search_host(Q, nq, k, 0, out, out_d, out_counts, true, SearchPredicate()); })
 }
 
 int vss_search_exact_batch_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, int64_t *out, float *out_d,
@@ -3082,33 +3111,28 @@ int vss_search_exact_batch_device(vss_index *h, const float *Q, uint64_t nq, uin
 
 // Exact top-k under per-query predicates: only the rows a query's group admits are scored (exact_filtered_kernels.h).  The table
 // and the admission rule are vss_search_batch_filtered_groups'; group_of == NULL gives every query bitmap 0.
-#define VSS_CHECK_EXACT_FILTER_GROUPS(h, what)                                                                         \
-	if (nq && k) {                                                                                                     \
-		if (!Q || !out || !out_counts)                                                                                 \
-			return (h)->fail(what ": null query / row-id / count pointer");                                            \
-		if (!allowed)                                                                                                  \
-			return (h)->fail(what ": exact filtered search needs the groups' row-id bitmaps");                         \
-		if (!n_groups)                                                                                                 \
-			return (h)->fail(what ": exact filtered search needs at least one group");                                 \
-		if (n_groups > 0xFFFFFFFFull || !filter_group_table_fits(n_groups, n_bits))                                    \
-			return (h)->fail(what ": %llu groups of %llu bits are more than a table can hold",                          \
-			                 (unsigned long long)n_groups, (unsigned long long)n_bits);                                \
-		if (nq > 0xFFFFFFFFull)                                                                                        \
-			return (h)->fail(what ": at most 2^32 - 1 queries per call");                                              \
-	} else                                                                                                             \
-		return VSS_OK;
+static int check_exact_filtered(vss_index *h, const char *what, const float *Q, uint64_t nq, const FilterGroupBatch &table,
+                                uint64_t n_bits, const int64_t *out, const uint32_t *out_counts) {
+	if (!Q || !out || !out_counts)
+		return h->fail("%s: null query / row-id / count pointer", what);
+	if (check_table(h, what, -1, table, n_bits, false) != VSS_OK)
+		return VSS_ERROR;
+	if (nq > 0xFFFFFFFFull)
+		return h->fail("%s: at most 2^32 - 1 queries per call", what);
+	return VSS_OK;
+}
 
 int vss_search_exact_batch_filtered_groups(vss_index *h, const float *Q, uint64_t nq, uint64_t k, const uint64_t *allowed,
                                            uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, int64_t *out,
                                            float *out_d, uint32_t *out_counts) {
 	VSS_SHARED(h, {
-		VSS_CHECK_EXACT_FILTER_GROUPS(h, "vss_search_exact_batch_filtered_groups")
-		if (group_of) { // refused before anything is uploaded or launched
-			const uint64_t bad = first_unknown_group(group_of, nq, n_groups);
-			if (bad != NO_BAD_GROUP)
-				return h->fail("vss_search_exact_batch_filtered_groups: query %llu names group %u, the table holds %llu",
-				               (unsigned long long)bad, group_of[bad], (unsigned long long)n_groups);
-		}
+		const char *what = "vss_search_exact_batch_filtered_groups";
+		const FilterGroupBatch table = {allowed, group_of, n_groups};
+		if (!nq || !k)
+			return VSS_OK;
+		if (check_exact_filtered(h, what, Q, nq, table, n_bits, out, out_counts) != VSS_OK ||
+		    (group_of && check_group_numbers(h, what, table, nq) != VSS_OK))
+			return VSS_ERROR;
 		return h->exact_filtered_host(Q, nq, k, allowed, n_groups, n_bits, group_of, out, out_d, out_counts);
 	})
 }
@@ -3117,7 +3141,11 @@ int vss_search_exact_batch_filtered_groups_device(vss_index *h, const float *Q, 
                                                   const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits,
                                                   const uint32_t *group_of, int64_t *out, float *out_d, uint32_t *out_counts) {
 	VSS_SHARED(h, {
-		VSS_CHECK_EXACT_FILTER_GROUPS(h, "vss_search_exact_batch_filtered_groups_device")
+		const FilterGroupBatch table = {allowed, group_of, n_groups};
+		if (!nq || !k)
+			return VSS_OK;
+		if (check_exact_filtered(h, "vss_search_exact_batch_filtered_groups_device", Q, nq, table, n_bits, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
 		// the plan needs every group's queries on the host: 4 bytes per query come back
 		std::vector<uint32_t> groups_h;
 		if (group_of) {

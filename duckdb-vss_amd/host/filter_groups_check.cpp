@@ -1,6 +1,6 @@
 // filter_groups_check.cpp — the group table of vss_search_batch_filtered_groups on a CPU: the engine's own arithmetic and
-// validation (csrc/filter_groups.h: the words of a group, whether a table fits, the first query of an unknown group — the very
-// functions vss_engine.hip calls) and the host's packing of a correlated join chunk (filter_group_tables.hpp).  How the
+// validation (csrc/filter_groups.h: the words of a group, whether a table fits, the first rule a table's description breaks, the
+// first query of an unknown group — the very functions vss_engine.hip and sharded_index.hpp call) and the host's packing of a correlated join chunk (filter_group_tables.hpp).  How the
 // KERNELS read a bitmap is not restated here: tests/test_gpu_filter_groups.py checks that on the device.  A
 // stand-alone program: no HIP, no GPU; tests/test_gpu_filter_groups_host.py builds it under -fsanitize=address,undefined.
 #include <cstdio>
@@ -33,6 +33,55 @@ int main() {
 	EXPECT(first_unknown_group(groups, 6, 8) == NO_BAD_GROUP && first_unknown_group(groups, 0, 1) == NO_BAD_GROUP);
 	EXPECT(first_unknown_group(groups, 6, 3) == 3 && first_unknown_group(groups, 6, 7) == 4);
 	EXPECT(first_unknown_group(groups, 3, 3) == NO_BAD_GROUP && first_unknown_group(groups, 6, 0) == 0);
+
+	// validation of a table's description: the FIRST rule it breaks, in the order no bitmaps, no group numbers, no groups,
+	// too large (nothing is dereferenced: any non-null address stands for a table)
+	{
+		using F = FilterTableFault;
+		const uint64_t bitmaps[1] = {0}, *const B = bitmaps, *const NO_B = nullptr;
+		const uint32_t *const G = groups, *const NO_G = nullptr;
+		const uint64_t two_32 = uint64_t(1) << 32, two_40 = uint64_t(1) << 40;
+		const struct {
+			const uint64_t *allowed;
+			uint64_t n_groups, n_bits;
+			const uint32_t *group_of;
+			bool required;
+			F expected;
+		} cases[] = {
+		    {B, 3, 1000, G, true, F::NONE},
+		    {B, 3, 1000, G, false, F::NONE},
+		    // each rule alone
+		    {NO_B, 3, 1000, G, true, F::NO_BITMAPS},
+		    {B, 3, 1000, NO_G, true, F::NO_GROUP_NUMBERS},
+		    {B, 0, 1000, G, true, F::NO_GROUPS},
+		    {B, two_40, two_40, G, true, F::TOO_LARGE}, // 2^40 groups of 2^34 words: does not fit
+		    // group numbers optional: their absence is no fault, and the rules after it still hold
+		    {B, 3, 1000, NO_G, false, F::NONE},
+		    {NO_B, 3, 1000, NO_G, false, F::NO_BITMAPS},
+		    {B, 0, 1000, NO_G, false, F::NO_GROUPS},
+		    {B, two_40, two_40, NO_G, false, F::TOO_LARGE},
+		    // two rules broken at once: the first in the order is reported
+		    {NO_B, 3, 1000, NO_G, true, F::NO_BITMAPS},
+		    {NO_B, 0, 1000, G, true, F::NO_BITMAPS},
+		    {NO_B, two_32, 1000, G, true, F::NO_BITMAPS},
+		    {B, 0, 1000, NO_G, true, F::NO_GROUP_NUMBERS},
+		    {B, two_32, 1000, NO_G, true, F::NO_GROUP_NUMBERS},
+		    {B, 0, ~uint64_t(0), G, true, F::NO_GROUPS}, // (no groups of any width: not "too large")
+		    // group numbers are 32 bits wide: 2^32 - 1 groups are the most, whatever their width
+		    {B, two_32 - 1, 0, G, true, F::NONE},
+		    {B, two_32, 0, G, true, F::TOO_LARGE},
+		    {B, two_32, 64, G, false, F::TOO_LARGE},
+		    // no bits: groups of no words, a table that always fits
+		    {B, 1, 0, G, true, F::NONE},
+		    {B, two_32 - 1, 0, NO_G, false, F::NONE},
+		    {B, 0, 0, G, true, F::NO_GROUPS},
+		    // the widest group there is: one fits a size_t, sixteen do not
+		    {B, 1, ~uint64_t(0), G, true, F::NONE},
+		    {B, 16, ~uint64_t(0), G, true, F::TOO_LARGE},
+		};
+		for (const auto &c : cases)
+			EXPECT(check_filter_table(c.allowed, c.n_groups, c.n_bits, c.group_of, c.required) == c.expected);
+	}
 
 	// the packing, at widths on both sides of a word edge
 	for (uint64_t n_bits : {1ull, 63ull, 64ull, 65ull, 7997ull}) {

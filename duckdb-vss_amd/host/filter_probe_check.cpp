@@ -1,5 +1,5 @@
-// filter_probe_check.cpp — the resolve step of a filtered launch that carries several batches, each under its own table
-// (vss_search_multi_filtered_device_begin), on a CPU: csrc/filter_groups.h's filter_group_batch_of / filter_group_word_offset
+// filter_probe_check.cpp — the resolve step of a launch with per-query predicates, every batch of it under its own table
+// (vss_search_multi_filtered_device_begin; a single-table call is a launch of one batch), on a CPU: csrc/filter_groups.h's filter_group_batch_of / filter_group_word_offset
 // are the very functions k_resolve_filter_group_batches calls, one thread per launch-wide query.  Here a loop plays the
 // threads, over tables and group arrays that are exactly as large as the contract says (so the sanitizers see any read
 // outside batch b's n_groups[b] * words words or its n_per_batch group numbers).  A stand-alone program: no HIP, no GPU;
@@ -113,7 +113,7 @@ int main() {
 			for (uint64_t n_per_batch : {1ull, 2ull, 13ull})
 				Launch(n_batches, n_per_batch, n_bits);
 
-	// one descriptor, n_per_batch = n_queries: the single-table form (k_resolve_filter_groups) restated
+	// one descriptor, n_per_batch = n_queries: how the single-table calls (vss_search_batch_filtered_groups*) go through the kernel
 	const uint32_t groups[6] = {0, 2, 1, 3, 7, 3};
 	const uint64_t words = filter_group_words(65);
 	auto table = Exactly<uint64_t>(4 * words);

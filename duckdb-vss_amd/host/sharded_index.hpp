@@ -80,16 +80,10 @@ public:
 			(void)vss_exchange_destroy(c);
 		for (auto &s : shards)
 			s.Release();
-		for (auto &b : bitmaps)
-			if (b.words) {
-				(void)hipSetDevice(b.device);
-				(void)hipFree(b.words);
-			}
-		for (auto &b : bitmaps)
-			if (b.group_of) {
-				(void)hipSetDevice(b.device);
-				(void)hipFree(b.group_of);
-			}
+		for (auto &b : bitmaps) {
+			(void)hipSetDevice(b.device);
+			(void)hipFree(b.words), (void)hipFree(b.group_of);
+		}
 		if (m_dist) {
 			(void)hipSetDevice(shards[0].device);
 			(void)hipFree(m_dist), (void)hipFree(m_keys), (void)hipFree(o_dist), (void)hipFree(o_keys), (void)hipFree(o_cnt);
@@ -337,10 +331,9 @@ public:
 
 	// ---- the same probe with a predicate pushed into the traversal (vss_search_batch_filtered_device per shard): a row is
 	// admitted iff it is live and bit `rowid` of `allowed` is set.  The bitmap is over GLOBAL row ids, (n_bits + 63) / 64 host
-	// words; it is uploaded once per device that holds a shard, not once per shard.  Same exchange and merge as SearchBatch, and
-	// like it every shard is started through the engine's _begin form before the first is waited for: all G search at once.
-	// The uploaded bitmap stays in bitmaps[] until every shard's vss_search_batch_end has returned (the engine reads it again when
-	// it re-runs a query), on the error path too: DrainProbes.
+	// words (UploadTables).  Same exchange and merge as SearchBatch, and like it every shard is started through the engine's
+	// _begin form before the first is waited for: all G search at once.  The uploaded bitmap stays in bitmaps[] until every shard's
+	// vss_search_batch_end has returned (the engine reads it again when it re-runs a query), on the error path too: DrainProbes.
 	void SearchBatchFiltered(const float *queries, idx_t n, idx_t k, idx_t ef, const uint64_t *allowed, idx_t n_bits,
 	                         row_t *out_rowids, float *out_distances, uint32_t *out_counts) {
 		if (!n || !k)
@@ -348,82 +341,28 @@ public:
 		if (!allowed)
 			throw InternalException("Failed to search the HNSW index: filtered search needs a row-id bitmap");
 		Ensure(n, k);
-		const idx_t words = (n_bits + 63) / 64;
-		for (auto &b : bitmaps) {
-			Hip(hipSetDevice(b.device), "hipSetDevice");
-			if (b.capacity < std::max<idx_t>(words, 1)) {
-				(void)hipFree(b.words);
-				b.words = nullptr, b.capacity = 0;
-				Hip(hipMalloc((void **)&b.words, std::max<idx_t>(words, 1) * sizeof(uint64_t)), "hipMalloc");
-				b.capacity = std::max<idx_t>(words, 1);
-			}
-			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmap");
-		}
-		try {
-			Probe(
-			    queries, n, k, out_rowids, out_distances, out_counts,
-			    [&](Shard &s, row_t *keys, float *dist) {
-				    Vss(s, vss_search_batch_filtered_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, bitmaps[s.bitmap].words,
-				                                                  n_bits, keys, dist, s.d_cnt));
-			    },
-			    [&](Shard &s) { Vss(s, vss_search_batch_end(s.index->Handle(), 0)); });
-		} catch (...) {
-			DrainProbes();
-			throw;
-		}
+		UploadTables(allowed, vss::host::filter_group_words(n_bits), nullptr, 0);
+		ProbeThroughBegin(queries, n, k, out_rowids, out_distances, out_counts, [&](Shard &s, row_t *keys, float *dist) {
+			Vss(s, vss_search_batch_filtered_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, bitmaps[s.bitmap].words, n_bits,
+			                                              keys, dist, s.d_cnt));
+		});
 	}
 
 	// ---- the same probe with a predicate PER QUERY (vss_search_batch_filtered_groups_device per shard): the chunk of a join whose
 	// subquery is correlated.  `allowed` = n_groups bitmaps over GLOBAL row ids laid end to end, (n_bits + 63) / 64 host words
-	// each; query q is filtered by bitmap group_of[q] < n_groups (checked here, before any device is touched).  Table and group
-	// numbers are uploaded once per device that holds a shard, not once per shard.  Exchange and merge are SearchBatchFiltered's.
+	// each; query q is filtered by bitmap group_of[q] < n_groups (CheckTables).  Exchange and merge are SearchBatchFiltered's.
 	void SearchBatchFilteredGroups(const float *queries, idx_t n, idx_t k, idx_t ef, const uint64_t *allowed, idx_t n_groups,
 	                               idx_t n_bits, const uint32_t *group_of, row_t *out_rowids, float *out_distances,
 	                               uint32_t *out_counts) {
 		if (!n || !k)
 			return;
-		if (!allowed || !group_of || !n_groups)
-			throw InternalException("Failed to search the HNSW index: grouped filtered search needs the groups' row-id bitmaps "
-			                        "and the group of every query");
-		for (idx_t q = 0; q != n; ++q)
-			if (group_of[q] >= n_groups)
-				throw InternalException("Failed to search the HNSW index: query " + std::to_string(q) + " names group " +
-				                        std::to_string(group_of[q]) + ", the table holds " + std::to_string(n_groups));
-		if (n_groups > 0xFFFFFFFFull || !vss::host::filter_group_table_fits(n_groups, n_bits))
-			throw InternalException("Failed to search the HNSW index: " + std::to_string(n_groups) + " groups of " +
-			                        std::to_string(n_bits) + " bits are more than a table can hold");
+		CheckTables(allowed, n_groups, n_bits, group_of, true, n);
 		Ensure(n, k);
-		const idx_t words = vss::host::filter_group_words(n_bits) * n_groups; // (the engine's own arithmetic: no wrap)
-		for (auto &b : bitmaps) {
-			Hip(hipSetDevice(b.device), "hipSetDevice");
-			if (b.capacity < std::max<idx_t>(words, 1)) { // (allocate, then free: a failed allocation leaves the slot as it was)
-				uint64_t *grown = nullptr;
-				Hip(hipMalloc((void **)&grown, std::max<idx_t>(words, 1) * sizeof(uint64_t)), "hipMalloc");
-				(void)hipFree(b.words);
-				b.words = grown, b.capacity = std::max<idx_t>(words, 1);
-			}
-			if (b.group_capacity < n) {
-				uint32_t *grown = nullptr;
-				Hip(hipMalloc((void **)&grown, n * sizeof(uint32_t)), "hipMalloc");
-				(void)hipFree(b.group_of);
-				b.group_of = grown, b.group_capacity = n;
-			}
-			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
-			Hip(hipMemcpy(b.group_of, group_of, n * sizeof(uint32_t), hipMemcpyHostToDevice), "copy groups");
-		}
-		try {
-			Probe(
-			    queries, n, k, out_rowids, out_distances, out_counts,
-			    [&](Shard &s, row_t *keys, float *dist) {
-				    Vss(s, vss_search_batch_filtered_groups_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, bitmaps[s.bitmap].words,
-				                                                         n_groups, n_bits, bitmaps[s.bitmap].group_of, keys, dist,
-				                                                         s.d_cnt));
-			    },
-			    [&](Shard &s) { Vss(s, vss_search_batch_end(s.index->Handle(), 0)); });
-		} catch (...) {
-			DrainProbes();
-			throw;
-		}
+		UploadTables(allowed, vss::host::filter_group_words(n_bits) * n_groups, group_of, n); // (checked: no wrap)
+		ProbeThroughBegin(queries, n, k, out_rowids, out_distances, out_counts, [&](Shard &s, row_t *keys, float *dist) {
+			Vss(s, vss_search_batch_filtered_groups_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, bitmaps[s.bitmap].words,
+			                                                     n_groups, n_bits, bitmaps[s.bitmap].group_of, keys, dist, s.d_cnt));
+		});
 	}
 
 	// ---- brute force over every live row of every shard (vss_search_exact_batch_device per shard, the same exchange and
@@ -451,35 +390,9 @@ public:
 	                                    const uint32_t *group_of, row_t *out_rowids, float *out_distances, uint32_t *out_counts) {
 		if (!n || !k)
 			return;
-		if (!allowed || !n_groups)
-			throw InternalException("Failed to search the HNSW index: exact filtered search needs the groups' row-id bitmaps");
-		for (idx_t q = 0; group_of && q != n; ++q)
-			if (group_of[q] >= n_groups)
-				throw InternalException("Failed to search the HNSW index: query " + std::to_string(q) + " names group " +
-				                        std::to_string(group_of[q]) + ", the table holds " + std::to_string(n_groups));
-		if (n_groups > 0xFFFFFFFFull || !vss::host::filter_group_table_fits(n_groups, n_bits))
-			throw InternalException("Failed to search the HNSW index: " + std::to_string(n_groups) + " groups of " +
-			                        std::to_string(n_bits) + " bits are more than a table can hold");
+		CheckTables(allowed, n_groups, n_bits, group_of, false, n);
 		Ensure(n, k);
-		const idx_t words = vss::host::filter_group_words(n_bits) * n_groups;
-		for (auto &b : bitmaps) {
-			Hip(hipSetDevice(b.device), "hipSetDevice");
-			if (b.capacity < std::max<idx_t>(words, 1)) { // (allocate, then free: a failed allocation leaves the slot as it was)
-				uint64_t *grown = nullptr;
-				Hip(hipMalloc((void **)&grown, std::max<idx_t>(words, 1) * sizeof(uint64_t)), "hipMalloc");
-				(void)hipFree(b.words);
-				b.words = grown, b.capacity = std::max<idx_t>(words, 1);
-			}
-			if (group_of && b.group_capacity < n) {
-				uint32_t *grown = nullptr;
-				Hip(hipMalloc((void **)&grown, n * sizeof(uint32_t)), "hipMalloc");
-				(void)hipFree(b.group_of);
-				b.group_of = grown, b.group_capacity = n;
-			}
-			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
-			if (group_of)
-				Hip(hipMemcpy(b.group_of, group_of, n * sizeof(uint32_t), hipMemcpyHostToDevice), "copy groups");
-		}
+		UploadTables(allowed, vss::host::filter_group_words(n_bits) * n_groups, group_of, n);
 		Probe(
 		    queries, n, k, out_rowids, out_distances, out_counts,
 		    [&](Shard &s, row_t *keys, float *dist) {
@@ -491,6 +404,61 @@ public:
 	}
 
 private:
+	// A table of per-query predicates, refused here before any device is touched: the rules of csrc/filter_groups.h in this
+	// layer's words.  An unknown group is reported ahead of a table too large to exist, as it always was.
+	static void CheckTables(const uint64_t *allowed, idx_t n_groups, idx_t n_bits, const uint32_t *group_of, bool group_of_required,
+	                        idx_t n) {
+		using vss::host::FilterTableFault;
+		const std::string failed = "Failed to search the HNSW index: ";
+		const FilterTableFault fault = vss::host::check_filter_table(allowed, n_groups, n_bits, group_of, group_of_required);
+		if (fault != FilterTableFault::NONE && fault != FilterTableFault::TOO_LARGE)
+			throw InternalException(failed + "filtered search needs " +
+			                        (fault == FilterTableFault::NO_GROUPS          ? "at least one group"
+			                         : fault == FilterTableFault::NO_GROUP_NUMBERS ? "the group of every query"
+			                                                                       : "the groups' row-id bitmaps"));
+		const uint64_t bad = group_of ? vss::host::first_unknown_group(group_of, n, n_groups) : vss::host::NO_BAD_GROUP;
+		if (bad != vss::host::NO_BAD_GROUP)
+			throw InternalException(failed + "query " + std::to_string(bad) + " names group " + std::to_string(group_of[bad]) +
+			                        ", the table holds " + std::to_string(n_groups));
+		if (fault == FilterTableFault::TOO_LARGE)
+			throw InternalException(failed + std::to_string(n_groups) + " groups of " + std::to_string(n_bits) +
+			                        " bits are more than a table can hold");
+	}
+
+	// `words` bitmap words and, where the call has them, the group numbers of n queries to every device that holds a shard (once
+	// per device, not once per shard).  A slot grows by "allocate, then free": a failed allocation leaves it as it was.
+	void UploadTables(const uint64_t *allowed, idx_t words, const uint32_t *group_of, idx_t n) {
+		auto grow = [](auto *&p, idx_t &capacity, idx_t want) {
+			if (capacity >= want)
+				return;
+			std::remove_reference_t<decltype(p)> grown = nullptr;
+			Hip(hipMalloc((void **)&grown, want * sizeof *p), "hipMalloc");
+			(void)hipFree(p);
+			p = grown, capacity = want;
+		};
+		for (auto &b : bitmaps) {
+			Hip(hipSetDevice(b.device), "hipSetDevice");
+			grow(b.words, b.capacity, std::max<idx_t>(words, 1));
+			if (group_of)
+				grow(b.group_of, b.group_capacity, n);
+			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
+			if (group_of)
+				Hip(hipMemcpy(b.group_of, group_of, n * sizeof(uint32_t), hipMemcpyHostToDevice), "copy groups");
+		}
+	}
+
+	// A filtered probe through the engine's _begin form: `begin(shard, keys, dist)` starts a shard, vss_search_batch_end finishes it.
+	template <class Begin>
+	void ProbeThroughBegin(const float *queries, idx_t n, idx_t k, row_t *out_rowids, float *out_distances, uint32_t *out_counts,
+	                       Begin begin) {
+		try {
+			Probe(queries, n, k, out_rowids, out_distances, out_counts, begin,
+			      [&](Shard &s) { Vss(s, vss_search_batch_end(s.index->Handle(), 0)); });
+		} catch (...) {
+			DrainProbes();
+			throw;
+		}
+	}
 	// An error between launch and finish of a filtered probe: every shard's probe is completed and its stream drained before the
 	// error leaves the call, so that no kernel (and no re-run round of vss_search_batch_end) still reads the tables in bitmaps[]
 	// when a later call grows or frees them, and context 0 of every shard is free again.

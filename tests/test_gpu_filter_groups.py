@@ -285,6 +285,50 @@ def test_g_errors():
                                                 d_keys.data_ptr(), d_dist.data_ptr(), d_cnt.data_ptr())
 
 
+def test_h_one_table_across_a_block_edge_of_the_resolve_kernel():
+    """The single-table device calls resolve their bitmaps through the batched resolve kernel, as a launch of one batch: 257
+    queries are two 256-thread blocks of it, the second with one live thread.  Queries 0, 255 and 256 — the first thread, the
+    last of block 0 and the only one of block 1 — name groups the table does not hold and come back empty; every other query
+    gets what search_batch_filtered returns for it under its own group's bitmap.  The pipelined form on context 1 returns the
+    same cells."""
+    import torch
+    g = graph_a("l2sq")
+    nq, k, ef = 257, 10, 64
+    rng = np.random.default_rng(257)
+    Q = np.ascontiguousarray(np.tile(g.Q, (6, 1))[:nq] + rng.normal(0, 0.05, size=(nq, g.dim)).astype(np.float32))
+    group_of = (np.arange(nq) % 3).astype(np.uint32)
+    unknown = np.array([0, 255, 256])
+    group_of[unknown] = (3, 7, 4000000000)
+    known = np.setdiff1d(np.arange(nq), unknown)
+    pk, pd, pcnt = g.per_group(Q, g.three, g.n_bits, group_of, k, ef)  # (groups 0-2 only: the unknown stay -1 / +inf / 0)
+
+    d_Q = torch.from_numpy(Q).cuda()
+    d_tables = torch.from_numpy(np.ascontiguousarray(g.three).view(np.int64)).cuda()
+    d_groups = torch.from_numpy(group_of.view(np.int32)).cuda()
+
+    def cells(run):
+        d_keys = torch.full((nq, k), -7, dtype=torch.int64, device="cuda")
+        d_dist = torch.zeros((nq, k), dtype=torch.float32, device="cuda")
+        d_cnt = torch.full((nq,), 99, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        run(d_Q.data_ptr(), nq, k, ef, d_tables.data_ptr(), 3, g.n_bits, d_groups.data_ptr(), d_keys.data_ptr(),
+            d_dist.data_ptr(), d_cnt.data_ptr())
+        torch.cuda.synchronize()
+        return d_keys.cpu().numpy(), d_dist.cpu().numpy(), d_cnt.cpu().numpy().view(np.uint32)
+
+    def pipelined(*args):
+        g.gpu.search_filtered_groups_begin(1, *args)
+        g.gpu.search_end(1)
+
+    dk, dd, dc = cells(g.gpu.search_batch_filtered_groups_device)
+    for q in unknown:
+        assert dc[q] == 0 and np.all(dk[q] == -1) and np.all(np.isposinf(dd[q])), (q, dk[q], dd[q], dc[q])
+    assert np.array_equal(dk[known], pk[known]) and np.array_equal(_bits(dd[known]), _bits(pd[known]))
+    assert np.array_equal(dc[known], pcnt[known]) and np.all(dc[known] > 0)
+    bk, bd, bc = cells(pipelined)
+    assert np.array_equal(bk, dk) and np.array_equal(_bits(bd), _bits(dd)) and np.array_equal(bc, dc)
+
+
 def test_group_tables_are_counted_in_memory_usage():
     g = graph_a("l2sq")
     fresh = gc.gpu_index(g.dim, "l2sq")
