@@ -92,6 +92,11 @@ SIGNATURES = {
     "vss_search_exact_batch_filtered_groups": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_exact_batch_filtered_groups_device": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_exact_filtered": (_int, [_vp, _vp]),
+    "vss_search_batch_filtered_groups_auto": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp,
+                                                     _vp]),
+    "vss_search_batch_filtered_groups_auto_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp,
+                                                            _vp, _vp]),
+    "vss_last_filter_route": (_int, [_vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -364,6 +369,42 @@ class GpuIndex:
         scratch held] of the last search_exact_batch_filtered_groups call."""
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_exact_filtered(self.h, _p(out)))
+        return out
+
+    def search_batch_filtered_groups_auto(self, Q, k, ef, bitmaps, n_bits, group_of=None, route_c=0):
+        """vss_search_batch_filtered_groups_auto: every group answered by the cheaper of search_batch_filtered_groups and
+        search_exact_batch_filtered_groups, decided from its count of live admitted rows (route_c=0: the default constant).
+        Returns (ids, distances, counts, route); route[q] is 0 (graph) or 1 (exact)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        bitmaps = np.ascontiguousarray(bitmaps, dtype=np.uint64)
+        words = (n_bits + 63) // 64
+        if bitmaps.ndim != 2 or bitmaps.shape[1] != words:
+            raise ValueError("bitmaps must be n_groups x %d uint64 words for %d bits, got shape %r"
+                             % (words, n_bits, bitmaps.shape))
+        nq = len(Q)
+        if group_of is not None:
+            group_of = np.ascontiguousarray(group_of, dtype=np.uint32)
+            if group_of.shape != (nq,):
+                raise ValueError("group_of must name one group per query: %d queries, shape %r" % (nq, group_of.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        route = np.zeros(nq, dtype=np.uint8)
+        self._check(self.lib.vss_search_batch_filtered_groups_auto(self.h, _p(Q), nq, k, ef, _p(bitmaps), len(bitmaps), n_bits,
+                                                                   _p(group_of), route_c, _p(keys), _p(d), _p(cnt), _p(route)))
+        return keys, d, cnt, route
+
+    def search_batch_filtered_groups_auto_device(self, d_Q, nq, k, ef, d_bitmaps, n_groups, n_bits, d_group_of, d_keys, d_dist,
+                                                 d_counts, d_route=None, route_c=0):
+        """The same over raw device pointers (d_group_of, d_dist and d_route may be None); blocking."""
+        self._check(self.lib.vss_search_batch_filtered_groups_auto_device(self.h, d_Q, nq, k, ef, d_bitmaps, n_groups, n_bits,
+                                                                          d_group_of, route_c, d_keys, d_dist, d_counts, d_route))
+
+    def last_filter_route(self):
+        """[queries routed graph, queries routed exact, groups in use routed graph, groups in use routed exact, L, C, limit, 0]
+        of the last search_batch_filtered_groups_auto call."""
+        out = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.vss_last_filter_route(self.h, _p(out)))
         return out
 
     def search_batch_device(self, d_Q, nq, k, ef, d_keys, d_dist, d_counts, exact=False):

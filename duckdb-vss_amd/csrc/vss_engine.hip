@@ -28,6 +28,7 @@
 #include "host_logic.h"
 #include "filter_groups.h"
 #include "exact_filtered_kernels.h"
+#include "filter_route_kernels.h"
 #include "row_codes.h"
 
 using namespace vss;
@@ -238,6 +239,10 @@ struct vss_index {
 		DevBuf<uint32_t> d_group_of;     // ... and the group of every query of the call
 		DevBuf<const unsigned long long *> d_group_bitmap; // the address of every query's bitmap (either form of the call)
 		uint64_t group_bytes = 0; // of these three, as counted in vss_index::group_table_bytes
+		// vss_search_batch_filtered_groups_auto: the compact batch of the graph-routed queries and its answers
+		DevBuf<float> d_route_q, d_route_d;
+		DevBuf<int64_t> d_route_keys;
+		DevBuf<uint32_t> d_route_group, d_route_count, d_route_map;
 		unsigned char *pinned_io = nullptr;
 		size_t pinned_cap = 0;
 		bool leased = false;
@@ -301,6 +306,7 @@ struct vss_index {
 	}
 	std::mutex ctx0_mu;  // blocking device-pointer searches share context 0
 	std::mutex exact_mu; // the exact path's scratch (score tiles, norms) is shared: exact searches take turns
+	std::mutex route_mu; // the routed device-pointer calls share context 0's compact batch
 
 	// ---- row codes (row_codes.h): derived data of d_vectors for the scoring waves' pre-scoring (search.prescore, DESIGN.md §4.2, "Pre-scoring").
 	// ONE mechanism keeps them valid: every path that writes rows marks its slots in `codes_stale` (or everything), and
@@ -405,6 +411,7 @@ struct vss_index {
 	DevBuf<uint32_t> d_xf_lists, d_xf_counts, d_xf_tables;
 	uint64_t exact_filter_budget = EXACT_FILTER_LIST_ENTRIES;
 	uint64_t last_exact_filtered[4] = {0, 0, 0, 0}; // vss_last_exact_filtered
+	uint64_t last_filter_route[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // vss_last_filter_route (under exact_mu too)
 	std::atomic<uint64_t> exact_filter_bytes {0};   // of the three buffers (vss_memory_usage, read without a lock)
 	uint64_t mutations = 0;
 
@@ -481,6 +488,7 @@ struct vss_index {
 			c.d_queue.free(), c.d_list_buf.free(), c.d_cand_buf.free();
 			c.d_q.free(), c.d_out_d.free(), c.d_out_keys.free(), c.d_out_count.free(), c.d_filter.free();
 			c.d_group_filter.free(), c.d_group_of.free(), c.d_group_bitmap.free();
+			c.d_route_q.free(), c.d_route_d.free(), c.d_route_keys.free(), c.d_route_group.free(), c.d_route_count.free(), c.d_route_map.free();
 			c.d_prescore.free();
 			if (c.h_prescore)
 				(void)hipHostFree(c.h_prescore);
@@ -1813,6 +1821,7 @@ struct vss_index {
 	// Carries out the plan of exact_filtered_plan.h: list the live admitted slots of every group in use, score each query
 	// against its group's list only, keep the K' smallest (distance, slot) pairs per query, re-rank.  Distances are the metric's
 	// own from the start, so nothing is certified and nothing redone.  group_of: HOST memory, or nullptr (all take bitmap 0).
+	// In two steps, both under exact_mu, because the routed call (filtered_auto) decides between them which groups get lists.
 	int exact_filtered_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, const uint64_t *d_table,
 	                          uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, int64_t *d_keys_out, float *d_dist_out,
 	                          uint32_t *d_count_out) {
@@ -1821,53 +1830,98 @@ struct vss_index {
 		std::fill(last_exact_filtered, last_exact_filtered + 4, 0);
 		if (k + 8 > SEL_KP_MAX)
 			return fail("exact filtered search supports k <= %d", SEL_KP_MAX - 8);
-		const uint32_t qt = (uint32_t)std::min<uint64_t>(MS_QT, (160 * 1024) / ((uint64_t)V * 16));
-		if (!qt)
-			return fail("exact filtered search: a row of %llu dimensions does not fit the scoring kernel's LDS", (unsigned long long)dim);
-		const uint64_t KP = k + 8, CH = 32768, rows = count;
 		ExactFilterPlan plan;
 		exact_filter_order(group_of, nq, n_groups, plan);
-		const uint64_t nu = plan.groups.size();
-		const uint64_t n_blocks = (rows + FL_WAVE_SLOTS - 1) / FL_WAVE_SLOTS;
-		// d_xf_tables: [groups nu][totals nu] | [list_base nu][order nq][offset nq][length nq][tiles 5 x (<= nq)]
-		const uint64_t at_totals = nu, at_base = 2 * nu, at_order = 3 * nu, at_offset = at_order + nq, at_length = at_offset + nq,
-		               at_tiles = at_length + nq;
-		static_assert(sizeof(ExactFilterTile) == 20, "five words per tile");
-		if (!d_xf_tables.try_grow(at_tiles + 5 * nq) || !d_xf_counts.try_grow(std::max<uint64_t>(nu * n_blocks, 1)) ||
-		    !d_scores.try_grow(nq * CH) || !d_best_s.try_grow(nq * KP) || !d_best_i.try_grow(nq * KP))
-			return fail("exact filtered search: no device memory for %llu queries over %llu groups in use", (unsigned long long)nq,
-			            (unsigned long long)nu);
-		auto count_scratch = [&] {
-			last_exact_filtered[3] = (d_xf_lists.n + d_xf_counts.n + d_xf_tables.n) * 4;
-			exact_filter_bytes.store(last_exact_filtered[3], std::memory_order_relaxed);
-		};
-		count_scratch();
-		ensure_events();
-		HIP_TRY(hipEventRecord(ev[0], stream));
-		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, nq * KP * 4, stream)); // 0x7F7F7F7F = 3.39e38 (acts as +inf)
-		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, nq * KP * 4, stream));
+		std::vector<uint32_t> lengths;
+		if (const int rc = exact_filtered_count(plan, nq, 1, d_table, n_bits, lengths))
+			return rc;
+		return exact_filtered_score(plan, lengths, d_xf_counts.p, true, d_queries, q_stride, k, d_table, n_bits, d_keys_out, d_dist_out,
+		                            d_count_out);
+	}
+
+	// d_xf_tables of a plan over nu used groups and nq queries: [groups nu][totals nu] | [list_base nu][order nq][offset nq]
+	// [length nq][tiles 5 x (<= nq)]
+	struct ExactFilterTables {
+		uint64_t at_totals, at_base, at_order, at_offset, at_length, at_tiles, words;
+		ExactFilterTables(uint64_t nu, uint64_t nq)
+		    : at_totals(nu), at_base(2 * nu), at_order(3 * nu), at_offset(at_order + nq), at_length(at_offset + nq),
+		      at_tiles(at_length + nq), words(at_tiles + 5 * nq) {
+		}
+	};
+	void count_exact_filter_scratch() {
+		last_exact_filtered[3] = (d_xf_lists.n + d_xf_counts.n + d_xf_tables.n) * 4;
+		exact_filter_bytes.store(last_exact_filtered[3], std::memory_order_relaxed);
+	}
+	FilterListArgs exact_filter_list_args(const uint64_t *d_table, uint64_t n_bits, uint64_t nu, const ExactFilterTables &t) const {
 		FilterListArgs l;
-		l.keys = d_keys.p, l.rows = (uint32_t)rows, l.n_blocks = (uint32_t)n_blocks;
+		l.keys = d_keys.p, l.rows = (uint32_t)count, l.n_blocks = (uint32_t)((count + FL_WAVE_SLOTS - 1) / FL_WAVE_SLOTS);
 		l.table = d_table, l.words = filter_group_words(n_bits), l.n_bits = n_bits;
-		l.groups = d_xf_tables.p, l.totals = d_xf_tables.p + at_totals, l.list_base = d_xf_tables.p + at_base;
+		l.groups = d_xf_tables.p, l.totals = d_xf_tables.p + t.at_totals, l.list_base = d_xf_tables.p + t.at_base;
 		l.u_begin = 0, l.u_end = (uint32_t)nu;
 		l.counts = d_xf_counts.p, l.lists = nullptr;
-		const dim3 list_grid((uint32_t)((n_blocks + 3) / 4));
-		std::vector<uint32_t> lengths(nu);
+		return l;
+	}
+
+	// step 1: lengths[u] = live admitted rows of used group u of `plan` (a plan over nq queries); their block counts stay in
+	// rows [0, nu) of d_xf_counts, which has room for count_copies times as many
+	int exact_filtered_count(const ExactFilterPlan &plan, uint64_t nq, uint64_t count_copies, const uint64_t *d_table, uint64_t n_bits,
+	                         std::vector<uint32_t> &lengths) {
+		const uint64_t nu = plan.groups.size(), rows = count;
+		const ExactFilterTables t(nu, nq);
+		static_assert(sizeof(ExactFilterTile) == 20, "five words per tile");
+		FilterListArgs l = exact_filter_list_args(d_table, n_bits, nu, t);
+		if (!d_xf_tables.try_grow(t.words) || !d_xf_counts.try_grow(std::max<uint64_t>(count_copies * nu * l.n_blocks, 1)))
+			return fail("exact filtered search: no device memory for %llu queries over %llu groups in use", (unsigned long long)nq,
+			            (unsigned long long)nu);
+		l = exact_filter_list_args(d_table, n_bits, nu, t); // (the buffers may have moved)
+		count_exact_filter_scratch();
+		ensure_events();
+		HIP_TRY(hipEventRecord(ev[0], stream));
+		lengths.assign(nu, 0);
 		if (nu && rows) { // (an empty index lists nothing: every length stays 0)
 			HIP_TRY(hipMemcpyAsync(d_xf_tables.p, plan.groups.data(), nu * 4, hipMemcpyHostToDevice, stream));
-			hipLaunchKernelGGL(k_filter_list_count, list_grid, dim3(256), 0, stream, l);
+			hipLaunchKernelGGL(k_filter_list_count, dim3((l.n_blocks + 3) / 4), dim3(256), 0, stream, l);
 			hipLaunchKernelGGL(k_filter_list_scan, dim3((uint32_t)nu), dim3(256), 0, stream, l);
 			HIP_TRY(hipMemcpyAsync(lengths.data(), l.totals, nu * 4, hipMemcpyDeviceToHost, stream));
 			HIP_TRY(hipStreamSynchronize(stream));
 		}
+		return VSS_OK;
+	}
+
+	// step 2: answers the queries plan.order names (rows of d_queries, cells of the outputs) from lists of lengths[u] rows each;
+	// `counts`: row u = the scanned block counts of plan.groups[u]; groups_resident: step 1 ran over this very plan.  No other
+	// query's cells are written.
+	int exact_filtered_score(ExactFilterPlan &plan, const std::vector<uint32_t> &lengths, uint32_t *counts, bool groups_resident,
+	                         const float *d_queries,
+	                         uint32_t q_stride, uint64_t k, const uint64_t *d_table, uint64_t n_bits, int64_t *d_keys_out,
+	                         float *d_dist_out, uint32_t *d_count_out) {
+		if (k + 8 > SEL_KP_MAX)
+			return fail("exact filtered search supports k <= %d", SEL_KP_MAX - 8);
+		const uint32_t qt = (uint32_t)std::min<uint64_t>(MS_QT, (160 * 1024) / ((uint64_t)V * 16));
+		if (!qt)
+			return fail("exact filtered search: a row of %llu dimensions does not fit the scoring kernel's LDS", (unsigned long long)dim);
+		const uint64_t KP = k + 8, CH = 32768, rows = count, nq = plan.order.size(), nu = plan.groups.size();
+		if (!nq)
+			return VSS_OK;
+		const ExactFilterTables t(nu, nq);
+		const uint64_t at_base = t.at_base, at_order = t.at_order, at_offset = t.at_offset, at_length = t.at_length, at_tiles = t.at_tiles;
+		if (!d_xf_tables.try_grow(t.words) || !d_scores.try_grow(nq * CH) || !d_best_s.try_grow(nq * KP) || !d_best_i.try_grow(nq * KP))
+			return fail("exact filtered search: no device memory for %llu queries over %llu groups in use", (unsigned long long)nq,
+			            (unsigned long long)nu);
+		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, nq * KP * 4, stream)); // 0x7F7F7F7F = 3.39e38 (acts as +inf)
+		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, nq * KP * 4, stream));
+		FilterListArgs l = exact_filter_list_args(d_table, n_bits, nu, t);
+		l.counts = counts;
+		const dim3 list_grid((l.n_blocks + 3) / 4);
+		if (!groups_resident && nu) // (plan.groups outlives the copy: this step ends synchronised)
+			HIP_TRY(hipMemcpyAsync(d_xf_tables.p, plan.groups.data(), nu * 4, hipMemcpyHostToDevice, stream));
 		exact_filter_pack(lengths.data(), std::max<uint64_t>(exact_filter_budget, rows), qt, plan);
 		uint64_t entries_max = 0;
 		for (const ExactFilterPass &pass : plan.passes)
 			entries_max = std::max(entries_max, pass.entries);
 		if (!d_xf_lists.try_grow(std::max<uint64_t>(entries_max, 1)))
 			return fail("exact filtered search: no device memory for lists of %llu rows", (unsigned long long)entries_max);
-		count_scratch();
+		count_exact_filter_scratch();
 		last_exact_filtered[0] = plan.listed, last_exact_filtered[1] = plan.distances, last_exact_filtered[2] = plan.passes.size();
 		{
 			std::vector<uint32_t> up(at_tiles - at_base + 5 * plan.tiles.size());
@@ -1967,6 +2021,118 @@ struct vss_index {
 		                                         c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p))
 			return rc;
 		fetch_results(c, nq, k, out_keys, out_d, out_counts);
+		return VSS_OK;
+	}
+
+	// ------------------------------------------------------------------ filtered search, routed per group (filter_route.h)
+	// One count pass over every group in use feeds the rule and the exact plan; the exact-routed queries are answered straight
+	// into the caller's cells by the exact step over lists of exact-routed groups only; the graph-routed ones are gathered into
+	// a compact batch of context `slot`, walked by one ordinary search launch and scattered back.  Everything is DEVICE memory
+	// but group_of (HOST, or nullptr: every query takes bitmap 0, and d_group_of is nullptr too) and `route` (HOST: filled here).
+	int filtered_auto(int slot, const float *d_queries, uint64_t nq, uint64_t k, uint64_t ef, const uint64_t *d_table,
+	                  uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, const uint32_t *d_group_of, uint64_t route_c,
+	                  int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out, std::vector<uint8_t> &route) {
+		const uint64_t limit = filter_route_limit(k, ef, efs), C = route_c ? route_c : FILTER_ROUTE_C, L = count - tombstones;
+		SearchCtx &c = context(slot);
+		FilterRoutePlan rp;
+		{
+			std::lock_guard<std::mutex> exact_lock(exact_mu);
+			last_exact_fallbacks = 0;
+			std::fill(last_exact_filtered, last_exact_filtered + 4, 0);
+			std::fill(last_filter_route, last_filter_route + 8, 0);
+			ExactFilterPlan all;
+			exact_filter_order(group_of, nq, n_groups, all);
+			std::vector<uint32_t> lengths;
+			if (const int rc = exact_filtered_count(all, nq, 2, d_table, n_bits, lengths))
+				return rc;
+			filter_route_partition(all, lengths.data(), group_of, nq, L, limit, C, route_c ? 0 : FILTER_ROUTE_MIN_WALK, rp);
+			const uint64_t nu = all.groups.size(), nx = rp.exact.groups.size();
+			if (!rp.exact.order.empty()) {
+				uint32_t *counts = d_xf_counts.p;
+				const uint32_t n_blocks = (uint32_t)((count + FL_WAVE_SLOTS - 1) / FL_WAVE_SLOTS);
+				if (nx != nu && n_blocks) {
+					// the exact-routed groups' rows of counts, made consecutive behind the nu rows of the count pass; which rows:
+					// behind the groups of the count pass's table, whose totals have been read
+					counts = d_xf_counts.p + nu * n_blocks;
+					HIP_TRY(hipMemcpyAsync(d_xf_tables.p + nu, rp.exact_rows.data(), nx * 4, hipMemcpyHostToDevice, stream));
+					const dim3 grid(std::min<uint32_t>((n_blocks + 255) / 256, 64), (uint32_t)std::min<uint64_t>(nx, 65535));
+					hipLaunchKernelGGL(k_route_take_rows, grid, dim3(256), 0, stream, d_xf_counts.p, d_xf_tables.p + nu, (uint32_t)nx, n_blocks,
+					                   counts);
+					HIP_TRY(hipStreamSynchronize(stream)); // (the score step rewrites d_xf_tables)
+				}
+				if (const int rc = exact_filtered_score(rp.exact, rp.exact_lengths, counts, nx == nu, d_queries, (uint32_t)dim, k, d_table,
+				                                        n_bits, d_keys_out, d_dist_out, d_count_out))
+					return rc;
+			}
+			last_filter_route[0] = rp.graph_queries.size(), last_filter_route[1] = rp.exact.order.size();
+			last_filter_route[2] = rp.n_graph_groups, last_filter_route[3] = rp.n_exact_groups;
+			last_filter_route[4] = L, last_filter_route[5] = C, last_filter_route[6] = limit;
+		}
+		route = rp.route;
+		const uint64_t ng = rp.graph_queries.size(), n_unknown = rp.unknown_queries.size();
+		if (!ng) { // no walk: the search counters describe none
+			std::lock_guard<std::mutex> lk(stats_mu);
+			std::fill(last_stats, last_stats + 4, 0);
+			std::fill(last_shape, last_shape + 8, 0);
+			std::fill(last_prescore, last_prescore + 4, 0);
+			last_prescore_descent[0] = last_prescore_descent[1] = 0;
+		}
+		if (!ng && !n_unknown)
+			return VSS_OK;
+		std::unique_lock<std::mutex> route_lock(route_mu, std::defer_lock);
+		if (slot == 0)
+			route_lock.lock();
+		if (!c.d_route_map.try_grow(ng + n_unknown) || !c.d_route_q.try_grow(std::max<uint64_t>(ng * dim, 1)) ||
+		    !c.d_route_group.try_grow(std::max<uint64_t>(ng, 1)) || !c.d_route_keys.try_grow(std::max<uint64_t>(ng * k, 1)) ||
+		    !c.d_route_d.try_grow(std::max<uint64_t>(ng * k, 1)) || !c.d_route_count.try_grow(std::max<uint64_t>(ng, 1)))
+			return fail("routed filtered search: no device memory for a compact batch of %llu queries", (unsigned long long)ng);
+		if (n_unknown) {
+			HIP_TRY(hipMemcpyAsync(c.d_route_map.p + ng, rp.unknown_queries.data(), n_unknown * 4, hipMemcpyHostToDevice, c.stream));
+			hipLaunchKernelGGL(k_route_blank, dim3((uint32_t)((n_unknown + 3) / 4)), dim3(256), 0, c.stream, c.d_route_map.p + ng,
+			                   (uint32_t)n_unknown, (uint32_t)k, d_keys_out, d_dist_out, d_count_out);
+		}
+		if (ng) {
+			HIP_TRY(hipMemcpyAsync(c.d_route_map.p, rp.graph_queries.data(), ng * 4, hipMemcpyHostToDevice, c.stream));
+			RouteGatherArgs g;
+			g.queries = d_queries, g.group_of = d_group_of, g.map = c.d_route_map.p;
+			g.n = (uint32_t)ng, g.q_stride = (uint32_t)dim;
+			g.vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(d_queries) % 16 == 0 && reinterpret_cast<uintptr_t>(c.d_route_q.p) % 16 == 0;
+			g.out_queries = c.d_route_q.p, g.out_group_of = c.d_route_group.p;
+			hipLaunchKernelGGL(k_route_gather, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, g);
+			HIP_TRY(hipGetLastError());
+			SearchRequest r = request(slot, &c.d_route_q.p, 1, ng, k, ef, &c.d_route_keys.p, &c.d_route_d.p, &c.d_route_count.p);
+			r.predicate = d_group_of ? SearchPredicate::one_table(d_table, c.d_route_group.p, n_groups, n_bits)
+			                         : SearchPredicate::one_bitmap(d_table, n_bits);
+			if (const int rc = search_launch(r))
+				return rc;
+			RouteScatterArgs s;
+			s.map = c.d_route_map.p, s.n = (uint32_t)ng, s.k = (uint32_t)k;
+			s.keys = c.d_route_keys.p, s.dist = c.d_route_d.p, s.count = c.d_route_count.p;
+			s.out_keys = d_keys_out, s.out_dist = d_dist_out, s.out_count = d_count_out;
+			hipLaunchKernelGGL(k_route_scatter, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, s);
+		}
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(c.stream));
+		return VSS_OK;
+	}
+
+	// the host-pointer form: staged through a leased context, which also carries the walk
+	int filtered_auto_host(const float *queries, uint64_t nq, uint64_t k, uint64_t ef, const uint64_t *allowed, uint64_t n_groups,
+	                       uint64_t n_bits, const uint32_t *group_of, uint64_t route_c, int64_t *out_keys, float *out_d,
+	                       uint32_t *out_counts, uint8_t *out_route) {
+		Lease lease(this);
+		SearchCtx &c = context(lease.slot);
+		if (const int rc = stage_group_table(c, FilterGroupBatch {allowed, group_of, n_groups}, n_bits, nq))
+			return rc;
+		stage_queries(c, queries, nq, k);
+		HIP_TRY(hipStreamSynchronize(c.stream)); // the count and exact kernels run on the index stream
+		std::vector<uint8_t> route;
+		if (const int rc = filtered_auto(lease.slot, c.d_q.p, nq, k, ef, c.d_group_filter.p, n_groups, n_bits, group_of,
+		                                 group_of ? c.d_group_of.p : nullptr, route_c, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p, route))
+			return rc;
+		fetch_results(c, nq, k, out_keys, out_d, out_counts);
+		if (out_route)
+			std::memcpy(out_route, route.data(), nq);
 		return VSS_OK;
 	}
 
@@ -3163,6 +3329,60 @@ int vss_last_exact_filtered(vss_index *h, uint64_t *out4) {
 		return VSS_ERROR;
 	std::lock_guard<std::mutex> lk(h->exact_mu);
 	std::memcpy(out4, h->last_exact_filtered, sizeof h->last_exact_filtered);
+	return VSS_OK;
+}
+
+// Per-query predicates, each group answered by the cheaper of the two calls above (filter_route.h has the rule).  route_c is an
+// argument and not an option: no option changes an answer, and this value chooses between two answers.
+int vss_search_batch_filtered_groups_auto(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef,
+                                          const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
+                                          uint64_t route_c, int64_t *out, float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		const char *what = "vss_search_batch_filtered_groups_auto";
+		const FilterGroupBatch table = {allowed, group_of, n_groups};
+		if (!nq || !k)
+			return VSS_OK;
+		if (check_exact_filtered(h, what, Q, nq, table, n_bits, out, out_counts) != VSS_OK ||
+		    (group_of && check_group_numbers(h, what, table, nq) != VSS_OK))
+			return VSS_ERROR;
+		return h->filtered_auto_host(Q, nq, k, ef, allowed, n_groups, n_bits, group_of, route_c, out, out_d, out_counts, out_route);
+	})
+}
+
+int vss_search_batch_filtered_groups_auto_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef,
+                                                 const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits,
+                                                 const uint32_t *group_of, uint64_t route_c, int64_t *out, float *out_d,
+                                                 uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		const FilterGroupBatch table = {allowed, group_of, n_groups};
+		if (!nq || !k)
+			return VSS_OK;
+		if (check_exact_filtered(h, "vss_search_batch_filtered_groups_auto_device", Q, nq, table, n_bits, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
+		// the rule and the plans need every group's queries on the host: 4 bytes per query come back
+		std::vector<uint32_t> groups_h;
+		if (group_of) {
+			groups_h.resize(nq);
+			HIP_TRY(hipMemcpyAsync(groups_h.data(), group_of, nq * 4, hipMemcpyDeviceToHost, h->stream));
+			HIP_TRY(hipStreamSynchronize(h->stream));
+		}
+		std::vector<uint8_t> route;
+		if (const int rc = h->filtered_auto(0, Q, nq, k, ef, allowed, n_groups, n_bits, group_of ? groups_h.data() : nullptr, group_of,
+		                                    route_c, out, out_d, out_counts, route))
+			return rc;
+		if (out_route) {
+			HIP_TRY(hipMemcpyAsync(out_route, route.data(), nq, hipMemcpyHostToDevice, h->stream));
+			HIP_TRY(hipStreamSynchronize(h->stream));
+		}
+		return VSS_OK;
+	})
+}
+
+int vss_last_filter_route(vss_index *h, uint64_t *out8) {
+	if (!h || !out8)
+		return VSS_ERROR;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	std::memcpy(out8, h->last_filter_route, sizeof h->last_filter_route);
 	return VSS_OK;
 }
 

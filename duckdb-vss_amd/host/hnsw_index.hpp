@@ -284,6 +284,35 @@ public:
 			*counts_out = counts;
 		return total;
 	}
+	// The same chunk with every group answered by the cheaper of the two calls above (vss_search_batch_filtered_groups_auto): the
+	// engine counts the live rows each predicate admits and decides per group — the call for an operator that has bitmaps and
+	// no idea how selective each is.  group_of may be nullptr; route_c = 0 takes the engine's constant;
+	// routes_out (optional) receives 0 (graph) or 1 (exact) per outer row.
+	idx_t ExecuteMultiScanBatchGroupedAuto(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit,
+	                                       const uint64_t *allowed, idx_t n_groups, idx_t n_bits, const uint32_t *group_of,
+	                                       std::vector<uint32_t> *counts_out, std::vector<uint8_t> *routes_out = nullptr,
+	                                       uint64_t route_c = 0) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::vector<row_t> ids(n_queries * limit);
+		std::vector<uint32_t> counts(n_queries);
+		std::vector<uint8_t> routes(n_queries);
+		{
+			std::shared_lock<std::shared_mutex> lock(rwlock);
+			Check(vss_search_batch_filtered_groups_auto(index, queries, n_queries, limit, state.ef_search, allowed, n_groups, n_bits,
+			                                            group_of, route_c, ids.data(), nullptr, counts.data(), routes.data()),
+			      "search");
+		}
+		idx_t total = 0;
+		for (idx_t q = 0; q != n_queries; ++q) {
+			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
+			total += counts[q];
+		}
+		if (counts_out)
+			*counts_out = counts;
+		if (routes_out)
+			*routes_out = routes;
+		return total;
+	}
 	const std::vector<row_t> &GetMultiScanResult(IndexScanState &state) {
 		return static_cast<MultiScanState &>(state).row_ids;
 	}

@@ -403,6 +403,35 @@ public:
 		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
 	}
 
+	// ---- the same chunk with every group answered by the cheaper of the two calls above (vss_search_batch_filtered_groups_auto_device
+	// per shard): each shard routes by ITS OWN counts of live admitted rows and ITS OWN live rows — a tenant that is large in
+	// one shard and tiny in another is walked here and scanned there.  route_c as in the engine (0: the default constant).
+	// shard_routes (optional) receives the route tables, shard after shard: [g * n + q] = 0 graph, 1 exact.  Upload, exchange and
+	// merge are SearchExactBatchFilteredGroups'; rows at exactly equal distance come back by (distance, row id).
+	void SearchBatchFilteredGroupsAuto(const float *queries, idx_t n, idx_t k, idx_t ef, const uint64_t *allowed, idx_t n_groups,
+	                                   idx_t n_bits, const uint32_t *group_of, uint64_t route_c, row_t *out_rowids, float *out_distances,
+	                                   uint32_t *out_counts, std::vector<uint8_t> *shard_routes = nullptr) {
+		if (shard_routes)
+			shard_routes->assign(shards.size() * n, 0);
+		if (!n || !k)
+			return;
+		CheckTables(allowed, n_groups, n_bits, group_of, false, n);
+		Ensure(n, k);
+		UploadTables(allowed, vss::host::filter_group_words(n_bits) * n_groups, group_of, n);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_batch_filtered_groups_auto_device(s.index->Handle(), s.d_q, n, k, ef, bitmaps[s.bitmap].words, n_groups,
+			                                                        n_bits, group_of ? bitmaps[s.bitmap].group_of : nullptr, route_c,
+			                                                        keys, dist, s.d_cnt, s.d_route));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		for (size_t g = 0; shard_routes && g != shards.size(); ++g) {
+			Hip(hipSetDevice(shards[g].device), "hipSetDevice");
+			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
+		}
+	}
+
 private:
 	// A table of per-query predicates, refused here before any device is touched: the rules of csrc/filter_groups.h in this
 	// layer's words.  An unknown group is reported ahead of a table too large to exist, as it always was.
@@ -672,12 +701,13 @@ private:
 		float *d_q = nullptr, *d_dist = nullptr;
 		row_t *d_keys = nullptr;
 		uint32_t *d_cnt = nullptr;
+		uint8_t *d_route = nullptr; // SearchBatchFilteredGroupsAuto: this shard's route of every query
 		unsigned char *d_block = nullptr, *d_gathered = nullptr; // RCCL exchange: this shard's packed block, all G blocks
 		void Release() {
 			if (!stream)
 				return;
 			(void)hipSetDevice(device);
-			(void)hipFree(d_q), (void)hipFree(d_dist), (void)hipFree(d_keys), (void)hipFree(d_cnt);
+			(void)hipFree(d_q), (void)hipFree(d_dist), (void)hipFree(d_keys), (void)hipFree(d_cnt), (void)hipFree(d_route);
 			(void)hipFree(d_block), (void)hipFree(d_gathered);
 			(void)hipStreamDestroy(stream);
 			stream = nullptr;
@@ -702,11 +732,12 @@ private:
 			Hip(hipSetDevice(s.device), "hipSetDevice");
 			if (!s.stream)
 				Hip(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), "stream");
-			(void)hipFree(s.d_q), (void)hipFree(s.d_dist), (void)hipFree(s.d_keys), (void)hipFree(s.d_cnt);
+			(void)hipFree(s.d_q), (void)hipFree(s.d_dist), (void)hipFree(s.d_keys), (void)hipFree(s.d_cnt), (void)hipFree(s.d_route);
 			Hip(hipMalloc((void **)&s.d_q, cap_n * dim * sizeof(float)), "hipMalloc");
 			Hip(hipMalloc((void **)&s.d_dist, cap_n * cap_k * sizeof(float)), "hipMalloc");
 			Hip(hipMalloc((void **)&s.d_keys, cap_n * cap_k * sizeof(row_t)), "hipMalloc");
 			Hip(hipMalloc((void **)&s.d_cnt, cap_n * sizeof(uint32_t)), "hipMalloc");
+			Hip(hipMalloc((void **)&s.d_route, cap_n), "hipMalloc");
 			if (!comms.empty()) {
 				(void)hipFree(s.d_block), (void)hipFree(s.d_gathered);
 				const uint64_t block = vss_packed_block_bytes(cap_n, cap_k);

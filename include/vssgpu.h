@@ -203,6 +203,44 @@ int vss_search_exact_batch_filtered_groups_device(vss_index *index, const float 
 /* The last such call: out4[0] = admitted rows listed, summed over the groups that had queries; [1] = (query, row) distances
  * computed; [2] = passes; [3] = bytes of list scratch held.  Results never depend on it. */
 int vss_last_exact_filtered(vss_index *index, uint64_t *out4);
+/* Per-query predicates, every GROUP answered by the cheaper of the two calls above — the call for a chunk that names large and
+ * tiny tenants at once, and for a caller that has bitmaps but no idea how many live rows each admits.  Table layout, n_bits and
+ * the admission rule are those of the two calls; group_of == NULL is legal (every query takes bitmap 0).
+ * The rule (csrc/filter_route.h): the engine counts len_u, the live admitted rows of every group u in use, on the device — the
+ * first step of the exact call, run once — and group u goes EXACT iff  len_u^2 * 64 <= C * limit * L,  where L = live linked
+ * rows, limit = max(k, ef) (ef == 0: the index's ef_search) and C = route_c, or 62 500 where route_c == 0.  len_u == 0 and an
+ * empty index are exact; route_c == UINT64_MAX routes everything exact.  route_c is an argument and no option of
+ * vss_set_option because it can change an answer.  Under a named route_c a query's route depends on its group alone, never on
+ * the other groups or on the batch size.  With route_c == 0 one more step applies, the minimum walk: where some exact-routed
+ * group admits a row (so lists are built anyway) and the graph-routed groups together amount to fewer than 2^24
+ * (query, admitted row) pairs, those groups are scanned as well — a walk is a launch of its own and has a floor of one to three
+ * milliseconds.
+ * out_route (may be NULL), one byte per query: 0 = graph, 1 = exact, 255 = its group is not in the table (device form only).
+ * Contract: a query of route 1 gets, bit for bit (row ids, f32 distances, count), what vss_search_exact_batch_filtered_groups
+ * gives it; a query of route 0 what vss_search_batch_filtered_groups gives it under the same k and ef (group_of == NULL:
+ * vss_search_batch_filtered with bitmap 0); a query of route 255 count 0, cells -1 / +inf.  out_distances may be NULL.
+ * Mechanism (csrc/filter_route_kernels.h): lists are built for exact-routed groups only and their queries answered straight
+ * into the caller's cells; the graph-routed queries are gathered into a compact batch, walked by ONE ordinary filtered search
+ * launch — no walker sees an exact-routed query, and there is no launch when nothing is graph-routed — and scattered back.
+ * The two parts run one after the other.
+ * Errors are those of the two calls; the host form refuses a group_of[q] >= n_groups before anything runs (the message names
+ * the first such query); k <= 4088 holds only if some query is exact-routed.  n_queries == 0 or k == 0: VSS_OK.
+ * Reader lock; the exact path's mutex around the count and the exact part; the host form walks on a leased context, the
+ * device form on the index stream (context 0) and copies d_group_of back (4 bytes per query).  d_out_route is device memory
+ * there.  Results are valid when the call returns.
+ * Afterwards vss_last_search_stats / _shape / _prescore describe the graph part (all zero if there was none; per-query
+ * counters are not kept), vss_last_exact_filtered the exact part ([0] = rows listed over the exact-routed groups in use). */
+int vss_search_batch_filtered_groups_auto(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                          const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
+                                          uint64_t route_c, int64_t *out_rowids, float *out_distances, uint32_t *out_counts,
+                                          uint8_t *out_route);
+int vss_search_batch_filtered_groups_auto_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k,
+                                                 uint64_t ef, const uint64_t *d_allowed, uint64_t n_groups, uint64_t n_bits,
+                                                 const uint32_t *d_group_of, uint64_t route_c, int64_t *d_out_rowids,
+                                                 float *d_out_distances, uint32_t *d_out_counts, uint8_t *d_out_route);
+/* The last such call: out8[0] = queries routed graph, [1] = queries routed exact, [2] / [3] = groups in use routed graph /
+ * exact, [4] = L, [5] = the C used, [6] = limit, [7] = 0. */
+int vss_last_filter_route(vss_index *index, uint64_t *out8);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
