@@ -97,6 +97,12 @@ SIGNATURES = {
     "vss_search_batch_filtered_groups_auto_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp,
                                                             _vp, _vp]),
     "vss_last_filter_route": (_int, [_vp, _vp]),
+    "vss_set_labels": (_int, [_vp, _u64, _vp, _u64]),
+    "vss_set_labels_device": (_int, [_vp, _u64, _vp, _u64]),
+    "vss_clear_labels": (_int, [_vp]),
+    "vss_labelled_rows": (_u64, [_vp]),
+    "vss_search_batch_by_label": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_by_label_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -406,6 +412,48 @@ class GpuIndex:
         out = np.zeros(8, dtype=np.uint64)
         self._check(self.lib.vss_last_filter_route(self.h, _p(out)))
         return out
+
+    # ---- the label column (include/vssgpu.h, "Equality predicates on a resident label column")
+    NO_LABEL = 0xFFFFFFFF
+    BY_LABEL_MODES = {"graph": 0, "exact": 1, "auto": 2}
+
+    def set_labels(self, first_rowid, labels):
+        """vss_set_labels: cells first_rowid .. first_rowid + len(labels) - 1 of the per-row-id label column."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        if labels.ndim != 1:
+            raise ValueError("labels must be one uint32 per row id, got shape %r" % (labels.shape,))
+        self._check(self.lib.vss_set_labels(self.h, first_rowid, _p(labels), len(labels)))
+
+    def set_labels_device(self, first_rowid, d_labels, n):
+        """The same from a raw device pointer."""
+        self._check(self.lib.vss_set_labels_device(self.h, first_rowid, d_labels, n))
+
+    def clear_labels(self):
+        self._check(self.lib.vss_clear_labels(self.h))
+
+    def labelled_rows(self):
+        return int(self.lib.vss_labelled_rows(self.h))
+
+    def search_batch_by_label(self, Q, k, ef, want, mode="auto", route_c=0):
+        """vss_search_batch_by_label: query q admits the live rows whose label is want[q] (NO_LABEL wants nothing).  mode:
+        "graph", "exact" or "auto" (or 0 / 1 / 2).  Returns (ids, distances, counts, route)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        want = np.ascontiguousarray(want, dtype=np.uint32)
+        nq = len(Q)
+        if want.shape != (nq,):
+            raise ValueError("want must name one label per query: %d queries, shape %r" % (nq, want.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        route = np.zeros(nq, dtype=np.uint8)
+        self._check(self.lib.vss_search_batch_by_label(self.h, _p(Q), nq, k, ef, _p(want), self.BY_LABEL_MODES.get(mode, mode),
+                                                       route_c, _p(keys), _p(d), _p(cnt), _p(route)))
+        return keys, d, cnt, route
+
+    def search_batch_by_label_device(self, d_Q, nq, k, ef, d_want, d_keys, d_dist, d_counts, d_route=None, mode="auto", route_c=0):
+        """The same over raw device pointers (d_dist and d_route may be None); blocking."""
+        self._check(self.lib.vss_search_batch_by_label_device(self.h, d_Q, nq, k, ef, d_want, self.BY_LABEL_MODES.get(mode, mode),
+                                                              route_c, d_keys, d_dist, d_counts, d_route))
 
     def search_batch_device(self, d_Q, nq, k, ef, d_keys, d_dist, d_counts, exact=False):
         if exact:

@@ -16,6 +16,7 @@
 #pragma once
 #include "exact_filtered_plan.h"
 #include "exact_kernels.h"
+#include "label_filter.h"
 
 namespace vss {
 
@@ -112,6 +113,107 @@ __global__ __launch_bounds__(256) void k_filter_list_scatter(FilterListArgs a) {
 			at += __popcll(m);
 		}
 	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same lists from the label column (vss_search_batch_by_label, label_filter.h): used group u is a wanted VALUE, and a slot
+// belongs to at most one of them — the one label_lookup finds its row's label to be.  A wave reads keys[slot] and labels[key]
+// once per launch and then visits only the groups its FL_WAVE_SLOTS slots carry, one turn of the loop each: no pass over the
+// groups, so the cost of a launch does not depend on how many values it lists.  Same counts[u][block] layout as above — the
+// scan kernel is k_filter_list_scan — but a wave writes only the cells of the groups it meets: `counts` is ZEROED beforehand.
+struct LabelListArgs {
+	const int64_t *keys;
+	uint32_t rows, n_blocks;
+	const uint32_t *labels;   // one cell per row id below labelled_rows
+	uint64_t labelled_rows;
+	const uint32_t *values;   // [u]: the wanted value of used group u, ascending in u
+	uint32_t u_begin, u_end;  // the used groups this launch lists
+	uint32_t *counts;
+	const uint32_t *list_base;
+	uint32_t *lists;
+};
+
+// used group of slots block * FL_WAVE_SLOTS + s * 64 + lane among [u_begin, u_end), or NO_LABEL_GROUP
+// (host::label_lookup in its pieces: the lane's FL_KEYS_PER_LANE lookups take every step together — their loads are in flight
+//  side by side — and the number of steps is the launch's, floor(log2(groups)) + 1)
+__device__ __forceinline__ void label_list_groups(const LabelListArgs &a, uint32_t block, uint32_t (&u)[FL_KEYS_PER_LANE]) {
+	const uint32_t *values = a.values + a.u_begin;
+	const uint32_t n = a.u_end - a.u_begin;
+	uint32_t label[FL_KEYS_PER_LANE], lo[FL_KEYS_PER_LANE], hi[FL_KEYS_PER_LANE];
+#pragma unroll
+	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+		const uint32_t slot = block * FL_WAVE_SLOTS + s * 64 + lane_id();
+		const int64_t key = slot < a.rows ? a.keys[slot] : host::EXACT_FILTER_FREE_KEY;
+		const bool has_cell = key != host::EXACT_FILTER_FREE_KEY && key >= 0 && (uint64_t)key < a.labelled_rows;
+		label[s] = has_cell ? a.labels[key] : host::NO_LABEL;
+		lo[s] = 0, hi[s] = label[s] == host::NO_LABEL ? 0 : n; // (a row without a label looks nothing up)
+	}
+	for (uint32_t step = host::label_lookup_steps(n); step; --step) {
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			host::label_lookup_step(values, label[s], lo[s], hi[s]);
+	}
+#pragma unroll
+	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+		const uint32_t g = host::label_lookup_result(values, n, label[s], lo[s]);
+		u[s] = g == host::NO_LABEL_GROUP ? host::NO_LABEL_GROUP : a.u_begin + g;
+	}
+}
+
+// Calls visit(group) once for every group some lane still carries — the group of the lowest such lane's first such slot
+// (wave-uniform) — and takes that group's slots out.  Inside, `u[s] == group` names the group's slots in (s, lane) order.
+template <class Visit>
+__device__ __forceinline__ void label_list_each_group(uint32_t (&u)[FL_KEYS_PER_LANE], Visit visit) {
+	for (;;) {
+		uint32_t mine = host::NO_LABEL_GROUP;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			mine = mine == host::NO_LABEL_GROUP ? u[s] : mine;
+		const unsigned long long holders = __ballot(mine != host::NO_LABEL_GROUP);
+		if (!holders)
+			return;
+		const uint32_t group = (uint32_t)__builtin_amdgcn_readlane((int)mine, uniform(__ffsll((long long)holders) - 1));
+		visit(group);
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) // (unrolled without being asked; asked, the pass order makes it a warning)
+			u[s] = u[s] == group ? host::NO_LABEL_GROUP : u[s];
+	}
+}
+
+__global__ __launch_bounds__(256) void k_label_list_count(LabelListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks) // (wave-uniform; no barrier below)
+		return;
+	uint32_t u[FL_KEYS_PER_LANE];
+	label_list_groups(a, block, u);
+	label_list_each_group(u, [&](uint32_t group) {
+		uint32_t n = 0;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			n += __popcll(__ballot(u[s] == group));
+		if (lane_id() == 0)
+			a.counts[(size_t)group * a.n_blocks + block] = n;
+	});
+}
+
+__global__ __launch_bounds__(256) void k_label_list_scatter(LabelListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks)
+		return;
+	uint32_t u[FL_KEYS_PER_LANE];
+	label_list_groups(a, block, u);
+	const int lane = lane_id();
+	label_list_each_group(u, [&](uint32_t group) {
+		// the rows this block found in the count pass (the index is read-locked in between: the same rows now)
+		uint32_t at = a.list_base[group] + a.counts[(size_t)group * a.n_blocks + block];
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+			const bool in = u[s] == group;
+			const unsigned long long m = __ballot(in);
+			if (in)
+				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;
+			at += __popcll(m);
+		}
+	});
 }
 
 // ---------------------------------------------------------------------------------------------------------

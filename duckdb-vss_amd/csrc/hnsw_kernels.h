@@ -22,6 +22,7 @@
 #include "engine_layout.h"
 #include "prescore_bound.h"
 #include "filter_groups.h"
+#include "label_filter.h"
 #include <type_traits>
 
 namespace vss {
@@ -34,6 +35,11 @@ constexpr int64_t FREE_KEY = 0x7FFFFFFFFFFFFFFFll;
 // launches run the k_search_groups / k_search_solo_groups kernels (below): the lookup costs the walker a vector register
 // wherever it is compiled in, so the kernels of every other launch do not contain it.
 constexpr uint64_t FILTER_PER_QUERY = 1ull << 63;
+// One wanted LABEL per query (vss_search_batch_by_label): filter_bits carries FILTER_BY_LABEL beside FILTER_PER_QUERY, its low
+// bits are the label column's cells, and GraphView::filter is the table k_resolve_label_wants has written — cell 0 the column's
+// address, cell 1 + q what query q's rows must hold (host::label_want_cell).  Such launches run the k_search_labels /
+// k_search_solo_labels kernels: neither GraphView nor any other kernel knows of the column.
+constexpr uint64_t FILTER_BY_LABEL = 1ull << 62;
 
 struct GraphView {
 	RowSpace sp;
@@ -71,6 +77,19 @@ struct GraphView {
 		if (!mine)
 			return false;
 		return key >= 0 && (uint64_t)key < (filter_bits & ~FILTER_PER_QUERY) && ((mine[key >> 6] >> (key & 63)) & 1ull);
+	}
+
+	// The same with one wanted label per query (the k_search_labels / k_search_solo_labels kernels only): the row is live, its row
+	// id has a cell of the column, and the cell holds what the query wants (host::label_admits; a query that wants NO_LABEL has a
+	// cell value no label widens to).
+	__device__ __forceinline__ bool admitted_label(uint32_t slot, uint32_t query) const {
+		const int64_t key = keys[slot];
+		if (key == 0x7FFFFFFFFFFFFFFFll)
+			return false;
+		if (key < 0 || (uint64_t)key >= (filter_bits & ~(FILTER_PER_QUERY | FILTER_BY_LABEL)))
+			return false;
+		const uint32_t *labels = reinterpret_cast<const uint32_t *>(filter[0]);
+		return (unsigned long long)labels[key] == filter[1 + query];
 	}
 
 	__device__ __forceinline__ uint32_t *list_ptr(uint32_t slot, int level) const {
@@ -1105,8 +1124,9 @@ struct RowTouch {
 
 // PK: neighbour lists kept in flight (0 = the list type's default); MERGE_REGS: widest register list whose accepted
 // candidates are merged in batches (the 1024-thread search engine cannot afford the temporaries of an 8-register merge)
-// PER_QUERY (TOMB, the *_groups kernels): the predicate is the one of the query being answered, GraphView::admitted_for
-template <int MT, bool INSERT, bool TOMB, int PK = 0, int MERGE_REGS = MAX_LIST_REGS, bool PER_QUERY = false, class List, class Queue,
+// PER_QUERY (TOMB): 1 (the *_groups kernels) the predicate is the one of the query being answered, GraphView::admitted_for;
+// 2 (the *_labels kernels) it is the query's wanted label, GraphView::admitted_label
+template <int MT, bool INSERT, bool TOMB, int PK = 0, int MERGE_REGS = MAX_LIST_REGS, int PER_QUERY = 0, class List, class Queue,
           class Scorer>
 __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &lds, float qa2, uint32_t start,
                                                  uint32_t new_slot, int level, int limit, List &L, Queue &cq,
@@ -1124,7 +1144,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 	if (TOMB) {
 		cq.restart();
 		cq.push(d0, start, 0.f, false);
-		if (PER_QUERY ? gv.admitted_for(start, lds.query) : gv.admitted(start))
+		if (PER_QUERY == 2 ? gv.admitted_label(start, lds.query) : PER_QUERY == 1 ? gv.admitted_for(start, lds.query) : gv.admitted(start))
 			L.template insert<INSERT>(d0, start);
 	} else {
 		L.template insert<INSERT>(d0, start);
@@ -1221,7 +1241,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 			const bool have = off + lane < n;
 			const float d = have ? lds.dist[off + lane] : 0.f;
 			const uint32_t id = have ? lds.ids[off + lane] : 0;
-			const uint32_t live = (TOMB && have) ? ((PER_QUERY ? gv.admitted_for(id, lds.query) : gv.admitted(id)) ? 1u : 0u) : 0u;
+			const uint32_t live = (TOMB && have) ? ((PER_QUERY == 2 ? gv.admitted_label(id, lds.query) : PER_QUERY == 1 ? gv.admitted_for(id, lds.query) : gv.admitted(id)) ? 1u : 0u) : 0u;
 			unsigned long long pass = __ballot(have && (L.size < limit || d < radius));
 			if constexpr (TOUCH_L) {
 				// ListTouch: a row about to enter the candidate list will be asked for its neighbour list by the look-ahead of one
@@ -1997,8 +2017,9 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 // WIDE_LIST_THREADS for the pipelined 8-register list (round 5)
 constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS = 8)
 // GROUPS: the body of k_search_groups — a launch with one predicate per query (always a TOMB launch): the level search looks
-// the query's own bitmap up, and the paths such a launch never takes are not compiled.
-template <int MT, int NCH, int R, int E, int THREADS, bool GROUPS>
+// the query's own bitmap up (1) or compares the row's label with the query's (2: k_search_labels), and the paths such a launch
+// never takes are not compiled.
+template <int MT, int NCH, int R, int E, int THREADS, int GROUPS>
 __device__ __forceinline__ void search_engine(SearchArgs &a) {
 	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2238,12 +2259,17 @@ __device__ __forceinline__ void search_engine(SearchArgs &a) {
 
 template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search(SearchArgs a) {
-	search_engine<MT, NCH, R, E, THREADS, false>(a);
+	search_engine<MT, NCH, R, E, THREADS, 0>(a);
 }
 // the same engine for launches with one predicate per query (vss_search_batch_filtered_groups)
 template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search_groups(SearchArgs a) {
-	search_engine<MT, NCH, R, E, THREADS, true>(a);
+	search_engine<MT, NCH, R, E, THREADS, 1>(a);
+}
+// ... and for launches with one wanted label per query (vss_search_batch_by_label)
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search_labels(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, 2>(a);
 }
 
 // =========================================================================================================
@@ -2261,7 +2287,7 @@ __global__ __launch_bounds__(THREADS) void k_search_groups(SearchArgs a) {
 // scheduler from trading the row window's registers for an occupancy nobody can use)
 // T > 1: a team — T - 1 helper waves score a share of every expansion's rows (TeamScorer above); R is then the row window
 // of EACH wave.
-template <int MT, int NCH, int R, int E, int T, bool GROUPS>
+template <int MT, int NCH, int R, int E, int T, int GROUPS>
 __device__ __forceinline__ void search_solo(SearchArgs &a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	TeamBox &team_box = *reinterpret_cast<TeamBox *>(smem); // teams: the first bytes of the workgroup's LDS (host: + TEAM_BOX_BYTES)
@@ -2361,11 +2387,15 @@ __device__ __forceinline__ void search_solo(SearchArgs &a) {
 
 template <int MT, int NCH, int R, int E, int T = 1>
 __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo(SearchArgs a) {
-	search_solo<MT, NCH, R, E, T, false>(a);
+	search_solo<MT, NCH, R, E, T, 0>(a);
 }
 template <int MT, int NCH, int R, int E, int T = 1>
 __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_groups(SearchArgs a) {
-	search_solo<MT, NCH, R, E, T, true>(a);
+	search_solo<MT, NCH, R, E, T, 1>(a);
+}
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_labels(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, 2>(a);
 }
 
 // =========================================================================================================
@@ -2543,6 +2573,23 @@ __global__ __launch_bounds__(256) void k_resolve_filter_group_batches(ResolveBat
 	const host::FilterGroupBatch &d = a.batch[host::filter_group_batch_of(a.n_per_batch, q)];
 	const uint64_t at = host::filter_group_word_offset(d, a.n_per_batch, a.words, q);
 	a.bitmap_of[q] = at != host::NO_GROUP_BITMAP ? reinterpret_cast<const unsigned long long *>(d.allowed) + at : nullptr;
+}
+
+// Ahead of a launch with one wanted label per query: the table GraphView::admitted_label reads.  `want` is one value per query
+// of the launch, in DEVICE memory.
+struct ResolveLabelsArgs {
+	const uint32_t *labels;
+	const uint32_t *want;
+	uint32_t n_queries;
+	unsigned long long *table; // 1 + n_queries cells
+};
+
+__global__ __launch_bounds__(256) void k_resolve_label_wants(ResolveLabelsArgs a) {
+	const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+	if (q == 0)
+		a.table[0] = (unsigned long long)reinterpret_cast<uintptr_t>(a.labels);
+	if (q < a.n_queries)
+		a.table[1 + q] = host::label_want_cell(a.want[q]);
 }
 
 // Reused slots, before phase A: blank every list of the node (update() zeroes the node tape, index.hpp:2837-2840).

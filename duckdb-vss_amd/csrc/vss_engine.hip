@@ -27,6 +27,7 @@
 #include "launchers.h"
 #include "host_logic.h"
 #include "filter_groups.h"
+#include "label_filter.h"
 #include "exact_filtered_kernels.h"
 #include "filter_route_kernels.h"
 #include "row_codes.h"
@@ -125,10 +126,18 @@ static thread_local std::string tls_error;
 // What a search launch filters its results by.  The pointers are device memory for search_begin / search_launch and host
 // memory for search_host, which stages what they name and hands search_launch the staged copy.
 struct SearchPredicate {
-	enum Kind { NONE, ONE_BITMAP, PER_QUERY } kind = NONE;
+	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL } kind = NONE;
 	const uint64_t *bitmap = nullptr;                        // ONE_BITMAP: the whole launch's; bit set = row id admitted
 	FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES] = {}; // PER_QUERY: the table of every batch of the launch
-	uint64_t n_bits = 0;
+	uint64_t n_bits = 0;                                     // (BY_LABEL: the cells of the index's label column)
+	const uint32_t *want = nullptr;                          // BY_LABEL: the label every query of the (one) batch wants
+
+	// a launch of one batch against the index's label column: query q admits the rows labelled want[q]
+	static SearchPredicate by_label(const uint32_t *want, uint64_t labelled_rows) {
+		SearchPredicate p;
+		p.kind = BY_LABEL, p.n_bits = labelled_rows, p.want = want;
+		return p;
+	}
 
 	static SearchPredicate one_bitmap(const uint64_t *bitmap, uint64_t n_bits) {
 		return {ONE_BITMAP, bitmap, {}, n_bits};
@@ -210,6 +219,13 @@ struct vss_index {
 	DevBuf<uint32_t> d_links0, d_links_up, d_upper_off, d_list_owner;
 	DevBuf<uint8_t> d_levels;
 	DevBuf<int64_t> d_keys;
+
+	// The label column (label_filter.h): one 32-bit cell per ROW ID below `labelled_rows`, NO_LABEL where none was set.  By row
+	// id like the callers' bitmaps, so slot reuse and vss_compact do not touch it; not serialized.  Written under the exclusive
+	// lock only (vss_set_labels); d_labels.n may exceed labelled_rows (it grows by halves).
+	DevBuf<uint32_t> d_labels;
+	uint64_t labelled_rows = 0;
+	std::atomic<uint64_t> label_bytes {0}; // vss_memory_usage (read without a lock)
 
 	// build scratch
 	DevBuf<uint32_t> d_req_list, d_req_src, d_req_rank, d_sorted_src, d_touched, d_list_count, d_list_offset,
@@ -460,6 +476,7 @@ struct vss_index {
 	void release() {
 		d_vectors.free(), d_links0.free(), d_links_up.free(), d_upper_off.free(), d_list_owner.free();
 		d_levels.free(), d_keys.free();
+		clear_labels();
 		free_codes();
 		d_req_list.free(), d_req_src.free(), d_req_rank.free(), d_sorted_src.free(), d_touched.free();
 		d_list_count.free(), d_list_offset.free(), d_counters.free(), d_req_d.free(), d_sorted_d.free();
@@ -527,6 +544,61 @@ struct vss_index {
 		for (int i = 0; i != MAX_CTX; ++i)
 			if (ctx[i].pending)
 				return fail("%s while search context %d still has a batch in flight (call vss_search_batch_end first)", what, i);
+		return VSS_OK;
+	}
+
+	// ------------------------------------------------------------------ the label column (label_filter.h)
+	void clear_labels() {
+		d_labels.free();
+		labelled_rows = 0;
+		label_bytes.store(0, std::memory_order_relaxed);
+	}
+
+	// cells [first_rowid, first_rowid + n) = labels[0 .. n), from HOST or DEVICE memory; cells the write skips over become NO_LABEL.
+	// Under the exclusive lock.  The column grows into a NEW buffer, and the old one goes only once the new one holds its cells: a
+	// device without room fails this call and leaves the column as it was (nothing is visible before labelled_rows moves).
+	int set_labels(const char *what, uint64_t first_rowid, const uint32_t *labels, uint64_t n, bool on_device) {
+		const LabelRangeFault fault = check_label_range(labels, first_rowid, n);
+		if (fault == LabelRangeFault::NO_LABELS)
+			return fail("%s: null label pointer", what);
+		if (fault == LabelRangeFault::TOO_FAR)
+			return fail("%s: %llu cells from row id %llu end beyond row id 2^32 - 1", what, (unsigned long long)n,
+			            (unsigned long long)first_rowid);
+		if (!n)
+			return VSS_OK;
+		if (refuse_while_probing(what) != VSS_OK)
+			return VSS_ERROR;
+		const LabelWrite w = label_write(labelled_rows, first_rowid, n);
+		if (w.rows_after > d_labels.n) {
+			// by halves, so that a column written chunk by chunk next to the appends is not copied once per chunk
+			const uint64_t roomy = std::min<uint64_t>(w.rows_after + w.rows_after / 2, LABEL_ROWS_MAX);
+			uint32_t *np = nullptr;
+			uint64_t got = roomy;
+			if (hipMalloc(&np, roomy * 4) != hipSuccess) {
+				(void)hipGetLastError();
+				got = w.rows_after;
+				if (hipMalloc(&np, got * 4) != hipSuccess) {
+					(void)hipGetLastError();
+					return fail("%s: no device memory for a label column of %llu rows (it keeps its %llu)", what,
+					            (unsigned long long)w.rows_after, (unsigned long long)labelled_rows);
+				}
+			}
+			hipError_t e = labelled_rows ? hipMemcpyAsync(np, d_labels.p, labelled_rows * 4, hipMemcpyDeviceToDevice, stream) : hipSuccess;
+			if (e == hipSuccess)
+				e = hipStreamSynchronize(stream);
+			if (e != hipSuccess) {
+				(void)hipFree(np);
+				throw HipError {e, "label column growth"};
+			}
+			d_labels.free();
+			d_labels.p = np, d_labels.n = got;
+			label_bytes.store(got * 4, std::memory_order_relaxed);
+		}
+		if (w.gap_end > w.gap_begin)
+			HIP_TRY(hipMemsetAsync(d_labels.p + w.gap_begin, 0xFF, (w.gap_end - w.gap_begin) * 4, stream)); // NO_LABEL
+		HIP_TRY(hipMemcpyAsync(d_labels.p + first_rowid, labels, n * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		labelled_rows = w.rows_after;
 		return VSS_OK;
 	}
 
@@ -1262,10 +1334,12 @@ struct vss_index {
 		SearchArgs &a = c.args;
 		a.gv = view();
 		// The launch's predicate becomes the kernels' view of it HERE and nowhere else.  (Row ids are below 2^63 — 2^63 - 1 is the
-		// free key — so a wider bitmap admits nothing more; the top bit is the kernels' FILTER_PER_QUERY.)
+		// free key — so a wider bitmap admits nothing more; the top bit is the kernels' FILTER_PER_QUERY.  The bit below it is
+		// FILTER_BY_LABEL, which chooses the launch's kernels: a bitmap of 2^62 bits is 2^59 bytes, more than any address space
+		// holds, so cutting a caller's n_bits there takes no row away that a bitmap in memory could admit.)
 		const SearchPredicate &p = r.predicate;
 		a.gv.filter = p.kind == SearchPredicate::ONE_BITMAP ? reinterpret_cast<const unsigned long long *>(p.bitmap) : nullptr;
-		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_PER_QUERY - 1);
+		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_BY_LABEL - 1);
 		if (p.kind == SearchPredicate::PER_QUERY) {
 			// Descriptor b = batch b's table.  A small kernel ahead of the launch resolves every query's bitmap address; the walkers
 			// of the *_groups kernels read that (GraphView::admitted_for).  The descriptors go to it by value, so the launch path
@@ -1279,6 +1353,19 @@ struct vss_index {
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits |= FILTER_PER_QUERY;
+		} else if (p.kind == SearchPredicate::BY_LABEL) {
+			// The same table, read by the *_labels kernels (GraphView::admitted_label): cell 0 the column, then what every query's
+			// rows must hold.  The re-run rounds of search_end read it again.
+			if (n_batches != 1 || !d_labels.p)
+				return fail("search by label: one batch per launch, over an index whose labels have been set");
+			if (!c.d_group_bitmap.try_grow(cap_q + 1))
+				return fail("search by label: no device memory for the wanted labels of %llu queries", (unsigned long long)cap_q);
+			count_group_tables(c);
+			ResolveLabelsArgs res = {d_labels.p, p.want, (uint32_t)nq, reinterpret_cast<unsigned long long *>(c.d_group_bitmap.p)};
+			hipLaunchKernelGGL(k_resolve_label_wants, dim3((uint32_t)(nq / 256 + 1)), dim3(256), 0, c.stream, res);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits = std::min<uint64_t>(labelled_rows, FILTER_BY_LABEL - 1) | FILTER_PER_QUERY | FILTER_BY_LABEL;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
@@ -1504,6 +1591,14 @@ struct vss_index {
 			HIP_TRY(hipMemcpyAsync(c.d_group_of.p, table.group_of, nq * 4, hipMemcpyHostToDevice, c.stream));
 		return VSS_OK;
 	}
+	// the wanted labels of a call by label (HOST memory): where a table's group numbers go, 4 bytes per query
+	int stage_wanted_labels(SearchCtx &c, const uint32_t *want, uint64_t nq) {
+		if (!c.d_group_of.try_grow(nq))
+			return fail("search by label: no device memory for the wanted labels of %llu queries", (unsigned long long)nq);
+		count_group_tables(c);
+		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, want, nq * 4, hipMemcpyHostToDevice, c.stream));
+		return VSS_OK;
+	}
 	// queries in, result buffers ensured ...
 	void stage_queries(SearchCtx &c, const float *queries, uint64_t nq, uint64_t k) {
 		c.d_q.ensure(nq * dim, 0, c.stream), c.d_out_count.ensure(nq, 0, c.stream);
@@ -1572,6 +1667,10 @@ struct vss_index {
 			c.d_filter.ensure(std::max<uint64_t>(words, 1), 0, c.stream);
 			HIP_TRY(hipMemcpyAsync(c.d_filter.p, filter.bitmap, words * 8, hipMemcpyHostToDevice, c.stream));
 			r.predicate = SearchPredicate::one_bitmap(c.d_filter.p, filter.n_bits);
+		} else if (filter.kind == SearchPredicate::BY_LABEL) {
+			if (const int rc = stage_wanted_labels(c, filter.want, nq))
+				return rc;
+			r.predicate = SearchPredicate::by_label(c.d_group_of.p, filter.n_bits);
 		}
 		stage_queries(c, queries, nq, k);
 		int rc;
@@ -1824,7 +1923,7 @@ struct vss_index {
 	// In two steps, both under exact_mu, because the routed call (filtered_auto) decides between them which groups get lists.
 	int exact_filtered_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, const uint64_t *d_table,
 	                          uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, int64_t *d_keys_out, float *d_dist_out,
-	                          uint32_t *d_count_out) {
+	                          uint32_t *d_count_out, const uint32_t *label_values = nullptr) {
 		std::lock_guard<std::mutex> exact_lock(exact_mu); // scores, running lists and the index stream are shared
 		last_exact_fallbacks = 0;
 		std::fill(last_exact_filtered, last_exact_filtered + 4, 0);
@@ -1833,10 +1932,10 @@ struct vss_index {
 		ExactFilterPlan plan;
 		exact_filter_order(group_of, nq, n_groups, plan);
 		std::vector<uint32_t> lengths;
-		if (const int rc = exact_filtered_count(plan, nq, 1, d_table, n_bits, lengths))
+		if (const int rc = exact_filtered_count(plan, nq, 1, d_table, n_bits, lengths, label_values))
 			return rc;
 		return exact_filtered_score(plan, lengths, d_xf_counts.p, true, d_queries, q_stride, k, d_table, n_bits, d_keys_out, d_dist_out,
-		                            d_count_out);
+		                            d_count_out, label_values);
 	}
 
 	// d_xf_tables of a plan over nu used groups and nq queries: [groups nu][totals nu] | [list_base nu][order nq][offset nq]
@@ -1862,10 +1961,34 @@ struct vss_index {
 		return l;
 	}
 
+	// The label form of both steps (vss_search_batch_by_label): label_values != nullptr — HOST memory, the ascending distinct wanted
+	// values — makes table group g "the rows labelled label_values[g]".  The plan, its tables and the counts' layout are the same;
+	// the cells that name the used groups hold their VALUES (ascending, as the groups are), and the label kernels list the rows.
+	LabelListArgs label_list_args(const FilterListArgs &l) const {
+		LabelListArgs a;
+		a.keys = l.keys, a.rows = l.rows, a.n_blocks = l.n_blocks;
+		a.labels = d_labels.p, a.labelled_rows = labelled_rows;
+		a.values = l.groups, a.u_begin = l.u_begin, a.u_end = l.u_end;
+		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
+		return a;
+	}
+	// the cells of the used groups, to d_xf_tables: plan.groups, or their values (`scratch` outlives the copy like plan.groups)
+	void upload_used_groups(const ExactFilterPlan &plan, const uint32_t *label_values, std::vector<uint32_t> &scratch) {
+		const uint64_t nu = plan.groups.size();
+		const uint32_t *cells = plan.groups.data();
+		if (label_values) {
+			scratch.resize(nu);
+			for (uint64_t u = 0; u != nu; ++u)
+				scratch[u] = label_values[plan.groups[u]];
+			cells = scratch.data();
+		}
+		HIP_TRY(hipMemcpyAsync(d_xf_tables.p, cells, nu * 4, hipMemcpyHostToDevice, stream));
+	}
+
 	// step 1: lengths[u] = live admitted rows of used group u of `plan` (a plan over nq queries); their block counts stay in
 	// rows [0, nu) of d_xf_counts, which has room for count_copies times as many
 	int exact_filtered_count(const ExactFilterPlan &plan, uint64_t nq, uint64_t count_copies, const uint64_t *d_table, uint64_t n_bits,
-	                         std::vector<uint32_t> &lengths) {
+	                         std::vector<uint32_t> &lengths, const uint32_t *label_values = nullptr) {
 		const uint64_t nu = plan.groups.size(), rows = count;
 		const ExactFilterTables t(nu, nq);
 		static_assert(sizeof(ExactFilterTile) == 20, "five words per tile");
@@ -1878,9 +2001,14 @@ struct vss_index {
 		ensure_events();
 		HIP_TRY(hipEventRecord(ev[0], stream));
 		lengths.assign(nu, 0);
+		std::vector<uint32_t> values;
 		if (nu && rows) { // (an empty index lists nothing: every length stays 0)
-			HIP_TRY(hipMemcpyAsync(d_xf_tables.p, plan.groups.data(), nu * 4, hipMemcpyHostToDevice, stream));
-			hipLaunchKernelGGL(k_filter_list_count, dim3((l.n_blocks + 3) / 4), dim3(256), 0, stream, l);
+			upload_used_groups(plan, label_values, values);
+			if (label_values) { // (a wave writes the counts of the groups it meets only)
+				HIP_TRY(hipMemsetAsync(d_xf_counts.p, 0, nu * l.n_blocks * 4, stream));
+				hipLaunchKernelGGL(k_label_list_count, dim3((l.n_blocks + 3) / 4), dim3(256), 0, stream, label_list_args(l));
+			} else
+				hipLaunchKernelGGL(k_filter_list_count, dim3((l.n_blocks + 3) / 4), dim3(256), 0, stream, l);
 			hipLaunchKernelGGL(k_filter_list_scan, dim3((uint32_t)nu), dim3(256), 0, stream, l);
 			HIP_TRY(hipMemcpyAsync(lengths.data(), l.totals, nu * 4, hipMemcpyDeviceToHost, stream));
 			HIP_TRY(hipStreamSynchronize(stream));
@@ -1894,7 +2022,7 @@ struct vss_index {
 	int exact_filtered_score(ExactFilterPlan &plan, const std::vector<uint32_t> &lengths, uint32_t *counts, bool groups_resident,
 	                         const float *d_queries,
 	                         uint32_t q_stride, uint64_t k, const uint64_t *d_table, uint64_t n_bits, int64_t *d_keys_out,
-	                         float *d_dist_out, uint32_t *d_count_out) {
+	                         float *d_dist_out, uint32_t *d_count_out, const uint32_t *label_values = nullptr) {
 		if (k + 8 > SEL_KP_MAX)
 			return fail("exact filtered search supports k <= %d", SEL_KP_MAX - 8);
 		const uint32_t qt = (uint32_t)std::min<uint64_t>(MS_QT, (160 * 1024) / ((uint64_t)V * 16));
@@ -1913,8 +2041,9 @@ struct vss_index {
 		FilterListArgs l = exact_filter_list_args(d_table, n_bits, nu, t);
 		l.counts = counts;
 		const dim3 list_grid((l.n_blocks + 3) / 4);
-		if (!groups_resident && nu) // (plan.groups outlives the copy: this step ends synchronised)
-			HIP_TRY(hipMemcpyAsync(d_xf_tables.p, plan.groups.data(), nu * 4, hipMemcpyHostToDevice, stream));
+		std::vector<uint32_t> values;
+		if (!groups_resident && nu) // (plan.groups and `values` outlive the copy: this step ends synchronised)
+			upload_used_groups(plan, label_values, values);
 		exact_filter_pack(lengths.data(), std::max<uint64_t>(exact_filter_budget, rows), qt, plan);
 		uint64_t entries_max = 0;
 		for (const ExactFilterPass &pass : plan.passes)
@@ -1959,7 +2088,10 @@ struct vss_index {
 			if (!n_tiles)
 				continue; // (none of its groups admits a row)
 			l.u_begin = pass.group_begin, l.u_end = pass.group_end;
-			hipLaunchKernelGGL(k_filter_list_scatter, list_grid, dim3(256), 0, stream, l);
+			if (label_values)
+				hipLaunchKernelGGL(k_label_list_scatter, list_grid, dim3(256), 0, stream, label_list_args(l));
+			else
+				hipLaunchKernelGGL(k_filter_list_scatter, list_grid, dim3(256), 0, stream, l);
 			m.tiles = reinterpret_cast<const ExactFilterTile *>(d_xf_tables.p + at_tiles) + pass.tile_begin;
 			s.query_begin = pass.query_begin;
 			for (uint64_t p0 = 0; p0 < pass.longest; p0 += CH) {
@@ -2031,7 +2163,8 @@ struct vss_index {
 	// but group_of (HOST, or nullptr: every query takes bitmap 0, and d_group_of is nullptr too) and `route` (HOST: filled here).
 	int filtered_auto(int slot, const float *d_queries, uint64_t nq, uint64_t k, uint64_t ef, const uint64_t *d_table,
 	                  uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, const uint32_t *d_group_of, uint64_t route_c,
-	                  int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out, std::vector<uint8_t> &route) {
+	                  int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out, std::vector<uint8_t> &route,
+	                  const uint32_t *label_values = nullptr) {
 		const uint64_t limit = filter_route_limit(k, ef, efs), C = route_c ? route_c : FILTER_ROUTE_C, L = count - tombstones;
 		SearchCtx &c = context(slot);
 		FilterRoutePlan rp;
@@ -2043,7 +2176,7 @@ struct vss_index {
 			ExactFilterPlan all;
 			exact_filter_order(group_of, nq, n_groups, all);
 			std::vector<uint32_t> lengths;
-			if (const int rc = exact_filtered_count(all, nq, 2, d_table, n_bits, lengths))
+			if (const int rc = exact_filtered_count(all, nq, 2, d_table, n_bits, lengths, label_values))
 				return rc;
 			filter_route_partition(all, lengths.data(), group_of, nq, L, limit, C, route_c ? 0 : FILTER_ROUTE_MIN_WALK, rp);
 			const uint64_t nu = all.groups.size(), nx = rp.exact.groups.size();
@@ -2061,7 +2194,7 @@ struct vss_index {
 					HIP_TRY(hipStreamSynchronize(stream)); // (the score step rewrites d_xf_tables)
 				}
 				if (const int rc = exact_filtered_score(rp.exact, rp.exact_lengths, counts, nx == nu, d_queries, (uint32_t)dim, k, d_table,
-				                                        n_bits, d_keys_out, d_dist_out, d_count_out))
+				                                        n_bits, d_keys_out, d_dist_out, d_count_out, label_values))
 					return rc;
 			}
 			last_filter_route[0] = rp.graph_queries.size(), last_filter_route[1] = rp.exact.order.size();
@@ -2101,8 +2234,10 @@ struct vss_index {
 			hipLaunchKernelGGL(k_route_gather, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, g);
 			HIP_TRY(hipGetLastError());
 			SearchRequest r = request(slot, &c.d_route_q.p, 1, ng, k, ef, &c.d_route_keys.p, &c.d_route_d.p, &c.d_route_count.p);
-			r.predicate = d_group_of ? SearchPredicate::one_table(d_table, c.d_route_group.p, n_groups, n_bits)
-			                         : SearchPredicate::one_bitmap(d_table, n_bits);
+			// (the label form: d_group_of is the queries' wanted labels, so the compact batch's "groups" are its wanted labels)
+			r.predicate = label_values ? SearchPredicate::by_label(c.d_route_group.p, labelled_rows)
+			              : d_group_of ? SearchPredicate::one_table(d_table, c.d_route_group.p, n_groups, n_bits)
+			                           : SearchPredicate::one_bitmap(d_table, n_bits);
 			if (const int rc = search_launch(r))
 				return rc;
 			RouteScatterArgs s;
@@ -2129,6 +2264,44 @@ struct vss_index {
 		std::vector<uint8_t> route;
 		if (const int rc = filtered_auto(lease.slot, c.d_q.p, nq, k, ef, c.d_group_filter.p, n_groups, n_bits, group_of,
 		                                 group_of ? c.d_group_of.p : nullptr, route_c, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p, route))
+			return rc;
+		fetch_results(c, nq, k, out_keys, out_d, out_counts);
+		if (out_route)
+			std::memcpy(out_route, route.data(), nq);
+		return VSS_OK;
+	}
+
+	// ------------------------------------------------------------------ search by label (label_filter.h)
+	// The exact scan (exact == true) or the routed call over the table label_groups() makes of `want` (HOST memory; d_want: the
+	// same values in DEVICE memory, read by the walk of the graph-routed queries): group g = the rows labelled values[g].  No
+	// bitmap exists anywhere; the plans, the rule and the counters are those of the bitmap calls.
+	int by_label_launch(int slot, bool exact, const float *d_queries, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *want,
+	                    const uint32_t *d_want, uint64_t route_c, int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out,
+	                    std::vector<uint8_t> &route) {
+		std::vector<uint32_t> values, group_of;
+		label_groups(want, nq, values, group_of);
+		if (exact) {
+			route.assign(nq, FILTER_ROUTE_EXACT);
+			return exact_filtered_launch(d_queries, (uint32_t)dim, nq, k, nullptr, values.size(), labelled_rows, group_of.data(), d_keys_out,
+			                             d_dist_out, d_count_out, values.data());
+		}
+		return filtered_auto(slot, d_queries, nq, k, ef, nullptr, values.size(), labelled_rows, group_of.data(), d_want, route_c, d_keys_out,
+		                     d_dist_out, d_count_out, route, values.data());
+	}
+
+	// the host-pointer form of those two: staged through a leased context, as exact_filtered_host / filtered_auto_host do
+	int by_label_host(bool exact, const float *queries, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *want, uint64_t route_c,
+	                  int64_t *out_keys, float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+		Lease lease(this);
+		SearchCtx &c = context(lease.slot);
+		if (!exact)
+			if (const int rc = stage_wanted_labels(c, want, nq))
+				return rc;
+		stage_queries(c, queries, nq, k);
+		HIP_TRY(hipStreamSynchronize(c.stream)); // the count and exact kernels run on the index stream
+		std::vector<uint8_t> route;
+		if (const int rc = by_label_launch(lease.slot, exact, c.d_q.p, nq, k, ef, want, exact ? nullptr : c.d_group_of.p, route_c,
+		                                   c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p, route))
 			return rc;
 		fetch_results(c, nq, k, out_keys, out_d, out_counts);
 		if (out_route)
@@ -3386,6 +3559,91 @@ int vss_last_filter_route(vss_index *h, uint64_t *out8) {
 	return VSS_OK;
 }
 
+// ---- the label column and the search by label (label_filter.h; include/vssgpu.h has the contract)
+int vss_set_labels(vss_index *h, uint64_t first_rowid, const uint32_t *labels, uint64_t n) {
+	VSS_GUARD(h, { return h->set_labels("vss_set_labels", first_rowid, labels, n, false); })
+}
+
+int vss_set_labels_device(vss_index *h, uint64_t first_rowid, const uint32_t *d_labels, uint64_t n) {
+	VSS_GUARD(h, { return h->set_labels("vss_set_labels_device", first_rowid, d_labels, n, true); })
+}
+
+int vss_clear_labels(vss_index *h) {
+	VSS_GUARD(h, {
+		if (h->refuse_while_probing("vss_clear_labels") != VSS_OK)
+			return VSS_ERROR;
+		h->clear_labels();
+		return VSS_OK;
+	})
+}
+
+uint64_t vss_labelled_rows(const vss_index *h) {
+	if (!h)
+		return 0;
+	std::shared_lock<std::shared_mutex> lk(const_cast<vss_index *>(h)->rw);
+	return h->labelled_rows;
+}
+
+// what every form of the call refuses before it stages or launches anything
+static int check_by_label(vss_index *h, const char *what, const float *Q, uint64_t nq, const uint32_t *want, int mode,
+                          const int64_t *out, const uint32_t *out_counts) {
+	if (mode != VSS_BY_LABEL_GRAPH && mode != VSS_BY_LABEL_EXACT && mode != VSS_BY_LABEL_AUTO)
+		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
+	if (!h->d_labels.p)
+		return h->fail("%s: the index has no label column (call vss_set_labels first; vss_load and vss_clear_labels drop it)", what);
+	if (!Q || !want || !out || !out_counts)
+		return h->fail("%s: null query / wanted-label / row-id / count pointer", what);
+	if (nq > 0xFFFFFFFFull)
+		return h->fail("%s: at most 2^32 - 1 queries per call", what);
+	return VSS_OK;
+}
+
+int vss_search_batch_by_label(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *want, int mode,
+                              uint64_t route_c, int64_t *out, float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		if (check_by_label(h, "vss_search_batch_by_label", Q, nq, want, mode, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		if (mode != VSS_BY_LABEL_GRAPH)
+			return h->by_label_host(mode == VSS_BY_LABEL_EXACT, Q, nq, k, ef, want, route_c, out, out_d, out_counts, out_route);
+		if (out_route)
+			std::memset(out_route, FILTER_ROUTE_GRAPH, nq);
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, SearchPredicate::by_label(want, h->labelled_rows));
+	})
+}
+
+int vss_search_batch_by_label_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *want,
+                                     int mode, uint64_t route_c, int64_t *out, float *out_d, uint32_t *out_counts,
+                                     uint8_t *out_route) {
+	VSS_SHARED(h, {
+		if (check_by_label(h, "vss_search_batch_by_label_device", Q, nq, want, mode, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		std::vector<uint8_t> route(nq, FILTER_ROUTE_GRAPH);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+			r.predicate = SearchPredicate::by_label(want, h->labelled_rows);
+			if (const int rc = h->search_launch(r))
+				return rc;
+		} else {
+			// the plans need every query's wanted label on the host: 4 bytes per query come back
+			std::vector<uint32_t> want_h(nq);
+			HIP_TRY(hipMemcpyAsync(want_h.data(), want, nq * 4, hipMemcpyDeviceToHost, h->stream));
+			HIP_TRY(hipStreamSynchronize(h->stream));
+			if (const int rc = h->by_label_launch(0, mode == VSS_BY_LABEL_EXACT, Q, nq, k, ef, want_h.data(), want, route_c, out, out_d,
+			                                      out_counts, route))
+				return rc;
+		}
+		if (out_route) {
+			HIP_TRY(hipMemcpyAsync(out_route, route.data(), nq, hipMemcpyHostToDevice, h->stream));
+			HIP_TRY(hipStreamSynchronize(h->stream));
+		}
+		return VSS_OK;
+	})
+}
+
 int vss_last_search_stats(vss_index *h, uint64_t *out4) {
 	VSS_SHARED(h, {
 		std::lock_guard<std::mutex> lk(h->stats_mu);
@@ -3533,7 +3791,7 @@ uint64_t vss_memory_usage(vss_index *h) {
 	const uint64_t group_tables = h->group_table_bytes.load(std::memory_order_relaxed);
 	return h->d_vectors.n * 4 + h->d_links0.n * 4 + h->d_links_up.n * 4 + h->d_upper_off.n * 4 + h->d_levels.n +
 	       h->d_keys.n * 8 + h->d_list_owner.n * 4 + h->d_codes.n * sizeof(uint32_t) + h->d_code_meta.n * sizeof(RowCodeMeta) +
-	       group_tables + h->exact_filter_bytes.load(std::memory_order_relaxed);
+	       group_tables + h->exact_filter_bytes.load(std::memory_order_relaxed) + h->label_bytes.load(std::memory_order_relaxed);
 }
 
 int vss_level_stats(vss_index *h, uint64_t level, uint64_t *out4) {
@@ -3557,8 +3815,10 @@ int vss_save(vss_index *h, vss_write_cb write, void *ctx) {
 int vss_load(vss_index *h, vss_read_cb read, void *ctx) {
 	VSS_GUARD(h, {
 		const int rc = h->load(read, ctx);
-		if (rc == VSS_OK)
+		if (rc == VSS_OK) {
+			h->clear_labels(); // (the stream's row ids are another table's: the caller sets its labels again)
 			h->refresh_codes();
+		}
 		return rc;
 	})
 }

@@ -313,6 +313,48 @@ public:
 			*routes_out = routes;
 		return total;
 	}
+	// The correlated chunk whose predicate is an EQUALITY on one column (`WHERE items.tenant = q.tenant`), without bitmaps: the
+	// index holds the column's 32-bit value of every row id (SetLabels, written next to the rows in Append), outer row q brings the
+	// one value it wants, and vss_search_batch_by_label does the rest — mode VSS_BY_LABEL_AUTO routes every value to the walk or
+	// the scan like ExecuteMultiScanBatchGroupedAuto, _GRAPH and _EXACT force one.  VSS_NO_LABEL (a NULL tenant) wants nothing.
+	// Any other predicate keeps the bitmap calls above.
+	idx_t ExecuteMultiScanBatchByLabel(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit, const uint32_t *want,
+	                                   std::vector<uint32_t> *counts_out, std::vector<uint8_t> *routes_out = nullptr,
+	                                   int mode = VSS_BY_LABEL_AUTO, uint64_t route_c = 0) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::vector<row_t> ids(n_queries * limit);
+		std::vector<uint32_t> counts(n_queries);
+		std::vector<uint8_t> routes(n_queries);
+		{
+			std::shared_lock<std::shared_mutex> lock(rwlock);
+			Check(vss_search_batch_by_label(index, queries, n_queries, limit, state.ef_search, want, mode, route_c, ids.data(), nullptr,
+			                                counts.data(), routes.data()),
+			      "search");
+		}
+		idx_t total = 0;
+		for (idx_t q = 0; q != n_queries; ++q) {
+			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
+			total += counts[q];
+		}
+		if (counts_out)
+			*counts_out = counts;
+		if (routes_out)
+			*routes_out = routes;
+		return total;
+	}
+	// The label column: cells first_rowid .. first_rowid + n - 1 (vss_set_labels).  Not persisted: after LoadFromBlocks the owner
+	// writes it again from the table.
+	void SetLabels(idx_t first_rowid, const uint32_t *labels, idx_t n) {
+		std::unique_lock<std::shared_mutex> lock(rwlock);
+		Check(vss_set_labels(index, first_rowid, labels, n), "label");
+	}
+	void ClearLabels() {
+		std::unique_lock<std::shared_mutex> lock(rwlock);
+		Check(vss_clear_labels(index), "label");
+	}
+	idx_t LabelledRows() const {
+		return vss_labelled_rows(index);
+	}
 	const std::vector<row_t> &GetMultiScanResult(IndexScanState &state) {
 		return static_cast<MultiScanState &>(state).row_ids;
 	}

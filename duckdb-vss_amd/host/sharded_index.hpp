@@ -432,6 +432,44 @@ public:
 		}
 	}
 
+	// ---- equality predicates on the label column (vss_search_batch_by_label_device per shard), no bitmaps.  Row ids are GLOBAL,
+	// so every shard's engine gets the whole column: SetLabels writes the same cells into each (4 bytes per row id and shard).
+	// Not persisted: set again after Load.
+	void SetLabels(idx_t first_rowid, const uint32_t *labels, idx_t n) {
+		for (auto &s : shards)
+			s.index->SetLabels(first_rowid, labels, n);
+	}
+	void ClearLabels() {
+		for (auto &s : shards)
+			s.index->ClearLabels();
+	}
+	// Query q admits the live rows labelled want[q] (VSS_NO_LABEL: none).  mode VSS_BY_LABEL_AUTO: every shard routes every
+	// value by ITS OWN count of such rows and ITS OWN live rows, as in SearchBatchFilteredGroupsAuto; _GRAPH / _EXACT force one
+	// way in all of them.  shard_routes (optional): [g * n + q].  The wanted values travel as UploadTables' group numbers; the
+	// exchange and merge are SearchExactBatchFilteredGroups' — rows at exactly equal distance come back by (distance, row id).
+	void SearchBatchByLabel(const float *queries, idx_t n, idx_t k, idx_t ef, const uint32_t *want, int mode, uint64_t route_c,
+	                        row_t *out_rowids, float *out_distances, uint32_t *out_counts, std::vector<uint8_t> *shard_routes = nullptr) {
+		if (shard_routes)
+			shard_routes->assign(shards.size() * n, 0);
+		if (!n || !k)
+			return;
+		if (!want)
+			throw InternalException("Failed to search the HNSW index: search by label needs the wanted label of every query");
+		Ensure(n, k);
+		UploadTables(nullptr, 0, want, n);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_batch_by_label_device(s.index->Handle(), s.d_q, n, k, ef, bitmaps[s.bitmap].group_of, mode, route_c, keys,
+			                                            dist, s.d_cnt, s.d_route));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		for (size_t g = 0; shard_routes && g != shards.size(); ++g) {
+			Hip(hipSetDevice(shards[g].device), "hipSetDevice");
+			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
+		}
+	}
+
 private:
 	// A table of per-query predicates, refused here before any device is touched: the rules of csrc/filter_groups.h in this
 	// layer's words.  An unknown group is reported ahead of a table too large to exist, as it always was.
@@ -470,7 +508,8 @@ private:
 			grow(b.words, b.capacity, std::max<idx_t>(words, 1));
 			if (group_of)
 				grow(b.group_of, b.group_capacity, n);
-			Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
+			if (words) // (none: SearchBatchByLabel brings wanted labels only)
+				Hip(hipMemcpy(b.words, allowed, words * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bitmaps");
 			if (group_of)
 				Hip(hipMemcpy(b.group_of, group_of, n * sizeof(uint32_t), hipMemcpyHostToDevice), "copy groups");
 		}

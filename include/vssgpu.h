@@ -241,6 +241,41 @@ int vss_search_batch_filtered_groups_auto_device(vss_index *index, const float *
 /* The last such call: out8[0] = queries routed graph, [1] = queries routed exact, [2] / [3] = groups in use routed graph /
  * exact, [4] = L, [5] = the C used, [6] = limit, [7] = 0. */
 int vss_last_filter_route(vss_index *index, uint64_t *out8);
+
+/* ---- Equality predicates on a resident label column (csrc/label_filter.h) ------------------------------------------------
+ * For the predicate `items.tenant = q.tenant`: the index keeps one 32-bit label per ROW ID on the device, a query brings the
+ * one value it wants, and no bitmap is built, uploaded or read.  The column is indexed by row id like the bitmaps of the
+ * calls above, so removals, reused slots and vss_compact need no label call; it is NOT part of the stream (vss_save) and
+ * vss_load clears it — set the labels again after a load.  Every other predicate keeps the bitmap calls.
+ *
+ * vss_set_labels writes cells first_rowid .. first_rowid + n - 1 (overwriting), grows the column when it must and fills a
+ * gap it skips over with VSS_NO_LABEL.  first_rowid + n > 2^32 is refused; n == 0 is a no-op.  Without room on the device
+ * the call fails and the column stays as it was.  Writer lock; refused while a _begin context is in flight.
+ * vss_labelled_rows: row ids [0, this) have a cell; 0 = no column.  vss_memory_usage counts the column. */
+#define VSS_NO_LABEL 0xFFFFFFFFu
+int vss_set_labels(vss_index *index, uint64_t first_rowid, const uint32_t *labels, uint64_t n); /* host memory */
+int vss_set_labels_device(vss_index *index, uint64_t first_rowid, const uint32_t *d_labels, uint64_t n);
+int vss_clear_labels(vss_index *index);
+uint64_t vss_labelled_rows(const vss_index *index);
+/* Query q admits a live row of id r iff 0 <= r < vss_labelled_rows(), labels[r] == want[q] and want[q] != VSS_NO_LABEL (a
+ * NULL tenant equals nothing: count 0, ids -1, distances +inf — as for a value no row carries).
+ * mode: VSS_BY_LABEL_GRAPH the walk of vss_search_batch_filtered_groups, VSS_BY_LABEL_EXACT the scan of
+ * vss_search_exact_batch_filtered_groups (ef unused), VSS_BY_LABEL_AUTO the rule and minimum walk of ..._groups_auto with
+ * the same route_c.  out_route (may be NULL): all 0 in mode GRAPH, all 1 in mode EXACT, the routes in mode AUTO.
+ * Contract: with v_0 < v_1 < ... the distinct values of `want`, bitmap g = {r < labelled rows : labels[r] == v_g != VSS_NO_LABEL}
+ * and group_of[q] = the index of want[q], the call returns cell for cell what the bitmap call of the same mode returns for
+ * that table — row ids, f32 distance bits, counts, routes — and leaves the same vss_last_exact_filtered [0..2],
+ * vss_last_filter_route, vss_last_search_stats / _shape / _prescore values behind.
+ * Errors: no column set; a mode other than the three (refused before anything is staged); those of the call of the mode.
+ * The _device form takes device pointers (d_out_distances and d_out_route may be NULL), copies d_want back (4 bytes per
+ * query) and runs on context 0.  Not available in the pipelined / multi-batch _begin forms. */
+enum { VSS_BY_LABEL_GRAPH = 0, VSS_BY_LABEL_EXACT = 1, VSS_BY_LABEL_AUTO = 2 };
+int vss_search_batch_by_label(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                              const uint32_t *want, int mode, uint64_t route_c, int64_t *out_rowids, float *out_distances,
+                              uint32_t *out_counts, uint8_t *out_route);
+int vss_search_batch_by_label_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                     const uint32_t *d_want, int mode, uint64_t route_c, int64_t *d_out_rowids,
+                                     float *d_out_distances, uint32_t *d_out_counts, uint8_t *d_out_route);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
