@@ -166,6 +166,116 @@ struct SearchRequest {
 	bool keep_query_stats = false; // search_launch: keep every query's counters for vss_last_query_stats
 };
 
+// ---- the scan side's counterpart of the two values above (the exact scan under predicates, the routed call, the calls by label)
+// A per-query column of 32-bit words, marked by the memory it lives in: the plans read such a column on the host, the walk on the
+// device, and both are `const uint32_t *`.
+struct HostWords {
+	const uint32_t *p;
+	explicit HostWords(const uint32_t *host) : p(host) {
+	}
+};
+struct DeviceWords {
+	const uint32_t *p;
+	explicit DeviceWords(const uint32_t *device) : p(device) {
+	}
+};
+
+// The groups the rows of a scan call are listed by, made by one of the two factories only.  Bitmaps: group g = the rows bitmap g
+// of a DEVICE table admits.  Labels: group g = the rows the index's label column gives values[g], the ascending distinct wanted
+// values (HOST memory); no bitmap exists.  Either way query q reads group group_of[q] (HOST memory; nullptr: all read group 0),
+// and the walk of the graph-routed queries reads the column's DEVICE twin: group numbers under bitmaps, wanted labels under labels.
+struct GroupedRows {
+	const uint64_t *d_table = nullptr;  // bitmaps: n_groups bitmaps of n_bits bits
+	uint64_t n_groups = 0, n_bits = 0;  // (labels: the distinct wanted values; the cells of the label column)
+	const uint32_t *values = nullptr;   // labels: HOST
+	const uint32_t *d_labels = nullptr; // labels: the label column
+	const uint32_t *group_of = nullptr, *d_group_of = nullptr;
+
+	static GroupedRows bitmaps(const uint64_t *d_table, uint64_t n_groups, uint64_t n_bits, HostWords group_of, DeviceWords d_group_of) {
+		GroupedRows g;
+		g.d_table = d_table, g.n_groups = n_groups, g.n_bits = n_bits, g.group_of = group_of.p, g.d_group_of = d_group_of.p;
+		return g;
+	}
+	static GroupedRows labels(const std::vector<uint32_t> &values, const uint32_t *d_labels, uint64_t labelled_rows, HostWords group_of,
+	                          DeviceWords d_want) {
+		GroupedRows g;
+		g.by_label = true, g.values = values.data(), g.d_labels = d_labels;
+		g.n_groups = values.size(), g.n_bits = labelled_rows, g.group_of = group_of.p, g.d_group_of = d_want.p;
+		return g;
+	}
+
+	// the list kernels' arguments in the label form: table group g is "the rows labelled values[g]", so the cells that name the
+	// used groups hold their VALUES (ascending, as the groups are); the plan, its tables and the counts' layout are the same
+	LabelListArgs label_list_args(const FilterListArgs &l) const {
+		LabelListArgs a;
+		a.keys = l.keys, a.rows = l.rows, a.n_blocks = l.n_blocks;
+		a.labels = d_labels, a.labelled_rows = n_bits;
+		a.values = l.groups, a.u_begin = l.u_begin, a.u_end = l.u_end;
+		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
+		return a;
+	}
+	// the cells of a plan's used groups: plan.groups, or their values in `scratch` (which outlives the upload like plan.groups)
+	const uint32_t *used_group_cells(const ExactFilterPlan &plan, std::vector<uint32_t> &scratch) const {
+		if (!by_label)
+			return plan.groups.data();
+		scratch.resize(plan.groups.size());
+		for (size_t u = 0; u != scratch.size(); ++u)
+			scratch[u] = values[plan.groups[u]];
+		return scratch.data();
+	}
+	// step 1 of the listing: the block counts of used groups [l.u_begin, l.u_end)
+	void launch_count(const FilterListArgs &l, hipStream_t stream) const {
+		const dim3 grid((l.n_blocks + 3) / 4);
+		if (by_label) { // (a wave writes the counts of the groups it meets only)
+			HIP_TRY(hipMemsetAsync(l.counts, 0, (uint64_t)(l.u_end - l.u_begin) * l.n_blocks * 4, stream));
+			hipLaunchKernelGGL(k_label_list_count, grid, dim3(256), 0, stream, label_list_args(l));
+		} else
+			hipLaunchKernelGGL(k_filter_list_count, grid, dim3(256), 0, stream, l);
+	}
+	// step 3: the lists themselves, from the scanned counts
+	void launch_scatter(const FilterListArgs &l, hipStream_t stream) const {
+		const dim3 grid((l.n_blocks + 3) / 4);
+		if (by_label)
+			hipLaunchKernelGGL(k_label_list_scatter, grid, dim3(256), 0, stream, label_list_args(l));
+		else
+			hipLaunchKernelGGL(k_filter_list_scatter, grid, dim3(256), 0, stream, l);
+	}
+	// what the walk of a compact batch of graph-routed queries filters by; d_compact_groups: their cells of d_group_of, gathered
+	SearchPredicate walk_predicate(const uint32_t *d_compact_groups) const {
+		if (by_label)
+			return SearchPredicate::by_label(d_compact_groups, n_bits);
+		return d_group_of ? SearchPredicate::one_table(d_table, d_compact_groups, n_groups, n_bits)
+		                  : SearchPredicate::one_bitmap(d_table, n_bits);
+	}
+
+private:
+	bool by_label = false;
+	GroupedRows() = default;
+};
+
+// One batch in DEVICE memory: query q at d_queries + q * q_stride.  slot: the context that carries its walk, as SearchRequest's.
+struct DeviceBatch {
+	int slot;
+	const float *d_queries;
+	uint32_t q_stride;
+	uint64_t nq, k, ef;
+};
+// ... and where its answers go, in DEVICE memory: k cells per query of keys / dist, one of count
+struct DeviceAnswers {
+	int64_t *keys;
+	float *dist;
+	uint32_t *count;
+};
+// One host-pointer call: what staged_call moves to and from a leased context (out_d, out_counts, out_route may be nullptr)
+struct HostCall {
+	const float *queries;
+	uint64_t nq, k, ef;
+	int64_t *out_keys;
+	float *out_d;
+	uint32_t *out_counts;
+	uint8_t *out_route;
+};
+
 struct vss_index {
 	// Reader/writer discipline of the reference (SURVEY §8b "Threading"): any number of concurrent searches (shared), every
 	// call that changes the graph or its buffers exclusive.  Searches lease one of the pooled contexts below.
@@ -1614,6 +1724,28 @@ struct vss_index {
 			HIP_TRY(hipMemcpyAsync(out_counts, c.d_out_count.p, nq * 4, hipMemcpyDeviceToHost, c.stream));
 		HIP_TRY(hipStreamSynchronize(c.stream));
 	}
+	// One host-pointer call answered through a leased context.  stage(c) puts the call's predicate into the context's buffers;
+	// run(c, batch, answers, route) answers the staged batch into the context's result buffers and may fill `route`, a byte per
+	// query, for hc.out_route.  on_index_stream: `run` launches on the index stream (the count and exact kernels do), so what was
+	// staged on the context's stream has to have landed first.  A failure of either step returns before any answer is written.
+	template <typename Stage, typename Run>
+	int staged_call(const HostCall &hc, bool on_index_stream, Stage stage, Run run) {
+		Lease lease(this);
+		SearchCtx &c = context(lease.slot);
+		if (const int rc = stage(c))
+			return rc;
+		stage_queries(c, hc.queries, hc.nq, hc.k);
+		if (on_index_stream)
+			HIP_TRY(hipStreamSynchronize(c.stream));
+		std::vector<uint8_t> route;
+		if (const int rc = run(c, DeviceBatch {lease.slot, c.d_q.p, (uint32_t)dim, hc.nq, hc.k, hc.ef},
+		                       DeviceAnswers {c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p}, route))
+			return rc;
+		fetch_results(c, hc.nq, hc.k, hc.out_keys, hc.out_d, hc.out_counts);
+		if (hc.out_route)
+			std::memcpy(hc.out_route, route.data(), hc.nq);
+		return VSS_OK;
+	}
 
 	// `filter`: the predicate in HOST memory (of one batch: batches[0] where it has tables); exact search takes none
 	static constexpr uint64_t DIRECT_IO_MAX_QUERIES = 256;
@@ -1621,14 +1753,14 @@ struct vss_index {
 	                uint32_t *out_counts, bool exact, const SearchPredicate &filter) {
 		if (!nq || !k)
 			return VSS_OK;
-		Lease lease(this);
-		SearchCtx &c = context(lease.slot);
 		// Small batches — the one-query probe of HNSW_INDEX_SCAN (hnsw_index.cpp:315-356) and the chunks of HNSW_INDEX_JOIN
 		// (hnsw_optimize_join.cpp:111-168; 204 queries at 768 dims): the kernel reads the queries from, and writes ids /
 		// distances / counts / status straight into, one pinned host block.  No staging copies; the only host-device
 		// interaction is the launch and one synchronisation.  (Up to DIRECT_IO_MAX_QUERIES — a query per compute unit: such a
 		// launch is bound by its longest query, and a walker reads its 3 KiB over PCIe once per ~0.4 ms of work.)
 		if (!exact && filter.kind == SearchPredicate::NONE && nq <= DIRECT_IO_MAX_QUERIES && count) {
+			Lease lease(this);
+			SearchCtx &c = context(lease.slot);
 			const size_t q_bytes = (nq * dim * 4 + 15) & ~size_t(15), key_bytes = nq * k * 8;
 			const size_t d_bytes = (nq * k * 4 + 15) & ~size_t(15), c_bytes = (nq * 4 + 15) & ~size_t(15);
 			const size_t need = q_bytes + key_bytes + d_bytes + c_bytes;
@@ -1655,35 +1787,35 @@ struct vss_index {
 				std::memcpy(out_counts, pc, nq * 4);
 			return VSS_OK;
 		}
-		SearchRequest r = request(lease.slot, &c.d_q.p, 1, nq, k, ef, &c.d_out_keys.p, &c.d_out_d.p, &c.d_out_count.p);
-		r.keep_query_stats = true;
-		if (filter.kind == SearchPredicate::PER_QUERY) {
-			const FilterGroupBatch &table = filter.batches[0];
-			if (const int rc = stage_group_table(c, table, filter.n_bits, nq))
-				return rc;
-			r.predicate = SearchPredicate::one_table(c.d_group_filter.p, c.d_group_of.p, table.n_groups, filter.n_bits);
-		} else if (filter.kind == SearchPredicate::ONE_BITMAP) {
-			const uint64_t words = filter_group_words(filter.n_bits);
-			c.d_filter.ensure(std::max<uint64_t>(words, 1), 0, c.stream);
-			HIP_TRY(hipMemcpyAsync(c.d_filter.p, filter.bitmap, words * 8, hipMemcpyHostToDevice, c.stream));
-			r.predicate = SearchPredicate::one_bitmap(c.d_filter.p, filter.n_bits);
-		} else if (filter.kind == SearchPredicate::BY_LABEL) {
-			if (const int rc = stage_wanted_labels(c, filter.want, nq))
-				return rc;
-			r.predicate = SearchPredicate::by_label(c.d_group_of.p, filter.n_bits);
-		}
-		stage_queries(c, queries, nq, k);
-		int rc;
-		if (exact) {
-			HIP_TRY(hipStreamSynchronize(c.stream)); // the exact kernels run on the index stream
-			rc = exact_launch(c.d_q.p, (uint32_t)dim, nq, k, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p);
-		} else {
-			rc = search_launch(r);
-		}
-		if (rc != VSS_OK)
-			return rc;
-		fetch_results(c, nq, k, out_keys, out_d, out_counts);
-		return VSS_OK;
+		SearchPredicate staged; // the predicate of the launch: `filter`, in the context's buffers
+		return staged_call(
+		    {queries, nq, k, ef, out_keys, out_d, out_counts, nullptr}, exact,
+		    [&](SearchCtx &c) -> int {
+			    if (filter.kind == SearchPredicate::PER_QUERY) {
+				    const FilterGroupBatch &table = filter.batches[0];
+				    if (const int rc = stage_group_table(c, table, filter.n_bits, nq))
+					    return rc;
+				    staged = SearchPredicate::one_table(c.d_group_filter.p, c.d_group_of.p, table.n_groups, filter.n_bits);
+			    } else if (filter.kind == SearchPredicate::ONE_BITMAP) {
+				    const uint64_t words = filter_group_words(filter.n_bits);
+				    c.d_filter.ensure(std::max<uint64_t>(words, 1), 0, c.stream);
+				    HIP_TRY(hipMemcpyAsync(c.d_filter.p, filter.bitmap, words * 8, hipMemcpyHostToDevice, c.stream));
+				    staged = SearchPredicate::one_bitmap(c.d_filter.p, filter.n_bits);
+			    } else if (filter.kind == SearchPredicate::BY_LABEL) {
+				    if (const int rc = stage_wanted_labels(c, filter.want, nq))
+					    return rc;
+				    staged = SearchPredicate::by_label(c.d_group_of.p, filter.n_bits);
+			    }
+			    return VSS_OK;
+		    },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &) -> int {
+			    if (exact)
+				    return exact_launch(b.d_queries, b.q_stride, nq, k, out.keys, out.dist, out.count);
+			    SearchRequest r = request(b.slot, &c.d_q.p, 1, nq, k, ef, &c.d_out_keys.p, &c.d_out_d.p, &c.d_out_count.p);
+			    r.keep_query_stats = true;
+			    r.predicate = staged;
+			    return search_launch(r);
+		    });
 	}
 
 	// ------------------------------------------------------------------ exact search
@@ -1919,23 +2051,20 @@ struct vss_index {
 	// ------------------------------------------------------------------ exact search under per-query predicates
 	// Carries out the plan of exact_filtered_plan.h: list the live admitted slots of every group in use, score each query
 	// against its group's list only, keep the K' smallest (distance, slot) pairs per query, re-rank.  Distances are the metric's
-	// own from the start, so nothing is certified and nothing redone.  group_of: HOST memory, or nullptr (all take bitmap 0).
+	// own from the start, so nothing is certified and nothing redone.  `g` names the groups, by bitmaps or by labels (GroupedRows).
 	// In two steps, both under exact_mu, because the routed call (filtered_auto) decides between them which groups get lists.
-	int exact_filtered_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, const uint64_t *d_table,
-	                          uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, int64_t *d_keys_out, float *d_dist_out,
-	                          uint32_t *d_count_out, const uint32_t *label_values = nullptr) {
+	int exact_filtered_launch(const DeviceBatch &b, const GroupedRows &g, const DeviceAnswers &out) {
 		std::lock_guard<std::mutex> exact_lock(exact_mu); // scores, running lists and the index stream are shared
 		last_exact_fallbacks = 0;
 		std::fill(last_exact_filtered, last_exact_filtered + 4, 0);
-		if (k + 8 > SEL_KP_MAX)
+		if (b.k + 8 > SEL_KP_MAX)
 			return fail("exact filtered search supports k <= %d", SEL_KP_MAX - 8);
 		ExactFilterPlan plan;
-		exact_filter_order(group_of, nq, n_groups, plan);
+		exact_filter_order(g.group_of, b.nq, g.n_groups, plan);
 		std::vector<uint32_t> lengths;
-		if (const int rc = exact_filtered_count(plan, nq, 1, d_table, n_bits, lengths, label_values))
+		if (const int rc = exact_filtered_count(plan, b.nq, 1, g, lengths))
 			return rc;
-		return exact_filtered_score(plan, lengths, d_xf_counts.p, true, d_queries, q_stride, k, d_table, n_bits, d_keys_out, d_dist_out,
-		                            d_count_out, label_values);
+		return exact_filtered_score(plan, lengths, nullptr, b, g, out);
 	}
 
 	// d_xf_tables of a plan over nu used groups and nq queries: [groups nu][totals nu] | [list_base nu][order nq][offset nq]
@@ -1951,64 +2080,40 @@ struct vss_index {
 		last_exact_filtered[3] = (d_xf_lists.n + d_xf_counts.n + d_xf_tables.n) * 4;
 		exact_filter_bytes.store(last_exact_filtered[3], std::memory_order_relaxed);
 	}
-	FilterListArgs exact_filter_list_args(const uint64_t *d_table, uint64_t n_bits, uint64_t nu, const ExactFilterTables &t) const {
+	FilterListArgs exact_filter_list_args(const GroupedRows &g, uint64_t nu, const ExactFilterTables &t) const {
 		FilterListArgs l;
 		l.keys = d_keys.p, l.rows = (uint32_t)count, l.n_blocks = (uint32_t)((count + FL_WAVE_SLOTS - 1) / FL_WAVE_SLOTS);
-		l.table = d_table, l.words = filter_group_words(n_bits), l.n_bits = n_bits;
+		l.table = g.d_table, l.words = filter_group_words(g.n_bits), l.n_bits = g.n_bits;
 		l.groups = d_xf_tables.p, l.totals = d_xf_tables.p + t.at_totals, l.list_base = d_xf_tables.p + t.at_base;
 		l.u_begin = 0, l.u_end = (uint32_t)nu;
 		l.counts = d_xf_counts.p, l.lists = nullptr;
 		return l;
 	}
-
-	// The label form of both steps (vss_search_batch_by_label): label_values != nullptr — HOST memory, the ascending distinct wanted
-	// values — makes table group g "the rows labelled label_values[g]".  The plan, its tables and the counts' layout are the same;
-	// the cells that name the used groups hold their VALUES (ascending, as the groups are), and the label kernels list the rows.
-	LabelListArgs label_list_args(const FilterListArgs &l) const {
-		LabelListArgs a;
-		a.keys = l.keys, a.rows = l.rows, a.n_blocks = l.n_blocks;
-		a.labels = d_labels.p, a.labelled_rows = labelled_rows;
-		a.values = l.groups, a.u_begin = l.u_begin, a.u_end = l.u_end;
-		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
-		return a;
-	}
-	// the cells of the used groups, to d_xf_tables: plan.groups, or their values (`scratch` outlives the copy like plan.groups)
-	void upload_used_groups(const ExactFilterPlan &plan, const uint32_t *label_values, std::vector<uint32_t> &scratch) {
-		const uint64_t nu = plan.groups.size();
-		const uint32_t *cells = plan.groups.data();
-		if (label_values) {
-			scratch.resize(nu);
-			for (uint64_t u = 0; u != nu; ++u)
-				scratch[u] = label_values[plan.groups[u]];
-			cells = scratch.data();
-		}
-		HIP_TRY(hipMemcpyAsync(d_xf_tables.p, cells, nu * 4, hipMemcpyHostToDevice, stream));
+	// the cells of the used groups, to d_xf_tables (`scratch` outlives the copy like plan.groups)
+	void upload_used_groups(const ExactFilterPlan &plan, const GroupedRows &g, std::vector<uint32_t> &scratch) {
+		HIP_TRY(hipMemcpyAsync(d_xf_tables.p, g.used_group_cells(plan, scratch), plan.groups.size() * 4, hipMemcpyHostToDevice, stream));
 	}
 
 	// step 1: lengths[u] = live admitted rows of used group u of `plan` (a plan over nq queries); their block counts stay in
 	// rows [0, nu) of d_xf_counts, which has room for count_copies times as many
-	int exact_filtered_count(const ExactFilterPlan &plan, uint64_t nq, uint64_t count_copies, const uint64_t *d_table, uint64_t n_bits,
-	                         std::vector<uint32_t> &lengths, const uint32_t *label_values = nullptr) {
+	int exact_filtered_count(const ExactFilterPlan &plan, uint64_t nq, uint64_t count_copies, const GroupedRows &g,
+	                         std::vector<uint32_t> &lengths) {
 		const uint64_t nu = plan.groups.size(), rows = count;
 		const ExactFilterTables t(nu, nq);
 		static_assert(sizeof(ExactFilterTile) == 20, "five words per tile");
-		FilterListArgs l = exact_filter_list_args(d_table, n_bits, nu, t);
+		FilterListArgs l = exact_filter_list_args(g, nu, t);
 		if (!d_xf_tables.try_grow(t.words) || !d_xf_counts.try_grow(std::max<uint64_t>(count_copies * nu * l.n_blocks, 1)))
 			return fail("exact filtered search: no device memory for %llu queries over %llu groups in use", (unsigned long long)nq,
 			            (unsigned long long)nu);
-		l = exact_filter_list_args(d_table, n_bits, nu, t); // (the buffers may have moved)
+		l = exact_filter_list_args(g, nu, t); // (the buffers may have moved)
 		count_exact_filter_scratch();
 		ensure_events();
 		HIP_TRY(hipEventRecord(ev[0], stream));
 		lengths.assign(nu, 0);
 		std::vector<uint32_t> values;
 		if (nu && rows) { // (an empty index lists nothing: every length stays 0)
-			upload_used_groups(plan, label_values, values);
-			if (label_values) { // (a wave writes the counts of the groups it meets only)
-				HIP_TRY(hipMemsetAsync(d_xf_counts.p, 0, nu * l.n_blocks * 4, stream));
-				hipLaunchKernelGGL(k_label_list_count, dim3((l.n_blocks + 3) / 4), dim3(256), 0, stream, label_list_args(l));
-			} else
-				hipLaunchKernelGGL(k_filter_list_count, dim3((l.n_blocks + 3) / 4), dim3(256), 0, stream, l);
+			upload_used_groups(plan, g, values);
+			g.launch_count(l, stream);
 			hipLaunchKernelGGL(k_filter_list_scan, dim3((uint32_t)nu), dim3(256), 0, stream, l);
 			HIP_TRY(hipMemcpyAsync(lengths.data(), l.totals, nu * 4, hipMemcpyDeviceToHost, stream));
 			HIP_TRY(hipStreamSynchronize(stream));
@@ -2016,13 +2121,13 @@ struct vss_index {
 		return VSS_OK;
 	}
 
-	// step 2: answers the queries plan.order names (rows of d_queries, cells of the outputs) from lists of lengths[u] rows each;
-	// `counts`: row u = the scanned block counts of plan.groups[u]; groups_resident: step 1 ran over this very plan.  No other
-	// query's cells are written.
-	int exact_filtered_score(ExactFilterPlan &plan, const std::vector<uint32_t> &lengths, uint32_t *counts, bool groups_resident,
-	                         const float *d_queries,
-	                         uint32_t q_stride, uint64_t k, const uint64_t *d_table, uint64_t n_bits, int64_t *d_keys_out,
-	                         float *d_dist_out, uint32_t *d_count_out, const uint32_t *label_values = nullptr) {
+	// step 2: answers the queries plan.order names (rows of b.d_queries, cells of `out`) from lists of lengths[u] rows each.
+	// taken_counts: nullptr where step 1 ran over this very plan (its groups and their scanned block counts are in place); else
+	// row u = the scanned block counts of plan.groups[u], and the groups' cells are uploaded here.  No other query's cells are
+	// written.
+	int exact_filtered_score(ExactFilterPlan &plan, const std::vector<uint32_t> &lengths, uint32_t *taken_counts, const DeviceBatch &b,
+	                         const GroupedRows &g, const DeviceAnswers &out) {
+		const uint64_t k = b.k;
 		if (k + 8 > SEL_KP_MAX)
 			return fail("exact filtered search supports k <= %d", SEL_KP_MAX - 8);
 		const uint32_t qt = (uint32_t)std::min<uint64_t>(MS_QT, (160 * 1024) / ((uint64_t)V * 16));
@@ -2038,12 +2143,13 @@ struct vss_index {
 			            (unsigned long long)nu);
 		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, nq * KP * 4, stream)); // 0x7F7F7F7F = 3.39e38 (acts as +inf)
 		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, nq * KP * 4, stream));
-		FilterListArgs l = exact_filter_list_args(d_table, n_bits, nu, t);
-		l.counts = counts;
-		const dim3 list_grid((l.n_blocks + 3) / 4);
+		FilterListArgs l = exact_filter_list_args(g, nu, t);
 		std::vector<uint32_t> values;
-		if (!groups_resident && nu) // (plan.groups and `values` outlive the copy: this step ends synchronised)
-			upload_used_groups(plan, label_values, values);
+		if (taken_counts) {
+			l.counts = taken_counts;
+			if (nu) // (plan.groups and `values` outlive the copy: this step ends synchronised)
+				upload_used_groups(plan, g, values);
+		}
 		exact_filter_pack(lengths.data(), std::max<uint64_t>(exact_filter_budget, rows), qt, plan);
 		uint64_t entries_max = 0;
 		for (const ExactFilterPass &pass : plan.passes)
@@ -2066,8 +2172,8 @@ struct vss_index {
 		l.lists = d_xf_lists.p;
 		FilteredScoreArgs m;
 		m.sp = view().sp;
-		m.queries = d_queries;
-		m.q_stride = q_stride, m.dim = (uint32_t)dim;
+		m.queries = b.d_queries;
+		m.q_stride = b.q_stride, m.dim = (uint32_t)dim;
 		m.order = d_xf_tables.p + at_order;
 		m.lists = d_xf_lists.p;
 		m.chunk_stride = (uint32_t)CH;
@@ -2088,10 +2194,7 @@ struct vss_index {
 			if (!n_tiles)
 				continue; // (none of its groups admits a row)
 			l.u_begin = pass.group_begin, l.u_end = pass.group_end;
-			if (label_values)
-				hipLaunchKernelGGL(k_label_list_scatter, list_grid, dim3(256), 0, stream, label_list_args(l));
-			else
-				hipLaunchKernelGGL(k_filter_list_scatter, list_grid, dim3(256), 0, stream, l);
+			g.launch_scatter(l, stream);
 			m.tiles = reinterpret_cast<const ExactFilterTile *>(d_xf_tables.p + at_tiles) + pass.tile_begin;
 			s.query_begin = pass.query_begin;
 			for (uint64_t p0 = 0; p0 < pass.longest; p0 += CH) {
@@ -2114,15 +2217,15 @@ struct vss_index {
 		// admits nothing, or of an empty index still has its empty list: count 0, cells -1 / +inf.
 		RerankArgs r;
 		r.gv = view();
-		r.queries = d_queries;
-		r.q_stride = q_stride;
+		r.queries = b.d_queries;
+		r.q_stride = b.q_stride;
 		r.n_queries = (uint32_t)nq;
 		r.k = (uint32_t)k;
 		r.KP = (uint32_t)KP;
 		r.best_i = d_best_i.p;
-		r.out_keys = d_keys_out;
-		r.out_d = d_dist_out;
-		r.out_count = d_count_out;
+		r.out_keys = out.keys;
+		r.out_d = out.dist;
+		r.out_count = out.count;
 		r.best_s = nullptr, r.norm_ext = nullptr, r.certified = nullptr;
 		r.query_map = d_xf_tables.p + at_order;
 		const uint32_t lds = align16(V * 16) + 2 * align16((uint32_t)KP * 4);
@@ -2139,34 +2242,24 @@ struct vss_index {
 		return VSS_OK;
 	}
 
-	// the host-pointer form: queries, table and answers staged through a leased context, as search_host does
-	int exact_filtered_host(const float *queries, uint64_t nq, uint64_t k, const uint64_t *allowed, uint64_t n_groups,
-	                        uint64_t n_bits, const uint32_t *group_of, int64_t *out_keys, float *out_d, uint32_t *out_counts) {
-		Lease lease(this);
-		SearchCtx &c = context(lease.slot);
-		// (the plan reads the group numbers on the host: only the bitmaps are staged)
-		if (const int rc = stage_group_table(c, FilterGroupBatch {allowed, nullptr, n_groups}, n_bits, nq))
-			return rc;
-		stage_queries(c, queries, nq, k);
-		HIP_TRY(hipStreamSynchronize(c.stream)); // the exact kernels run on the index stream
-		if (const int rc = exact_filtered_launch(c.d_q.p, (uint32_t)dim, nq, k, c.d_group_filter.p, n_groups, n_bits, group_of,
-		                                         c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p))
-			return rc;
-		fetch_results(c, nq, k, out_keys, out_d, out_counts);
-		return VSS_OK;
+	// the host-pointer form: only the bitmaps are staged, because the plan reads the group numbers on the host
+	int exact_filtered_host(const HostCall &hc, const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of) {
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return stage_group_table(c, FilterGroupBatch {allowed, nullptr, n_groups}, n_bits, hc.nq); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &) {
+			    return exact_filtered_launch(
+			        b, GroupedRows::bitmaps(c.d_group_filter.p, n_groups, n_bits, HostWords(group_of), DeviceWords(nullptr)), out);
+		    });
 	}
 
 	// ------------------------------------------------------------------ filtered search, routed per group (filter_route.h)
 	// One count pass over every group in use feeds the rule and the exact plan; the exact-routed queries are answered straight
 	// into the caller's cells by the exact step over lists of exact-routed groups only; the graph-routed ones are gathered into
-	// a compact batch of context `slot`, walked by one ordinary search launch and scattered back.  Everything is DEVICE memory
-	// but group_of (HOST, or nullptr: every query takes bitmap 0, and d_group_of is nullptr too) and `route` (HOST: filled here).
-	int filtered_auto(int slot, const float *d_queries, uint64_t nq, uint64_t k, uint64_t ef, const uint64_t *d_table,
-	                  uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of, const uint32_t *d_group_of, uint64_t route_c,
-	                  int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out, std::vector<uint8_t> &route,
-	                  const uint32_t *label_values = nullptr) {
-		const uint64_t limit = filter_route_limit(k, ef, efs), C = route_c ? route_c : FILTER_ROUTE_C, L = count - tombstones;
-		SearchCtx &c = context(slot);
+	// a compact batch of context b.slot, walked by one ordinary search launch and scattered back.  `route` (HOST) is filled here.
+	int filtered_auto(const DeviceBatch &b, const GroupedRows &g, uint64_t route_c, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+		const uint64_t nq = b.nq, k = b.k;
+		const uint64_t limit = filter_route_limit(k, b.ef, efs), C = route_c ? route_c : FILTER_ROUTE_C, L = count - tombstones;
+		SearchCtx &c = context(b.slot);
 		FilterRoutePlan rp;
 		{
 			std::lock_guard<std::mutex> exact_lock(exact_mu);
@@ -2174,27 +2267,26 @@ struct vss_index {
 			std::fill(last_exact_filtered, last_exact_filtered + 4, 0);
 			std::fill(last_filter_route, last_filter_route + 8, 0);
 			ExactFilterPlan all;
-			exact_filter_order(group_of, nq, n_groups, all);
+			exact_filter_order(g.group_of, nq, g.n_groups, all);
 			std::vector<uint32_t> lengths;
-			if (const int rc = exact_filtered_count(all, nq, 2, d_table, n_bits, lengths, label_values))
+			if (const int rc = exact_filtered_count(all, nq, 2, g, lengths))
 				return rc;
-			filter_route_partition(all, lengths.data(), group_of, nq, L, limit, C, route_c ? 0 : FILTER_ROUTE_MIN_WALK, rp);
+			filter_route_partition(all, lengths.data(), g.group_of, nq, L, limit, C, route_c ? 0 : FILTER_ROUTE_MIN_WALK, rp);
 			const uint64_t nu = all.groups.size(), nx = rp.exact.groups.size();
 			if (!rp.exact.order.empty()) {
-				uint32_t *counts = d_xf_counts.p;
+				uint32_t *taken_counts = nx == nu ? nullptr : d_xf_counts.p; // (nullptr: the count pass ran over these very groups)
 				const uint32_t n_blocks = (uint32_t)((count + FL_WAVE_SLOTS - 1) / FL_WAVE_SLOTS);
 				if (nx != nu && n_blocks) {
 					// the exact-routed groups' rows of counts, made consecutive behind the nu rows of the count pass; which rows:
 					// behind the groups of the count pass's table, whose totals have been read
-					counts = d_xf_counts.p + nu * n_blocks;
+					taken_counts = d_xf_counts.p + nu * n_blocks;
 					HIP_TRY(hipMemcpyAsync(d_xf_tables.p + nu, rp.exact_rows.data(), nx * 4, hipMemcpyHostToDevice, stream));
 					const dim3 grid(std::min<uint32_t>((n_blocks + 255) / 256, 64), (uint32_t)std::min<uint64_t>(nx, 65535));
 					hipLaunchKernelGGL(k_route_take_rows, grid, dim3(256), 0, stream, d_xf_counts.p, d_xf_tables.p + nu, (uint32_t)nx, n_blocks,
-					                   counts);
+					                   taken_counts);
 					HIP_TRY(hipStreamSynchronize(stream)); // (the score step rewrites d_xf_tables)
 				}
-				if (const int rc = exact_filtered_score(rp.exact, rp.exact_lengths, counts, nx == nu, d_queries, (uint32_t)dim, k, d_table,
-				                                        n_bits, d_keys_out, d_dist_out, d_count_out, label_values))
+				if (const int rc = exact_filtered_score(rp.exact, rp.exact_lengths, taken_counts, b, g, out))
 					return rc;
 			}
 			last_filter_route[0] = rp.graph_queries.size(), last_filter_route[1] = rp.exact.order.size();
@@ -2213,7 +2305,7 @@ struct vss_index {
 		if (!ng && !n_unknown)
 			return VSS_OK;
 		std::unique_lock<std::mutex> route_lock(route_mu, std::defer_lock);
-		if (slot == 0)
+		if (b.slot == 0)
 			route_lock.lock();
 		if (!c.d_route_map.try_grow(ng + n_unknown) || !c.d_route_q.try_grow(std::max<uint64_t>(ng * dim, 1)) ||
 		    !c.d_route_group.try_grow(std::max<uint64_t>(ng, 1)) || !c.d_route_keys.try_grow(std::max<uint64_t>(ng * k, 1)) ||
@@ -2222,28 +2314,25 @@ struct vss_index {
 		if (n_unknown) {
 			HIP_TRY(hipMemcpyAsync(c.d_route_map.p + ng, rp.unknown_queries.data(), n_unknown * 4, hipMemcpyHostToDevice, c.stream));
 			hipLaunchKernelGGL(k_route_blank, dim3((uint32_t)((n_unknown + 3) / 4)), dim3(256), 0, c.stream, c.d_route_map.p + ng,
-			                   (uint32_t)n_unknown, (uint32_t)k, d_keys_out, d_dist_out, d_count_out);
+			                   (uint32_t)n_unknown, (uint32_t)k, out.keys, out.dist, out.count);
 		}
 		if (ng) {
 			HIP_TRY(hipMemcpyAsync(c.d_route_map.p, rp.graph_queries.data(), ng * 4, hipMemcpyHostToDevice, c.stream));
-			RouteGatherArgs g;
-			g.queries = d_queries, g.group_of = d_group_of, g.map = c.d_route_map.p;
-			g.n = (uint32_t)ng, g.q_stride = (uint32_t)dim;
-			g.vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(d_queries) % 16 == 0 && reinterpret_cast<uintptr_t>(c.d_route_q.p) % 16 == 0;
-			g.out_queries = c.d_route_q.p, g.out_group_of = c.d_route_group.p;
-			hipLaunchKernelGGL(k_route_gather, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, g);
+			RouteGatherArgs ga;
+			ga.queries = b.d_queries, ga.group_of = g.d_group_of, ga.map = c.d_route_map.p;
+			ga.n = (uint32_t)ng, ga.q_stride = (uint32_t)dim;
+			ga.vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(b.d_queries) % 16 == 0 && reinterpret_cast<uintptr_t>(c.d_route_q.p) % 16 == 0;
+			ga.out_queries = c.d_route_q.p, ga.out_group_of = c.d_route_group.p;
+			hipLaunchKernelGGL(k_route_gather, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, ga);
 			HIP_TRY(hipGetLastError());
-			SearchRequest r = request(slot, &c.d_route_q.p, 1, ng, k, ef, &c.d_route_keys.p, &c.d_route_d.p, &c.d_route_count.p);
-			// (the label form: d_group_of is the queries' wanted labels, so the compact batch's "groups" are its wanted labels)
-			r.predicate = label_values ? SearchPredicate::by_label(c.d_route_group.p, labelled_rows)
-			              : d_group_of ? SearchPredicate::one_table(d_table, c.d_route_group.p, n_groups, n_bits)
-			                           : SearchPredicate::one_bitmap(d_table, n_bits);
+			SearchRequest r = request(b.slot, &c.d_route_q.p, 1, ng, k, b.ef, &c.d_route_keys.p, &c.d_route_d.p, &c.d_route_count.p);
+			r.predicate = g.walk_predicate(c.d_route_group.p);
 			if (const int rc = search_launch(r))
 				return rc;
 			RouteScatterArgs s;
 			s.map = c.d_route_map.p, s.n = (uint32_t)ng, s.k = (uint32_t)k;
 			s.keys = c.d_route_keys.p, s.dist = c.d_route_d.p, s.count = c.d_route_count.p;
-			s.out_keys = d_keys_out, s.out_dist = d_dist_out, s.out_count = d_count_out;
+			s.out_keys = out.keys, s.out_dist = out.dist, s.out_count = out.count;
 			hipLaunchKernelGGL(k_route_scatter, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, s);
 		}
 		HIP_TRY(hipGetLastError());
@@ -2251,62 +2340,60 @@ struct vss_index {
 		return VSS_OK;
 	}
 
-	// the host-pointer form: staged through a leased context, which also carries the walk
-	int filtered_auto_host(const float *queries, uint64_t nq, uint64_t k, uint64_t ef, const uint64_t *allowed, uint64_t n_groups,
-	                       uint64_t n_bits, const uint32_t *group_of, uint64_t route_c, int64_t *out_keys, float *out_d,
-	                       uint32_t *out_counts, uint8_t *out_route) {
-		Lease lease(this);
-		SearchCtx &c = context(lease.slot);
-		if (const int rc = stage_group_table(c, FilterGroupBatch {allowed, group_of, n_groups}, n_bits, nq))
-			return rc;
-		stage_queries(c, queries, nq, k);
-		HIP_TRY(hipStreamSynchronize(c.stream)); // the count and exact kernels run on the index stream
-		std::vector<uint8_t> route;
-		if (const int rc = filtered_auto(lease.slot, c.d_q.p, nq, k, ef, c.d_group_filter.p, n_groups, n_bits, group_of,
-		                                 group_of ? c.d_group_of.p : nullptr, route_c, c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p, route))
-			return rc;
-		fetch_results(c, nq, k, out_keys, out_d, out_counts);
-		if (out_route)
-			std::memcpy(out_route, route.data(), nq);
-		return VSS_OK;
+	// the host-pointer form: the whole table is staged, and the leased context also carries the walk
+	int filtered_auto_host(const HostCall &hc, const uint64_t *allowed, uint64_t n_groups, uint64_t n_bits, const uint32_t *group_of,
+	                       uint64_t route_c) {
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return stage_group_table(c, FilterGroupBatch {allowed, group_of, n_groups}, n_bits, hc.nq); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+			    const DeviceWords d_group_of(group_of ? c.d_group_of.p : nullptr);
+			    return filtered_auto(b, GroupedRows::bitmaps(c.d_group_filter.p, n_groups, n_bits, HostWords(group_of), d_group_of), route_c,
+			                         out, route);
+		    });
 	}
 
 	// ------------------------------------------------------------------ search by label (label_filter.h)
-	// The exact scan (exact == true) or the routed call over the table label_groups() makes of `want` (HOST memory; d_want: the
-	// same values in DEVICE memory, read by the walk of the graph-routed queries): group g = the rows labelled values[g].  No
-	// bitmap exists anywhere; the plans, the rule and the counters are those of the bitmap calls.
-	int by_label_launch(int slot, bool exact, const float *d_queries, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *want,
-	                    const uint32_t *d_want, uint64_t route_c, int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out,
+	// The routed call over the table label_groups() makes of `want`: group g = the rows labelled values[g].  d_want: the same
+	// values for the walk of the graph-routed queries; nullptr asks for the exact scan of every query, which has no walk to read
+	// them.  No bitmap exists anywhere; the plans, the rule and the counters are those of the bitmap calls.
+	int by_label_launch(const DeviceBatch &b, HostWords want, DeviceWords d_want, uint64_t route_c, const DeviceAnswers &out,
 	                    std::vector<uint8_t> &route) {
 		std::vector<uint32_t> values, group_of;
-		label_groups(want, nq, values, group_of);
-		if (exact) {
-			route.assign(nq, FILTER_ROUTE_EXACT);
-			return exact_filtered_launch(d_queries, (uint32_t)dim, nq, k, nullptr, values.size(), labelled_rows, group_of.data(), d_keys_out,
-			                             d_dist_out, d_count_out, values.data());
+		label_groups(want.p, b.nq, values, group_of);
+		const GroupedRows g = GroupedRows::labels(values, d_labels.p, labelled_rows, HostWords(group_of.data()), d_want);
+		if (!d_want.p) {
+			route.assign(b.nq, FILTER_ROUTE_EXACT);
+			return exact_filtered_launch(b, g, out);
 		}
-		return filtered_auto(slot, d_queries, nq, k, ef, nullptr, values.size(), labelled_rows, group_of.data(), d_want, route_c, d_keys_out,
-		                     d_dist_out, d_count_out, route, values.data());
+		return filtered_auto(b, g, route_c, out, route);
 	}
 
-	// the host-pointer form of those two: staged through a leased context, as exact_filtered_host / filtered_auto_host do
-	int by_label_host(bool exact, const float *queries, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *want, uint64_t route_c,
-	                  int64_t *out_keys, float *out_d, uint32_t *out_counts, uint8_t *out_route) {
-		Lease lease(this);
-		SearchCtx &c = context(lease.slot);
-		if (!exact)
-			if (const int rc = stage_wanted_labels(c, want, nq))
-				return rc;
-		stage_queries(c, queries, nq, k);
-		HIP_TRY(hipStreamSynchronize(c.stream)); // the count and exact kernels run on the index stream
-		std::vector<uint8_t> route;
-		if (const int rc = by_label_launch(lease.slot, exact, c.d_q.p, nq, k, ef, want, exact ? nullptr : c.d_group_of.p, route_c,
-		                                   c.d_out_keys.p, c.d_out_d.p, c.d_out_count.p, route))
-			return rc;
-		fetch_results(c, nq, k, out_keys, out_d, out_counts);
-		if (out_route)
-			std::memcpy(out_route, route.data(), nq);
-		return VSS_OK;
+	// the host-pointer form of those two: the exact scan stages no wanted labels
+	int by_label_host(const HostCall &hc, bool exact, const uint32_t *want, uint64_t route_c) {
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_wanted_labels(c, want, hc.nq); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+			    return by_label_launch(b, HostWords(want), DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
+		    });
+	}
+
+	// The device forms of these calls: the plans and the rule read a per-query column on the host, so 4 bytes per query come back
+	// first (d_words == nullptr: there is no column, and the vector stays empty) ...
+	std::vector<uint32_t> words_to_host(const uint32_t *d_words, uint64_t nq) {
+		std::vector<uint32_t> words;
+		if (d_words) {
+			words.resize(nq);
+			HIP_TRY(hipMemcpyAsync(words.data(), d_words, nq * 4, hipMemcpyDeviceToHost, stream));
+			HIP_TRY(hipStreamSynchronize(stream));
+		}
+		return words;
+	}
+	// ... and the route table goes to the caller's DEVICE cells last (d_out_route may be nullptr)
+	void route_to_device(const std::vector<uint8_t> &route, uint8_t *d_out_route) {
+		if (!d_out_route)
+			return;
+		HIP_TRY(hipMemcpyAsync(d_out_route, route.data(), route.size(), hipMemcpyHostToDevice, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
 	}
 
 	// ------------------------------------------------------------------ remove
@@ -3472,7 +3559,7 @@ int vss_search_exact_batch_filtered_groups(vss_index *h, const float *Q, uint64_
 		if (check_exact_filtered(h, what, Q, nq, table, n_bits, out, out_counts) != VSS_OK ||
 		    (group_of && check_group_numbers(h, what, table, nq) != VSS_OK))
 			return VSS_ERROR;
-		return h->exact_filtered_host(Q, nq, k, allowed, n_groups, n_bits, group_of, out, out_d, out_counts);
+		return h->exact_filtered_host({Q, nq, k, 0, out, out_d, out_counts, nullptr}, allowed, n_groups, n_bits, group_of);
 	})
 }
 
@@ -3485,15 +3572,10 @@ int vss_search_exact_batch_filtered_groups_device(vss_index *h, const float *Q, 
 			return VSS_OK;
 		if (check_exact_filtered(h, "vss_search_exact_batch_filtered_groups_device", Q, nq, table, n_bits, out, out_counts) != VSS_OK)
 			return VSS_ERROR;
-		// the plan needs every group's queries on the host: 4 bytes per query come back
-		std::vector<uint32_t> groups_h;
-		if (group_of) {
-			groups_h.resize(nq);
-			HIP_TRY(hipMemcpyAsync(groups_h.data(), group_of, nq * 4, hipMemcpyDeviceToHost, h->stream));
-			HIP_TRY(hipStreamSynchronize(h->stream));
-		}
-		return h->exact_filtered_launch(Q, (uint32_t)h->dim, nq, k, allowed, n_groups, n_bits, group_of ? groups_h.data() : nullptr,
-		                                out, out_d, out_counts);
+		const std::vector<uint32_t> groups_h = h->words_to_host(group_of, nq); // (the plan reads the group numbers on the host)
+		const HostWords groups(group_of ? groups_h.data() : nullptr);
+		return h->exact_filtered_launch({0, Q, (uint32_t)h->dim, nq, k, 0},
+		                                GroupedRows::bitmaps(allowed, n_groups, n_bits, groups, DeviceWords(group_of)), {out, out_d, out_counts});
 	})
 }
 
@@ -3518,7 +3600,7 @@ int vss_search_batch_filtered_groups_auto(vss_index *h, const float *Q, uint64_t
 		if (check_exact_filtered(h, what, Q, nq, table, n_bits, out, out_counts) != VSS_OK ||
 		    (group_of && check_group_numbers(h, what, table, nq) != VSS_OK))
 			return VSS_ERROR;
-		return h->filtered_auto_host(Q, nq, k, ef, allowed, n_groups, n_bits, group_of, route_c, out, out_d, out_counts, out_route);
+		return h->filtered_auto_host({Q, nq, k, ef, out, out_d, out_counts, out_route}, allowed, n_groups, n_bits, group_of, route_c);
 	})
 }
 
@@ -3532,21 +3614,14 @@ int vss_search_batch_filtered_groups_auto_device(vss_index *h, const float *Q, u
 			return VSS_OK;
 		if (check_exact_filtered(h, "vss_search_batch_filtered_groups_auto_device", Q, nq, table, n_bits, out, out_counts) != VSS_OK)
 			return VSS_ERROR;
-		// the rule and the plans need every group's queries on the host: 4 bytes per query come back
-		std::vector<uint32_t> groups_h;
-		if (group_of) {
-			groups_h.resize(nq);
-			HIP_TRY(hipMemcpyAsync(groups_h.data(), group_of, nq * 4, hipMemcpyDeviceToHost, h->stream));
-			HIP_TRY(hipStreamSynchronize(h->stream));
-		}
+		const std::vector<uint32_t> groups_h = h->words_to_host(group_of, nq); // (the rule and the plans read them on the host)
+		const HostWords groups(group_of ? groups_h.data() : nullptr);
 		std::vector<uint8_t> route;
-		if (const int rc = h->filtered_auto(0, Q, nq, k, ef, allowed, n_groups, n_bits, group_of ? groups_h.data() : nullptr, group_of,
-		                                    route_c, out, out_d, out_counts, route))
+		if (const int rc = h->filtered_auto({0, Q, (uint32_t)h->dim, nq, k, ef},
+		                                    GroupedRows::bitmaps(allowed, n_groups, n_bits, groups, DeviceWords(group_of)), route_c,
+		                                    {out, out_d, out_counts}, route))
 			return rc;
-		if (out_route) {
-			HIP_TRY(hipMemcpyAsync(out_route, route.data(), nq, hipMemcpyHostToDevice, h->stream));
-			HIP_TRY(hipStreamSynchronize(h->stream));
-		}
+		h->route_to_device(route, out_route);
 		return VSS_OK;
 	})
 }
@@ -3606,7 +3681,7 @@ int vss_search_batch_by_label(vss_index *h, const float *Q, uint64_t nq, uint64_
 		if (!nq || !k)
 			return VSS_OK;
 		if (mode != VSS_BY_LABEL_GRAPH)
-			return h->by_label_host(mode == VSS_BY_LABEL_EXACT, Q, nq, k, ef, want, route_c, out, out_d, out_counts, out_route);
+			return h->by_label_host({Q, nq, k, ef, out, out_d, out_counts, out_route}, mode == VSS_BY_LABEL_EXACT, want, route_c);
 		if (out_route)
 			std::memset(out_route, FILTER_ROUTE_GRAPH, nq);
 		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, SearchPredicate::by_label(want, h->labelled_rows));
@@ -3628,18 +3703,13 @@ int vss_search_batch_by_label_device(vss_index *h, const float *Q, uint64_t nq, 
 			if (const int rc = h->search_launch(r))
 				return rc;
 		} else {
-			// the plans need every query's wanted label on the host: 4 bytes per query come back
-			std::vector<uint32_t> want_h(nq);
-			HIP_TRY(hipMemcpyAsync(want_h.data(), want, nq * 4, hipMemcpyDeviceToHost, h->stream));
-			HIP_TRY(hipStreamSynchronize(h->stream));
-			if (const int rc = h->by_label_launch(0, mode == VSS_BY_LABEL_EXACT, Q, nq, k, ef, want_h.data(), want, route_c, out, out_d,
-			                                      out_counts, route))
+			const std::vector<uint32_t> want_h = h->words_to_host(want, nq); // (the plans read the wanted labels on the host)
+			const DeviceWords d_want(mode == VSS_BY_LABEL_EXACT ? nullptr : want);
+			if (const int rc = h->by_label_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(want_h.data()), d_want, route_c,
+			                                      {out, out_d, out_counts}, route))
 				return rc;
 		}
-		if (out_route) {
-			HIP_TRY(hipMemcpyAsync(out_route, route.data(), nq, hipMemcpyHostToDevice, h->stream));
-			HIP_TRY(hipStreamSynchronize(h->stream));
-		}
+		h->route_to_device(route, out_route);
 		return VSS_OK;
 	})
 }

@@ -16,36 +16,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <random>
 
 #include "filter_group_tables.hpp"
-#include "sharded_index.hpp"
+#include "harness_common.hpp"
 
 using namespace vss_host;
-
-#define EXPECT(cond)                                                                                                   \
-	do {                                                                                                               \
-		if (!(cond)) {                                                                                                 \
-			std::fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);                               \
-			std::fflush(nullptr);                                                                                      \
-			std::_Exit(1);                                                                                             \
-		}                                                                                                              \
-	} while (0)
 
 namespace {
 
 constexpr idx_t DIM = 32, N = 6001, NQ = 257, K = 10, TENANTS = 16, N_BITS = N - 3;
 
-struct Results {
-	std::vector<row_t> ids;
-	std::vector<float> dist;
-	std::vector<uint32_t> counts;
-	Results() : ids(NQ * K, -2), dist(NQ * K, -1.f), counts(NQ, 77) {
-	}
-	bool operator==(const Results &o) const {
-		return ids == o.ids && counts == o.counts && !std::memcmp(dist.data(), o.dist.data(), NQ * K * sizeof(float));
-	}
-};
+using Results = ResultsOf<K, NQ>;
 
 std::vector<float> vecs(N *DIM), queries(NQ *DIM);
 std::vector<row_t> ids(N), dead;
@@ -87,16 +68,7 @@ void ExpectBruteForce(const FilterGroupTables &t, const Results &r) {
 }
 
 Results SingleIndex(const FilterGroupTables &t) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	single_p = std::make_unique<HNSWIndex>(DIM, options, N);
-	HNSWIndex &index = *single_p;
-	index.BulkReserve(N, 8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	index.Delete(dead.data(), dead.size());
+	HNSWIndex &index = BuildSingle(single_p, DIM, vecs, ids, dead);
 	EXPECT(index.Count() == N - dead.size());
 
 	Results exact;
@@ -133,16 +105,7 @@ Results SingleIndex(const FilterGroupTables &t) {
 
 void Sharded(const FilterGroupTables &t, const Results &single, const Results &single_ones, const std::vector<int> &devices,
              std::unique_ptr<ShardedHNSWIndex> &holder) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	holder = std::make_unique<ShardedHNSWIndex>(DIM, options, N, devices);
-	ShardedHNSWIndex &index = *holder;
-	index.BulkReserve(8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	EXPECT(index.Delete(dead.data(), dead.size()) == dead.size());
+	ShardedHNSWIndex &index = BuildSharded(holder, DIM, vecs, ids, dead, devices);
 
 	Results got;
 	index.SearchExactBatchFilteredGroups(queries.data(), NQ, K, t.allowed.data(), t.n_groups, t.n_bits, t.group_of.data(),
@@ -171,20 +134,9 @@ void Sharded(const FilterGroupTables &t, const Results &single, const Results &s
 } // namespace
 
 int main() {
-	std::mt19937 rng(20260926);
-	std::normal_distribution<float> gauss(0.f, 1.f);
-	std::vector<float> centres(64 * DIM);
-	for (auto &c : centres)
-		c = gauss(rng);
-	auto draw = [&](float *dst) {
-		const size_t c = rng() % 64;
-		for (idx_t d = 0; d != DIM; ++d)
-			dst[d] = centres[c * DIM + d] + 0.3f * gauss(rng);
-	};
+	ClusteredData(20260926, DIM, N, NQ, 64, 0.3f, vecs, queries);
 	for (idx_t i = 0; i != N; ++i)
-		draw(&vecs[i * DIM]), ids[i] = (row_t)i;
-	for (idx_t i = 0; i != NQ; ++i)
-		draw(&queries[i * DIM]);
+		ids[i] = (row_t)i;
 	for (idx_t i = 0; i != N; ++i)
 		if (!Live(i))
 			dead.push_back((row_t)i);

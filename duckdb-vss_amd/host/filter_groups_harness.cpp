@@ -14,33 +14,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <random>
 
 #include "filter_group_tables.hpp"
-#include "sharded_index.hpp"
+#include "harness_common.hpp"
 
 using namespace vss_host;
-
-#define EXPECT(cond)                                                                                                   \
-	do {                                                                                                               \
-		if (!(cond)) {                                                                                                 \
-			std::fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);                               \
-			std::fflush(nullptr);                                                                                      \
-			std::_Exit(1);                                                                                             \
-		}                                                                                                              \
-	} while (0)
 
 namespace {
 
 constexpr idx_t DIM = 32, N = 6001, NQ = 257, K = 10, EF = 64, TENANTS = 4, N_BITS = N - 3;
 
-struct Results {
-	std::vector<row_t> ids;
-	std::vector<float> dist;
-	std::vector<uint32_t> counts;
-	explicit Results(idx_t nq) : ids(nq * K, -2), dist(nq * K, -1.f), counts(nq, 77) {
-	}
-};
+using Results = ResultsOf<K>;
 
 std::vector<float> vecs(N *DIM), queries(NQ *DIM);
 std::vector<row_t> ids(N), dead;
@@ -69,16 +53,7 @@ void ExpectOwnPredicate(const FilterGroupTables &t, const Results &r) {
 }
 
 void SingleIndex(const FilterGroupTables &t) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	single_p = std::make_unique<HNSWIndex>(DIM, options, N);
-	HNSWIndex &index = *single_p;
-	index.BulkReserve(N, 8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	index.Delete(dead.data(), dead.size());
+	HNSWIndex &index = BuildSingle(single_p, DIM, vecs, ids, dead);
 	EXPECT(index.Count() == N - dead.size());
 
 	// the C entry point: ids, distance bits and counts of every query are those of its group's own filtered call
@@ -135,16 +110,7 @@ void SingleIndex(const FilterGroupTables &t) {
 }
 
 void Sharded(const FilterGroupTables &t, const std::vector<int> &devices, std::unique_ptr<ShardedHNSWIndex> &holder) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	holder = std::make_unique<ShardedHNSWIndex>(DIM, options, N, devices);
-	ShardedHNSWIndex &index = *holder;
-	index.BulkReserve(8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	EXPECT(index.Delete(dead.data(), dead.size()) == dead.size());
+	ShardedHNSWIndex &index = BuildSharded(holder, DIM, vecs, ids, dead, devices);
 
 	Results grouped(NQ);
 	index.SearchBatchFilteredGroups(queries.data(), NQ, K, EF, t.allowed.data(), t.n_groups, t.n_bits, t.group_of.data(),
@@ -178,20 +144,9 @@ void Sharded(const FilterGroupTables &t, const std::vector<int> &devices, std::u
 } // namespace
 
 int main() {
-	std::mt19937 rng(20260926);
-	std::normal_distribution<float> gauss(0.f, 1.f);
-	std::vector<float> centres(64 * DIM);
-	for (auto &c : centres)
-		c = gauss(rng);
-	auto draw = [&](float *dst) {
-		const size_t c = rng() % 64;
-		for (idx_t d = 0; d != DIM; ++d)
-			dst[d] = centres[c * DIM + d] + 0.3f * gauss(rng);
-	};
+	ClusteredData(20260926, DIM, N, NQ, 64, 0.3f, vecs, queries);
 	for (idx_t i = 0; i != N; ++i)
-		draw(&vecs[i * DIM]), ids[i] = (row_t)i;
-	for (idx_t i = 0; i != NQ; ++i)
-		draw(&queries[i * DIM]);
+		ids[i] = (row_t)i;
 	for (idx_t i = 0; i != N; ++i)
 		if (!Live(i))
 			dead.push_back((row_t)i);

@@ -16,37 +16,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
-#include <random>
 
 #include "filter_group_tables.hpp"
-#include "sharded_index.hpp"
+#include "harness_common.hpp"
 
 using namespace vss_host;
-
-#define EXPECT(cond)                                                                                                   \
-	do {                                                                                                               \
-		if (!(cond)) {                                                                                                 \
-			std::fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);                               \
-			std::fflush(nullptr);                                                                                      \
-			std::_Exit(1);                                                                                             \
-		}                                                                                                              \
-	} while (0)
 
 namespace {
 
 constexpr idx_t DIM = 32, N = 6001, NQ = 256, K = 10, EF = 64, N_BITS = N - 3, CHUNKS = 4, PER_CHUNK = NQ / CHUNKS;
 
-struct Results {
-	std::vector<row_t> ids;
-	std::vector<float> dist;
-	std::vector<uint32_t> counts;
-	explicit Results(idx_t nq) : ids(nq * K, -2), dist(nq * K, -1.f), counts(nq, 77) {
-	}
-	bool operator==(const Results &o) const {
-		return ids == o.ids && counts == o.counts && !std::memcmp(dist.data(), o.dist.data(), dist.size() * sizeof(float));
-	}
-};
+using Results = ResultsOf<K>;
 
 std::vector<float> vecs(N *DIM), queries(NQ *DIM);
 std::vector<row_t> ids(N), dead;
@@ -88,16 +68,7 @@ std::unique_ptr<HNSWIndex> single_p;
 std::unique_ptr<ShardedHNSWIndex> sharded_p[2];
 
 void SingleIndex(const FilterGroupTables &t) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	single_p = std::make_unique<HNSWIndex>(DIM, options, N);
-	HNSWIndex &index = *single_p;
-	index.BulkReserve(N, 8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	index.Delete(dead.data(), dead.size());
+	HNSWIndex &index = BuildSingle(single_p, DIM, vecs, ids, dead);
 	vss_index *h = index.Handle();
 	const float *d_q = Device(queries.data(), NQ * DIM);
 	const uint64_t *d_table = Device(t.allowed.data(), t.allowed.size());
@@ -195,36 +166,8 @@ void SingleIndex(const FilterGroupTables &t) {
 	            (size_t)CHUNKS);
 }
 
-// ascending (distance, row id) over the shards' answers: what vss_merge_topk_device computes
-Results Merge(const std::vector<Results> &parts, idx_t nq) {
-	Results merged(nq);
-	for (idx_t q = 0; q != nq; ++q) {
-		std::vector<std::pair<float, row_t>> all;
-		for (auto &p : parts)
-			for (idx_t j = 0; j != p.counts[q]; ++j)
-				all.emplace_back(p.dist[q * K + j], p.ids[q * K + j]);
-		std::sort(all.begin(), all.end());
-		const idx_t n = std::min<idx_t>(all.size(), K);
-		for (idx_t j = 0; j != K; ++j) {
-			merged.ids[q * K + j] = j < n ? all[j].second : -1;
-			merged.dist[q * K + j] = j < n ? all[j].first : std::numeric_limits<float>::infinity();
-		}
-		merged.counts[q] = (uint32_t)n;
-	}
-	return merged;
-}
-
 void Sharded(const FilterGroupTables &t, const std::vector<int> &devices, std::unique_ptr<ShardedHNSWIndex> &holder) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	holder = std::make_unique<ShardedHNSWIndex>(DIM, options, N, devices);
-	ShardedHNSWIndex &index = *holder;
-	index.BulkReserve(8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	EXPECT(index.Delete(dead.data(), dead.size()) == dead.size());
+	ShardedHNSWIndex &index = BuildSharded(holder, DIM, vecs, ids, dead, devices);
 
 	// one bitmap: tenant 1's
 	std::vector<Results> parts;
@@ -275,20 +218,9 @@ void Sharded(const FilterGroupTables &t, const std::vector<int> &devices, std::u
 } // namespace
 
 int main() {
-	std::mt19937 rng(20260926);
-	std::normal_distribution<float> gauss(0.f, 1.f);
-	std::vector<float> centres(64 * DIM);
-	for (auto &c : centres)
-		c = gauss(rng);
-	auto draw = [&](float *dst) {
-		const size_t c = rng() % 64;
-		for (idx_t d = 0; d != DIM; ++d)
-			dst[d] = centres[c * DIM + d] + 0.3f * gauss(rng);
-	};
+	ClusteredData(20260926, DIM, N, NQ, 64, 0.3f, vecs, queries);
 	for (idx_t i = 0; i != N; ++i)
-		draw(&vecs[i * DIM]), ids[i] = (row_t)i;
-	for (idx_t i = 0; i != NQ; ++i)
-		draw(&queries[i * DIM]);
+		ids[i] = (row_t)i;
 	for (idx_t i = 0; i != N; ++i)
 		if (!Live(i))
 			dead.push_back((row_t)i);

@@ -18,38 +18,19 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <random>
 
 #include "../csrc/filter_route.h"
 #include "filter_group_tables.hpp"
-#include "sharded_index.hpp"
+#include "harness_common.hpp"
 
 using namespace vss_host;
-
-#define EXPECT(cond)                                                                                                   \
-	do {                                                                                                               \
-		if (!(cond)) {                                                                                                 \
-			std::fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);                               \
-			std::fflush(nullptr);                                                                                      \
-			std::_Exit(1);                                                                                             \
-		}                                                                                                              \
-	} while (0)
 
 namespace {
 
 constexpr idx_t DIM = 32, N = 6001, NQ = 257, K = 10, EF = 64, TENANTS = 16, N_BITS = N - 3;
 constexpr uint64_t ROUTE_C = 1500;
 
-struct Results {
-	std::vector<row_t> ids;
-	std::vector<float> dist;
-	std::vector<uint32_t> counts;
-	Results() : ids(NQ * K, -2), dist(NQ * K, -1.f), counts(NQ, 77) {
-	}
-	bool operator==(const Results &o) const {
-		return ids == o.ids && counts == o.counts && !std::memcmp(dist.data(), o.dist.data(), NQ * K * sizeof(float));
-	}
-};
+using Results = ResultsOf<K, NQ>;
 
 std::vector<float> vecs(N *DIM), queries(NQ *DIM);
 std::vector<row_t> ids(N), dead;
@@ -105,16 +86,7 @@ Results Assembled(vss_index *h, const uint64_t *allowed, uint64_t n_groups, uint
 }
 
 Results SingleIndex(const FilterGroupTables &t, std::vector<uint8_t> &route) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	single_p = std::make_unique<HNSWIndex>(DIM, options, N);
-	HNSWIndex &index = *single_p;
-	index.BulkReserve(N, 8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	index.Delete(dead.data(), dead.size());
+	HNSWIndex &index = BuildSingle(single_p, DIM, vecs, ids, dead);
 	EXPECT(index.Count() == N - dead.size());
 
 	Results routed;
@@ -156,35 +128,8 @@ Results SingleIndex(const FilterGroupTables &t, std::vector<uint8_t> &route) {
 	return routed;
 }
 
-// the union of the shards' answers by (distance, row id): the k best per query
-Results Merge(const std::vector<Results> &per_shard) {
-	Results out;
-	for (idx_t q = 0; q != NQ; ++q) {
-		std::vector<std::pair<float, row_t>> all;
-		for (const Results &r : per_shard)
-			for (idx_t j = 0; j != r.counts[q]; ++j)
-				all.push_back({r.dist[q * K + j], r.ids[q * K + j]});
-		std::sort(all.begin(), all.end());
-		out.counts[q] = (uint32_t)std::min<size_t>(K, all.size());
-		for (idx_t j = 0; j != K; ++j) {
-			out.ids[q * K + j] = j < out.counts[q] ? all[j].second : -1;
-			out.dist[q * K + j] = j < out.counts[q] ? all[j].first : INFINITY;
-		}
-	}
-	return out;
-}
-
 void Sharded(const FilterGroupTables &t, const std::vector<int> &devices, std::unique_ptr<ShardedHNSWIndex> &holder) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	holder = std::make_unique<ShardedHNSWIndex>(DIM, options, N, devices);
-	ShardedHNSWIndex &index = *holder;
-	index.BulkReserve(8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	EXPECT(index.Delete(dead.data(), dead.size()) == dead.size());
+	ShardedHNSWIndex &index = BuildSharded(holder, DIM, vecs, ids, dead, devices);
 	const idx_t G = index.ShardCount();
 
 	// with group numbers, then without (every query under bitmap 0 — here the all-ones group's words, a table of one)
@@ -207,7 +152,7 @@ void Sharded(const FilterGroupTables &t, const std::vector<int> &devices, std::u
 			per_shard.push_back(Assembled(index.ShardHandle(g), allowed, n_groups, t.n_bits, group_of, route));
 		}
 		EXPECT(n_exact + n_graph == G * NQ && n_graph > 0 && (leg || n_exact > 0));
-		EXPECT(got == Merge(per_shard));
+		EXPECT(got == Merge(per_shard, NQ));
 	}
 	std::vector<uint32_t> bad = t.group_of;
 	bad[NQ - 1] = (uint32_t)t.n_groups;
@@ -226,20 +171,9 @@ void Sharded(const FilterGroupTables &t, const std::vector<int> &devices, std::u
 } // namespace
 
 int main() {
-	std::mt19937 rng(20260926);
-	std::normal_distribution<float> gauss(0.f, 1.f);
-	std::vector<float> centres(64 * DIM);
-	for (auto &c : centres)
-		c = gauss(rng);
-	auto draw = [&](float *dst) {
-		const size_t c = rng() % 64;
-		for (idx_t d = 0; d != DIM; ++d)
-			dst[d] = centres[c * DIM + d] + 0.3f * gauss(rng);
-	};
+	ClusteredData(20260926, DIM, N, NQ, 64, 0.3f, vecs, queries);
 	for (idx_t i = 0; i != N; ++i)
-		draw(&vecs[i * DIM]), ids[i] = (row_t)i;
-	for (idx_t i = 0; i != NQ; ++i)
-		draw(&queries[i * DIM]);
+		ids[i] = (row_t)i;
 	for (idx_t i = 0; i != N; ++i)
 		if (!Live(i))
 			dead.push_back((row_t)i);

@@ -218,22 +218,9 @@ public:
 	// (hnsw_optimize_join.cpp:137-149).  Row ids are appended query after query; per-query counts optional.
 	idx_t ExecuteMultiScanBatch(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit,
 	                            std::vector<uint32_t> *counts_out) {
-		auto &state = static_cast<MultiScanState &>(state_p);
-		std::vector<row_t> ids(n_queries * limit);
-		std::vector<uint32_t> counts(n_queries);
-		{
-			std::shared_lock<std::shared_mutex> lock(rwlock);
-			Check(vss_search_batch(index, queries, n_queries, limit, state.ef_search, ids.data(), nullptr, counts.data()),
-			      "search");
-		}
-		idx_t total = 0;
-		for (idx_t q = 0; q != n_queries; ++q) {
-			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
-			total += counts[q];
-		}
-		if (counts_out)
-			*counts_out = counts;
-		return total;
+		return ScanChunk(state_p, n_queries, limit, counts_out, nullptr, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *) {
+			return vss_search_batch(index, queries, n_queries, limit, ef, ids, nullptr, counts);
+		});
 	}
 	// The chunk form of ExecuteMultiScanBatch for a join whose LATERAL subquery is correlated (`WHERE items.tenant = q.tenant`,
 	// hnsw_optimize_join.cpp:111-168 with the predicate pushed into the traversal): outer row q is answered under bitmap
@@ -242,23 +229,10 @@ public:
 	idx_t ExecuteMultiScanBatchGrouped(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit,
 	                                   const uint64_t *allowed, idx_t n_groups, idx_t n_bits, const uint32_t *group_of,
 	                                   std::vector<uint32_t> *counts_out) {
-		auto &state = static_cast<MultiScanState &>(state_p);
-		std::vector<row_t> ids(n_queries * limit);
-		std::vector<uint32_t> counts(n_queries);
-		{
-			std::shared_lock<std::shared_mutex> lock(rwlock);
-			Check(vss_search_batch_filtered_groups(index, queries, n_queries, limit, state.ef_search, allowed, n_groups, n_bits,
-			                                       group_of, ids.data(), nullptr, counts.data()),
-			      "search");
-		}
-		idx_t total = 0;
-		for (idx_t q = 0; q != n_queries; ++q) {
-			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
-			total += counts[q];
-		}
-		if (counts_out)
-			*counts_out = counts;
-		return total;
+		return ScanChunk(state_p, n_queries, limit, counts_out, nullptr, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *) {
+			return vss_search_batch_filtered_groups(index, queries, n_queries, limit, ef, allowed, n_groups, n_bits, group_of, ids, nullptr,
+			                                        counts);
+		});
 	}
 	// The same chunk answered EXACTLY, scoring only the rows each outer row's predicate admits (vss_search_exact_batch_filtered_groups):
 	// the call for selective predicates — tenants of a sixteenth of the table and less —, where the graph
@@ -266,23 +240,10 @@ public:
 	idx_t ExecuteMultiScanBatchGroupedExact(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit,
 	                                        const uint64_t *allowed, idx_t n_groups, idx_t n_bits, const uint32_t *group_of,
 	                                        std::vector<uint32_t> *counts_out) {
-		auto &state = static_cast<MultiScanState &>(state_p);
-		std::vector<row_t> ids(n_queries * limit);
-		std::vector<uint32_t> counts(n_queries);
-		{
-			std::shared_lock<std::shared_mutex> lock(rwlock);
-			Check(vss_search_exact_batch_filtered_groups(index, queries, n_queries, limit, allowed, n_groups, n_bits, group_of,
-			                                             ids.data(), nullptr, counts.data()),
-			      "search");
-		}
-		idx_t total = 0;
-		for (idx_t q = 0; q != n_queries; ++q) {
-			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
-			total += counts[q];
-		}
-		if (counts_out)
-			*counts_out = counts;
-		return total;
+		return ScanChunk(state_p, n_queries, limit, counts_out, nullptr, [&](idx_t, row_t *ids, uint32_t *counts, uint8_t *) {
+			return vss_search_exact_batch_filtered_groups(index, queries, n_queries, limit, allowed, n_groups, n_bits, group_of, ids, nullptr,
+			                                              counts);
+		});
 	}
 	// The same chunk with every group answered by the cheaper of the two calls above (vss_search_batch_filtered_groups_auto): the
 	// engine counts the live rows each predicate admits and decides per group — the call for an operator that has bitmaps and
@@ -292,26 +253,10 @@ public:
 	                                       const uint64_t *allowed, idx_t n_groups, idx_t n_bits, const uint32_t *group_of,
 	                                       std::vector<uint32_t> *counts_out, std::vector<uint8_t> *routes_out = nullptr,
 	                                       uint64_t route_c = 0) {
-		auto &state = static_cast<MultiScanState &>(state_p);
-		std::vector<row_t> ids(n_queries * limit);
-		std::vector<uint32_t> counts(n_queries);
-		std::vector<uint8_t> routes(n_queries);
-		{
-			std::shared_lock<std::shared_mutex> lock(rwlock);
-			Check(vss_search_batch_filtered_groups_auto(index, queries, n_queries, limit, state.ef_search, allowed, n_groups, n_bits,
-			                                            group_of, route_c, ids.data(), nullptr, counts.data(), routes.data()),
-			      "search");
-		}
-		idx_t total = 0;
-		for (idx_t q = 0; q != n_queries; ++q) {
-			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
-			total += counts[q];
-		}
-		if (counts_out)
-			*counts_out = counts;
-		if (routes_out)
-			*routes_out = routes;
-		return total;
+		return ScanChunk(state_p, n_queries, limit, counts_out, routes_out, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *routes) {
+			return vss_search_batch_filtered_groups_auto(index, queries, n_queries, limit, ef, allowed, n_groups, n_bits, group_of, route_c,
+			                                             ids, nullptr, counts, routes);
+		});
 	}
 	// The correlated chunk whose predicate is an EQUALITY on one column (`WHERE items.tenant = q.tenant`), without bitmaps: the
 	// index holds the column's 32-bit value of every row id (SetLabels, written next to the rows in Append), outer row q brings the
@@ -321,26 +266,9 @@ public:
 	idx_t ExecuteMultiScanBatchByLabel(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit, const uint32_t *want,
 	                                   std::vector<uint32_t> *counts_out, std::vector<uint8_t> *routes_out = nullptr,
 	                                   int mode = VSS_BY_LABEL_AUTO, uint64_t route_c = 0) {
-		auto &state = static_cast<MultiScanState &>(state_p);
-		std::vector<row_t> ids(n_queries * limit);
-		std::vector<uint32_t> counts(n_queries);
-		std::vector<uint8_t> routes(n_queries);
-		{
-			std::shared_lock<std::shared_mutex> lock(rwlock);
-			Check(vss_search_batch_by_label(index, queries, n_queries, limit, state.ef_search, want, mode, route_c, ids.data(), nullptr,
-			                                counts.data(), routes.data()),
-			      "search");
-		}
-		idx_t total = 0;
-		for (idx_t q = 0; q != n_queries; ++q) {
-			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
-			total += counts[q];
-		}
-		if (counts_out)
-			*counts_out = counts;
-		if (routes_out)
-			*routes_out = routes;
-		return total;
+		return ScanChunk(state_p, n_queries, limit, counts_out, routes_out, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *routes) {
+			return vss_search_batch_by_label(index, queries, n_queries, limit, ef, want, mode, route_c, ids, nullptr, counts, routes);
+		});
 	}
 	// The label column: cells first_rowid .. first_rowid + n - 1 (vss_set_labels).  Not persisted: after LoadFromBlocks the owner
 	// writes it again from the table.
@@ -517,6 +445,31 @@ private:
 	void Check(int rc, const char *what) {
 		if (rc != VSS_OK)
 			throw InternalException(std::string("Failed to ") + what + " the HNSW index: " + vss_last_error(index));
+	}
+	// One chunk of a batched probe: call(ef_search, ids, counts, routes) is the C call, answering into n_queries * limit row ids,
+	// a count and a route byte per query, under the shared lock.  The first counts[q] ids of every query are appended to the scan
+	// state, query after query; the counts and the routes are handed out where asked for.  Returns the ids appended.
+	template <typename Call>
+	idx_t ScanChunk(IndexScanState &state_p, idx_t n_queries, idx_t limit, std::vector<uint32_t> *counts_out,
+	                std::vector<uint8_t> *routes_out, Call call) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::vector<row_t> ids(n_queries * limit);
+		std::vector<uint32_t> counts(n_queries);
+		std::vector<uint8_t> routes(n_queries);
+		{
+			std::shared_lock<std::shared_mutex> lock(rwlock);
+			Check(call(state.ef_search, ids.data(), counts.data(), routes.data()), "search");
+		}
+		idx_t total = 0;
+		for (idx_t q = 0; q != n_queries; ++q) {
+			state.row_ids.insert(state.row_ids.end(), ids.begin() + q * limit, ids.begin() + q * limit + counts[q]);
+			total += counts[q];
+		}
+		if (counts_out)
+			*counts_out = std::move(counts);
+		if (routes_out)
+			*routes_out = std::move(routes);
+		return total;
 	}
 
 	vss_index *index = nullptr; // replaces `unum::usearch::index_dense_gt<row_t> index` (hnsw_index.hpp:45)

@@ -19,21 +19,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <random>
 
 #include "../csrc/label_filter.h"
-#include "sharded_index.hpp"
+#include "harness_common.hpp"
 
 using namespace vss_host;
-
-#define EXPECT(cond)                                                                                                   \
-	do {                                                                                                               \
-		if (!(cond)) {                                                                                                 \
-			std::fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);                               \
-			std::fflush(nullptr);                                                                                      \
-			std::_Exit(1);                                                                                             \
-		}                                                                                                              \
-	} while (0)
 
 namespace {
 
@@ -41,20 +31,7 @@ constexpr idx_t DIM = 32, N = 6001, NQ = 257, K = 10, EF = 64, LABELLED = N - 3;
 constexpr uint64_t ROUTE_C = 1000;
 constexpr int MODES[3] = {VSS_BY_LABEL_GRAPH, VSS_BY_LABEL_EXACT, VSS_BY_LABEL_AUTO};
 
-struct Results {
-	std::vector<row_t> ids;
-	std::vector<float> dist;
-	std::vector<uint32_t> counts;
-	std::vector<uint8_t> route;
-	Results() : ids(NQ * K, -2), dist(NQ * K, -1.f), counts(NQ, 77), route(NQ, 9) {
-	}
-	bool SameAnswers(const Results &o) const {
-		return ids == o.ids && counts == o.counts && !std::memcmp(dist.data(), o.dist.data(), NQ * K * sizeof(float));
-	}
-	bool operator==(const Results &o) const {
-		return SameAnswers(o) && route == o.route;
-	}
-};
+using Results = ResultsOf<K, NQ>;
 
 std::vector<float> vecs(N *DIM), queries(NQ *DIM);
 std::vector<row_t> ids(N), dead;
@@ -99,19 +76,11 @@ Results ByBitmaps(vss_index *h, int mode) {
 }
 
 void SingleIndex(Results (&answers)[3]) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	single_p = std::make_unique<HNSWIndex>(DIM, options, N);
-	HNSWIndex &index = *single_p;
-	index.BulkReserve(N, 8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-		// the labels travel with the rows, chunk by chunk: the column grows as the table does
+	// the labels travel with the rows, chunk by chunk: the column grows as the table does
+	HNSWIndex &index = BuildSingle(single_p, DIM, vecs, ids, dead, [](idx_t c, idx_t cnt) {
 		if (c < LABELLED)
-			index.SetLabels(c, labels.data() + c, std::min<idx_t>(cnt, LABELLED - c));
-	}
-	index.BulkFinalize();
-	index.Delete(dead.data(), dead.size());
+			single_p->SetLabels(c, labels.data() + c, std::min<idx_t>(cnt, LABELLED - c));
+	});
 	EXPECT(index.LabelledRows() == LABELLED);
 	for (int m = 0; m != 3; ++m) {
 		answers[m] = ByLabel(index.Handle(), MODES[m]);
@@ -166,35 +135,8 @@ void Refused() {
 	}
 }
 
-// the union of the shards' answers by (distance, row id): the k best per query
-Results Merge(const std::vector<Results> &per_shard) {
-	Results out;
-	for (idx_t q = 0; q != NQ; ++q) {
-		std::vector<std::pair<float, row_t>> all;
-		for (const Results &r : per_shard)
-			for (idx_t j = 0; j != r.counts[q]; ++j)
-				all.push_back({r.dist[q * K + j], r.ids[q * K + j]});
-		std::sort(all.begin(), all.end());
-		out.counts[q] = (uint32_t)std::min<size_t>(K, all.size());
-		for (idx_t j = 0; j != K; ++j) {
-			out.ids[q * K + j] = j < out.counts[q] ? all[j].second : -1;
-			out.dist[q * K + j] = j < out.counts[q] ? all[j].first : INFINITY;
-		}
-	}
-	return out;
-}
-
 void Sharded(const std::vector<int> &devices, std::unique_ptr<ShardedHNSWIndex> &holder, const Results (&single)[3]) {
-	const OptionMap options = {{"metric", OptionValue::String("l2sq")}};
-	holder = std::make_unique<ShardedHNSWIndex>(DIM, options, N, devices);
-	ShardedHNSWIndex &index = *holder;
-	index.BulkReserve(8);
-	for (idx_t c = 0; c < N; c += STANDARD_VECTOR_SIZE) {
-		const idx_t cnt = std::min<idx_t>(STANDARD_VECTOR_SIZE, N - c);
-		index.BulkAppendChunk(vecs.data() + c * DIM, ids.data() + c, nullptr, cnt);
-	}
-	index.BulkFinalize();
-	EXPECT(index.Delete(dead.data(), dead.size()) == dead.size());
+	ShardedHNSWIndex &index = BuildSharded(holder, DIM, vecs, ids, dead, devices);
 	index.SetLabels(0, labels.data(), LABELLED);
 	const idx_t G = index.ShardCount();
 	for (int m = 0; m != 3; ++m) {
@@ -208,7 +150,7 @@ void Sharded(const std::vector<int> &devices, std::unique_ptr<ShardedHNSWIndex> 
 			per_shard.push_back(ByLabel(index.ShardHandle(g), MODES[m]));
 			EXPECT(!std::memcmp(routes.data() + g * NQ, per_shard.back().route.data(), NQ)); // each shard by its own counts
 		}
-		EXPECT(got.SameAnswers(Merge(per_shard)));
+		EXPECT(got.SameAnswers(Merge(per_shard, NQ)));
 		if (MODES[m] == VSS_BY_LABEL_EXACT || G == 1) // the exact answer does not depend on the sharding; one shard is the single index
 			EXPECT(got.SameAnswers(single[m]));
 	}
@@ -219,20 +161,9 @@ void Sharded(const std::vector<int> &devices, std::unique_ptr<ShardedHNSWIndex> 
 } // namespace
 
 int main() {
-	std::mt19937 rng(20261020);
-	std::normal_distribution<float> gauss(0.f, 1.f);
-	std::vector<float> centres(64 * DIM);
-	for (auto &c : centres)
-		c = gauss(rng);
-	auto draw = [&](float *dst) {
-		const size_t c = rng() % 64;
-		for (idx_t d = 0; d != DIM; ++d)
-			dst[d] = centres[c * DIM + d] + 0.3f * gauss(rng);
-	};
+	ClusteredData(20261020, DIM, N, NQ, 64, 0.3f, vecs, queries);
 	for (idx_t i = 0; i != N; ++i)
-		draw(&vecs[i * DIM]), ids[i] = (row_t)i;
-	for (idx_t i = 0; i != NQ; ++i)
-		draw(&queries[i * DIM]);
+		ids[i] = (row_t)i;
 	for (idx_t i = 0; i != N; ++i)
 		if (i % 9 == 4)
 			dead.push_back((row_t)i);

@@ -386,3 +386,82 @@ def test_refusals(base):
         g.search_end(1)
     assert g.labelled_rows() == rows
     base.check(Q, 10, 64, want, 1500, "after the refusals", modes=("auto",))
+
+
+# ------------------------------------------------------------------------------------------------- 6. one staging path
+def test_call_kinds_share_one_leased_context():
+    """The host-pointer forms of four call kinds stage through the same leased context (a serial caller always leases the first
+    free one), whose buffers are reused: group numbers and wanted labels land in the SAME cells, bitmaps next to them.  Seven calls
+    of alternating kinds at growing and shrinking batch sizes; every answer — ids, distance bits, counts, routes — is that of the
+    _device form of the same call on freshly uploaded tensors, which stages nothing.  Group g of the table is never label g: a
+    staged cell that still held the previous call's kind of word would name another predicate."""
+    import torch
+    n, dim, k, ef, route_c = 3000, 32, 10, 64, 100
+    X, Q = gc.make_data(n, dim, "l2sq", 1780, nq=257)
+    keys = np.arange(n, dtype=np.int64)
+    gpu = build(dim, "l2sq", X, keys)
+    assert gpu.remove(keys[4::9]) == len(keys[4::9])
+    labels = np.where(keys % 2 == 0, 100, keys % 16).astype(np.uint32)
+    gpu.set_labels(0, labels)
+    values = np.concatenate([[100], np.arange(16)]).astype(np.uint32)  # group 0: half the rows; the even values: nobody
+    bitmaps = np.stack([_bitmap(n, np.nonzero(labels == v)[0]) for v in values])
+    assert bitmaps.shape[0] == 17
+
+    def dev(a, as_type):
+        return torch.from_numpy(np.ascontiguousarray(a).view(as_type)).cuda()
+
+    def on_device(call, nq, routed):
+        d_keys = torch.zeros((nq, k), dtype=torch.int64, device="cuda")
+        d_dist = torch.zeros((nq, k), dtype=torch.float32, device="cuda")
+        d_cnt = torch.full((nq,), 77, dtype=torch.int32, device="cuda")
+        d_route = torch.full((nq,), 9, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        call(d_keys.data_ptr(), d_dist.data_ptr(), d_cnt.data_ptr(), d_route.data_ptr())
+        out = (d_keys.cpu().numpy(), d_dist.cpu().numpy(), d_cnt.cpu().numpy().astype(np.uint32))
+        return out + ((d_route.cpu().numpy(),) if routed else ())
+
+    both_routes = False
+    for nq in (65, 7, 257, 7):
+        rng = np.random.default_rng(1781 + nq)
+        group_of = rng.integers(0, 17, nq).astype(np.uint32)
+        want = values[group_of]
+        q = Q[:nq]
+
+        def by_label(mode):
+            d_q, d_want = dev(q, np.float32), dev(want, np.int32)
+            return (gpu.search_batch_by_label(q, k, ef, want, mode, route_c),
+                    on_device(lambda ids, dist, cnt, route: gpu.search_batch_by_label_device(
+                        d_q.data_ptr(), nq, k, ef, d_want.data_ptr(), ids, dist, cnt, route, mode, route_c), nq, True))
+
+        def groups_auto():
+            d_q, d_tables, d_groups = dev(q, np.float32), dev(bitmaps, np.int64), dev(group_of, np.int32)
+            return (gpu.search_batch_filtered_groups_auto(q, k, ef, bitmaps, n, group_of, route_c),
+                    on_device(lambda ids, dist, cnt, route: gpu.search_batch_filtered_groups_auto_device(
+                        d_q.data_ptr(), nq, k, ef, d_tables.data_ptr(), 17, n, d_groups.data_ptr(), ids, dist, cnt, route, route_c),
+                        nq, True))
+
+        def groups_exact_bitmap_0():
+            d_q, d_tables = dev(q, np.float32), dev(bitmaps, np.int64)
+            return (gpu.search_exact_batch_filtered_groups(q, k, bitmaps, n, None),
+                    on_device(lambda ids, dist, cnt, route: gpu.search_exact_batch_filtered_groups_device(
+                        d_q.data_ptr(), nq, k, d_tables.data_ptr(), 17, n, None, ids, dist, cnt), nq, False))
+
+        def groups_graph():
+            d_q, d_tables, d_groups = dev(q, np.float32), dev(bitmaps, np.int64), dev(group_of, np.int32)
+            return (gpu.search_batch_filtered_groups(q, k, ef, bitmaps, n, group_of),
+                    on_device(lambda ids, dist, cnt, route: gpu.search_batch_filtered_groups_device(
+                        d_q.data_ptr(), nq, k, ef, d_tables.data_ptr(), 17, n, d_groups.data_ptr(), ids, dist, cnt), nq, False))
+
+        calls = [("by label, auto", lambda: by_label("auto")), ("groups, auto", groups_auto),
+                 ("groups, exact, bitmap 0", groups_exact_bitmap_0), ("by label, exact", lambda: by_label("exact")),
+                 ("groups, graph", groups_graph), ("by label, graph", lambda: by_label("graph")),
+                 ("by label, auto again", lambda: by_label("auto"))]
+        for name, call in calls:
+            where = "%d queries, %s" % (nq, name)
+            host, device = call()
+            assert len(host) == len(device), where
+            assert_same(host[:3], device[:3], where)
+            if len(host) == 4:
+                assert np.array_equal(host[3], device[3]), where + ": routes"
+                both_routes |= name == "by label, auto" and set(host[3]) == {0, 1}
+    assert both_routes  # (len^2 <= route_c * live rows: the eight small tenants are scanned, tenant 100 is walked)
