@@ -103,6 +103,8 @@ SIGNATURES = {
     "vss_labelled_rows": (_u64, [_vp]),
     "vss_search_batch_by_label": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_by_label_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_by_label_range": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_by_label_range_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -454,6 +456,32 @@ class GpuIndex:
         """The same over raw device pointers (d_dist and d_route may be None); blocking."""
         self._check(self.lib.vss_search_batch_by_label_device(self.h, d_Q, nq, k, ef, d_want, self.BY_LABEL_MODES.get(mode, mode),
                                                               route_c, d_keys, d_dist, d_counts, d_route))
+
+    def search_batch_by_label_range(self, Q, k, ef, lo, hi, mode="auto", route_c=0):
+        """vss_search_batch_by_label_range: query q admits the live rows whose label lies in [lo[q], hi[q]], both ends inclusive,
+        unsigned (lo > hi admits nothing, hi = NO_LABEL is no upper bound, a NO_LABEL cell is in no range).  mode as for
+        search_batch_by_label.  Returns (ids, distances, counts, route)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        lo = np.ascontiguousarray(lo, dtype=np.uint32)
+        hi = np.ascontiguousarray(hi, dtype=np.uint32)
+        nq = len(Q)
+        if lo.shape != (nq,) or hi.shape != (nq,):
+            raise ValueError("lo and hi must name one range per query: %d queries, shapes %r and %r" % (nq, lo.shape, hi.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        route = np.zeros(nq, dtype=np.uint8)
+        self._check(self.lib.vss_search_batch_by_label_range(self.h, _p(Q), nq, k, ef, _p(lo), _p(hi),
+                                                             self.BY_LABEL_MODES.get(mode, mode), route_c, _p(keys), _p(d), _p(cnt),
+                                                             _p(route)))
+        return keys, d, cnt, route
+
+    def search_batch_by_label_range_device(self, d_Q, nq, k, ef, d_lo, d_hi, d_keys, d_dist, d_counts, d_route=None, mode="auto",
+                                           route_c=0):
+        """The same over raw device pointers (d_dist and d_route may be None); blocking."""
+        self._check(self.lib.vss_search_batch_by_label_range_device(self.h, d_Q, nq, k, ef, d_lo, d_hi,
+                                                                    self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
+                                                                    d_counts, d_route))
 
     def search_batch_device(self, d_Q, nq, k, ef, d_keys, d_dist, d_counts, exact=False):
         if exact:

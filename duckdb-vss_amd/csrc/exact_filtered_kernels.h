@@ -4,7 +4,8 @@
 //   listing    k_filter_list_count -> k_filter_list_scan -> k_filter_list_scatter: for every group IN USE, the ASCENDING list of
 //              the live slots its bitmap admits.  A wave owns FL_WAVE_SLOTS consecutive slots and keeps their keys in registers:
 //              keys[slot] is read once per launch, however many groups the launch lists.  Ascending, so that position order in a
-//              list is slot order and ties come back by slot.
+//              list is slot order and ties come back by slot.  k_label_list_* and k_range_list_* make the same lists from the
+//              index's label column, for wanted values and for label ranges (label_filter.h).
 //   scoring    k_exact_filtered_scores: k_exact_metric_scores with the rows gathered through a list — the same lane-to-component
 //              partition, accumulate4 / group_butterfly / finish_distance order, hence the bits k_exact_rerank computes.  One
 //              launch covers every group of a pass through the plan's tile table.
@@ -214,6 +215,74 @@ __global__ __launch_bounds__(256) void k_label_list_scatter(LabelListArgs a) {
 			at += __popcll(m);
 		}
 	});
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same lists under label RANGES (vss_search_batch_by_label_range, label_filter.h): used group u is a raw pair (lo, hi), cells
+// 2u and 2u + 1 of `pairs`.  Ranges overlap, so a slot may belong to many groups and the wave loops over the used groups as
+// k_filter_list_count does — but what it tests is in registers: keys[slot] and labels[key] are read ONCE per launch, and a group
+// costs a slot two register compares where the bitmap form costs it a load.  Every counts[u][block] cell is written: no zeroing.
+struct RangeListArgs {
+	const int64_t *keys;
+	uint32_t rows, n_blocks;
+	const uint32_t *labels;   // one cell per row id below labelled_rows
+	uint64_t labelled_rows;
+	const uint32_t *pairs;    // [2u], [2u + 1]: lo and hi of used group u
+	uint32_t u_begin, u_end;  // the used groups this launch lists
+	uint32_t *counts;
+	const uint32_t *list_base;
+	uint32_t *lists;
+};
+
+// cells of slots block * FL_WAVE_SLOTS + s * 64 + lane: a free slot, a key without a cell and a row without a label all become
+// NO_LABEL, which host::label_in_range finds in no range
+__device__ __forceinline__ void range_list_labels(const RangeListArgs &a, uint32_t block, uint32_t (&label)[FL_KEYS_PER_LANE]) {
+#pragma unroll
+	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+		const uint32_t slot = block * FL_WAVE_SLOTS + s * 64 + lane_id();
+		const int64_t key = slot < a.rows ? a.keys[slot] : host::EXACT_FILTER_FREE_KEY;
+		const bool has_cell = key != host::EXACT_FILTER_FREE_KEY && key >= 0 && (uint64_t)key < a.labelled_rows;
+		label[s] = has_cell ? a.labels[key] : host::NO_LABEL;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_range_list_count(RangeListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks) // (wave-uniform; no barrier below)
+		return;
+	uint32_t label[FL_KEYS_PER_LANE];
+	range_list_labels(a, block, label);
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t lo = a.pairs[2 * (size_t)u], hi = a.pairs[2 * (size_t)u + 1];
+		uint32_t n = 0;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			n += __popcll(__ballot(host::label_in_range(label[s], lo, hi)));
+		if (lane_id() == 0)
+			a.counts[(size_t)u * a.n_blocks + block] = n;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_range_list_scatter(RangeListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks)
+		return;
+	uint32_t label[FL_KEYS_PER_LANE];
+	range_list_labels(a, block, label);
+	const int lane = lane_id();
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t lo = a.pairs[2 * (size_t)u], hi = a.pairs[2 * (size_t)u + 1];
+		// the rows this block found in the count pass (the index is read-locked in between: the same rows now)
+		uint32_t at = a.list_base[u] + a.counts[(size_t)u * a.n_blocks + block];
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+			const bool in = host::label_in_range(label[s], lo, hi);
+			const unsigned long long m = __ballot(in);
+			if (in)
+				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;
+			at += __popcll(m);
+		}
+	}
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 // exact-routed ones — neither sees a query of the other.
 //
 //   k_route_gather     compact row i <- query map[i] (and its group number)          before the walk
+//   k_route_gather_words  a second per-query column of the compact batch (the `hi` of a call by label range)
 //   k_route_scatter    the caller's cells of query map[i] <- compact answer i        after the walk
 //   k_route_blank      count 0, cells -1 / +inf for the queries of unknown groups
 //   k_route_take_rows  block counts of the exact-routed used groups, made consecutive for k_filter_list_scatter
@@ -44,6 +45,14 @@ __global__ __launch_bounds__(256) void k_route_gather(RouteGatherArgs a) {
 	}
 	if (a.group_of && lane == 0)
 		a.out_group_of[i] = a.group_of[q];
+}
+
+// one more per-query column for the compact batch (a call by label range carries two words per query: k_route_gather takes
+// `lo` along as its group column, this takes `hi`): out[i] = words[map[i]]
+__global__ __launch_bounds__(256) void k_route_gather_words(const uint32_t *words, const uint32_t *map, uint32_t n, uint32_t *out) {
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i < n)
+		out[i] = words[map[i]];
 }
 
 struct RouteScatterArgs {

@@ -40,6 +40,12 @@ constexpr uint64_t FILTER_PER_QUERY = 1ull << 63;
 // address, cell 1 + q what query q's rows must hold (host::label_want_cell).  Such launches run the k_search_labels /
 // k_search_solo_labels kernels: neither GraphView nor any other kernel knows of the column.
 constexpr uint64_t FILTER_BY_LABEL = 1ull << 62;
+// One label RANGE per query (vss_search_batch_by_label_range): filter_bits carries FILTER_BY_RANGE beside FILTER_PER_QUERY, its
+// low bits are again the column's cells, and the table is k_resolve_label_ranges': cell 0 the column's address, cells 1 + 2q and
+// 2 + 2q query q's range as host::label_range_cells.  Such launches run the k_search_ranges / k_search_solo_ranges kernels.
+// Three flag bits leave 61 for a bitmap's n_bits: the engine cuts a caller's n_bits at 2^61 - 1, and a bitmap of 2^61 bits is
+// 2^58 bytes, still more than any address space holds — no row that a bitmap in memory could admit is lost.
+constexpr uint64_t FILTER_BY_RANGE = 1ull << 61;
 
 struct GraphView {
 	RowSpace sp;
@@ -90,6 +96,19 @@ struct GraphView {
 			return false;
 		const uint32_t *labels = reinterpret_cast<const uint32_t *>(filter[0]);
 		return (unsigned long long)labels[key] == filter[1 + query];
+	}
+
+	// The same with one label range per query (the k_search_ranges / k_search_solo_ranges kernels only): the row is live, its row
+	// id has a cell, and the cell lies within the query's two cells (host::label_range_cell_admits: one subtraction, one
+	// comparison; the NO_LABEL cell and an empty range fail it without a branch).
+	__device__ __forceinline__ bool admitted_range(uint32_t slot, uint32_t query) const {
+		const int64_t key = keys[slot];
+		if (key == 0x7FFFFFFFFFFFFFFFll)
+			return false;
+		if (key < 0 || (uint64_t)key >= (filter_bits & ~(FILTER_PER_QUERY | FILTER_BY_LABEL | FILTER_BY_RANGE)))
+			return false;
+		const uint32_t *labels = reinterpret_cast<const uint32_t *>(filter[0]);
+		return host::label_range_cell_admits(labels[key], filter[1 + 2 * (size_t)query], filter[2 + 2 * (size_t)query]);
 	}
 
 	__device__ __forceinline__ uint32_t *list_ptr(uint32_t slot, int level) const {
@@ -1125,7 +1144,8 @@ struct RowTouch {
 // PK: neighbour lists kept in flight (0 = the list type's default); MERGE_REGS: widest register list whose accepted
 // candidates are merged in batches (the 1024-thread search engine cannot afford the temporaries of an 8-register merge)
 // PER_QUERY (TOMB): 1 (the *_groups kernels) the predicate is the one of the query being answered, GraphView::admitted_for;
-// 2 (the *_labels kernels) it is the query's wanted label, GraphView::admitted_label
+// 2 (the *_labels kernels) it is the query's wanted label, GraphView::admitted_label; 3 (the *_ranges kernels) the query's
+// label range, GraphView::admitted_range
 template <int MT, bool INSERT, bool TOMB, int PK = 0, int MERGE_REGS = MAX_LIST_REGS, int PER_QUERY = 0, class List, class Queue,
           class Scorer>
 __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &lds, float qa2, uint32_t start,
@@ -1144,7 +1164,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 	if (TOMB) {
 		cq.restart();
 		cq.push(d0, start, 0.f, false);
-		if (PER_QUERY == 2 ? gv.admitted_label(start, lds.query) : PER_QUERY == 1 ? gv.admitted_for(start, lds.query) : gv.admitted(start))
+		if (PER_QUERY == 3 ? gv.admitted_range(start, lds.query) : PER_QUERY == 2 ? gv.admitted_label(start, lds.query) : PER_QUERY == 1 ? gv.admitted_for(start, lds.query) : gv.admitted(start))
 			L.template insert<INSERT>(d0, start);
 	} else {
 		L.template insert<INSERT>(d0, start);
@@ -1241,7 +1261,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 			const bool have = off + lane < n;
 			const float d = have ? lds.dist[off + lane] : 0.f;
 			const uint32_t id = have ? lds.ids[off + lane] : 0;
-			const uint32_t live = (TOMB && have) ? ((PER_QUERY == 2 ? gv.admitted_label(id, lds.query) : PER_QUERY == 1 ? gv.admitted_for(id, lds.query) : gv.admitted(id)) ? 1u : 0u) : 0u;
+			const uint32_t live = (TOMB && have) ? ((PER_QUERY == 3 ? gv.admitted_range(id, lds.query) : PER_QUERY == 2 ? gv.admitted_label(id, lds.query) : PER_QUERY == 1 ? gv.admitted_for(id, lds.query) : gv.admitted(id)) ? 1u : 0u) : 0u;
 			unsigned long long pass = __ballot(have && (L.size < limit || d < radius));
 			if constexpr (TOUCH_L) {
 				// ListTouch: a row about to enter the candidate list will be asked for its neighbour list by the look-ahead of one
@@ -2017,8 +2037,8 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 // WIDE_LIST_THREADS for the pipelined 8-register list (round 5)
 constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS = 8)
 // GROUPS: the body of k_search_groups — a launch with one predicate per query (always a TOMB launch): the level search looks
-// the query's own bitmap up (1) or compares the row's label with the query's (2: k_search_labels), and the paths such a launch
-// never takes are not compiled.
+// the query's own bitmap up (1), compares the row's label with the query's (2: k_search_labels) or tests it against the query's
+// range (3: k_search_ranges), and the paths such a launch never takes are not compiled.
 template <int MT, int NCH, int R, int E, int THREADS, int GROUPS>
 __device__ __forceinline__ void search_engine(SearchArgs &a) {
 	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
@@ -2271,6 +2291,11 @@ template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search_labels(SearchArgs a) {
 	search_engine<MT, NCH, R, E, THREADS, 2>(a);
 }
+// ... and with one label range per query (vss_search_batch_by_label_range)
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search_ranges(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, 3>(a);
+}
 
 // =========================================================================================================
 // k_search_solo — the search engine's shape for FEW queries (the single-query probe of HNSW_INDEX_SCAN, reference
@@ -2396,6 +2421,10 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 template <int MT, int NCH, int R, int E, int T = 1>
 __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_labels(SearchArgs a) {
 	search_solo<MT, NCH, R, E, T, 2>(a);
+}
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_ranges(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, 3>(a);
 }
 
 // =========================================================================================================
@@ -2590,6 +2619,25 @@ __global__ __launch_bounds__(256) void k_resolve_label_wants(ResolveLabelsArgs a
 		a.table[0] = (unsigned long long)reinterpret_cast<uintptr_t>(a.labels);
 	if (q < a.n_queries)
 		a.table[1 + q] = host::label_want_cell(a.want[q]);
+}
+
+// Ahead of a launch with one label range per query: the table GraphView::admitted_range reads.  `lo` and `hi` are one value each
+// per query of the launch, in DEVICE memory.
+struct ResolveRangesArgs {
+	const uint32_t *labels;
+	const uint32_t *lo, *hi;
+	uint32_t n_queries;
+	unsigned long long *table; // 1 + 2 * n_queries cells
+};
+
+__global__ __launch_bounds__(256) void k_resolve_label_ranges(ResolveRangesArgs a) {
+	const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+	if (q == 0)
+		a.table[0] = (unsigned long long)reinterpret_cast<uintptr_t>(a.labels);
+	if (q < a.n_queries) {
+		const host::LabelRangeCells c = host::label_range_cells(a.lo[q], a.hi[q]);
+		a.table[1 + 2 * (size_t)q] = c.lo, a.table[2 + 2 * (size_t)q] = c.width;
+	}
 }
 
 // Reused slots, before phase A: blank every list of the node (update() zeroes the node tape, index.hpp:2837-2840).

@@ -5,6 +5,8 @@
 // want[q], and admits the live rows whose cell holds it.  The engine answers such a call as the bitmap calls answer the table
 // this header defines: the distinct values of `want`, ascending, are the groups, group g's bitmap has bit r set iff
 // label_admits(labels, labelled_rows, r, value g), and query q takes the group label_groups() gives it.
+// vss_search_batch_by_label_range tests the same column against one inclusive range per query: its rule, the walker's and the
+// listing's forms of it and its groups are further down (host/label_range_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -69,7 +71,64 @@ inline void label_groups(const uint32_t *want, uint64_t n, std::vector<uint32_t>
 		group_of[q] = (uint32_t)(std::lower_bound(values.begin(), values.end(), want[q]) - values.begin());
 }
 
-// vss_set_labels(first_rowid, n): what the range breaks, or NONE.  Cells end at 2^32 (first_rowid + n == 2^32 is the last range
+// ---- per-query RANGES over the same column (vss_search_batch_by_label_range): query q admits the live rows whose cell holds a
+// label in [lo[q], hi[q]], both ends inclusive, compared as unsigned 32-bit values.  lo > hi is the empty predicate, hi = NO_LABEL
+// is "no upper bound", and a cell holding NO_LABEL is admitted by nothing.  The derived table: the distinct RAW pairs of the call,
+// ascending by (lo, hi), are the groups — nothing is canonicalised, two different empty pairs are two groups — and bitmap g has
+// bit r set iff label_range_admits(labels, labelled_rows, r, pair g).
+
+// what a range makes of one cell's value (the listing kernels keep cells in registers; NO_LABEL there is also "no cell at all"):
+// hi is cut below NO_LABEL, so that two comparisons exclude the NO_LABEL cell and every lo > hi without a third
+inline constexpr bool label_in_range(uint32_t label, uint32_t lo, uint32_t hi) {
+	return lo <= label && label <= (hi == NO_LABEL ? NO_LABEL - 1 : hi);
+}
+
+// THE admission rule of a range, but for the row being live: the row id has a cell, the cell holds a label, and the label lies
+// within the query's ends.  constexpr: the kernels and the CPU check (host/label_range_check.cpp) run this very code.
+inline constexpr bool label_range_admits(const uint32_t *labels, uint64_t labelled_rows, int64_t key, uint32_t lo, uint32_t hi) {
+	return key >= 0 && (uint64_t)key < labelled_rows && labels[key] != NO_LABEL && lo <= labels[key] && labels[key] <= hi;
+}
+
+// What the walker tests a row's cell with: two 64-bit cells per query, {lo, min(hi, NO_LABEL - 1) - lo}, and for a range that
+// admits no label {2^32, 0}.  Admission is then ONE subtraction and ONE comparison, label_range_cell_admits: the difference
+// wraps beyond every width for a label below lo (and for every 32-bit label under the empty form), and the NO_LABEL cell lies
+// beyond every width because hi is cut below it.
+struct LabelRangeCells {
+	uint64_t lo, width;
+};
+inline constexpr LabelRangeCells label_range_cells(uint32_t lo, uint32_t hi) {
+	const uint32_t top = hi == NO_LABEL ? NO_LABEL - 1 : hi;
+	return lo > top ? LabelRangeCells {1ull << 32, 0} : LabelRangeCells {lo, (uint64_t)(top - lo)};
+}
+inline constexpr bool label_range_cell_admits(uint32_t label, uint64_t cell_lo, uint64_t cell_width) {
+	return (uint64_t)label - cell_lo <= cell_width;
+}
+
+// one pair of a call; ordered by (lo, hi)
+struct LabelRange {
+	uint32_t lo, hi;
+};
+inline constexpr bool operator<(const LabelRange &a, const LabelRange &b) {
+	return a.lo != b.lo ? a.lo < b.lo : a.hi < b.hi;
+}
+inline constexpr bool operator==(const LabelRange &a, const LabelRange &b) {
+	return a.lo == b.lo && a.hi == b.hi;
+}
+
+// the distinct raw pairs (lo[q], hi[q]) of q in [0, n), ascending, and the group of every query: label_groups' counterpart
+inline void label_range_groups(const uint32_t *lo, const uint32_t *hi, uint64_t n, std::vector<LabelRange> &pairs,
+                               std::vector<uint32_t> &group_of) {
+	pairs.resize(n);
+	for (uint64_t q = 0; q != n; ++q)
+		pairs[q] = {lo[q], hi[q]};
+	std::sort(pairs.begin(), pairs.end());
+	pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+	group_of.resize(n);
+	for (uint64_t q = 0; q != n; ++q)
+		group_of[q] = (uint32_t)(std::lower_bound(pairs.begin(), pairs.end(), LabelRange {lo[q], hi[q]}) - pairs.begin());
+}
+
+// vss_set_labels(first_rowid, n): what the range breaks, or NONE. Cells end at 2^32 (first_rowid + n == 2^32 is the last range
 // that fits); the sum is formed without wrapping.
 enum class LabelRangeFault { NONE, NO_LABELS, TOO_FAR };
 

@@ -126,16 +126,24 @@ static thread_local std::string tls_error;
 // What a search launch filters its results by.  The pointers are device memory for search_begin / search_launch and host
 // memory for search_host, which stages what they name and hands search_launch the staged copy.
 struct SearchPredicate {
-	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL } kind = NONE;
+	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE } kind = NONE;
 	const uint64_t *bitmap = nullptr;                        // ONE_BITMAP: the whole launch's; bit set = row id admitted
 	FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES] = {}; // PER_QUERY: the table of every batch of the launch
 	uint64_t n_bits = 0;                                     // (BY_LABEL: the cells of the index's label column)
 	const uint32_t *want = nullptr;                          // BY_LABEL: the label every query of the (one) batch wants
+	const uint32_t *lo = nullptr, *hi = nullptr;             // BY_RANGE: the ends of every query's label range, both inclusive
 
 	// a launch of one batch against the index's label column: query q admits the rows labelled want[q]
 	static SearchPredicate by_label(const uint32_t *want, uint64_t labelled_rows) {
 		SearchPredicate p;
 		p.kind = BY_LABEL, p.n_bits = labelled_rows, p.want = want;
+		return p;
+	}
+
+	// ... query q admits the rows whose label lies in [lo[q], hi[q]]
+	static SearchPredicate by_range(const uint32_t *lo, const uint32_t *hi, uint64_t labelled_rows) {
+		SearchPredicate p;
+		p.kind = BY_RANGE, p.n_bits = labelled_rows, p.lo = lo, p.hi = hi;
 		return p;
 	}
 
@@ -180,16 +188,20 @@ struct DeviceWords {
 	}
 };
 
-// The groups the rows of a scan call are listed by, made by one of the two factories only.  Bitmaps: group g = the rows bitmap g
+// The groups the rows of a scan call are listed by, made by one of the three factories only.  Bitmaps: group g = the rows bitmap g
 // of a DEVICE table admits.  Labels: group g = the rows the index's label column gives values[g], the ascending distinct wanted
 // values (HOST memory); no bitmap exists.  Either way query q reads group group_of[q] (HOST memory; nullptr: all read group 0),
 // and the walk of the graph-routed queries reads the column's DEVICE twin: group numbers under bitmaps, wanted labels under labels.
+// Ranges: group g = the rows whose label lies within pairs[g], the ascending distinct raw (lo, hi) pairs of the call (HOST memory);
+// the walk reads TWO device columns, every query's lo (d_group_of) and hi (d_hi).
 struct GroupedRows {
 	const uint64_t *d_table = nullptr;  // bitmaps: n_groups bitmaps of n_bits bits
 	uint64_t n_groups = 0, n_bits = 0;  // (labels: the distinct wanted values; the cells of the label column)
 	const uint32_t *values = nullptr;   // labels: HOST
 	const uint32_t *d_labels = nullptr; // labels: the label column
+	const LabelRange *pairs = nullptr;  // ranges: HOST
 	const uint32_t *group_of = nullptr, *d_group_of = nullptr;
+	const uint32_t *d_hi = nullptr;     // ranges: every query's upper end (d_group_of holds the lower ends)
 
 	static GroupedRows bitmaps(const uint64_t *d_table, uint64_t n_groups, uint64_t n_bits, HostWords group_of, DeviceWords d_group_of) {
 		GroupedRows g;
@@ -203,6 +215,22 @@ struct GroupedRows {
 		g.n_groups = values.size(), g.n_bits = labelled_rows, g.group_of = group_of.p, g.d_group_of = d_want.p;
 		return g;
 	}
+	static GroupedRows ranges(const std::vector<LabelRange> &pairs, const uint32_t *d_labels, uint64_t labelled_rows, HostWords group_of,
+	                          DeviceWords d_lo, DeviceWords d_hi) {
+		GroupedRows g;
+		g.by_range = true, g.pairs = pairs.data(), g.d_labels = d_labels;
+		g.n_groups = pairs.size(), g.n_bits = labelled_rows, g.group_of = group_of.p, g.d_group_of = d_lo.p, g.d_hi = d_hi.p;
+		return g;
+	}
+
+	// words that name one used group to the list kernels: its table group, its wanted value, or the two ends of its range
+	uint64_t group_cells() const {
+		return by_range ? 2 : 1;
+	}
+	// a second per-query column the walk of the graph-routed queries needs gathered beside d_group_of, or nullptr
+	const uint32_t *second_walk_column() const {
+		return by_range ? d_hi : nullptr;
+	}
 
 	// the list kernels' arguments in the label form: table group g is "the rows labelled values[g]", so the cells that name the
 	// used groups hold their VALUES (ascending, as the groups are); the plan, its tables and the counts' layout are the same
@@ -214,8 +242,24 @@ struct GroupedRows {
 		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
 		return a;
 	}
-	// the cells of a plan's used groups: plan.groups, or their values in `scratch` (which outlives the upload like plan.groups)
+	// ... and in the range form: the cells hold the groups' PAIRS, two words each
+	RangeListArgs range_list_args(const FilterListArgs &l) const {
+		RangeListArgs a;
+		a.keys = l.keys, a.rows = l.rows, a.n_blocks = l.n_blocks;
+		a.labels = d_labels, a.labelled_rows = n_bits;
+		a.pairs = l.groups, a.u_begin = l.u_begin, a.u_end = l.u_end;
+		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
+		return a;
+	}
+	// the cells of a plan's used groups, group_cells() words each: plan.groups, or their values / pairs in `scratch` (which
+	// outlives the upload like plan.groups)
 	const uint32_t *used_group_cells(const ExactFilterPlan &plan, std::vector<uint32_t> &scratch) const {
+		if (by_range) {
+			scratch.resize(2 * plan.groups.size());
+			for (size_t u = 0; u != plan.groups.size(); ++u)
+				scratch[2 * u] = pairs[plan.groups[u]].lo, scratch[2 * u + 1] = pairs[plan.groups[u]].hi;
+			return scratch.data();
+		}
 		if (!by_label)
 			return plan.groups.data();
 		scratch.resize(plan.groups.size());
@@ -229,7 +273,9 @@ struct GroupedRows {
 		if (by_label) { // (a wave writes the counts of the groups it meets only)
 			HIP_TRY(hipMemsetAsync(l.counts, 0, (uint64_t)(l.u_end - l.u_begin) * l.n_blocks * 4, stream));
 			hipLaunchKernelGGL(k_label_list_count, grid, dim3(256), 0, stream, label_list_args(l));
-		} else
+		} else if (by_range) // (every cell of the launch's groups is written)
+			hipLaunchKernelGGL(k_range_list_count, grid, dim3(256), 0, stream, range_list_args(l));
+		else
 			hipLaunchKernelGGL(k_filter_list_count, grid, dim3(256), 0, stream, l);
 	}
 	// step 3: the lists themselves, from the scanned counts
@@ -237,11 +283,16 @@ struct GroupedRows {
 		const dim3 grid((l.n_blocks + 3) / 4);
 		if (by_label)
 			hipLaunchKernelGGL(k_label_list_scatter, grid, dim3(256), 0, stream, label_list_args(l));
+		else if (by_range)
+			hipLaunchKernelGGL(k_range_list_scatter, grid, dim3(256), 0, stream, range_list_args(l));
 		else
 			hipLaunchKernelGGL(k_filter_list_scatter, grid, dim3(256), 0, stream, l);
 	}
-	// what the walk of a compact batch of graph-routed queries filters by; d_compact_groups: their cells of d_group_of, gathered
-	SearchPredicate walk_predicate(const uint32_t *d_compact_groups) const {
+	// what the walk of a compact batch of graph-routed queries filters by; d_compact_groups: their cells of d_group_of, gathered,
+	// and d_compact_second: those of second_walk_column()
+	SearchPredicate walk_predicate(const uint32_t *d_compact_groups, const uint32_t *d_compact_second) const {
+		if (by_range)
+			return SearchPredicate::by_range(d_compact_groups, d_compact_second, n_bits);
 		if (by_label)
 			return SearchPredicate::by_label(d_compact_groups, n_bits);
 		return d_group_of ? SearchPredicate::one_table(d_table, d_compact_groups, n_groups, n_bits)
@@ -249,7 +300,7 @@ struct GroupedRows {
 	}
 
 private:
-	bool by_label = false;
+	bool by_label = false, by_range = false;
 	GroupedRows() = default;
 };
 
@@ -1446,10 +1497,11 @@ struct vss_index {
 		// The launch's predicate becomes the kernels' view of it HERE and nowhere else.  (Row ids are below 2^63 — 2^63 - 1 is the
 		// free key — so a wider bitmap admits nothing more; the top bit is the kernels' FILTER_PER_QUERY.  The bit below it is
 		// FILTER_BY_LABEL, which chooses the launch's kernels: a bitmap of 2^62 bits is 2^59 bytes, more than any address space
-		// holds, so cutting a caller's n_bits there takes no row away that a bitmap in memory could admit.)
+		// holds, so cutting a caller's n_bits there takes no row away that a bitmap in memory could admit.  FILTER_BY_RANGE took one
+		// more bit: the cut is at 2^61 - 1, a bitmap of 2^58 bytes.)
 		const SearchPredicate &p = r.predicate;
 		a.gv.filter = p.kind == SearchPredicate::ONE_BITMAP ? reinterpret_cast<const unsigned long long *>(p.bitmap) : nullptr;
-		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_BY_LABEL - 1);
+		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_BY_RANGE - 1);
 		if (p.kind == SearchPredicate::PER_QUERY) {
 			// Descriptor b = batch b's table.  A small kernel ahead of the launch resolves every query's bitmap address; the walkers
 			// of the *_groups kernels read that (GraphView::admitted_for).  The descriptors go to it by value, so the launch path
@@ -1476,6 +1528,18 @@ struct vss_index {
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits = std::min<uint64_t>(labelled_rows, FILTER_BY_LABEL - 1) | FILTER_PER_QUERY | FILTER_BY_LABEL;
+		} else if (p.kind == SearchPredicate::BY_RANGE) {
+			// ... and by the *_ranges kernels (GraphView::admitted_range): cell 0 the column, then two cells per query
+			if (n_batches != 1 || !d_labels.p)
+				return fail("search by label range: one batch per launch, over an index whose labels have been set");
+			if (!c.d_group_bitmap.try_grow(2 * cap_q + 1))
+				return fail("search by label range: no device memory for the ranges of %llu queries", (unsigned long long)cap_q);
+			count_group_tables(c);
+			ResolveRangesArgs res = {d_labels.p, p.lo, p.hi, (uint32_t)nq, reinterpret_cast<unsigned long long *>(c.d_group_bitmap.p)};
+			hipLaunchKernelGGL(k_resolve_label_ranges, dim3((uint32_t)(nq / 256 + 1)), dim3(256), 0, c.stream, res);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits = std::min<uint64_t>(labelled_rows, FILTER_BY_RANGE - 1) | FILTER_PER_QUERY | FILTER_BY_RANGE;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
@@ -1709,6 +1773,15 @@ struct vss_index {
 		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, want, nq * 4, hipMemcpyHostToDevice, c.stream));
 		return VSS_OK;
 	}
+	// the ends of a call by label range (HOST memory), in the same buffer: lo in words [0, nq), hi in [nq, 2 nq)
+	int stage_label_ranges(SearchCtx &c, const uint32_t *lo, const uint32_t *hi, uint64_t nq) {
+		if (!c.d_group_of.try_grow(2 * nq))
+			return fail("search by label range: no device memory for the ranges of %llu queries", (unsigned long long)nq);
+		count_group_tables(c);
+		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, lo, nq * 4, hipMemcpyHostToDevice, c.stream));
+		HIP_TRY(hipMemcpyAsync(c.d_group_of.p + nq, hi, nq * 4, hipMemcpyHostToDevice, c.stream));
+		return VSS_OK;
+	}
 	// queries in, result buffers ensured ...
 	void stage_queries(SearchCtx &c, const float *queries, uint64_t nq, uint64_t k) {
 		c.d_q.ensure(nq * dim, 0, c.stream), c.d_out_count.ensure(nq, 0, c.stream);
@@ -1805,6 +1878,10 @@ struct vss_index {
 				    if (const int rc = stage_wanted_labels(c, filter.want, nq))
 					    return rc;
 				    staged = SearchPredicate::by_label(c.d_group_of.p, filter.n_bits);
+			    } else if (filter.kind == SearchPredicate::BY_RANGE) {
+				    if (const int rc = stage_label_ranges(c, filter.lo, filter.hi, nq))
+					    return rc;
+				    staged = SearchPredicate::by_range(c.d_group_of.p, c.d_group_of.p + nq, filter.n_bits);
 			    }
 			    return VSS_OK;
 		    },
@@ -2067,12 +2144,12 @@ struct vss_index {
 		return exact_filtered_score(plan, lengths, nullptr, b, g, out);
 	}
 
-	// d_xf_tables of a plan over nu used groups and nq queries: [groups nu][totals nu] | [list_base nu][order nq][offset nq]
-	// [length nq][tiles 5 x (<= nq)]
+	// d_xf_tables of a plan over nu used groups and nq queries: [groups nu x cells][totals nu] | [list_base nu][order nq][offset nq]
+	// [length nq][tiles 5 x (<= nq)]; cells: the words that name a used group (GroupedRows::group_cells)
 	struct ExactFilterTables {
 		uint64_t at_totals, at_base, at_order, at_offset, at_length, at_tiles, words;
-		ExactFilterTables(uint64_t nu, uint64_t nq)
-		    : at_totals(nu), at_base(2 * nu), at_order(3 * nu), at_offset(at_order + nq), at_length(at_offset + nq),
+		ExactFilterTables(uint64_t nu, uint64_t nq, uint64_t cells)
+		    : at_totals(cells * nu), at_base(at_totals + nu), at_order(at_base + nu), at_offset(at_order + nq), at_length(at_offset + nq),
 		      at_tiles(at_length + nq), words(at_tiles + 5 * nq) {
 		}
 	};
@@ -2091,7 +2168,8 @@ struct vss_index {
 	}
 	// the cells of the used groups, to d_xf_tables (`scratch` outlives the copy like plan.groups)
 	void upload_used_groups(const ExactFilterPlan &plan, const GroupedRows &g, std::vector<uint32_t> &scratch) {
-		HIP_TRY(hipMemcpyAsync(d_xf_tables.p, g.used_group_cells(plan, scratch), plan.groups.size() * 4, hipMemcpyHostToDevice, stream));
+		HIP_TRY(hipMemcpyAsync(d_xf_tables.p, g.used_group_cells(plan, scratch), plan.groups.size() * g.group_cells() * 4,
+		                       hipMemcpyHostToDevice, stream));
 	}
 
 	// step 1: lengths[u] = live admitted rows of used group u of `plan` (a plan over nq queries); their block counts stay in
@@ -2099,7 +2177,7 @@ struct vss_index {
 	int exact_filtered_count(const ExactFilterPlan &plan, uint64_t nq, uint64_t count_copies, const GroupedRows &g,
 	                         std::vector<uint32_t> &lengths) {
 		const uint64_t nu = plan.groups.size(), rows = count;
-		const ExactFilterTables t(nu, nq);
+		const ExactFilterTables t(nu, nq, g.group_cells());
 		static_assert(sizeof(ExactFilterTile) == 20, "five words per tile");
 		FilterListArgs l = exact_filter_list_args(g, nu, t);
 		if (!d_xf_tables.try_grow(t.words) || !d_xf_counts.try_grow(std::max<uint64_t>(count_copies * nu * l.n_blocks, 1)))
@@ -2136,7 +2214,7 @@ struct vss_index {
 		const uint64_t KP = k + 8, CH = 32768, rows = count, nq = plan.order.size(), nu = plan.groups.size();
 		if (!nq)
 			return VSS_OK;
-		const ExactFilterTables t(nu, nq);
+		const ExactFilterTables t(nu, nq, g.group_cells());
 		const uint64_t at_base = t.at_base, at_order = t.at_order, at_offset = t.at_offset, at_length = t.at_length, at_tiles = t.at_tiles;
 		if (!d_xf_tables.try_grow(t.words) || !d_scores.try_grow(nq * CH) || !d_best_s.try_grow(nq * KP) || !d_best_i.try_grow(nq * KP))
 			return fail("exact filtered search: no device memory for %llu queries over %llu groups in use", (unsigned long long)nq,
@@ -2280,9 +2358,10 @@ struct vss_index {
 					// the exact-routed groups' rows of counts, made consecutive behind the nu rows of the count pass; which rows:
 					// behind the groups of the count pass's table, whose totals have been read
 					taken_counts = d_xf_counts.p + nu * n_blocks;
-					HIP_TRY(hipMemcpyAsync(d_xf_tables.p + nu, rp.exact_rows.data(), nx * 4, hipMemcpyHostToDevice, stream));
+					uint32_t *d_rows = d_xf_tables.p + ExactFilterTables(nu, nq, g.group_cells()).at_totals;
+					HIP_TRY(hipMemcpyAsync(d_rows, rp.exact_rows.data(), nx * 4, hipMemcpyHostToDevice, stream));
 					const dim3 grid(std::min<uint32_t>((n_blocks + 255) / 256, 64), (uint32_t)std::min<uint64_t>(nx, 65535));
-					hipLaunchKernelGGL(k_route_take_rows, grid, dim3(256), 0, stream, d_xf_counts.p, d_xf_tables.p + nu, (uint32_t)nx, n_blocks,
+					hipLaunchKernelGGL(k_route_take_rows, grid, dim3(256), 0, stream, d_xf_counts.p, d_rows, (uint32_t)nx, n_blocks,
 					                   taken_counts);
 					HIP_TRY(hipStreamSynchronize(stream)); // (the score step rewrites d_xf_tables)
 				}
@@ -2308,7 +2387,7 @@ struct vss_index {
 		if (b.slot == 0)
 			route_lock.lock();
 		if (!c.d_route_map.try_grow(ng + n_unknown) || !c.d_route_q.try_grow(std::max<uint64_t>(ng * dim, 1)) ||
-		    !c.d_route_group.try_grow(std::max<uint64_t>(ng, 1)) || !c.d_route_keys.try_grow(std::max<uint64_t>(ng * k, 1)) ||
+		    !c.d_route_group.try_grow(std::max<uint64_t>(ng * g.group_cells(), 1)) || !c.d_route_keys.try_grow(std::max<uint64_t>(ng * k, 1)) ||
 		    !c.d_route_d.try_grow(std::max<uint64_t>(ng * k, 1)) || !c.d_route_count.try_grow(std::max<uint64_t>(ng, 1)))
 			return fail("routed filtered search: no device memory for a compact batch of %llu queries", (unsigned long long)ng);
 		if (n_unknown) {
@@ -2324,9 +2403,12 @@ struct vss_index {
 			ga.vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(b.d_queries) % 16 == 0 && reinterpret_cast<uintptr_t>(c.d_route_q.p) % 16 == 0;
 			ga.out_queries = c.d_route_q.p, ga.out_group_of = c.d_route_group.p;
 			hipLaunchKernelGGL(k_route_gather, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, ga);
+			if (const uint32_t *second = g.second_walk_column()) // (a range's upper ends, behind the ng lower ones)
+				hipLaunchKernelGGL(k_route_gather_words, dim3((uint32_t)((ng + 255) / 256)), dim3(256), 0, c.stream, second, c.d_route_map.p,
+				                   (uint32_t)ng, c.d_route_group.p + ng);
 			HIP_TRY(hipGetLastError());
 			SearchRequest r = request(b.slot, &c.d_route_q.p, 1, ng, k, b.ef, &c.d_route_keys.p, &c.d_route_d.p, &c.d_route_count.p);
-			r.predicate = g.walk_predicate(c.d_route_group.p);
+			r.predicate = g.walk_predicate(c.d_route_group.p, c.d_route_group.p + ng);
 			if (const int rc = search_launch(r))
 				return rc;
 			RouteScatterArgs s;
@@ -2374,6 +2456,32 @@ struct vss_index {
 		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_wanted_labels(c, want, hc.nq); },
 		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
 			    return by_label_launch(b, HostWords(want), DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
+		    });
+	}
+
+	// ------------------------------------------------------------------ search by label range (label_filter.h)
+	// The same over the table label_range_groups() makes of (lo, hi): group g = the rows whose label lies within pairs[g].  d_lo /
+	// d_hi: the ends for the walk of the graph-routed queries; nullptr asks for the exact scan of every query.
+	int by_range_launch(const DeviceBatch &b, HostWords lo, HostWords hi, DeviceWords d_lo, DeviceWords d_hi, uint64_t route_c,
+	                    const DeviceAnswers &out, std::vector<uint8_t> &route) {
+		std::vector<LabelRange> pairs;
+		std::vector<uint32_t> group_of;
+		label_range_groups(lo.p, hi.p, b.nq, pairs, group_of);
+		const GroupedRows g = GroupedRows::ranges(pairs, d_labels.p, labelled_rows, HostWords(group_of.data()), d_lo, d_hi);
+		if (!d_lo.p) {
+			route.assign(b.nq, FILTER_ROUTE_EXACT);
+			return exact_filtered_launch(b, g, out);
+		}
+		return filtered_auto(b, g, route_c, out, route);
+	}
+
+	// the host-pointer form of those two: the exact scan stages no ends
+	int by_range_host(const HostCall &hc, bool exact, const uint32_t *lo, const uint32_t *hi, uint64_t route_c) {
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_ranges(c, lo, hi, hc.nq); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+			    return by_range_launch(b, HostWords(lo), HostWords(hi), DeviceWords(exact ? nullptr : c.d_group_of.p),
+			                           DeviceWords(exact ? nullptr : c.d_group_of.p + hc.nq), route_c, out, route);
 		    });
 	}
 
@@ -3706,6 +3814,66 @@ int vss_search_batch_by_label_device(vss_index *h, const float *Q, uint64_t nq, 
 			const std::vector<uint32_t> want_h = h->words_to_host(want, nq); // (the plans read the wanted labels on the host)
 			const DeviceWords d_want(mode == VSS_BY_LABEL_EXACT ? nullptr : want);
 			if (const int rc = h->by_label_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(want_h.data()), d_want, route_c,
+			                                      {out, out_d, out_counts}, route))
+				return rc;
+		}
+		h->route_to_device(route, out_route);
+		return VSS_OK;
+	})
+}
+
+// ---- the search by label range: the mode is refused first, before anything is read or staged
+static int check_by_label_range(vss_index *h, const char *what, const float *Q, uint64_t nq, const uint32_t *lo, const uint32_t *hi,
+                                int mode, const int64_t *out, const uint32_t *out_counts) {
+	if (mode != VSS_BY_LABEL_GRAPH && mode != VSS_BY_LABEL_EXACT && mode != VSS_BY_LABEL_AUTO)
+		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
+	if (!h->d_labels.p)
+		return h->fail("%s: the index has no label column (call vss_set_labels first; vss_load and vss_clear_labels drop it)", what);
+	if (nq && (!lo || !hi))
+		return h->fail("%s: null lo / hi pointer for %llu queries", what, (unsigned long long)nq);
+	if (nq && (!Q || !out || !out_counts))
+		return h->fail("%s: null query / row-id / count pointer", what);
+	if (nq > 0xFFFFFFFFull)
+		return h->fail("%s: at most 2^32 - 1 queries per call", what);
+	return VSS_OK;
+}
+
+int vss_search_batch_by_label_range(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *lo,
+                                    const uint32_t *hi, int mode, uint64_t route_c, int64_t *out, float *out_d, uint32_t *out_counts,
+                                    uint8_t *out_route) {
+	VSS_SHARED(h, {
+		if (check_by_label_range(h, "vss_search_batch_by_label_range", Q, nq, lo, hi, mode, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		if (mode != VSS_BY_LABEL_GRAPH)
+			return h->by_range_host({Q, nq, k, ef, out, out_d, out_counts, out_route}, mode == VSS_BY_LABEL_EXACT, lo, hi, route_c);
+		if (out_route)
+			std::memset(out_route, FILTER_ROUTE_GRAPH, nq);
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, SearchPredicate::by_range(lo, hi, h->labelled_rows));
+	})
+}
+
+int vss_search_batch_by_label_range_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *lo,
+                                           const uint32_t *hi, int mode, uint64_t route_c, int64_t *out, float *out_d,
+                                           uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		if (check_by_label_range(h, "vss_search_batch_by_label_range_device", Q, nq, lo, hi, mode, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		std::vector<uint8_t> route(nq, FILTER_ROUTE_GRAPH);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+			r.predicate = SearchPredicate::by_range(lo, hi, h->labelled_rows);
+			if (const int rc = h->search_launch(r))
+				return rc;
+		} else {
+			// (the plans read the ends on the host)
+			const std::vector<uint32_t> lo_h = h->words_to_host(lo, nq), hi_h = h->words_to_host(hi, nq);
+			const bool exact = mode == VSS_BY_LABEL_EXACT;
+			if (const int rc = h->by_range_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(lo_h.data()), HostWords(hi_h.data()),
+			                                      DeviceWords(exact ? nullptr : lo), DeviceWords(exact ? nullptr : hi), route_c,
 			                                      {out, out_d, out_counts}, route))
 				return rc;
 		}

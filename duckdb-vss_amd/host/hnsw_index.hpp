@@ -270,6 +270,17 @@ public:
 			return vss_search_batch_by_label(index, queries, n_queries, limit, ef, want, mode, route_c, ids, nullptr, counts, routes);
 		});
 	}
+	// The correlated chunk whose predicate is an INTERVAL on that column (`items.ts >= q.since`, `items.price BETWEEN q.lo AND q.hi`,
+	// `items.day < q.cutoff`): outer row q brings the inclusive range [lo[q], hi[q]] of unsigned 32-bit labels (INTEGRATION.md §5 has
+	// the maps from INTEGER, FLOAT and DATE), and vss_search_batch_by_label_range does the rest, modes as above.  lo > hi admits
+	// nothing, hi = 0xFFFFFFFF is "no upper bound", a row whose cell is VSS_NO_LABEL is in no range.
+	idx_t ExecuteMultiScanBatchByLabelRange(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit, const uint32_t *lo,
+	                                        const uint32_t *hi, std::vector<uint32_t> *counts_out, std::vector<uint8_t> *routes_out = nullptr,
+	                                        int mode = VSS_BY_LABEL_AUTO, uint64_t route_c = 0) {
+		return ScanChunk(state_p, n_queries, limit, counts_out, routes_out, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *routes) {
+			return vss_search_batch_by_label_range(index, queries, n_queries, limit, ef, lo, hi, mode, route_c, ids, nullptr, counts, routes);
+		});
+	}
 	// The label column: cells first_rowid .. first_rowid + n - 1 (vss_set_labels).  Not persisted: after LoadFromBlocks the owner
 	// writes it again from the table.
 	void SetLabels(idx_t first_rowid, const uint32_t *labels, idx_t n) {

@@ -469,6 +469,35 @@ public:
 			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
 		}
 	}
+	// Query q admits the live rows whose label lies in [lo[q], hi[q]], both ends inclusive and unsigned (lo > hi: none; a
+	// VSS_NO_LABEL cell is in no range): vss_search_batch_by_label_range_device per shard.  Modes, shard_routes, exchange and merge
+	// are SearchBatchByLabel's; the ends travel as UploadTables' group numbers, the n lower ends ahead of the n upper ones.
+	void SearchBatchByLabelRange(const float *queries, idx_t n, idx_t k, idx_t ef, const uint32_t *lo, const uint32_t *hi, int mode,
+	                             uint64_t route_c, row_t *out_rowids, float *out_distances, uint32_t *out_counts,
+	                             std::vector<uint8_t> *shard_routes = nullptr) {
+		if (shard_routes)
+			shard_routes->assign(shards.size() * n, 0);
+		if (!n || !k)
+			return;
+		if (!lo || !hi)
+			throw InternalException("Failed to search the HNSW index: search by label range needs both ends of every query's range");
+		Ensure(n, k);
+		std::vector<uint32_t> ends(lo, lo + n);
+		ends.insert(ends.end(), hi, hi + n);
+		UploadTables(nullptr, 0, ends.data(), 2 * n);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    const uint32_t *d_ends = bitmaps[s.bitmap].group_of;
+			    Vss(s, vss_search_batch_by_label_range_device(s.index->Handle(), s.d_q, n, k, ef, d_ends, d_ends + n, mode, route_c, keys,
+			                                                  dist, s.d_cnt, s.d_route));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		for (size_t g = 0; shard_routes && g != shards.size(); ++g) {
+			Hip(hipSetDevice(shards[g].device), "hipSetDevice");
+			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
+		}
+	}
 
 private:
 	// A table of per-query predicates, refused here before any device is touched: the rules of csrc/filter_groups.h in this

@@ -276,6 +276,30 @@ int vss_search_batch_by_label(vss_index *index, const float *queries, uint64_t n
 int vss_search_batch_by_label_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
                                      const uint32_t *d_want, int mode, uint64_t route_c, int64_t *d_out_rowids,
                                      float *d_out_distances, uint32_t *d_out_counts, uint8_t *d_out_route);
+/* ---- Range predicates on the same column (csrc/label_filter.h) -----------------------------------------------------------
+ * For `items.ts >= q.since`, `items.price BETWEEN q.lo AND q.hi`, `items.day < q.cutoff`: query q brings an inclusive range
+ * [lo[q], hi[q]] of UNSIGNED 32-bit labels (INTEGRATION.md section 5 has the order-preserving maps from INTEGER, FLOAT and DATE).
+ * Query q admits a live row of id r iff 0 <= r < vss_labelled_rows(), labels[r] != VSS_NO_LABEL and lo[q] <= labels[r] <= hi[q].
+ * lo[q] > hi[q] is the empty predicate (count 0, ids -1, distances +inf); hi[q] = 0xFFFFFFFF is "no upper bound", and a cell
+ * holding VSS_NO_LABEL is admitted by no range.  mode, route_c and out_route as for vss_search_batch_by_label.
+ * Contract: with p_0 < p_1 < ... the distinct RAW pairs (lo, hi) of the call, ascending lexicographically and not canonicalised
+ * (two different empty pairs are two groups), bitmap g = {r < labelled rows : labels[r] != VSS_NO_LABEL and labels[r] in p_g}
+ * and group_of[q] = the index of query q's pair, the call returns cell for cell what the bitmap call of the same mode returns
+ * for that table — row ids, f32 distance bits, counts, routes — and leaves the same vss_last_exact_filtered [0..2],
+ * vss_last_filter_route, vss_last_search_stats / _shape / _prescore / _prescore_descent values behind.  With lo == hi == want
+ * that is also the answer of vss_search_batch_by_label.  Ranges overlap: unlike labels, the lists of one call may together
+ * exceed the index's rows and take several passes (vss_last_exact_filtered [2]), as a bitmap table's do.
+ * Errors: a mode other than the three (refused first, before anything is staged); no column set; lo or hi NULL with
+ * n_queries > 0; those of the call of the mode.  n_queries == 0 or k == 0 returns VSS_OK.
+ * The _device form takes device pointers (d_out_distances and d_out_route may be NULL), copies d_lo and d_hi back (8 bytes
+ * per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin forms. */
+int vss_search_batch_by_label_range(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                    const uint32_t *lo, const uint32_t *hi, int mode, uint64_t route_c, int64_t *out_rowids,
+                                    float *out_distances, uint32_t *out_counts, uint8_t *out_route);
+int vss_search_batch_by_label_range_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                           const uint32_t *d_lo, const uint32_t *d_hi, int mode, uint64_t route_c,
+                                           int64_t *d_out_rowids, float *d_out_distances, uint32_t *d_out_counts,
+                                           uint8_t *d_out_route);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
