@@ -105,6 +105,8 @@ SIGNATURES = {
     "vss_search_batch_by_label_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_by_label_range": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_by_label_range_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_by_label_set": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_by_label_set_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -482,6 +484,46 @@ class GpuIndex:
         self._check(self.lib.vss_search_batch_by_label_range_device(self.h, d_Q, nq, k, ef, d_lo, d_hi,
                                                                     self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
                                                                     d_counts, d_route))
+
+    LABEL_SET_MAX = 32  # VSS_LABEL_SET_MAX
+
+    @staticmethod
+    def label_set_matrix(sets, nq):
+        """The nq x width uint32 matrix of a call by label set: `sets` as it is where it is one already, or a list of per-query
+        sequences padded with NO_LABEL to the longest (to width 1 where every one is empty)."""
+        if not isinstance(sets, np.ndarray):
+            rows = [np.asarray(r, dtype=np.uint32).reshape(-1) for r in sets]
+            width = max([len(r) for r in rows] + [1])
+            sets = np.full((len(rows), width), GpuIndex.NO_LABEL, dtype=np.uint32)
+            for q, r in enumerate(rows):
+                sets[q, :len(r)] = r
+        sets = np.ascontiguousarray(sets, dtype=np.uint32)
+        if sets.ndim != 2 or sets.shape[0] != nq:
+            raise ValueError("sets must be one row of labels per query: %d queries, shape %r" % (nq, sets.shape))
+        return sets
+
+    def search_batch_by_label_set(self, Q, k, ef, sets, mode="auto", route_c=0):
+        """vss_search_batch_by_label_set: query q admits the live rows whose label is one of sets[q] (an nq x width uint32 matrix,
+        width 1 .. LABEL_SET_MAX, NO_LABEL pads a shorter list and equals nothing; or a list of per-query sequences, padded
+        here).  mode as for search_batch_by_label.  Returns (ids, distances, counts, route)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        nq = len(Q)
+        sets = self.label_set_matrix(sets, nq)
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        route = np.zeros(nq, dtype=np.uint8)
+        self._check(self.lib.vss_search_batch_by_label_set(self.h, _p(Q), nq, k, ef, _p(sets), sets.shape[1],
+                                                           self.BY_LABEL_MODES.get(mode, mode), route_c, _p(keys), _p(d), _p(cnt),
+                                                           _p(route)))
+        return keys, d, cnt, route
+
+    def search_batch_by_label_set_device(self, d_Q, nq, k, ef, d_sets, width, d_keys, d_dist, d_counts, d_route=None, mode="auto",
+                                         route_c=0):
+        """The same over raw device pointers (d_sets: nq x width words, row-major; d_dist and d_route may be None); blocking."""
+        self._check(self.lib.vss_search_batch_by_label_set_device(self.h, d_Q, nq, k, ef, d_sets, width,
+                                                                  self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
+                                                                  d_counts, d_route))
 
     def search_batch_device(self, d_Q, nq, k, ef, d_keys, d_dist, d_counts, exact=False):
         if exact:

@@ -4,8 +4,8 @@
 //   listing    k_filter_list_count -> k_filter_list_scan -> k_filter_list_scatter: for every group IN USE, the ASCENDING list of
 //              the live slots its bitmap admits.  A wave owns FL_WAVE_SLOTS consecutive slots and keeps their keys in registers:
 //              keys[slot] is read once per launch, however many groups the launch lists.  Ascending, so that position order in a
-//              list is slot order and ties come back by slot.  k_label_list_* and k_range_list_* make the same lists from the
-//              index's label column, for wanted values and for label ranges (label_filter.h).
+//              list is slot order and ties come back by slot.  k_label_list_*, k_range_list_* and k_set_list_* make the same lists
+//              from the index's label column, for wanted values, label ranges and label sets (label_filter.h).
 //   scoring    k_exact_filtered_scores: k_exact_metric_scores with the rows gathered through a list — the same lane-to-component
 //              partition, accumulate4 / group_butterfly / finish_distance order, hence the bits k_exact_rerank computes.  One
 //              launch covers every group of a pass through the plan's tile table.
@@ -236,7 +236,9 @@ struct RangeListArgs {
 
 // cells of slots block * FL_WAVE_SLOTS + s * 64 + lane: a free slot, a key without a cell and a row without a label all become
 // NO_LABEL, which host::label_in_range finds in no range
-__device__ __forceinline__ void range_list_labels(const RangeListArgs &a, uint32_t block, uint32_t (&label)[FL_KEYS_PER_LANE]) {
+// (Args: RangeListArgs, or the SetListArgs of the lists by label set below)
+template <class Args>
+__device__ __forceinline__ void range_list_labels(const Args &a, uint32_t block, uint32_t (&label)[FL_KEYS_PER_LANE]) {
 #pragma unroll
 	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
 		const uint32_t slot = block * FL_WAVE_SLOTS + s * 64 + lane_id();
@@ -277,6 +279,63 @@ __global__ __launch_bounds__(256) void k_range_list_scatter(RangeListArgs a) {
 #pragma unroll
 		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
 			const bool in = host::label_in_range(label[s], lo, hi);
+			const unsigned long long m = __ballot(in);
+			if (in)
+				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;
+			at += __popcll(m);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same lists under label SETS (vss_search_batch_by_label_set, label_filter.h): used group u is a raw row of `width` words,
+// cells [u * width, (u + 1) * width) of `words`.  Sets overlap, so the wave loops over the used groups as k_range_list_count does,
+// with the eight labels of a lane read ONCE into registers (range_list_labels); a group's words are wave-uniform, and a group
+// costs a slot `width` register compares (host::label_in_set).  Every counts[u][block] cell is written: no zeroing.
+struct SetListArgs {
+	const int64_t *keys;
+	uint32_t rows, n_blocks;
+	const uint32_t *labels;   // one cell per row id below labelled_rows
+	uint64_t labelled_rows;
+	const uint32_t *words;    // [u * width + j]: word j of used group u
+	uint32_t width;           // 1 .. host::LABEL_SET_MAX
+	uint32_t u_begin, u_end;  // the used groups this launch lists
+	uint32_t *counts;
+	const uint32_t *list_base;
+	uint32_t *lists;
+};
+
+__global__ __launch_bounds__(256) void k_set_list_count(SetListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks) // (wave-uniform; no barrier below)
+		return;
+	uint32_t label[FL_KEYS_PER_LANE];
+	range_list_labels(a, block, label);
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *set = a.words + (size_t)u * a.width;
+		uint32_t n = 0;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			n += __popcll(__ballot(host::label_in_set(label[s], set, a.width)));
+		if (lane_id() == 0)
+			a.counts[(size_t)u * a.n_blocks + block] = n;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_set_list_scatter(SetListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks)
+		return;
+	uint32_t label[FL_KEYS_PER_LANE];
+	range_list_labels(a, block, label);
+	const int lane = lane_id();
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *set = a.words + (size_t)u * a.width;
+		// the rows this block found in the count pass (the index is read-locked in between: the same rows now)
+		uint32_t at = a.list_base[u] + a.counts[(size_t)u * a.n_blocks + block];
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+			const bool in = host::label_in_set(label[s], set, a.width);
 			const unsigned long long m = __ballot(in);
 			if (in)
 				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;

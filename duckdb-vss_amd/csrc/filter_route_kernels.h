@@ -4,7 +4,8 @@
 // exact-routed ones — neither sees a query of the other.
 //
 //   k_route_gather     compact row i <- query map[i] (and its group number)          before the walk
-//   k_route_gather_words  a second per-query column of the compact batch (the `hi` of a call by label range)
+//   k_route_gather_words  further per-query words of the compact batch: a second column (the `hi` of a call by label range), or
+//                         with a words-per-query stride the whole row of a matrix (a call by label set)
 //   k_route_scatter    the caller's cells of query map[i] <- compact answer i        after the walk
 //   k_route_blank      count 0, cells -1 / +inf for the queries of unknown groups
 //   k_route_take_rows  block counts of the exact-routed used groups, made consecutive for k_filter_list_scatter
@@ -53,6 +54,17 @@ __global__ __launch_bounds__(256) void k_route_gather_words(const uint32_t *word
 	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
 	if (i < n)
 		out[i] = words[map[i]];
+}
+
+// ... and with a words-per-query stride, for a call that carries a row-major MATRIX (a call by label set: every routed query's
+// whole row of `per` words, in one launch): out[i][j] = words[map[i]][j]
+__global__ __launch_bounds__(256) void k_route_gather_words(const uint32_t *words, const uint32_t *map, uint32_t n, uint32_t per,
+                                                            uint32_t *out) {
+	const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (t < (uint64_t)n * per) {
+		const uint64_t i = t / per, j = t - i * per;
+		out[t] = words[(uint64_t)map[i] * per + j];
+	}
 }
 
 struct RouteScatterArgs {

@@ -46,6 +46,14 @@ constexpr uint64_t FILTER_BY_LABEL = 1ull << 62;
 // Three flag bits leave 61 for a bitmap's n_bits: the engine cuts a caller's n_bits at 2^61 - 1, and a bitmap of 2^61 bits is
 // 2^58 bytes, still more than any address space holds — no row that a bitmap in memory could admit is lost.
 constexpr uint64_t FILTER_BY_RANGE = 1ull << 61;
+// One label SET per query (vss_search_batch_by_label_set): filter_bits carries FILTER_BY_SET beside FILTER_PER_QUERY, its low bits
+// are the column's cells, and the table is k_resolve_label_sets': cell 0 the column's address, cell 1 the width, and from cell 2 on
+// every query's words, 32 bits each, host::label_set_chunks(width) chunks of four per query (padded with NO_LABEL).  Such launches
+// run the k_search_sets / k_search_solo_sets kernels.  Four flag bits leave 60 for a bitmap's n_bits: the engine cuts a caller's
+// n_bits at 2^60 - 1, and a bitmap of 2^60 bits is 2^57 bytes — the address space of the device and of its hosts has 2^48 to
+// 2^57 bytes in all, the index included, so no row that a bitmap in memory could admit is lost.
+constexpr uint64_t FILTER_BY_SET = 1ull << 60;
+constexpr uint64_t FILTER_FLAGS = FILTER_PER_QUERY | FILTER_BY_LABEL | FILTER_BY_RANGE | FILTER_BY_SET;
 
 struct GraphView {
 	RowSpace sp;
@@ -109,6 +117,30 @@ struct GraphView {
 			return false;
 		const uint32_t *labels = reinterpret_cast<const uint32_t *>(filter[0]);
 		return host::label_range_cell_admits(labels[key], filter[1 + 2 * (size_t)query], filter[2 + 2 * (size_t)query]);
+	}
+
+	// The same with one label set per query (the k_search_sets / k_search_solo_sets kernels only): the row is live, its row id has
+	// a cell, and the cell — loaded ONCE — holds one of the query's words (host::label_in_padded_set).  `query` is wave-uniform:
+	// its number goes through readfirstlane and the table is read through the constant address space, so the words arrive by
+	// two-word scalar loads into SGPRs and cost the lanes compares only.  No VGPR holds the set, and no LDS.
+	__device__ __forceinline__ bool admitted_set(uint32_t slot, uint32_t query) const {
+		typedef uint32_t words2 __attribute__((ext_vector_type(2)));
+		const int64_t key = keys[slot];
+		if (key == 0x7FFFFFFFFFFFFFFFll)
+			return false;
+		if (key < 0 || (uint64_t)key >= (filter_bits & ~FILTER_FLAGS))
+			return false;
+		const auto *table = (const __attribute__((address_space(4))) unsigned long long *)filter;
+		const uint32_t label = reinterpret_cast<const uint32_t *>(table[0])[key];
+		const uint32_t pairs = 2 * host::label_set_chunks((uint32_t)table[1]);
+		const auto *mine = (const __attribute__((address_space(4))) words2 *)(table + 2) +
+		                   (size_t)__builtin_amdgcn_readfirstlane(query) * pairs;
+		bool hit = false;
+		for (uint32_t j = 0; j != pairs; ++j) {
+			const words2 w = mine[j];
+			hit |= host::label_hits2(label, w.x, w.y);
+		}
+		return hit & (label != host::NO_LABEL);
 	}
 
 	__device__ __forceinline__ uint32_t *list_ptr(uint32_t slot, int level) const {
@@ -1145,7 +1177,23 @@ struct RowTouch {
 // candidates are merged in batches (the 1024-thread search engine cannot afford the temporaries of an 8-register merge)
 // PER_QUERY (TOMB): 1 (the *_groups kernels) the predicate is the one of the query being answered, GraphView::admitted_for;
 // 2 (the *_labels kernels) it is the query's wanted label, GraphView::admitted_label; 3 (the *_ranges kernels) the query's
-// label range, GraphView::admitted_range
+// label range, GraphView::admitted_range; 4 (the *_sets kernels) the query's label set, GraphView::admitted_set
+// the admission test of a PER_QUERY value: what the kernel family compiles in, and nothing of the others
+template <int PER_QUERY>
+__device__ __forceinline__ bool admitted_as(const GraphView &gv, uint32_t slot, uint32_t query) {
+	static_assert(PER_QUERY >= 0 && PER_QUERY <= 4, "whole launch, groups, labels, ranges, sets");
+	if constexpr (PER_QUERY == 4)
+		return gv.admitted_set(slot, query);
+	else if constexpr (PER_QUERY == 3)
+		return gv.admitted_range(slot, query);
+	else if constexpr (PER_QUERY == 2)
+		return gv.admitted_label(slot, query);
+	else if constexpr (PER_QUERY == 1)
+		return gv.admitted_for(slot, query);
+	else
+		return gv.admitted(slot);
+}
+
 template <int MT, bool INSERT, bool TOMB, int PK = 0, int MERGE_REGS = MAX_LIST_REGS, int PER_QUERY = 0, class List, class Queue,
           class Scorer>
 __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &lds, float qa2, uint32_t start,
@@ -1164,7 +1212,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 	if (TOMB) {
 		cq.restart();
 		cq.push(d0, start, 0.f, false);
-		if (PER_QUERY == 3 ? gv.admitted_range(start, lds.query) : PER_QUERY == 2 ? gv.admitted_label(start, lds.query) : PER_QUERY == 1 ? gv.admitted_for(start, lds.query) : gv.admitted(start))
+		if (admitted_as<PER_QUERY>(gv, start, lds.query))
 			L.template insert<INSERT>(d0, start);
 	} else {
 		L.template insert<INSERT>(d0, start);
@@ -1261,7 +1309,7 @@ __device__ __forceinline__ int level_search_impl(const GraphView &gv, WaveLds &l
 			const bool have = off + lane < n;
 			const float d = have ? lds.dist[off + lane] : 0.f;
 			const uint32_t id = have ? lds.ids[off + lane] : 0;
-			const uint32_t live = (TOMB && have) ? ((PER_QUERY == 3 ? gv.admitted_range(id, lds.query) : PER_QUERY == 2 ? gv.admitted_label(id, lds.query) : PER_QUERY == 1 ? gv.admitted_for(id, lds.query) : gv.admitted(id)) ? 1u : 0u) : 0u;
+			const uint32_t live = (TOMB && have) ? (admitted_as<PER_QUERY>(gv, id, lds.query) ? 1u : 0u) : 0u;
 			unsigned long long pass = __ballot(have && (L.size < limit || d < radius));
 			if constexpr (TOUCH_L) {
 				// ListTouch: a row about to enter the candidate list will be asked for its neighbour list by the look-ahead of one
@@ -2038,7 +2086,7 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS = 8)
 // GROUPS: the body of k_search_groups — a launch with one predicate per query (always a TOMB launch): the level search looks
 // the query's own bitmap up (1), compares the row's label with the query's (2: k_search_labels) or tests it against the query's
-// range (3: k_search_ranges), and the paths such a launch never takes are not compiled.
+// range (3: k_search_ranges) or its set (4: k_search_sets), and the paths such a launch never takes are not compiled.
 template <int MT, int NCH, int R, int E, int THREADS, int GROUPS>
 __device__ __forceinline__ void search_engine(SearchArgs &a) {
 	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
@@ -2296,6 +2344,11 @@ template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search_ranges(SearchArgs a) {
 	search_engine<MT, NCH, R, E, THREADS, 3>(a);
 }
+// ... and with one label set per query (vss_search_batch_by_label_set)
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search_sets(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, 4>(a);
+}
 
 // =========================================================================================================
 // k_search_solo — the search engine's shape for FEW queries (the single-query probe of HNSW_INDEX_SCAN, reference
@@ -2425,6 +2478,10 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 template <int MT, int NCH, int R, int E, int T = 1>
 __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_ranges(SearchArgs a) {
 	search_solo<MT, NCH, R, E, T, 3>(a);
+}
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_sets(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, 4>(a);
 }
 
 // =========================================================================================================
@@ -2637,6 +2694,28 @@ __global__ __launch_bounds__(256) void k_resolve_label_ranges(ResolveRangesArgs 
 	if (q < a.n_queries) {
 		const host::LabelRangeCells c = host::label_range_cells(a.lo[q], a.hi[q]);
 		a.table[1 + 2 * (size_t)q] = c.lo, a.table[2 + 2 * (size_t)q] = c.width;
+	}
+}
+
+// Ahead of a launch with one label set per query: the table GraphView::admitted_set reads.  `sets` is the launch's n_queries x
+// width matrix, in DEVICE memory; a thread writes one 32-bit word of a query's padded row (host::label_set_table_word).
+struct ResolveSetsArgs {
+	const uint32_t *labels;
+	const uint32_t *sets;
+	uint32_t n_queries, width;
+	unsigned long long *table; // 2 + 2 * label_set_chunks(width) * n_queries cells
+};
+
+__global__ __launch_bounds__(256) void k_resolve_label_sets(ResolveSetsArgs a) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	const uint32_t padded = 4 * host::label_set_chunks(a.width);
+	if (i == 0) {
+		a.table[0] = (unsigned long long)reinterpret_cast<uintptr_t>(a.labels);
+		a.table[1] = a.width;
+	}
+	if (i < (uint64_t)a.n_queries * padded) {
+		const uint64_t q = i / padded;
+		reinterpret_cast<uint32_t *>(a.table + 2)[i] = host::label_set_table_word(a.sets + q * a.width, a.width, (uint32_t)(i - q * padded));
 	}
 }
 

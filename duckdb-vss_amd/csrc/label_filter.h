@@ -6,7 +6,8 @@
 // this header defines: the distinct values of `want`, ascending, are the groups, group g's bitmap has bit r set iff
 // label_admits(labels, labelled_rows, r, value g), and query q takes the group label_groups() gives it.
 // vss_search_batch_by_label_range tests the same column against one inclusive range per query: its rule, the walker's and the
-// listing's forms of it and its groups are further down (host/label_range_check.cpp).
+// listing's forms of it and its groups are further down (host/label_range_check.cpp), and so are those of
+// vss_search_batch_by_label_set, which tests it against a short list of values per query (host/label_set_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -126,6 +127,83 @@ inline void label_range_groups(const uint32_t *lo, const uint32_t *hi, uint64_t 
 	group_of.resize(n);
 	for (uint64_t q = 0; q != n; ++q)
 		group_of[q] = (uint32_t)(std::lower_bound(pairs.begin(), pairs.end(), LabelRange {lo[q], hi[q]}) - pairs.begin());
+}
+
+// ---- per-query SETS over the same column (vss_search_batch_by_label_set): a call brings `sets`, a row-major n_queries x width
+// matrix of 32-bit words, 1 <= width <= LABEL_SET_MAX, and query q admits the live rows whose cell holds one of the words of row q.
+// NO_LABEL is the padding of a shorter list: a word holding it equals nothing, a row that is all padding is the empty predicate,
+// order and repeats inside a row change nothing of what it admits — and a cell holding NO_LABEL is admitted by no set: the
+// padding must not match it.  The derived table: the distinct RAW rows of the call, ascending lexicographically as unsigned
+// words, are the groups — nothing is canonicalised, the same members in another order are another group — and bitmap g has bit r
+// set iff label_set_admits(labels, labelled_rows, r, row g, width).
+//
+// The cap is a design limit, not a measurement: the walker's test has to stay a short loop of register compares against
+// wave-uniform words, and the listing loop does the same per group.  Beyond a few dozen values a bitmap's one load per row is the
+// cheaper test, and the bitmap calls stay for that.
+constexpr uint32_t LABEL_SET_MAX = 32; // VSS_LABEL_SET_MAX
+
+// THE admission rule of a set, but for the row being live: the row id has a cell, the cell holds a label, and one of the row's
+// words is that label.  constexpr: the kernels and the CPU check (host/label_set_check.cpp) run this very code.
+inline constexpr bool label_set_admits(const uint32_t *labels, uint64_t labelled_rows, int64_t key, const uint32_t *set, uint32_t width) {
+	if (key < 0 || (uint64_t)key >= labelled_rows || labels[key] == NO_LABEL)
+		return false;
+	for (uint32_t j = 0; j != width; ++j)
+		if (labels[key] == set[j])
+			return true;
+	return false;
+}
+
+// The register form: `label` is a cell's value, or NO_LABEL for "no cell at all" (a free slot, a row id beyond the column).  No
+// early exit — every lane of a wave runs the same `width` compares against wave-uniform words — and ONE test of the label
+// against NO_LABEL at the end keeps the padding from matching the unlabelled cell.
+inline constexpr bool label_hits2(uint32_t label, uint32_t a, uint32_t b) { // (one step of the walker's loop)
+	return (label == a) | (label == b);
+}
+inline constexpr bool label_in_set(uint32_t label, const uint32_t *set, uint32_t width) {
+	bool hit = false;
+	for (uint32_t j = 0; j != width; ++j)
+		hit |= label == set[j];
+	return hit & (label != NO_LABEL);
+}
+
+// What the walker's table holds of one row: the raw words, padded with NO_LABEL to a multiple of FOUR, so that every row is whole,
+// aligned 16-byte chunks.  Padding equals nothing, so the padded row admits what the raw row admits.  The walker reads it by
+// two-word scalar loads (label_in_padded_set is its loop: label_in_set over the padded row, two words a step;
+// host/label_set_check.cpp proves both against the rule) — four words a step cost the few-query kernels, which sit at their
+// scalar-register limit, 36-52 bytes of scratch in seven instantiations.
+inline constexpr uint32_t label_set_chunks(uint32_t width) {
+	return (width + 3) / 4;
+}
+inline constexpr uint32_t label_set_table_word(const uint32_t *set, uint32_t width, uint32_t j) { // j < 4 * label_set_chunks(width)
+	return j < width ? set[j] : NO_LABEL;
+}
+inline constexpr bool label_in_padded_set(uint32_t label, const uint32_t *padded, uint32_t chunks) {
+	bool hit = false;
+	for (uint32_t j = 0; j != 2 * chunks; ++j)
+		hit |= label_hits2(label, padded[2 * j], padded[2 * j + 1]);
+	return hit & (label != NO_LABEL);
+}
+
+// the distinct raw rows of `sets` (n rows of `width` words), ascending lexicographically as unsigned words and flattened into
+// `rows` (rows.size() / width groups), and the group of every query: label_range_groups' counterpart
+inline void label_set_groups(const uint32_t *sets, uint64_t n, uint32_t width, std::vector<uint32_t> &rows, std::vector<uint32_t> &group_of) {
+	std::vector<uint64_t> order(n);
+	for (uint64_t q = 0; q != n; ++q)
+		order[q] = q;
+	const auto less = [&](uint64_t a, uint64_t b) {
+		return std::lexicographical_compare(sets + a * width, sets + (a + 1) * width, sets + b * width, sets + (b + 1) * width);
+	};
+	std::sort(order.begin(), order.end(), less);
+	rows.clear();
+	group_of.resize(n);
+	uint64_t groups = 0;
+	for (uint64_t i = 0; i != n; ++i) {
+		if (i == 0 || less(order[i - 1], order[i])) {
+			rows.insert(rows.end(), sets + order[i] * width, sets + (order[i] + 1) * width);
+			++groups;
+		}
+		group_of[order[i]] = (uint32_t)(groups - 1);
+	}
 }
 
 // vss_set_labels(first_rowid, n): what the range breaks, or NONE. Cells end at 2^32 (first_rowid + n == 2^32 is the last range

@@ -126,12 +126,14 @@ static thread_local std::string tls_error;
 // What a search launch filters its results by.  The pointers are device memory for search_begin / search_launch and host
 // memory for search_host, which stages what they name and hands search_launch the staged copy.
 struct SearchPredicate {
-	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE } kind = NONE;
+	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE, BY_SET } kind = NONE;
 	const uint64_t *bitmap = nullptr;                        // ONE_BITMAP: the whole launch's; bit set = row id admitted
 	FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES] = {}; // PER_QUERY: the table of every batch of the launch
 	uint64_t n_bits = 0;                                     // (BY_LABEL: the cells of the index's label column)
 	const uint32_t *want = nullptr;                          // BY_LABEL: the label every query of the (one) batch wants
 	const uint32_t *lo = nullptr, *hi = nullptr;             // BY_RANGE: the ends of every query's label range, both inclusive
+	const uint32_t *sets = nullptr;                          // BY_SET: `width` words per query, row-major
+	uint32_t width = 0;
 
 	// a launch of one batch against the index's label column: query q admits the rows labelled want[q]
 	static SearchPredicate by_label(const uint32_t *want, uint64_t labelled_rows) {
@@ -144,6 +146,13 @@ struct SearchPredicate {
 	static SearchPredicate by_range(const uint32_t *lo, const uint32_t *hi, uint64_t labelled_rows) {
 		SearchPredicate p;
 		p.kind = BY_RANGE, p.n_bits = labelled_rows, p.lo = lo, p.hi = hi;
+		return p;
+	}
+
+	// ... query q admits the rows whose label is one of sets[q * width .. (q + 1) * width)
+	static SearchPredicate by_set(const uint32_t *sets, uint32_t width, uint64_t labelled_rows) {
+		SearchPredicate p;
+		p.kind = BY_SET, p.n_bits = labelled_rows, p.sets = sets, p.width = width;
 		return p;
 	}
 
@@ -188,12 +197,14 @@ struct DeviceWords {
 	}
 };
 
-// The groups the rows of a scan call are listed by, made by one of the three factories only.  Bitmaps: group g = the rows bitmap g
+// The groups the rows of a scan call are listed by, made by one of the four factories only.  Bitmaps: group g = the rows bitmap g
 // of a DEVICE table admits.  Labels: group g = the rows the index's label column gives values[g], the ascending distinct wanted
 // values (HOST memory); no bitmap exists.  Either way query q reads group group_of[q] (HOST memory; nullptr: all read group 0),
 // and the walk of the graph-routed queries reads the column's DEVICE twin: group numbers under bitmaps, wanted labels under labels.
 // Ranges: group g = the rows whose label lies within pairs[g], the ascending distinct raw (lo, hi) pairs of the call (HOST memory);
 // the walk reads TWO device columns, every query's lo (d_group_of) and hi (d_hi).
+// Sets: group g = the rows whose label is one of the `width` words of rows[g], the ascending distinct raw rows of the call (HOST
+// memory, flattened); the walk reads every query's whole row of the DEVICE matrix d_sets, and d_group_of stays nullptr.
 struct GroupedRows {
 	const uint64_t *d_table = nullptr;  // bitmaps: n_groups bitmaps of n_bits bits
 	uint64_t n_groups = 0, n_bits = 0;  // (labels: the distinct wanted values; the cells of the label column)
@@ -202,6 +213,9 @@ struct GroupedRows {
 	const LabelRange *pairs = nullptr;  // ranges: HOST
 	const uint32_t *group_of = nullptr, *d_group_of = nullptr;
 	const uint32_t *d_hi = nullptr;     // ranges: every query's upper end (d_group_of holds the lower ends)
+	const uint32_t *rows = nullptr;     // sets: HOST, n_groups x width
+	const uint32_t *d_sets = nullptr;   // sets: the call's n_queries x width matrix
+	uint32_t width = 0;                 // sets: words per row
 
 	static GroupedRows bitmaps(const uint64_t *d_table, uint64_t n_groups, uint64_t n_bits, HostWords group_of, DeviceWords d_group_of) {
 		GroupedRows g;
@@ -223,13 +237,32 @@ struct GroupedRows {
 		return g;
 	}
 
-	// words that name one used group to the list kernels: its table group, its wanted value, or the two ends of its range
-	uint64_t group_cells() const {
-		return by_range ? 2 : 1;
+	static GroupedRows sets(const std::vector<uint32_t> &rows, uint32_t width, const uint32_t *d_labels, uint64_t labelled_rows,
+	                        HostWords group_of, DeviceWords d_sets) {
+		GroupedRows g;
+		g.by_set = true, g.rows = rows.data(), g.width = width, g.d_labels = d_labels;
+		g.n_groups = rows.size() / width, g.n_bits = labelled_rows, g.group_of = group_of.p, g.d_sets = d_sets.p;
+		return g;
 	}
-	// a second per-query column the walk of the graph-routed queries needs gathered beside d_group_of, or nullptr
-	const uint32_t *second_walk_column() const {
-		return by_range ? d_hi : nullptr;
+
+	// words that name one used group to the list kernels: its table group, its wanted value, the two ends of its range, or the
+	// words of its set.  The walk of the graph-routed queries needs as many words per query gathered into the compact batch.
+	uint64_t group_cells() const {
+		return by_set ? width : by_range ? 2 : 1;
+	}
+	// Those words beyond the one column k_route_gather takes along (d_group_of; under sets it takes none): `per` words a query,
+	// row-major from `words`, to word `at` of the compact batch's ng * group_cells() words — or words == nullptr, nothing more.
+	struct WalkWords {
+		const uint32_t *words;
+		uint32_t per;
+		uint64_t at;
+	};
+	WalkWords more_walk_words(uint64_t ng) const {
+		if (by_set)
+			return {d_sets, width, 0};
+		if (by_range)
+			return {d_hi, 1, ng};
+		return {nullptr, 0, 0};
 	}
 
 	// the list kernels' arguments in the label form: table group g is "the rows labelled values[g]", so the cells that name the
@@ -251,9 +284,24 @@ struct GroupedRows {
 		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
 		return a;
 	}
-	// the cells of a plan's used groups, group_cells() words each: plan.groups, or their values / pairs in `scratch` (which
+	// ... and in the set form: the cells hold the groups' ROWS, `width` words each
+	SetListArgs set_list_args(const FilterListArgs &l) const {
+		SetListArgs a;
+		a.keys = l.keys, a.rows = l.rows, a.n_blocks = l.n_blocks;
+		a.labels = d_labels, a.labelled_rows = n_bits;
+		a.words = l.groups, a.width = width, a.u_begin = l.u_begin, a.u_end = l.u_end;
+		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
+		return a;
+	}
+	// the cells of a plan's used groups, group_cells() words each: plan.groups, or their values / pairs / rows in `scratch` (which
 	// outlives the upload like plan.groups)
 	const uint32_t *used_group_cells(const ExactFilterPlan &plan, std::vector<uint32_t> &scratch) const {
+		if (by_set) {
+			scratch.resize((size_t)width * plan.groups.size());
+			for (size_t u = 0; u != plan.groups.size(); ++u)
+				std::copy(rows + (size_t)plan.groups[u] * width, rows + ((size_t)plan.groups[u] + 1) * width, scratch.begin() + u * width);
+			return scratch.data();
+		}
 		if (by_range) {
 			scratch.resize(2 * plan.groups.size());
 			for (size_t u = 0; u != plan.groups.size(); ++u)
@@ -275,6 +323,8 @@ struct GroupedRows {
 			hipLaunchKernelGGL(k_label_list_count, grid, dim3(256), 0, stream, label_list_args(l));
 		} else if (by_range) // (every cell of the launch's groups is written)
 			hipLaunchKernelGGL(k_range_list_count, grid, dim3(256), 0, stream, range_list_args(l));
+		else if (by_set) // (the same)
+			hipLaunchKernelGGL(k_set_list_count, grid, dim3(256), 0, stream, set_list_args(l));
 		else
 			hipLaunchKernelGGL(k_filter_list_count, grid, dim3(256), 0, stream, l);
 	}
@@ -285,14 +335,19 @@ struct GroupedRows {
 			hipLaunchKernelGGL(k_label_list_scatter, grid, dim3(256), 0, stream, label_list_args(l));
 		else if (by_range)
 			hipLaunchKernelGGL(k_range_list_scatter, grid, dim3(256), 0, stream, range_list_args(l));
+		else if (by_set)
+			hipLaunchKernelGGL(k_set_list_scatter, grid, dim3(256), 0, stream, set_list_args(l));
 		else
 			hipLaunchKernelGGL(k_filter_list_scatter, grid, dim3(256), 0, stream, l);
 	}
-	// what the walk of a compact batch of graph-routed queries filters by; d_compact_groups: their cells of d_group_of, gathered,
-	// and d_compact_second: those of second_walk_column()
-	SearchPredicate walk_predicate(const uint32_t *d_compact_groups, const uint32_t *d_compact_second) const {
+	// what the walk of a compact batch of ng graph-routed queries filters by; d_compact: their ng * group_cells() gathered words
+	// (k_route_gather's column first, more_walk_words() where it says)
+	SearchPredicate walk_predicate(const uint32_t *d_compact, uint64_t ng) const {
+		const uint32_t *d_compact_groups = d_compact;
+		if (by_set)
+			return SearchPredicate::by_set(d_compact, width, n_bits);
 		if (by_range)
-			return SearchPredicate::by_range(d_compact_groups, d_compact_second, n_bits);
+			return SearchPredicate::by_range(d_compact_groups, d_compact + more_walk_words(ng).at, n_bits);
 		if (by_label)
 			return SearchPredicate::by_label(d_compact_groups, n_bits);
 		return d_group_of ? SearchPredicate::one_table(d_table, d_compact_groups, n_groups, n_bits)
@@ -300,7 +355,7 @@ struct GroupedRows {
 	}
 
 private:
-	bool by_label = false, by_range = false;
+	bool by_label = false, by_range = false, by_set = false;
 	GroupedRows() = default;
 };
 
@@ -1498,10 +1553,11 @@ struct vss_index {
 		// free key — so a wider bitmap admits nothing more; the top bit is the kernels' FILTER_PER_QUERY.  The bit below it is
 		// FILTER_BY_LABEL, which chooses the launch's kernels: a bitmap of 2^62 bits is 2^59 bytes, more than any address space
 		// holds, so cutting a caller's n_bits there takes no row away that a bitmap in memory could admit.  FILTER_BY_RANGE took one
-		// more bit: the cut is at 2^61 - 1, a bitmap of 2^58 bytes.)
+		// more bit, FILTER_BY_SET a fourth: the cut is at 2^60 - 1, a bitmap of 2^57 bytes — as much as a 57-bit address space holds
+		// in all.)
 		const SearchPredicate &p = r.predicate;
 		a.gv.filter = p.kind == SearchPredicate::ONE_BITMAP ? reinterpret_cast<const unsigned long long *>(p.bitmap) : nullptr;
-		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_BY_RANGE - 1);
+		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_BY_SET - 1);
 		if (p.kind == SearchPredicate::PER_QUERY) {
 			// Descriptor b = batch b's table.  A small kernel ahead of the launch resolves every query's bitmap address; the walkers
 			// of the *_groups kernels read that (GraphView::admitted_for).  The descriptors go to it by value, so the launch path
@@ -1540,6 +1596,21 @@ struct vss_index {
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits = std::min<uint64_t>(labelled_rows, FILTER_BY_RANGE - 1) | FILTER_PER_QUERY | FILTER_BY_RANGE;
+		} else if (p.kind == SearchPredicate::BY_SET) {
+			// ... and by the *_sets kernels (GraphView::admitted_set): cell 0 the column, cell 1 the width, then every query's
+			// words in chunks of four, two cells a chunk
+			if (n_batches != 1 || !d_labels.p || p.width < 1 || p.width > LABEL_SET_MAX)
+				return fail("search by label set: one batch per launch, over an index whose labels have been set, width 1 to %u",
+				            (unsigned)LABEL_SET_MAX);
+			const uint64_t chunks = label_set_chunks(p.width);
+			if (!c.d_group_bitmap.try_grow(2 * chunks * cap_q + 2))
+				return fail("search by label set: no device memory for the sets of %llu queries", (unsigned long long)cap_q);
+			count_group_tables(c);
+			ResolveSetsArgs res = {d_labels.p, p.sets, (uint32_t)nq, p.width, reinterpret_cast<unsigned long long *>(c.d_group_bitmap.p)};
+			hipLaunchKernelGGL(k_resolve_label_sets, dim3((uint32_t)(nq * 4 * chunks / 256 + 1)), dim3(256), 0, c.stream, res);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits = std::min<uint64_t>(labelled_rows, FILTER_BY_SET - 1) | FILTER_PER_QUERY | FILTER_BY_SET;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
@@ -1782,6 +1853,14 @@ struct vss_index {
 		HIP_TRY(hipMemcpyAsync(c.d_group_of.p + nq, hi, nq * 4, hipMemcpyHostToDevice, c.stream));
 		return VSS_OK;
 	}
+	// the sets of a call by label set (HOST memory), in the same buffer: the nq x width matrix as it is
+	int stage_label_sets(SearchCtx &c, const uint32_t *sets, uint32_t width, uint64_t nq) {
+		if (!c.d_group_of.try_grow(nq * width))
+			return fail("search by label set: no device memory for the sets of %llu queries", (unsigned long long)nq);
+		count_group_tables(c);
+		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, sets, nq * width * 4, hipMemcpyHostToDevice, c.stream));
+		return VSS_OK;
+	}
 	// queries in, result buffers ensured ...
 	void stage_queries(SearchCtx &c, const float *queries, uint64_t nq, uint64_t k) {
 		c.d_q.ensure(nq * dim, 0, c.stream), c.d_out_count.ensure(nq, 0, c.stream);
@@ -1882,6 +1961,10 @@ struct vss_index {
 				    if (const int rc = stage_label_ranges(c, filter.lo, filter.hi, nq))
 					    return rc;
 				    staged = SearchPredicate::by_range(c.d_group_of.p, c.d_group_of.p + nq, filter.n_bits);
+			    } else if (filter.kind == SearchPredicate::BY_SET) {
+				    if (const int rc = stage_label_sets(c, filter.sets, filter.width, nq))
+					    return rc;
+				    staged = SearchPredicate::by_set(c.d_group_of.p, filter.width, filter.n_bits);
 			    }
 			    return VSS_OK;
 		    },
@@ -2403,12 +2486,20 @@ struct vss_index {
 			ga.vec4 = dim % 4 == 0 && reinterpret_cast<uintptr_t>(b.d_queries) % 16 == 0 && reinterpret_cast<uintptr_t>(c.d_route_q.p) % 16 == 0;
 			ga.out_queries = c.d_route_q.p, ga.out_group_of = c.d_route_group.p;
 			hipLaunchKernelGGL(k_route_gather, dim3((uint32_t)((ng + 3) / 4)), dim3(256), 0, c.stream, ga);
-			if (const uint32_t *second = g.second_walk_column()) // (a range's upper ends, behind the ng lower ones)
-				hipLaunchKernelGGL(k_route_gather_words, dim3((uint32_t)((ng + 255) / 256)), dim3(256), 0, c.stream, second, c.d_route_map.p,
-				                   (uint32_t)ng, c.d_route_group.p + ng);
+			// (a range's upper ends, behind the ng lower ones; a set's whole rows)
+			if (const GroupedRows::WalkWords w = g.more_walk_words(ng); w.words) {
+				const dim3 grid((uint32_t)((ng * w.per + 255) / 256));
+				void (*const column)(const uint32_t *, const uint32_t *, uint32_t, uint32_t *) = k_route_gather_words;
+				void (*const matrix)(const uint32_t *, const uint32_t *, uint32_t, uint32_t, uint32_t *) = k_route_gather_words;
+				if (w.per == 1) // (the kernel of the call by label range, as it was)
+					hipLaunchKernelGGL(column, grid, dim3(256), 0, c.stream, w.words, c.d_route_map.p, (uint32_t)ng, c.d_route_group.p + w.at);
+				else
+					hipLaunchKernelGGL(matrix, grid, dim3(256), 0, c.stream, w.words, c.d_route_map.p, (uint32_t)ng, w.per,
+					                   c.d_route_group.p + w.at);
+			}
 			HIP_TRY(hipGetLastError());
 			SearchRequest r = request(b.slot, &c.d_route_q.p, 1, ng, k, b.ef, &c.d_route_keys.p, &c.d_route_d.p, &c.d_route_count.p);
-			r.predicate = g.walk_predicate(c.d_route_group.p, c.d_route_group.p + ng);
+			r.predicate = g.walk_predicate(c.d_route_group.p, ng);
 			if (const int rc = search_launch(r))
 				return rc;
 			RouteScatterArgs s;
@@ -2482,6 +2573,30 @@ struct vss_index {
 		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
 			    return by_range_launch(b, HostWords(lo), HostWords(hi), DeviceWords(exact ? nullptr : c.d_group_of.p),
 			                           DeviceWords(exact ? nullptr : c.d_group_of.p + hc.nq), route_c, out, route);
+		    });
+	}
+
+	// ------------------------------------------------------------------ search by label set (label_filter.h)
+	// The same over the table label_set_groups() makes of `sets`: group g = the rows whose label is a word of rows[g].  d_sets: the
+	// matrix for the walk of the graph-routed queries; nullptr asks for the exact scan of every query.
+	int by_set_launch(const DeviceBatch &b, HostWords sets, uint32_t width, DeviceWords d_sets, uint64_t route_c, const DeviceAnswers &out,
+	                  std::vector<uint8_t> &route) {
+		std::vector<uint32_t> rows, group_of;
+		label_set_groups(sets.p, b.nq, width, rows, group_of);
+		const GroupedRows g = GroupedRows::sets(rows, width, d_labels.p, labelled_rows, HostWords(group_of.data()), d_sets);
+		if (!d_sets.p) {
+			route.assign(b.nq, FILTER_ROUTE_EXACT);
+			return exact_filtered_launch(b, g, out);
+		}
+		return filtered_auto(b, g, route_c, out, route);
+	}
+
+	// the host-pointer form of those two: the exact scan stages no sets
+	int by_set_host(const HostCall &hc, bool exact, const uint32_t *sets, uint32_t width, uint64_t route_c) {
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_sets(c, sets, width, hc.nq); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+			    return by_set_launch(b, HostWords(sets), width, DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
 		    });
 	}
 
@@ -3875,6 +3990,70 @@ int vss_search_batch_by_label_range_device(vss_index *h, const float *Q, uint64_
 			if (const int rc = h->by_range_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(lo_h.data()), HostWords(hi_h.data()),
 			                                      DeviceWords(exact ? nullptr : lo), DeviceWords(exact ? nullptr : hi), route_c,
 			                                      {out, out_d, out_counts}, route))
+				return rc;
+		}
+		h->route_to_device(route, out_route);
+		return VSS_OK;
+	})
+}
+
+// ---- the search by label set: the mode is refused first, then the width, then null sets — all before anything is launched or
+// written — and the missing column after them
+static_assert(LABEL_SET_MAX == VSS_LABEL_SET_MAX, "one cap, in the rule's header and in the C header");
+static int check_by_label_set(vss_index *h, const char *what, const float *Q, uint64_t nq, const uint32_t *sets, uint64_t width, int mode,
+                              const int64_t *out, const uint32_t *out_counts) {
+	if (mode != VSS_BY_LABEL_GRAPH && mode != VSS_BY_LABEL_EXACT && mode != VSS_BY_LABEL_AUTO)
+		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
+	if (width < 1 || width > VSS_LABEL_SET_MAX)
+		return h->fail("%s: width %llu is not within 1 .. VSS_LABEL_SET_MAX (%d); longer lists take the bitmap calls", what,
+		               (unsigned long long)width, VSS_LABEL_SET_MAX);
+	if (nq && !sets)
+		return h->fail("%s: null sets pointer for %llu queries", what, (unsigned long long)nq);
+	if (!h->d_labels.p)
+		return h->fail("%s: the index has no label column (call vss_set_labels first; vss_load and vss_clear_labels drop it)", what);
+	if (nq && (!Q || !out || !out_counts))
+		return h->fail("%s: null query / row-id / count pointer", what);
+	if (nq > 0xFFFFFFFFull)
+		return h->fail("%s: at most 2^32 - 1 queries per call", what);
+	return VSS_OK;
+}
+
+int vss_search_batch_by_label_set(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *sets, uint64_t width,
+                                  int mode, uint64_t route_c, int64_t *out, float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		if (check_by_label_set(h, "vss_search_batch_by_label_set", Q, nq, sets, width, mode, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		if (mode != VSS_BY_LABEL_GRAPH)
+			return h->by_set_host({Q, nq, k, ef, out, out_d, out_counts, out_route}, mode == VSS_BY_LABEL_EXACT, sets, (uint32_t)width,
+			                      route_c);
+		if (out_route)
+			std::memset(out_route, FILTER_ROUTE_GRAPH, nq);
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false, SearchPredicate::by_set(sets, (uint32_t)width, h->labelled_rows));
+	})
+}
+
+int vss_search_batch_by_label_set_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *sets,
+                                         uint64_t width, int mode, uint64_t route_c, int64_t *out, float *out_d, uint32_t *out_counts,
+                                         uint8_t *out_route) {
+	VSS_SHARED(h, {
+		if (check_by_label_set(h, "vss_search_batch_by_label_set_device", Q, nq, sets, width, mode, out, out_counts) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		std::vector<uint8_t> route(nq, FILTER_ROUTE_GRAPH);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+			r.predicate = SearchPredicate::by_set(sets, (uint32_t)width, h->labelled_rows);
+			if (const int rc = h->search_launch(r))
+				return rc;
+		} else {
+			// (the plans read the sets on the host: nq x width words come back first)
+			const std::vector<uint32_t> sets_h = h->words_to_host(sets, nq * width);
+			const bool exact = mode == VSS_BY_LABEL_EXACT;
+			if (const int rc = h->by_set_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(sets_h.data()), (uint32_t)width,
+			                                    DeviceWords(exact ? nullptr : sets), route_c, {out, out_d, out_counts}, route))
 				return rc;
 		}
 		h->route_to_device(route, out_route);

@@ -281,6 +281,18 @@ public:
 			return vss_search_batch_by_label_range(index, queries, n_queries, limit, ef, lo, hi, mode, route_c, ids, nullptr, counts, routes);
 		});
 	}
+	// The correlated chunk whose predicate is a SET on that column (`items.grp IN (...)`, `items.grp = ANY(q.groups)`,
+	// `list_contains(q.groups, items.grp)`): outer row q brings `width` labels, sets[q * width .. (q + 1) * width), a shorter list
+	// padded with VSS_NO_LABEL to the chunk's longest (1 <= width <= VSS_LABEL_SET_MAX; longer lists take the bitmap methods), and
+	// vss_search_batch_by_label_set does the rest, modes as above.  An all-padding row admits nothing, and a row whose cell is
+	// VSS_NO_LABEL is in no set.
+	idx_t ExecuteMultiScanBatchByLabelSet(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit, const uint32_t *sets,
+	                                      idx_t width, std::vector<uint32_t> *counts_out, std::vector<uint8_t> *routes_out = nullptr,
+	                                      int mode = VSS_BY_LABEL_AUTO, uint64_t route_c = 0) {
+		return ScanChunk(state_p, n_queries, limit, counts_out, routes_out, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *routes) {
+			return vss_search_batch_by_label_set(index, queries, n_queries, limit, ef, sets, width, mode, route_c, ids, nullptr, counts, routes);
+		});
+	}
 	// The label column: cells first_rowid .. first_rowid + n - 1 (vss_set_labels).  Not persisted: after LoadFromBlocks the owner
 	// writes it again from the table.
 	void SetLabels(idx_t first_rowid, const uint32_t *labels, idx_t n) {

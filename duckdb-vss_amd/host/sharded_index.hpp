@@ -498,6 +498,34 @@ public:
 			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
 		}
 	}
+	// Query q admits the live rows whose label is one of sets[q * width .. (q + 1) * width) (VSS_NO_LABEL pads a shorter list and
+	// equals nothing; a VSS_NO_LABEL cell is in no set): vss_search_batch_by_label_set_device per shard, every shard holding the
+	// whole column.  Modes, shard_routes, exchange and merge are SearchBatchByLabel's; the matrix travels as UploadTables' group
+	// numbers, n * width words.
+	void SearchBatchByLabelSet(const float *queries, idx_t n, idx_t k, idx_t ef, const uint32_t *sets, idx_t width, int mode, uint64_t route_c,
+	                           row_t *out_rowids, float *out_distances, uint32_t *out_counts, std::vector<uint8_t> *shard_routes = nullptr) {
+		if (shard_routes)
+			shard_routes->assign(shards.size() * n, 0);
+		if (!n || !k)
+			return;
+		if (width < 1 || width > VSS_LABEL_SET_MAX)
+			throw InternalException("Failed to search the HNSW index: search by label set takes a width of 1 to 32 labels per query");
+		if (!sets)
+			throw InternalException("Failed to search the HNSW index: search by label set needs every query's row of labels");
+		Ensure(n, k);
+		UploadTables(nullptr, 0, sets, n * width);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    Vss(s, vss_search_batch_by_label_set_device(s.index->Handle(), s.d_q, n, k, ef, bitmaps[s.bitmap].group_of, width, mode,
+			                                                route_c, keys, dist, s.d_cnt, s.d_route));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		for (size_t g = 0; shard_routes && g != shards.size(); ++g) {
+			Hip(hipSetDevice(shards[g].device), "hipSetDevice");
+			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
+		}
+	}
 
 private:
 	// A table of per-query predicates, refused here before any device is touched: the rules of csrc/filter_groups.h in this

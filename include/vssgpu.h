@@ -300,6 +300,37 @@ int vss_search_batch_by_label_range_device(vss_index *index, const float *d_quer
                                            const uint32_t *d_lo, const uint32_t *d_hi, int mode, uint64_t route_c,
                                            int64_t *d_out_rowids, float *d_out_distances, uint32_t *d_out_counts,
                                            uint8_t *d_out_route);
+/* ---- IN-list predicates on the same column (csrc/label_filter.h) ------------------------------------------------------------
+ * For `items.grp IN (...)`, `items.grp = ANY(q.groups)`, `list_contains(q.groups, items.grp)` — the access-control predicate of
+ * a shared store, the category list of a faceted search: the call brings `sets`, a row-major n_queries x width matrix of
+ * 32-bit labels, 1 <= width <= VSS_LABEL_SET_MAX.  Query q admits a live row of id r iff 0 <= r < vss_labelled_rows(),
+ * labels[r] != VSS_NO_LABEL and labels[r] == sets[q * width + j] for some j < width.
+ * VSS_NO_LABEL is the padding of a shorter list: a word holding it equals nothing, and a row of the matrix that is all padding
+ * is the empty predicate (count 0, ids -1, distances +inf).  Order and repeats inside a row do not change what it admits.  A
+ * cell of the column holding VSS_NO_LABEL is admitted by no set: the padding does not match it.
+ * The cap of 32 is a design limit, not a measurement: the test is a short loop of compares against the query's words, and beyond
+ * a few dozen values a bitmap's one load per row is the cheaper test — the bitmap calls stay for that.
+ * mode, route_c and out_route as for vss_search_batch_by_label.
+ * Contract: with s_0 < s_1 < ... the distinct RAW rows of `sets`, ascending lexicographically as unsigned words and not
+ * canonicalised (the same members in another order are another group), bitmap g = {r < labelled rows : the rule admits r for
+ * s_g} and group_of[q] = the index of query q's row, the call returns cell for cell what the bitmap call of the same mode
+ * returns for that table — row ids, f32 distance bits, counts, routes — and leaves the same vss_last_exact_filtered [0..2],
+ * vss_last_filter_route, vss_last_search_stats / _shape / _prescore / _prescore_descent values behind.  With width 1 that is
+ * also the answer of vss_search_batch_by_label, and a row of consecutive values a, a + 1, ... answers as the range does.  Sets
+ * overlap: the lists of one call may together exceed the index's rows and take several passes, as a bitmap table's do.
+ * Errors, in this order: a mode other than the three; width 0 or above VSS_LABEL_SET_MAX; sets NULL with n_queries > 0 (these
+ * three before anything is launched or written); no column set; those of the call of the mode.  n_queries == 0 or k == 0
+ * returns VSS_OK and writes nothing.
+ * The _device form takes device pointers (d_out_distances and d_out_route may be NULL), copies d_sets back (4 * width bytes
+ * per query) in modes exact and auto, and runs on context 0.  Not available in the pipelined / multi-batch _begin forms. */
+#define VSS_LABEL_SET_MAX 32
+int vss_search_batch_by_label_set(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                  const uint32_t *sets, uint64_t width, int mode, uint64_t route_c, int64_t *out_rowids,
+                                  float *out_distances, uint32_t *out_counts, uint8_t *out_route);
+int vss_search_batch_by_label_set_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                         const uint32_t *d_sets, uint64_t width, int mode, uint64_t route_c,
+                                         int64_t *d_out_rowids, float *d_out_distances, uint32_t *d_out_counts,
+                                         uint8_t *d_out_route);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
