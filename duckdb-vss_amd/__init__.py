@@ -107,6 +107,13 @@ SIGNATURES = {
     "vss_search_batch_by_label_range_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_by_label_set": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_by_label_set_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_set_label_column": (_int, [_vp, _u32, _u64, _vp, _u64]),
+    "vss_set_label_column_device": (_int, [_vp, _u32, _u64, _vp, _u64]),
+    "vss_clear_label_column": (_int, [_vp, _u32]),
+    "vss_label_column_rows": (_u64, [_vp, _u32]),
+    "vss_search_batch_by_label_box": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_by_label_box_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp,
+                                                    _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -484,6 +491,60 @@ class GpuIndex:
         self._check(self.lib.vss_search_batch_by_label_range_device(self.h, d_Q, nq, k, ef, d_lo, d_hi,
                                                                     self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
                                                                     d_counts, d_route))
+
+    LABEL_COLUMNS_MAX = 4  # VSS_LABEL_COLUMNS_MAX
+
+    def set_label_column(self, column, first_rowid, labels):
+        """vss_set_label_column: cells first_rowid .. first_rowid + len(labels) - 1 of label column `column` (0 .. 3; column 0 is
+        the column of set_labels)."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        if labels.ndim != 1:
+            raise ValueError("labels must be one uint32 per row id, got shape %r" % (labels.shape,))
+        self._check(self.lib.vss_set_label_column(self.h, column, first_rowid, _p(labels), len(labels)))
+
+    def set_label_column_device(self, column, first_rowid, d_labels, n):
+        """The same from a raw device pointer."""
+        self._check(self.lib.vss_set_label_column_device(self.h, column, first_rowid, d_labels, n))
+
+    def clear_label_column(self, column):
+        self._check(self.lib.vss_clear_label_column(self.h, column))
+
+    def label_column_rows(self, column):
+        return int(self.lib.vss_label_column_rows(self.h, column))
+
+    def search_batch_by_label_box(self, Q, k, ef, columns, lo, hi, mode="auto", route_c=0):
+        """vss_search_batch_by_label_box: `columns` names 1 .. LABEL_COLUMNS_MAX distinct label columns for the whole call, and
+        query q admits the live rows whose cell in columns[j] lies in [lo[q, j], hi[q, j]] for EVERY j (both ends inclusive,
+        unsigned; any lo > hi empties the box, hi = NO_LABEL is no upper bound, a NO_LABEL cell or a row beyond a named column
+        is in no box).  lo and hi are nq x len(columns) matrices.  mode as for search_batch_by_label.  Returns (ids, distances,
+        counts, route)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        lo = np.ascontiguousarray(lo, dtype=np.uint32)
+        hi = np.ascontiguousarray(hi, dtype=np.uint32)
+        nq = len(Q)
+        if columns.ndim != 1:
+            raise ValueError("columns must be a list of column numbers, got shape %r" % (columns.shape,))
+        if lo.shape != (nq, len(columns)) or hi.shape != (nq, len(columns)):
+            raise ValueError("lo and hi must hold one range per query and named column: %d queries x %d columns, shapes %r and %r"
+                             % (nq, len(columns), lo.shape, hi.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        route = np.zeros(nq, dtype=np.uint8)
+        self._check(self.lib.vss_search_batch_by_label_box(self.h, _p(Q), nq, k, ef, _p(columns), len(columns), _p(lo), _p(hi),
+                                                           self.BY_LABEL_MODES.get(mode, mode), route_c, _p(keys), _p(d), _p(cnt),
+                                                           _p(route)))
+        return keys, d, cnt, route
+
+    def search_batch_by_label_box_device(self, d_Q, nq, k, ef, columns, d_lo, d_hi, d_keys, d_dist, d_counts, d_route=None,
+                                         mode="auto", route_c=0):
+        """The same over raw device pointers (`columns` stays a host sequence; d_lo and d_hi: nq x len(columns) words, row-major;
+        d_dist and d_route may be None); blocking."""
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        self._check(self.lib.vss_search_batch_by_label_box_device(self.h, d_Q, nq, k, ef, _p(columns), len(columns), d_lo, d_hi,
+                                                                  self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
+                                                                  d_counts, d_route))
 
     LABEL_SET_MAX = 32  # VSS_LABEL_SET_MAX
 

@@ -5,7 +5,8 @@
 //              the live slots its bitmap admits.  A wave owns FL_WAVE_SLOTS consecutive slots and keeps their keys in registers:
 //              keys[slot] is read once per launch, however many groups the launch lists.  Ascending, so that position order in a
 //              list is slot order and ties come back by slot.  k_label_list_*, k_range_list_* and k_set_list_* make the same lists
-//              from the index's label column, for wanted values, label ranges and label sets (label_filter.h).
+//              from the index's label column, for wanted values, label ranges and label sets, and k_box_list_* from up to four
+//              label columns, for a range on each (label_filter.h).
 //   scoring    k_exact_filtered_scores: k_exact_metric_scores with the rows gathered through a list — the same lane-to-component
 //              partition, accumulate4 / group_butterfly / finish_distance order, hence the bits k_exact_rerank computes.  One
 //              launch covers every group of a pass through the plan's tile table.
@@ -336,6 +337,79 @@ __global__ __launch_bounds__(256) void k_set_list_scatter(SetListArgs a) {
 #pragma unroll
 		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
 			const bool in = host::label_in_set(label[s], set, a.width);
+			const unsigned long long m = __ballot(in);
+			if (in)
+				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;
+			at += __popcll(m);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same lists under BOXES over M label columns (vss_search_batch_by_label_box, label_filter.h): used group u is a raw row of
+// 2M words (lo_0, hi_0, lo_1, hi_1, ...), cells [2M u, 2M (u + 1)) of `boxes`.  A wave reads keys[slot] and the cell of each named
+// column ONCE into registers, FL_KEYS_PER_LANE x M words a lane; a slot without a cell in a column holds NO_LABEL there.  Then it
+// loops over the used groups: a group's words are wave-uniform, and a group costs a slot 2M register compares
+// (host::label_in_box).  Every counts[u][block] cell is written: no zeroing.  M is a template parameter so that the cells stay
+// in registers.
+struct BoxListArgs {
+	const int64_t *keys;
+	uint32_t rows, n_blocks;
+	const uint32_t *labels[host::LABEL_COLUMNS_MAX]; // the named columns in call order, [0, M) used: one cell per row id below
+	uint64_t labelled_rows[host::LABEL_COLUMNS_MAX]; // ... labelled_rows[j]
+	const uint32_t *boxes;                           // [2M u + 2j], [2M u + 2j + 1]: lo and hi of used group u in named column j
+	uint32_t u_begin, u_end;                         // the used groups this launch lists
+	uint32_t *counts;
+	const uint32_t *list_base;
+	uint32_t *lists;
+};
+
+template <uint32_t M>
+__device__ __forceinline__ void box_list_labels(const BoxListArgs &a, uint32_t block, uint32_t (&label)[FL_KEYS_PER_LANE][M]) {
+#pragma unroll
+	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+		const uint32_t slot = block * FL_WAVE_SLOTS + s * 64 + lane_id();
+		const int64_t key = slot < a.rows ? a.keys[slot] : host::EXACT_FILTER_FREE_KEY;
+		const bool live = key != host::EXACT_FILTER_FREE_KEY && key >= 0;
+#pragma unroll
+		for (uint32_t j = 0; j < M; ++j)
+			label[s][j] = live && (uint64_t)key < a.labelled_rows[j] ? a.labels[j][key] : host::NO_LABEL;
+	}
+}
+
+template <uint32_t M>
+__global__ __launch_bounds__(256) void k_box_list_count(BoxListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks) // (wave-uniform; no barrier below)
+		return;
+	uint32_t label[FL_KEYS_PER_LANE][M];
+	box_list_labels<M>(a, block, label);
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *box = a.boxes + (size_t)u * 2 * M;
+		uint32_t n = 0;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			n += __popcll(__ballot(host::label_in_box<M>(label[s], box)));
+		if (lane_id() == 0)
+			a.counts[(size_t)u * a.n_blocks + block] = n;
+	}
+}
+
+template <uint32_t M>
+__global__ __launch_bounds__(256) void k_box_list_scatter(BoxListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks)
+		return;
+	uint32_t label[FL_KEYS_PER_LANE][M];
+	box_list_labels<M>(a, block, label);
+	const int lane = lane_id();
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *box = a.boxes + (size_t)u * 2 * M;
+		// the rows this block found in the count pass (the index is read-locked in between: the same rows now)
+		uint32_t at = a.list_base[u] + a.counts[(size_t)u * a.n_blocks + block];
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+			const bool in = host::label_in_box<M>(label[s], box);
 			const unsigned long long m = __ballot(in);
 			if (in)
 				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;

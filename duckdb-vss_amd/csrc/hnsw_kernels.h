@@ -54,6 +54,16 @@ constexpr uint64_t FILTER_BY_RANGE = 1ull << 61;
 // 2^57 bytes in all, the index included, so no row that a bitmap in memory could admit is lost.
 constexpr uint64_t FILTER_BY_SET = 1ull << 60;
 constexpr uint64_t FILTER_FLAGS = FILTER_PER_QUERY | FILTER_BY_LABEL | FILTER_BY_RANGE | FILTER_BY_SET;
+// One BOX per query, a range on each of up to four label columns (vss_search_batch_by_label_box): no further bit — filter_bits
+// carries FILTER_BY_RANGE and FILTER_BY_SET TOGETHER beside FILTER_PER_QUERY, a combination no other launch sets, so the cut of a
+// caller's n_bits stays at 2^60 - 1.  Its low bits are the smallest number of cells among the named columns, and the table is
+// k_resolve_label_boxes' (host::label_box_table_cells): cell 0 the number of named columns m, cells 1 .. m their addresses, then
+// 2m cells per query, a host::label_range_cells pair per column.  Such launches run the k_search_boxes / k_search_solo_boxes
+// kernels.  The launchers test for the box before they test either bit alone.
+constexpr uint64_t FILTER_BY_BOX = FILTER_BY_RANGE | FILTER_BY_SET;
+__host__ __device__ constexpr bool filter_by_box(uint64_t filter_bits) {
+	return (filter_bits & FILTER_BY_BOX) == FILTER_BY_BOX;
+}
 
 struct GraphView {
 	RowSpace sp;
@@ -141,6 +151,33 @@ struct GraphView {
 			hit |= host::label_hits2(label, w.x, w.y);
 		}
 		return hit & (label != host::NO_LABEL);
+	}
+
+	// The same with one box per query (the k_search_boxes / k_search_solo_boxes kernels only): the row is live, its row id has a
+	// cell in EVERY named column (filter_bits carries the shortest one's cells), and each cell lies within the query's pair for
+	// that column.  The key is read and checked once; then the m cell loads go out, one per column and independent of one another;
+	// then m host::label_range_cell_admits are ANDed (host::label_box_cells_admit is this loop), no branch per column — j < m is
+	// wave-uniform.  `query` is wave-uniform too: m, the columns' addresses and the query's 2m cells come by scalar loads through
+	// the constant address space, as admitted_set's words do, and hold no VGPR: a lane keeps its key and m cells.
+	__device__ __forceinline__ bool admitted_box(uint32_t slot, uint32_t query) const {
+		const int64_t key = keys[slot];
+		if (key == 0x7FFFFFFFFFFFFFFFll)
+			return false;
+		if (key < 0 || (uint64_t)key >= (filter_bits & ~FILTER_FLAGS))
+			return false;
+		const auto *table = (const __attribute__((address_space(4))) unsigned long long *)filter;
+		const uint32_t m = (uint32_t)table[0];
+		const auto *mine = table + host::label_box_query_cell(m, __builtin_amdgcn_readfirstlane(query));
+		uint32_t cell[host::LABEL_COLUMNS_MAX];
+#pragma unroll
+		for (uint32_t j = 0; j < host::LABEL_COLUMNS_MAX; ++j)
+			cell[j] = j < m ? reinterpret_cast<const uint32_t *>(table[1 + j])[key] : 0u;
+		bool in = true;
+#pragma unroll
+		for (uint32_t j = 0; j < host::LABEL_COLUMNS_MAX; ++j)
+			if (j < m)
+				in &= host::label_range_cell_admits(cell[j], mine[2 * j], mine[2 * j + 1]);
+		return in;
 	}
 
 	__device__ __forceinline__ uint32_t *list_ptr(uint32_t slot, int level) const {
@@ -1177,12 +1214,15 @@ struct RowTouch {
 // candidates are merged in batches (the 1024-thread search engine cannot afford the temporaries of an 8-register merge)
 // PER_QUERY (TOMB): 1 (the *_groups kernels) the predicate is the one of the query being answered, GraphView::admitted_for;
 // 2 (the *_labels kernels) it is the query's wanted label, GraphView::admitted_label; 3 (the *_ranges kernels) the query's
-// label range, GraphView::admitted_range; 4 (the *_sets kernels) the query's label set, GraphView::admitted_set
+// label range, GraphView::admitted_range; 4 (the *_sets kernels) the query's label set, GraphView::admitted_set; 5 (the *_boxes
+// kernels) the query's box over several columns, GraphView::admitted_box
 // the admission test of a PER_QUERY value: what the kernel family compiles in, and nothing of the others
 template <int PER_QUERY>
 __device__ __forceinline__ bool admitted_as(const GraphView &gv, uint32_t slot, uint32_t query) {
-	static_assert(PER_QUERY >= 0 && PER_QUERY <= 4, "whole launch, groups, labels, ranges, sets");
-	if constexpr (PER_QUERY == 4)
+	static_assert(PER_QUERY >= 0 && PER_QUERY <= 5, "whole launch, groups, labels, ranges, sets, boxes");
+	if constexpr (PER_QUERY == 5)
+		return gv.admitted_box(slot, query);
+	else if constexpr (PER_QUERY == 4)
 		return gv.admitted_set(slot, query);
 	else if constexpr (PER_QUERY == 3)
 		return gv.admitted_range(slot, query);
@@ -2086,7 +2126,8 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS = 8)
 // GROUPS: the body of k_search_groups — a launch with one predicate per query (always a TOMB launch): the level search looks
 // the query's own bitmap up (1), compares the row's label with the query's (2: k_search_labels) or tests it against the query's
-// range (3: k_search_ranges) or its set (4: k_search_sets), and the paths such a launch never takes are not compiled.
+// range (3: k_search_ranges), its set (4: k_search_sets) or its box (5: k_search_boxes), and the paths such a launch never takes
+// are not compiled.
 template <int MT, int NCH, int R, int E, int THREADS, int GROUPS>
 __device__ __forceinline__ void search_engine(SearchArgs &a) {
 	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
@@ -2349,6 +2390,11 @@ template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search_sets(SearchArgs a) {
 	search_engine<MT, NCH, R, E, THREADS, 4>(a);
 }
+// ... and with one box per query (vss_search_batch_by_label_box)
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search_boxes(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, 5>(a);
+}
 
 // =========================================================================================================
 // k_search_solo — the search engine's shape for FEW queries (the single-query probe of HNSW_INDEX_SCAN, reference
@@ -2482,6 +2528,10 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 template <int MT, int NCH, int R, int E, int T = 1>
 __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_sets(SearchArgs a) {
 	search_solo<MT, NCH, R, E, T, 4>(a);
+}
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_boxes(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, 5>(a);
 }
 
 // =========================================================================================================
@@ -2716,6 +2766,27 @@ __global__ __launch_bounds__(256) void k_resolve_label_sets(ResolveSetsArgs a) {
 	if (i < (uint64_t)a.n_queries * padded) {
 		const uint64_t q = i / padded;
 		reinterpret_cast<uint32_t *>(a.table + 2)[i] = host::label_set_table_word(a.sets + q * a.width, a.width, (uint32_t)(i - q * padded));
+	}
+}
+
+// Ahead of a launch with one box per query: the table GraphView::admitted_box reads.  `boxes` is the launch's n_queries x 2m
+// matrix (lo_0, hi_0, lo_1, hi_1, ...), in DEVICE memory; a thread writes one column's pair of one query.
+struct ResolveBoxesArgs {
+	const uint32_t *columns[host::LABEL_COLUMNS_MAX]; // the named columns, in call order; [0, m) are used
+	const uint32_t *boxes;
+	uint32_t n_queries, m;
+	unsigned long long *table; // host::label_box_table_cells(m, n_queries) cells
+};
+
+__global__ __launch_bounds__(256) void k_resolve_label_boxes(ResolveBoxesArgs a) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i == 0)
+		a.table[0] = a.m;
+	if (i < a.m)
+		a.table[1 + i] = (unsigned long long)reinterpret_cast<uintptr_t>(a.columns[i]);
+	if (i < (uint64_t)a.n_queries * a.m) {
+		const host::LabelRangeCells c = host::label_range_cells(a.boxes[2 * i], a.boxes[2 * i + 1]);
+		a.table[1 + a.m + 2 * i] = c.lo, a.table[2 + a.m + 2 * i] = c.width;
 	}
 }
 

@@ -96,9 +96,26 @@ static hipError_t search_sets_e(const SearchArgs &a, const LaunchCfg &c) {
 		VSS_LAUNCH_T((k_search_sets<MT, NCH, RS, MAX_LIST_REGS>), a, c.threads);
 	VSS_LAUNCH_T((k_search_sets<MT, NCH, RS, 0>), a, c.threads);
 }
+// launches with one box per query (filter_bits carries FILTER_BY_RANGE and FILTER_BY_SET together): the *_boxes kernels, the
+// same ladders
+template <int MT, int NCH, int R>
+static hipError_t search_boxes_e(const SearchArgs &a, const LaunchCfg &c) {
+	constexpr int RS = NCH == 6 ? VSS_SEARCH_R6 : 4;
+	if (a.list_lds)
+		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, LDS_LIST_E>), a, c.threads);
+	if (c.regs <= 2)
+		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, 2>), a, c.threads);
+	if (c.regs <= 4)
+		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, 4>), a, c.threads);
+	if (c.regs <= MAX_LIST_REGS)
+		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, MAX_LIST_REGS>), a, c.threads);
+	VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, 0>), a, c.threads);
+}
 template <int MT, int NCH, int R>
 static hipError_t search_e(const SearchArgs &a, const LaunchCfg &c) {
 	constexpr int RS = NCH == 6 ? VSS_SEARCH_R6 : 4;
+	if (filter_by_box(a.gv.filter_bits)) // (before either of its two bits alone)
+		return search_boxes_e<MT, NCH, R>(a, c);
 	if (a.gv.filter_bits & FILTER_BY_SET)
 		return search_sets_e<MT, NCH, R>(a, c);
 	if (a.gv.filter_bits & FILTER_BY_RANGE)
@@ -134,6 +151,17 @@ static hipError_t search_team_e(const SearchArgs &a, const LaunchCfg &c) {
 #define VSS_TEAM_R (VSS_TEAM_WAVES <= 4 ? 4 : 2) // (a level-0 list of 32 rows at 128 dims: 4 rows per wave; A/B builds)
 #endif
 	constexpr int T = VSS_TEAM_WAVES, RT = VSS_TEAM_R;
+	if (filter_by_box(a.gv.filter_bits)) {
+		if (c.regs <= 1)
+			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 1, T>), a, T);
+		if (c.regs <= 2)
+			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 2, T>), a, T);
+		if (c.regs <= 4)
+			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 4, T>), a, T);
+		if (c.regs <= MAX_LIST_REGS)
+			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, MAX_LIST_REGS, T>), a, T);
+		VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 0, T>), a, T);
+	}
 	if (a.gv.filter_bits & FILTER_BY_SET) {
 		if (c.regs <= 1)
 			VSS_LAUNCH_W((k_search_solo_sets<MT, NCH, RT, 1, T>), a, T);
@@ -195,6 +223,17 @@ static hipError_t search_solo_e(const SearchArgs &a, const LaunchCfg &c) {
 			return search_team_e<MT, NCH>(a, c);
 	}
 	constexpr int RS = NCH == 1 ? 16 : (NCH == 6 || NCH == 4) ? 4 : 8;
+	if (filter_by_box(a.gv.filter_bits)) {
+		if (c.regs <= 1)
+			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 1>), a);
+		if (c.regs <= 2)
+			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 2>), a);
+		if (c.regs <= 4)
+			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 4>), a);
+		if (c.regs <= MAX_LIST_REGS)
+			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, MAX_LIST_REGS>), a);
+		VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 0>), a);
+	}
 	if (a.gv.filter_bits & FILTER_BY_SET) {
 		if (c.regs <= 1)
 			VSS_LAUNCH((k_search_solo_sets<MT, NCH, RS, 1>), a);

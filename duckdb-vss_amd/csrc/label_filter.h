@@ -7,7 +7,9 @@
 // label_admits(labels, labelled_rows, r, value g), and query q takes the group label_groups() gives it.
 // vss_search_batch_by_label_range tests the same column against one inclusive range per query: its rule, the walker's and the
 // listing's forms of it and its groups are further down (host/label_range_check.cpp), and so are those of
-// vss_search_batch_by_label_set, which tests it against a short list of values per query (host/label_set_check.cpp).
+// vss_search_batch_by_label_set, which tests it against a short list of values per query (host/label_set_check.cpp).  The index
+// keeps LABEL_COLUMNS_MAX such columns — the one above is column 0 — and vss_search_batch_by_label_box tests up to four of them
+// against one range each per query: the last part (host/label_box_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -204,6 +206,78 @@ inline void label_set_groups(const uint32_t *sets, uint64_t n, uint32_t width, s
 		}
 		group_of[order[i]] = (uint32_t)(groups - 1);
 	}
+}
+
+// ---- per-query BOXES over several columns (vss_search_batch_by_label_box): the index keeps LABEL_COLUMNS_MAX columns, each what
+// the one column is above (column 0 IS that column), and a call names m distinct ones, columns[0 .. m), 1 <= m <= 4, for all its
+// queries.  Query q brings one range per named column, lo[q * m + j] .. hi[q * m + j], and admits the live rows that
+// label_range_admits admits in EVERY named column: the row id has a cell there, the cell holds a label, the label lies within the
+// ends.  One empty range empties the box.  A column that is not named constrains nothing — not even its NO_LABEL cells.
+// Inside the engine a box travels as ONE row of 2m words, (lo_0, hi_0, lo_1, hi_1, ...): label_box_rows interleaves a call's two
+// matrices.  The derived table: the distinct RAW rows, ascending lexicographically as unsigned words, nothing canonicalised, are
+// the groups, and bitmap g has bit r set iff label_box_admits(..., r, row g); its n_bits is the smallest rows(c) of the named columns.
+constexpr uint32_t LABEL_COLUMNS_MAX = 4; // VSS_LABEL_COLUMNS_MAX
+
+// THE admission rule of a box, but for the row being live.  cells[c] / rows[c]: column c of the index; box: 2m words.
+// constexpr: the kernels and the CPU check (host/label_box_check.cpp) run this very code.
+inline constexpr bool label_box_admits(const uint32_t *const *cells, const uint64_t *rows, const uint32_t *columns, uint32_t m, int64_t key,
+                                       const uint32_t *box) {
+	for (uint32_t j = 0; j != m; ++j)
+		if (!label_range_admits(cells[columns[j]], rows[columns[j]], key, box[2 * j], box[2 * j + 1]))
+			return false;
+	return true;
+}
+
+// The register form of the listing kernels: label[j] is the row's cell in named column j, or NO_LABEL for "no cell at all".  No
+// early exit: 2m compares against wave-uniform words, ANDed.
+template <uint32_t M>
+inline constexpr bool label_in_box(const uint32_t (&label)[M], const uint32_t *box) {
+	bool in = true;
+	for (uint32_t j = 0; j != M; ++j)
+		in &= label_in_range(label[j], box[2 * j], box[2 * j + 1]);
+	return in;
+}
+
+// What the walker's table holds: cell 0 the number of named columns m, cells 1 .. m their addresses in call order, and from cell
+// 1 + m on 2m cells per query — named column j's pair at 2j and 2j + 1, exactly label_range_cells(lo, hi).
+inline constexpr uint64_t label_box_table_cells(uint32_t m, uint64_t n_queries) {
+	return 1 + m + 2 * (uint64_t)m * n_queries;
+}
+inline constexpr uint64_t label_box_query_cell(uint32_t m, uint64_t query) { // the first of query's 2m cells
+	return 1 + m + 2 * (uint64_t)m * query;
+}
+// the walker's test of a row whose cells are label[0 .. m) against a query's 2m table cells: m label_range_cell_admits, ANDed
+// without a branch per column
+inline constexpr bool label_box_cells_admit(const uint32_t *label, const uint64_t *cells, uint32_t m) {
+	bool in = true;
+	for (uint32_t j = 0; j != m; ++j)
+		in &= label_range_cell_admits(label[j], cells[2 * j], cells[2 * j + 1]);
+	return in;
+}
+
+// the n x 2m matrix of a call's boxes from its two n x m matrices
+inline void label_box_rows(const uint32_t *lo, const uint32_t *hi, uint64_t n, uint32_t m, std::vector<uint32_t> &boxes) {
+	boxes.resize(2 * (size_t)m * n);
+	for (uint64_t i = 0; i != n * m; ++i)
+		boxes[2 * i] = lo[i], boxes[2 * i + 1] = hi[i];
+}
+
+// the distinct raw rows of `boxes` (n rows of 2m words), ascending, flattened into `rows`, and the group of every query:
+// label_range_groups' counterpart (with m == 1 the same groups in the same order)
+inline void label_box_groups(const uint32_t *boxes, uint64_t n, uint32_t m, std::vector<uint32_t> &rows, std::vector<uint32_t> &group_of) {
+	label_set_groups(boxes, n, 2 * m, rows, group_of);
+}
+
+// the named columns of a call: which one breaks the rules (a number >= LABEL_COLUMNS_MAX, or one named before), or m for none
+inline constexpr uint32_t label_box_bad_column(const uint32_t *columns, uint32_t m) {
+	for (uint32_t j = 0; j != m; ++j) {
+		if (columns[j] >= LABEL_COLUMNS_MAX)
+			return j;
+		for (uint32_t i = 0; i != j; ++i)
+			if (columns[i] == columns[j])
+				return j;
+	}
+	return m;
 }
 
 // vss_set_labels(first_rowid, n): what the range breaks, or NONE. Cells end at 2^32 (first_rowid + n == 2^32 is the last range

@@ -126,7 +126,7 @@ static thread_local std::string tls_error;
 // What a search launch filters its results by.  The pointers are device memory for search_begin / search_launch and host
 // memory for search_host, which stages what they name and hands search_launch the staged copy.
 struct SearchPredicate {
-	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE, BY_SET } kind = NONE;
+	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE, BY_SET, BY_BOX } kind = NONE;
 	const uint64_t *bitmap = nullptr;                        // ONE_BITMAP: the whole launch's; bit set = row id admitted
 	FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES] = {}; // PER_QUERY: the table of every batch of the launch
 	uint64_t n_bits = 0;                                     // (BY_LABEL: the cells of the index's label column)
@@ -134,6 +134,8 @@ struct SearchPredicate {
 	const uint32_t *lo = nullptr, *hi = nullptr;             // BY_RANGE: the ends of every query's label range, both inclusive
 	const uint32_t *sets = nullptr;                          // BY_SET: `width` words per query, row-major
 	uint32_t width = 0;
+	const uint32_t *boxes = nullptr;                         // BY_BOX: 2 * n_columns words per query, (lo, hi) per named column
+	uint32_t n_columns = 0, columns[LABEL_COLUMNS_MAX] = {}; // BY_BOX: the label columns the call names (n_bits: the shortest one's cells)
 
 	// a launch of one batch against the index's label column: query q admits the rows labelled want[q]
 	static SearchPredicate by_label(const uint32_t *want, uint64_t labelled_rows) {
@@ -153,6 +155,14 @@ struct SearchPredicate {
 	static SearchPredicate by_set(const uint32_t *sets, uint32_t width, uint64_t labelled_rows) {
 		SearchPredicate p;
 		p.kind = BY_SET, p.n_bits = labelled_rows, p.sets = sets, p.width = width;
+		return p;
+	}
+
+	// ... query q admits the rows whose cell in named column j lies in [boxes[2 m q + 2 j], boxes[2 m q + 2 j + 1]] for every j < m
+	static SearchPredicate by_box(const uint32_t *boxes, const uint32_t *columns, uint32_t m, uint64_t shortest_rows) {
+		SearchPredicate p;
+		p.kind = BY_BOX, p.n_bits = shortest_rows, p.boxes = boxes, p.n_columns = m;
+		std::copy(columns, columns + m, p.columns);
 		return p;
 	}
 
@@ -196,8 +206,18 @@ struct DeviceWords {
 	explicit DeviceWords(const uint32_t *device) : p(device) {
 	}
 };
+// The label columns a call by label box names, in call order, as the index holds them while the call runs (under its lock): their
+// numbers, their DEVICE cells and how many cells each has.
+struct LabelBoxColumns {
+	uint32_t m = 0, columns[LABEL_COLUMNS_MAX] = {};
+	const uint32_t *cells[LABEL_COLUMNS_MAX] = {};
+	uint64_t rows[LABEL_COLUMNS_MAX] = {};
+	uint64_t shortest_rows() const {
+		return *std::min_element(rows, rows + m);
+	}
+};
 
-// The groups the rows of a scan call are listed by, made by one of the four factories only.  Bitmaps: group g = the rows bitmap g
+// The groups the rows of a scan call are listed by, made by one of the five factories only.  Bitmaps: group g = the rows bitmap g
 // of a DEVICE table admits.  Labels: group g = the rows the index's label column gives values[g], the ascending distinct wanted
 // values (HOST memory); no bitmap exists.  Either way query q reads group group_of[q] (HOST memory; nullptr: all read group 0),
 // and the walk of the graph-routed queries reads the column's DEVICE twin: group numbers under bitmaps, wanted labels under labels.
@@ -205,6 +225,9 @@ struct DeviceWords {
 // the walk reads TWO device columns, every query's lo (d_group_of) and hi (d_hi).
 // Sets: group g = the rows whose label is one of the `width` words of rows[g], the ascending distinct raw rows of the call (HOST
 // memory, flattened); the walk reads every query's whole row of the DEVICE matrix d_sets, and d_group_of stays nullptr.
+// Boxes: group g = the rows whose cells in the call's m named label columns lie within the m pairs of rows[g], the ascending distinct
+// raw rows of 2m words (HOST memory, flattened; width = 2m); the walk reads every query's row of the DEVICE matrix d_sets likewise.
+// n_bits is the shortest named column's cells.
 struct GroupedRows {
 	const uint64_t *d_table = nullptr;  // bitmaps: n_groups bitmaps of n_bits bits
 	uint64_t n_groups = 0, n_bits = 0;  // (labels: the distinct wanted values; the cells of the label column)
@@ -216,6 +239,7 @@ struct GroupedRows {
 	const uint32_t *rows = nullptr;     // sets: HOST, n_groups x width
 	const uint32_t *d_sets = nullptr;   // sets: the call's n_queries x width matrix
 	uint32_t width = 0;                 // sets: words per row
+	LabelBoxColumns box;                // boxes: the named columns
 
 	static GroupedRows bitmaps(const uint64_t *d_table, uint64_t n_groups, uint64_t n_bits, HostWords group_of, DeviceWords d_group_of) {
 		GroupedRows g;
@@ -245,10 +269,18 @@ struct GroupedRows {
 		return g;
 	}
 
-	// words that name one used group to the list kernels: its table group, its wanted value, the two ends of its range, or the
-	// words of its set.  The walk of the graph-routed queries needs as many words per query gathered into the compact batch.
+	static GroupedRows boxes(const std::vector<uint32_t> &rows, const LabelBoxColumns &box, HostWords group_of, DeviceWords d_boxes) {
+		GroupedRows g;
+		g.by_box = true, g.rows = rows.data(), g.width = 2 * box.m, g.box = box;
+		g.n_groups = rows.size() / g.width, g.n_bits = box.shortest_rows(), g.group_of = group_of.p, g.d_sets = d_boxes.p;
+		return g;
+	}
+
+	// words that name one used group to the list kernels: its table group, its wanted value, the two ends of its range, the
+	// words of its set, or the pairs of its box.  The walk of the graph-routed queries needs as many words per query gathered into
+	// the compact batch.
 	uint64_t group_cells() const {
-		return by_set ? width : by_range ? 2 : 1;
+		return by_set || by_box ? width : by_range ? 2 : 1;
 	}
 	// Those words beyond the one column k_route_gather takes along (d_group_of; under sets it takes none): `per` words a query,
 	// row-major from `words`, to word `at` of the compact batch's ng * group_cells() words — or words == nullptr, nothing more.
@@ -258,7 +290,7 @@ struct GroupedRows {
 		uint64_t at;
 	};
 	WalkWords more_walk_words(uint64_t ng) const {
-		if (by_set)
+		if (by_set || by_box)
 			return {d_sets, width, 0};
 		if (by_range)
 			return {d_hi, 1, ng};
@@ -293,10 +325,20 @@ struct GroupedRows {
 		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
 		return a;
 	}
+	// ... and in the box form: the cells hold the groups' ROWS, 2m words each
+	BoxListArgs box_list_args(const FilterListArgs &l) const {
+		BoxListArgs a = {};
+		a.keys = l.keys, a.rows = l.rows, a.n_blocks = l.n_blocks;
+		for (uint32_t j = 0; j != box.m; ++j)
+			a.labels[j] = box.cells[j], a.labelled_rows[j] = box.rows[j];
+		a.boxes = l.groups, a.u_begin = l.u_begin, a.u_end = l.u_end;
+		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
+		return a;
+	}
 	// the cells of a plan's used groups, group_cells() words each: plan.groups, or their values / pairs / rows in `scratch` (which
 	// outlives the upload like plan.groups)
 	const uint32_t *used_group_cells(const ExactFilterPlan &plan, std::vector<uint32_t> &scratch) const {
-		if (by_set) {
+		if (by_set || by_box) {
 			scratch.resize((size_t)width * plan.groups.size());
 			for (size_t u = 0; u != plan.groups.size(); ++u)
 				std::copy(rows + (size_t)plan.groups[u] * width, rows + ((size_t)plan.groups[u] + 1) * width, scratch.begin() + u * width);
@@ -325,6 +367,13 @@ struct GroupedRows {
 			hipLaunchKernelGGL(k_range_list_count, grid, dim3(256), 0, stream, range_list_args(l));
 		else if (by_set) // (the same)
 			hipLaunchKernelGGL(k_set_list_count, grid, dim3(256), 0, stream, set_list_args(l));
+		else if (by_box) // (the same; one kernel per number of named columns)
+			switch (box.m) {
+			case 1: hipLaunchKernelGGL(k_box_list_count<1>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			case 2: hipLaunchKernelGGL(k_box_list_count<2>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			case 3: hipLaunchKernelGGL(k_box_list_count<3>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			default: hipLaunchKernelGGL(k_box_list_count<4>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			}
 		else
 			hipLaunchKernelGGL(k_filter_list_count, grid, dim3(256), 0, stream, l);
 	}
@@ -337,6 +386,13 @@ struct GroupedRows {
 			hipLaunchKernelGGL(k_range_list_scatter, grid, dim3(256), 0, stream, range_list_args(l));
 		else if (by_set)
 			hipLaunchKernelGGL(k_set_list_scatter, grid, dim3(256), 0, stream, set_list_args(l));
+		else if (by_box)
+			switch (box.m) {
+			case 1: hipLaunchKernelGGL(k_box_list_scatter<1>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			case 2: hipLaunchKernelGGL(k_box_list_scatter<2>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			case 3: hipLaunchKernelGGL(k_box_list_scatter<3>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			default: hipLaunchKernelGGL(k_box_list_scatter<4>, grid, dim3(256), 0, stream, box_list_args(l)); break;
+			}
 		else
 			hipLaunchKernelGGL(k_filter_list_scatter, grid, dim3(256), 0, stream, l);
 	}
@@ -344,6 +400,8 @@ struct GroupedRows {
 	// (k_route_gather's column first, more_walk_words() where it says)
 	SearchPredicate walk_predicate(const uint32_t *d_compact, uint64_t ng) const {
 		const uint32_t *d_compact_groups = d_compact;
+		if (by_box)
+			return SearchPredicate::by_box(d_compact, box.columns, box.m, n_bits);
 		if (by_set)
 			return SearchPredicate::by_set(d_compact, width, n_bits);
 		if (by_range)
@@ -355,7 +413,7 @@ struct GroupedRows {
 	}
 
 private:
-	bool by_label = false, by_range = false, by_set = false;
+	bool by_label = false, by_range = false, by_set = false, by_box = false;
 	GroupedRows() = default;
 };
 
@@ -441,7 +499,18 @@ struct vss_index {
 	// lock only (vss_set_labels); d_labels.n may exceed labelled_rows (it grows by halves).
 	DevBuf<uint32_t> d_labels;
 	uint64_t labelled_rows = 0;
-	std::atomic<uint64_t> label_bytes {0}; // vss_memory_usage (read without a lock)
+	// That is column 0 of LABEL_COLUMNS_MAX; columns 1 .. 3 are the same thing each (vss_set_label_column), read by the search by
+	// label box only.  label_cells(c) / label_rows(c) name column c's pair.
+	DevBuf<uint32_t> d_more_labels[LABEL_COLUMNS_MAX - 1];
+	uint64_t more_labelled_rows[LABEL_COLUMNS_MAX - 1] = {};
+	uint64_t label_column_bytes[LABEL_COLUMNS_MAX] = {};
+	std::atomic<uint64_t> label_bytes {0}; // every column's; vss_memory_usage (read without a lock)
+	DevBuf<uint32_t> &label_cells(uint32_t column) {
+		return column ? d_more_labels[column - 1] : d_labels;
+	}
+	uint64_t &label_rows(uint32_t column) {
+		return column ? more_labelled_rows[column - 1] : labelled_rows;
+	}
 
 	// build scratch
 	DevBuf<uint32_t> d_req_list, d_req_src, d_req_rank, d_sorted_src, d_touched, d_list_count, d_list_offset,
@@ -764,16 +833,41 @@ struct vss_index {
 	}
 
 	// ------------------------------------------------------------------ the label column (label_filter.h)
-	void clear_labels() {
-		d_labels.free();
-		labelled_rows = 0;
-		label_bytes.store(0, std::memory_order_relaxed);
+	// the columns a call by label box names, as they are now: false where there are none or too many, one is out of range or named
+	// twice, or one has never been set
+	bool named_label_columns(const uint32_t *columns, uint64_t m, LabelBoxColumns &box) {
+		if (m < 1 || m > LABEL_COLUMNS_MAX || !columns || label_box_bad_column(columns, (uint32_t)m) != m)
+			return false;
+		box.m = (uint32_t)m;
+		for (uint32_t j = 0; j != box.m; ++j) {
+			box.columns[j] = columns[j], box.cells[j] = label_cells(columns[j]).p, box.rows[j] = label_rows(columns[j]);
+			if (!box.cells[j])
+				return false;
+		}
+		return true;
 	}
 
-	// cells [first_rowid, first_rowid + n) = labels[0 .. n), from HOST or DEVICE memory; cells the write skips over become NO_LABEL.
+	void clear_label_column(uint32_t column) {
+		label_cells(column).free();
+		label_rows(column) = 0;
+		label_bytes.fetch_sub(label_column_bytes[column], std::memory_order_relaxed);
+		label_column_bytes[column] = 0;
+	}
+	void clear_labels() { // every column
+		for (uint32_t c = 0; c != LABEL_COLUMNS_MAX; ++c)
+			clear_label_column(c);
+	}
+
+	// column `column`'s cells [first_rowid, first_rowid + n) = labels[0 .. n), from HOST or DEVICE memory; cells the write skips
+	// over become NO_LABEL.
 	// Under the exclusive lock.  The column grows into a NEW buffer, and the old one goes only once the new one holds its cells: a
 	// device without room fails this call and leaves the column as it was (nothing is visible before labelled_rows moves).
-	int set_labels(const char *what, uint64_t first_rowid, const uint32_t *labels, uint64_t n, bool on_device) {
+	int set_labels(const char *what, uint32_t column, uint64_t first_rowid, const uint32_t *labels, uint64_t n, bool on_device) {
+		if (column >= LABEL_COLUMNS_MAX)
+			return fail("%s: column %u is not below VSS_LABEL_COLUMNS_MAX (%u)", what, (unsigned)column, (unsigned)LABEL_COLUMNS_MAX);
+		// (these two shadow column 0's members on purpose: what follows is the one column's code, for whichever column)
+		DevBuf<uint32_t> &d_labels = label_cells(column);
+		uint64_t &labelled_rows = label_rows(column);
 		const LabelRangeFault fault = check_label_range(labels, first_rowid, n);
 		if (fault == LabelRangeFault::NO_LABELS)
 			return fail("%s: null label pointer", what);
@@ -808,7 +902,8 @@ struct vss_index {
 			}
 			d_labels.free();
 			d_labels.p = np, d_labels.n = got;
-			label_bytes.store(got * 4, std::memory_order_relaxed);
+			label_bytes.fetch_add(got * 4 - label_column_bytes[column], std::memory_order_relaxed);
+			label_column_bytes[column] = got * 4;
 		}
 		if (w.gap_end > w.gap_begin)
 			HIP_TRY(hipMemsetAsync(d_labels.p + w.gap_begin, 0xFF, (w.gap_end - w.gap_begin) * 4, stream)); // NO_LABEL
@@ -1611,6 +1706,24 @@ struct vss_index {
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits = std::min<uint64_t>(labelled_rows, FILTER_BY_SET - 1) | FILTER_PER_QUERY | FILTER_BY_SET;
+		} else if (p.kind == SearchPredicate::BY_BOX) {
+			// ... and by the *_boxes kernels (GraphView::admitted_box): cell 0 the number of named columns, then their addresses,
+			// then 2m cells per query.  No flag bit of its own: FILTER_BY_RANGE and FILTER_BY_SET together.
+			LabelBoxColumns box;
+			if (n_batches != 1 || !named_label_columns(p.columns, p.n_columns, box))
+				return fail("search by label box: one batch per launch, over 1 to %u distinct label columns that have been set",
+				            (unsigned)LABEL_COLUMNS_MAX);
+			if (!c.d_group_bitmap.try_grow(label_box_table_cells(box.m, cap_q)))
+				return fail("search by label box: no device memory for the boxes of %llu queries", (unsigned long long)cap_q);
+			count_group_tables(c);
+			ResolveBoxesArgs res = {};
+			std::copy(box.cells, box.cells + box.m, res.columns);
+			res.boxes = p.boxes, res.n_queries = (uint32_t)nq, res.m = box.m;
+			res.table = reinterpret_cast<unsigned long long *>(c.d_group_bitmap.p);
+			hipLaunchKernelGGL(k_resolve_label_boxes, dim3((uint32_t)(nq * box.m / 256 + 1)), dim3(256), 0, c.stream, res);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits = std::min<uint64_t>(box.shortest_rows(), FILTER_BY_SET - 1) | FILTER_PER_QUERY | FILTER_BY_BOX;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
@@ -1861,6 +1974,14 @@ struct vss_index {
 		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, sets, nq * width * 4, hipMemcpyHostToDevice, c.stream));
 		return VSS_OK;
 	}
+	// the boxes of a call by label box (HOST memory), in the same buffer: the nq x 2m matrix as it is
+	int stage_label_boxes(SearchCtx &c, const uint32_t *boxes, uint32_t m, uint64_t nq) {
+		if (!c.d_group_of.try_grow(nq * 2 * m))
+			return fail("search by label box: no device memory for the boxes of %llu queries", (unsigned long long)nq);
+		count_group_tables(c);
+		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, boxes, nq * 2 * m * 4, hipMemcpyHostToDevice, c.stream));
+		return VSS_OK;
+	}
 	// queries in, result buffers ensured ...
 	void stage_queries(SearchCtx &c, const float *queries, uint64_t nq, uint64_t k) {
 		c.d_q.ensure(nq * dim, 0, c.stream), c.d_out_count.ensure(nq, 0, c.stream);
@@ -1965,6 +2086,10 @@ struct vss_index {
 				    if (const int rc = stage_label_sets(c, filter.sets, filter.width, nq))
 					    return rc;
 				    staged = SearchPredicate::by_set(c.d_group_of.p, filter.width, filter.n_bits);
+			    } else if (filter.kind == SearchPredicate::BY_BOX) {
+				    if (const int rc = stage_label_boxes(c, filter.boxes, filter.n_columns, nq))
+					    return rc;
+				    staged = SearchPredicate::by_box(c.d_group_of.p, filter.columns, filter.n_columns, filter.n_bits);
 			    }
 			    return VSS_OK;
 		    },
@@ -2597,6 +2722,30 @@ struct vss_index {
 		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_sets(c, sets, width, hc.nq); },
 		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
 			    return by_set_launch(b, HostWords(sets), width, DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
+		    });
+	}
+
+	// ------------------------------------------------------------------ search by label box (label_filter.h)
+	// The same over the table label_box_groups() makes of `boxes` (nq x 2m, HOST): group g = the rows inside rows[g] in every named
+	// column.  d_boxes: the matrix for the walk of the graph-routed queries; nullptr asks for the exact scan of every query.
+	int by_box_launch(const DeviceBatch &b, HostWords boxes, const LabelBoxColumns &box, DeviceWords d_boxes, uint64_t route_c,
+	                  const DeviceAnswers &out, std::vector<uint8_t> &route) {
+		std::vector<uint32_t> rows, group_of;
+		label_box_groups(boxes.p, b.nq, box.m, rows, group_of);
+		const GroupedRows g = GroupedRows::boxes(rows, box, HostWords(group_of.data()), d_boxes);
+		if (!d_boxes.p) {
+			route.assign(b.nq, FILTER_ROUTE_EXACT);
+			return exact_filtered_launch(b, g, out);
+		}
+		return filtered_auto(b, g, route_c, out, route);
+	}
+
+	// the host-pointer form of those two: the exact scan stages no boxes
+	int by_box_host(const HostCall &hc, bool exact, const uint32_t *boxes, const LabelBoxColumns &box, uint64_t route_c) {
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_boxes(c, boxes, box.m, hc.nq); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+			    return by_box_launch(b, HostWords(boxes), box, DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
 		    });
 	}
 
@@ -3859,11 +4008,11 @@ int vss_last_filter_route(vss_index *h, uint64_t *out8) {
 
 // ---- the label column and the search by label (label_filter.h; include/vssgpu.h has the contract)
 int vss_set_labels(vss_index *h, uint64_t first_rowid, const uint32_t *labels, uint64_t n) {
-	VSS_GUARD(h, { return h->set_labels("vss_set_labels", first_rowid, labels, n, false); })
+	VSS_GUARD(h, { return h->set_labels("vss_set_labels", 0, first_rowid, labels, n, false); })
 }
 
 int vss_set_labels_device(vss_index *h, uint64_t first_rowid, const uint32_t *d_labels, uint64_t n) {
-	VSS_GUARD(h, { return h->set_labels("vss_set_labels_device", first_rowid, d_labels, n, true); })
+	VSS_GUARD(h, { return h->set_labels("vss_set_labels_device", 0, first_rowid, d_labels, n, true); })
 }
 
 int vss_clear_labels(vss_index *h) {
@@ -3880,6 +4029,35 @@ uint64_t vss_labelled_rows(const vss_index *h) {
 		return 0;
 	std::shared_lock<std::shared_mutex> lk(const_cast<vss_index *>(h)->rw);
 	return h->labelled_rows;
+}
+
+// ---- label columns 0 .. VSS_LABEL_COLUMNS_MAX - 1 (column 0 is the one above)
+static_assert(LABEL_COLUMNS_MAX == VSS_LABEL_COLUMNS_MAX, "one cap, in the rule's header and in the C header");
+int vss_set_label_column(vss_index *h, uint32_t column, uint64_t first_rowid, const uint32_t *labels, uint64_t n) {
+	VSS_GUARD(h, { return h->set_labels("vss_set_label_column", column, first_rowid, labels, n, false); })
+}
+
+int vss_set_label_column_device(vss_index *h, uint32_t column, uint64_t first_rowid, const uint32_t *d_labels, uint64_t n) {
+	VSS_GUARD(h, { return h->set_labels("vss_set_label_column_device", column, first_rowid, d_labels, n, true); })
+}
+
+int vss_clear_label_column(vss_index *h, uint32_t column) {
+	VSS_GUARD(h, {
+		if (column >= LABEL_COLUMNS_MAX)
+			return h->fail("vss_clear_label_column: column %u is not below VSS_LABEL_COLUMNS_MAX (%u)", (unsigned)column,
+			               (unsigned)LABEL_COLUMNS_MAX);
+		if (h->refuse_while_probing("vss_clear_label_column") != VSS_OK)
+			return VSS_ERROR;
+		h->clear_label_column(column);
+		return VSS_OK;
+	})
+}
+
+uint64_t vss_label_column_rows(const vss_index *h, uint32_t column) {
+	if (!h || column >= LABEL_COLUMNS_MAX)
+		return 0;
+	std::shared_lock<std::shared_mutex> lk(const_cast<vss_index *>(h)->rw);
+	return const_cast<vss_index *>(h)->label_rows(column);
 }
 
 // what every form of the call refuses before it stages or launches anything
@@ -4056,6 +4234,93 @@ int vss_search_batch_by_label_set_device(vss_index *h, const float *Q, uint64_t 
 			                                    DeviceWords(exact ? nullptr : sets), route_c, {out, out_d, out_counts}, route))
 				return rc;
 		}
+		h->route_to_device(route, out_route);
+		return VSS_OK;
+	})
+}
+
+// ---- the search by label box: the mode is refused first, then the number of columns, a null `columns`, a column out of range or
+// named twice, null lo / hi — all before anything is launched or written — and a named column that was never set after them
+static int check_by_label_box(vss_index *h, const char *what, const float *Q, uint64_t nq, const uint32_t *columns, uint64_t m,
+                              const uint32_t *lo, const uint32_t *hi, int mode, const int64_t *out, const uint32_t *out_counts,
+                              LabelBoxColumns &box) {
+	if (mode != VSS_BY_LABEL_GRAPH && mode != VSS_BY_LABEL_EXACT && mode != VSS_BY_LABEL_AUTO)
+		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
+	if (m < 1 || m > VSS_LABEL_COLUMNS_MAX)
+		return h->fail("%s: n_columns %llu is not within 1 .. VSS_LABEL_COLUMNS_MAX (%d)", what, (unsigned long long)m,
+		               VSS_LABEL_COLUMNS_MAX);
+	if (!columns)
+		return h->fail("%s: null columns pointer", what);
+	if (const uint32_t bad = label_box_bad_column(columns, (uint32_t)m); bad != m)
+		return columns[bad] >= LABEL_COLUMNS_MAX
+		           ? h->fail("%s: column %u is not below VSS_LABEL_COLUMNS_MAX (%d)", what, (unsigned)columns[bad], VSS_LABEL_COLUMNS_MAX)
+		           : h->fail("%s: column %u is named twice", what, (unsigned)columns[bad]);
+	if (nq && (!lo || !hi))
+		return h->fail("%s: null lo / hi pointer for %llu queries", what, (unsigned long long)nq);
+	for (uint32_t j = 0; j != m; ++j)
+		if (!h->label_cells(columns[j]).p)
+			return h->fail("%s: the index has no label column %u (call vss_set_label_column first; vss_load, vss_clear_labels and "
+			               "vss_clear_label_column drop it)", what, (unsigned)columns[j]);
+	if (nq && (!Q || !out || !out_counts))
+		return h->fail("%s: null query / row-id / count pointer", what);
+	if (nq > 0xFFFFFFFFull)
+		return h->fail("%s: at most 2^32 - 1 queries per call", what);
+	if (!h->named_label_columns(columns, m, box))
+		return h->fail("%s: the named label columns cannot be read", what);
+	return VSS_OK;
+}
+
+int vss_search_batch_by_label_box(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *columns,
+                                  uint64_t n_columns, const uint32_t *lo, const uint32_t *hi, int mode, uint64_t route_c, int64_t *out,
+                                  float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_by_label_box(h, "vss_search_batch_by_label_box", Q, nq, columns, n_columns, lo, hi, mode, out, out_counts, box) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		std::vector<uint32_t> boxes;
+		label_box_rows(lo, hi, nq, box.m, boxes);
+		if (mode != VSS_BY_LABEL_GRAPH)
+			return h->by_box_host({Q, nq, k, ef, out, out_d, out_counts, out_route}, mode == VSS_BY_LABEL_EXACT, boxes.data(), box, route_c);
+		if (out_route)
+			std::memset(out_route, FILTER_ROUTE_GRAPH, nq);
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false,
+		                      SearchPredicate::by_box(boxes.data(), box.columns, box.m, box.shortest_rows()));
+	})
+}
+
+int vss_search_batch_by_label_box_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *columns,
+                                         uint64_t n_columns, const uint32_t *lo, const uint32_t *hi, int mode, uint64_t route_c,
+                                         int64_t *out, float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_by_label_box(h, "vss_search_batch_by_label_box_device", Q, nq, columns, n_columns, lo, hi, mode, out, out_counts, box) !=
+		    VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		// the plans read the boxes on the host, and the walk reads them as ONE matrix of (lo, hi) pairs: both matrices come back
+		// (8 * n_columns bytes per query) and go to context 0 interleaved
+		const std::vector<uint32_t> lo_h = h->words_to_host(lo, nq * box.m), hi_h = h->words_to_host(hi, nq * box.m);
+		std::vector<uint32_t> boxes;
+		label_box_rows(lo_h.data(), hi_h.data(), nq, box.m, boxes);
+		auto &c = h->context(0);
+		const bool exact = mode == VSS_BY_LABEL_EXACT;
+		if (!exact) {
+			if (const int rc = h->stage_label_boxes(c, boxes.data(), box.m, nq))
+				return rc;
+			HIP_TRY(hipStreamSynchronize(c.stream)); // (`boxes` is pageable memory; the count kernels run on the index stream)
+		}
+		std::vector<uint8_t> route(nq, FILTER_ROUTE_GRAPH);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+			r.predicate = SearchPredicate::by_box(c.d_group_of.p, box.columns, box.m, box.shortest_rows());
+			if (const int rc = h->search_launch(r))
+				return rc;
+		} else if (const int rc = h->by_box_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(boxes.data()), box,
+		                                           DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, {out, out_d, out_counts}, route))
+			return rc;
 		h->route_to_device(route, out_route);
 		return VSS_OK;
 	})

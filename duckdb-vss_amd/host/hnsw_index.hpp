@@ -293,6 +293,33 @@ public:
 			return vss_search_batch_by_label_set(index, queries, n_queries, limit, ef, sets, width, mode, route_c, ids, nullptr, counts, routes);
 		});
 	}
+	// The correlated chunk whose predicate is a CONJUNCTION of intervals over several label columns (`items.tenant = q.tenant AND
+	// items.ts >= q.since [AND items.price BETWEEN ...]`): `columns` names the 1 .. VSS_LABEL_COLUMNS_MAX distinct columns of the
+	// predicate, the same for every outer row, and outer row q brings one inclusive range per named column, lo[q * n_columns + j] ..
+	// hi[q * n_columns + j] (`=` is lo == hi; a column the predicate does not constrain is not named).
+	// vss_search_batch_by_label_box does the rest, modes as above.  Any lo > hi admits nothing, and a row that is VSS_NO_LABEL or
+	// has no cell in a named column is in no box.  IN-lists or OR inside a box keep the bitmap methods.
+	idx_t ExecuteMultiScanBatchByLabelBox(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit, const uint32_t *columns,
+	                                      idx_t n_columns, const uint32_t *lo, const uint32_t *hi, std::vector<uint32_t> *counts_out,
+	                                      std::vector<uint8_t> *routes_out = nullptr, int mode = VSS_BY_LABEL_AUTO, uint64_t route_c = 0) {
+		return ScanChunk(state_p, n_queries, limit, counts_out, routes_out, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *routes) {
+			return vss_search_batch_by_label_box(index, queries, n_queries, limit, ef, columns, n_columns, lo, hi, mode, route_c, ids, nullptr,
+			                                     counts, routes);
+		});
+	}
+	// Label columns 0 .. VSS_LABEL_COLUMNS_MAX - 1 (vss_set_label_column; column 0 is the column of SetLabels).  ClearLabels clears
+	// every column.  Not persisted: after LoadFromBlocks the owner writes them again from the table.
+	void SetLabelColumn(uint32_t column, idx_t first_rowid, const uint32_t *labels, idx_t n) {
+		std::unique_lock<std::shared_mutex> lock(rwlock);
+		Check(vss_set_label_column(index, column, first_rowid, labels, n), "label");
+	}
+	void ClearLabelColumn(uint32_t column) {
+		std::unique_lock<std::shared_mutex> lock(rwlock);
+		Check(vss_clear_label_column(index, column), "label");
+	}
+	idx_t LabelColumnRows(uint32_t column) const {
+		return vss_label_column_rows(index, column);
+	}
 	// The label column: cells first_rowid .. first_rowid + n - 1 (vss_set_labels).  Not persisted: after LoadFromBlocks the owner
 	// writes it again from the table.
 	void SetLabels(idx_t first_rowid, const uint32_t *labels, idx_t n) {

@@ -498,6 +498,48 @@ public:
 			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
 		}
 	}
+	// Label columns 0 .. VSS_LABEL_COLUMNS_MAX - 1 (column 0 is the column of SetLabels): every shard gets the whole column, as
+	// SetLabels gives it.  ClearLabels clears every column.  Not persisted: set again after Load.
+	void SetLabelColumn(uint32_t column, idx_t first_rowid, const uint32_t *labels, idx_t n) {
+		for (auto &s : shards)
+			s.index->SetLabelColumn(column, first_rowid, labels, n);
+	}
+	void ClearLabelColumn(uint32_t column) {
+		for (auto &s : shards)
+			s.index->ClearLabelColumn(column);
+	}
+	// Query q admits the live rows whose cell in columns[j] lies in [lo[q * n_columns + j], hi[q * n_columns + j]] for EVERY j <
+	// n_columns (any lo > hi: none; hi = 0xFFFFFFFF: no upper bound; VSS_NO_LABEL or no cell in a named column: in no box):
+	// vss_search_batch_by_label_box_device per shard, every shard holding the whole columns.  Modes, shard_routes, exchange and
+	// merge are SearchBatchByLabelRange's; both matrices travel as UploadTables' group numbers, lo's n * n_columns words first.
+	void SearchBatchByLabelBox(const float *queries, idx_t n, idx_t k, idx_t ef, const uint32_t *columns, idx_t n_columns, const uint32_t *lo,
+	                           const uint32_t *hi, int mode, uint64_t route_c, row_t *out_rowids, float *out_distances, uint32_t *out_counts,
+	                           std::vector<uint8_t> *shard_routes = nullptr) {
+		if (shard_routes)
+			shard_routes->assign(shards.size() * n, 0);
+		if (!n || !k)
+			return;
+		if (n_columns < 1 || n_columns > VSS_LABEL_COLUMNS_MAX || !columns)
+			throw InternalException("Failed to search the HNSW index: search by label box names 1 to 4 label columns");
+		if (!lo || !hi)
+			throw InternalException("Failed to search the HNSW index: search by label box needs both ends of every query's ranges");
+		Ensure(n, k);
+		std::vector<uint32_t> ends(lo, lo + n * n_columns);
+		ends.insert(ends.end(), hi, hi + n * n_columns);
+		UploadTables(nullptr, 0, ends.data(), 2 * n * n_columns);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    const uint32_t *d_ends = bitmaps[s.bitmap].group_of;
+			    Vss(s, vss_search_batch_by_label_box_device(s.index->Handle(), s.d_q, n, k, ef, columns, n_columns, d_ends, d_ends + n * n_columns,
+			                                                mode, route_c, keys, dist, s.d_cnt, s.d_route));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		for (size_t g = 0; shard_routes && g != shards.size(); ++g) {
+			Hip(hipSetDevice(shards[g].device), "hipSetDevice");
+			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
+		}
+	}
 	// Query q admits the live rows whose label is one of sets[q * width .. (q + 1) * width) (VSS_NO_LABEL pads a shorter list and
 	// equals nothing; a VSS_NO_LABEL cell is in no set): vss_search_batch_by_label_set_device per shard, every shard holding the
 	// whole column.  Modes, shard_routes, exchange and merge are SearchBatchByLabel's; the matrix travels as UploadTables' group

@@ -331,6 +331,49 @@ int vss_search_batch_by_label_set_device(vss_index *index, const float *d_querie
                                          const uint32_t *d_sets, uint64_t width, int mode, uint64_t route_c,
                                          int64_t *d_out_rowids, float *d_out_distances, uint32_t *d_out_counts,
                                          uint8_t *d_out_route);
+/* ---- Conjunctions of ranges over several label columns (csrc/label_filter.h) -------------------------------------------------
+ * For `items.tenant = q.tenant AND items.ts >= q.since [AND items.price BETWEEN ...]`: the index keeps VSS_LABEL_COLUMNS_MAX
+ * label columns, 0 .. 3.  Each is what the one column above is — one 32-bit cell per ROW ID, its own number of cells,
+ * VSS_NO_LABEL where nothing was set, growth and gap fill as vss_set_labels does them — and column 0 IS that column:
+ * vss_set_labels, vss_set_labels_device and vss_labelled_rows mean column 0, and the three calls above read column 0.
+ * vss_set_label_column / _device write cells of one column, vss_clear_label_column frees one, vss_label_column_rows is its
+ * number of cells (0 = never set, or column out of range).  A column number >= VSS_LABEL_COLUMNS_MAX is refused.  vss_clear_labels
+ * and vss_load clear EVERY column; none is persisted; vss_memory_usage counts them all.  Writer lock; refused while a _begin
+ * context is in flight.
+ * The call: `columns` (always HOST memory) holds n_columns distinct column numbers, 1 <= n_columns <= 4, for the whole call — a
+ * join's predicate has one shape for all its outer rows — and lo, hi are row-major n_queries x n_columns matrices.  Query q
+ * admits a live row of id r iff for every j < n_columns, with c = columns[j]: r < vss_label_column_rows(c), cell_c[r] !=
+ * VSS_NO_LABEL and lo[q, j] <= cell_c[r] <= hi[q, j], compared unsigned.  Any lo > hi makes the box empty (count 0, ids -1,
+ * distances +inf); hi = 0xFFFFFFFF is "no upper bound"; `=` is lo == hi.  A column the predicate does not constrain is simply not
+ * named: naming it with [0, 0xFFFFFFFF] still rejects its NULLs (VSS_NO_LABEL cells and rows beyond its cells), as SQL's
+ * `x >= min` does.  mode, route_c, out_route, k and ef as for vss_search_batch_by_label_range.
+ * Contract: form the n_queries x 2 n_columns matrix whose row q is (lo[q,0], hi[q,0], lo[q,1], hi[q,1], ...).  With b_0 < b_1 <
+ * ... its distinct RAW rows, ascending lexicographically as unsigned words and not canonicalised (two different empty boxes are
+ * two groups), bitmap g = {r : the rule admits r for b_g}, n_bits = the smallest vss_label_column_rows(c) over the named columns,
+ * and group_of[q] = the index of query q's row, the call returns cell for cell what the bitmap call of the same mode returns for
+ * that table — row ids, f32 distance bits, counts, routes — and leaves the same vss_last_exact_filtered [0..2],
+ * vss_last_filter_route, vss_last_search_stats / _shape / _prescore / _prescore_descent values behind.  With n_columns == 1 and
+ * columns = {0} that is also, counters included, the answer of vss_search_batch_by_label_range.
+ * Errors, in this order, each before anything is launched or written: a mode other than the three; n_columns 0 or above 4;
+ * columns NULL; a column number >= 4 or one named twice (the message names it); lo or hi NULL with n_queries > 0; a named column
+ * that was never set ("no label column", with its number); those of the call of the mode.  n_queries == 0 or k == 0 returns
+ * VSS_OK and writes nothing.
+ * The _device form takes device pointers for everything but `columns` (d_out_distances and d_out_route may be NULL), copies d_lo
+ * and d_hi back (8 * n_columns bytes per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin
+ * forms; IN-lists or OR inside a box, 64-bit columns and more than four columns keep the bitmap calls. */
+#define VSS_LABEL_COLUMNS_MAX 4
+int vss_set_label_column(vss_index *index, uint32_t column, uint64_t first_rowid, const uint32_t *labels, uint64_t n);
+int vss_set_label_column_device(vss_index *index, uint32_t column, uint64_t first_rowid, const uint32_t *d_labels, uint64_t n);
+int vss_clear_label_column(vss_index *index, uint32_t column);
+uint64_t vss_label_column_rows(const vss_index *index, uint32_t column);
+int vss_search_batch_by_label_box(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                  const uint32_t *columns, uint64_t n_columns, const uint32_t *lo, const uint32_t *hi, int mode,
+                                  uint64_t route_c, int64_t *out_rowids, float *out_distances, uint32_t *out_counts,
+                                  uint8_t *out_route);
+int vss_search_batch_by_label_box_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                         const uint32_t *columns, uint64_t n_columns, const uint32_t *d_lo, const uint32_t *d_hi,
+                                         int mode, uint64_t route_c, int64_t *d_out_rowids, float *d_out_distances,
+                                         uint32_t *d_out_counts, uint8_t *d_out_route);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
