@@ -26,11 +26,12 @@ FREE_KEY = np.iinfo(np.int64).max
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-int-to-pointer-cast"]
 
 
-TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip"]
+TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip",
+                     "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip"]
 
 
 def build_library(force=False, extra_flags=(), out=None):
-    """hipcc cross-compiles the engine for gfx950 (works without a GPU): four translation units in parallel, then a
+    """hipcc cross-compiles the engine for gfx950 (works without a GPU): eight translation units in parallel, then a
     shared link.  Objects live in build/ (git-ignored)."""
     out = out or os.path.join(HERE, "libvssgpu.so")
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
@@ -114,6 +115,12 @@ SIGNATURES = {
     "vss_search_batch_by_label_box": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_by_label_box_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp,
                                                     _vp]),
+    "vss_set_label_column64": (_int, [_vp, _u32, _u64, _vp, _u64]),
+    "vss_set_label_column64_device": (_int, [_vp, _u32, _u64, _vp, _u64]),
+    "vss_label_column_width": (_u32, [_vp, _u32]),
+    "vss_search_batch_by_label_box64": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_batch_by_label_box64_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp,
+                                                      _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -545,6 +552,56 @@ class GpuIndex:
         self._check(self.lib.vss_search_batch_by_label_box_device(self.h, d_Q, nq, k, ef, _p(columns), len(columns), d_lo, d_hi,
                                                                   self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
                                                                   d_counts, d_route))
+
+    NO_LABEL64 = 0xFFFFFFFFFFFFFFFF  # VSS_NO_LABEL64
+
+    def set_label_column64(self, column, first_rowid, labels):
+        """vss_set_label_column64: the same with 64-bit cells (NO_LABEL64 is the NULL cell).  The column must be empty or 64 bits
+        wide already; clear_label_column forgets a column's width."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint64)
+        if labels.ndim != 1:
+            raise ValueError("labels must be one uint64 per row id, got shape %r" % (labels.shape,))
+        self._check(self.lib.vss_set_label_column64(self.h, column, first_rowid, _p(labels), len(labels)))
+
+    def set_label_column64_device(self, column, first_rowid, d_labels, n):
+        """The same from a raw device pointer."""
+        self._check(self.lib.vss_set_label_column64_device(self.h, column, first_rowid, d_labels, n))
+
+    def label_column_width(self, column):
+        """0 (no cells), 32 or 64."""
+        return int(self.lib.vss_label_column_width(self.h, column))
+
+    def search_batch_by_label_box64(self, Q, k, ef, columns, lo, hi, mode="auto", route_c=0):
+        """vss_search_batch_by_label_box64: search_batch_by_label_box with 64-bit ends; the named columns may be 32 or 64 bits
+        wide, mixed (a 32-bit cell is read zero-extended, NO_LABEL as NO_LABEL64).  hi = NO_LABEL64 is no upper bound.  lo and
+        hi are nq x len(columns) matrices of uint64.  Returns (ids, distances, counts, route)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        hi = np.ascontiguousarray(hi, dtype=np.uint64)
+        nq = len(Q)
+        if columns.ndim != 1:
+            raise ValueError("columns must be a list of column numbers, got shape %r" % (columns.shape,))
+        if lo.shape != (nq, len(columns)) or hi.shape != (nq, len(columns)):
+            raise ValueError("lo and hi must hold one range per query and named column: %d queries x %d columns, shapes %r and %r"
+                             % (nq, len(columns), lo.shape, hi.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        route = np.zeros(nq, dtype=np.uint8)
+        self._check(self.lib.vss_search_batch_by_label_box64(self.h, _p(Q), nq, k, ef, _p(columns), len(columns), _p(lo), _p(hi),
+                                                             self.BY_LABEL_MODES.get(mode, mode), route_c, _p(keys), _p(d),
+                                                             _p(cnt), _p(route)))
+        return keys, d, cnt, route
+
+    def search_batch_by_label_box64_device(self, d_Q, nq, k, ef, columns, d_lo, d_hi, d_keys, d_dist, d_counts, d_route=None,
+                                           mode="auto", route_c=0):
+        """The same over raw device pointers (`columns` stays a host sequence; d_lo and d_hi: nq x len(columns) uint64,
+        row-major; d_dist and d_route may be None); blocking."""
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        self._check(self.lib.vss_search_batch_by_label_box64_device(self.h, d_Q, nq, k, ef, _p(columns), len(columns), d_lo, d_hi,
+                                                                    self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
+                                                                    d_counts, d_route))
 
     LABEL_SET_MAX = 32  # VSS_LABEL_SET_MAX
 

@@ -6,7 +6,8 @@
 //              keys[slot] is read once per launch, however many groups the launch lists.  Ascending, so that position order in a
 //              list is slot order and ties come back by slot.  k_label_list_*, k_range_list_* and k_set_list_* make the same lists
 //              from the index's label column, for wanted values, label ranges and label sets, and k_box_list_* from up to four
-//              label columns, for a range on each (label_filter.h).
+//              label columns, for a range on each, and k_box64_list_* the same for 64-bit ends over columns of either width
+//              (label_filter.h).
 //   scoring    k_exact_filtered_scores: k_exact_metric_scores with the rows gathered through a list — the same lane-to-component
 //              partition, accumulate4 / group_butterfly / finish_distance order, hence the bits k_exact_rerank computes.  One
 //              launch covers every group of a pass through the plan's tile table.
@@ -410,6 +411,87 @@ __global__ __launch_bounds__(256) void k_box_list_scatter(BoxListArgs a) {
 #pragma unroll
 		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
 			const bool in = host::label_in_box<M>(label[s], box);
+			const unsigned long long m = __ballot(in);
+			if (in)
+				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;
+			at += __popcll(m);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same lists under boxes of 64-BIT ENDS over M label columns of either width (vss_search_batch_by_label_box64,
+// label_filter.h): used group u is a raw row of 4M 32-bit words, per named column lo then hi, each end as (high word, low word),
+// cells [4M u, 4M (u + 1)) of `boxes`.  A wave reads keys[slot] and the cell of each named column ONCE into registers, WIDENED to
+// 64 bits (a column's width is launch-uniform: bit j of `wide`), FL_KEYS_PER_LANE x M 64-bit values a lane; a slot without a cell
+// in a column holds NO_LABEL64 there.  A group's words are wave-uniform, and a group costs a slot 2M 64-bit register compares
+// (host::label_in_box64).  Every counts[u][block] cell is written: no zeroing.
+struct Box64ListArgs {
+	const int64_t *keys;
+	uint32_t rows, n_blocks;
+	const uint32_t *labels[host::LABEL_COLUMNS_MAX]; // the named columns in call order, [0, M) used: one cell per row id below
+	uint64_t labelled_rows[host::LABEL_COLUMNS_MAX]; // ... labelled_rows[j]
+	uint32_t wide;                                   // bit j: column j's cells are 64 bits wide (two words a cell)
+	const uint32_t *boxes;                           // [4M u + 4j .. + 3]: lo and hi of used group u in named column j
+	uint32_t u_begin, u_end;                         // the used groups this launch lists
+	uint32_t *counts;
+	const uint32_t *list_base;
+	uint32_t *lists;
+};
+
+template <uint32_t M>
+__device__ __forceinline__ void box64_list_labels(const Box64ListArgs &a, uint32_t block, uint64_t (&label)[FL_KEYS_PER_LANE][M]) {
+#pragma unroll
+	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+		const uint32_t slot = block * FL_WAVE_SLOTS + s * 64 + lane_id();
+		const int64_t key = slot < a.rows ? a.keys[slot] : host::EXACT_FILTER_FREE_KEY;
+		const bool live = key != host::EXACT_FILTER_FREE_KEY && key >= 0;
+#pragma unroll
+		for (uint32_t j = 0; j < M; ++j) {
+			label[s][j] = host::NO_LABEL64;
+			if (live && (uint64_t)key < a.labelled_rows[j]) {
+				if ((a.wide >> j) & 1)
+					label[s][j] = reinterpret_cast<const uint64_t *>(a.labels[j])[key];
+				else
+					label[s][j] = host::label_widen(a.labels[j][key]);
+			}
+		}
+	}
+}
+
+template <uint32_t M>
+__global__ __launch_bounds__(256) void k_box64_list_count(Box64ListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks) // (wave-uniform; no barrier below)
+		return;
+	uint64_t label[FL_KEYS_PER_LANE][M];
+	box64_list_labels<M>(a, block, label);
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *box = a.boxes + (size_t)u * 4 * M;
+		uint32_t n = 0;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			n += __popcll(__ballot(host::label_in_box64<M>(label[s], box)));
+		if (lane_id() == 0)
+			a.counts[(size_t)u * a.n_blocks + block] = n;
+	}
+}
+
+template <uint32_t M>
+__global__ __launch_bounds__(256) void k_box64_list_scatter(Box64ListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks)
+		return;
+	uint64_t label[FL_KEYS_PER_LANE][M];
+	box64_list_labels<M>(a, block, label);
+	const int lane = lane_id();
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *box = a.boxes + (size_t)u * 4 * M;
+		// the rows this block found in the count pass (the index is read-locked in between: the same rows now)
+		uint32_t at = a.list_base[u] + a.counts[(size_t)u * a.n_blocks + block];
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+			const bool in = host::label_in_box64<M>(label[s], box);
 			const unsigned long long m = __ballot(in);
 			if (in)
 				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;

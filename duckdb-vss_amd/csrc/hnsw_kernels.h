@@ -64,6 +64,16 @@ constexpr uint64_t FILTER_BY_BOX = FILTER_BY_RANGE | FILTER_BY_SET;
 __host__ __device__ constexpr bool filter_by_box(uint64_t filter_bits) {
 	return (filter_bits & FILTER_BY_BOX) == FILTER_BY_BOX;
 }
+// One box with 64-bit ENDS per query, over columns of either width (vss_search_batch_by_label_box64): again no further bit —
+// filter_bits carries FILTER_BY_LABEL, FILTER_BY_RANGE and FILTER_BY_SET, ALL THREE, beside FILTER_PER_QUERY.  No other launch sets
+// that combination (the 32-bit box sets the last two without FILTER_BY_LABEL), so the cut stays at 2^60 - 1.  The table is
+// k_resolve_label_boxes64's (host::label_box64_table_head and what follows it in label_filter.h).  Such launches run the
+// k_search_boxes64 / k_search_solo_boxes64 kernels.  The launchers test for this box FIRST, then for the 32-bit box, then for a bit
+// alone: filter_by_box() holds for both boxes.
+constexpr uint64_t FILTER_BY_BOX64 = FILTER_BY_LABEL | FILTER_BY_RANGE | FILTER_BY_SET;
+__host__ __device__ constexpr bool filter_by_box64(uint64_t filter_bits) {
+	return (filter_bits & FILTER_BY_BOX64) == FILTER_BY_BOX64;
+}
 
 struct GraphView {
 	RowSpace sp;
@@ -177,6 +187,42 @@ struct GraphView {
 		for (uint32_t j = 0; j < host::LABEL_COLUMNS_MAX; ++j)
 			if (j < m)
 				in &= host::label_range_cell_admits(cell[j], mine[2 * j], mine[2 * j + 1]);
+		return in;
+	}
+
+	// The same with one box of 64-bit ends per query (the k_search_boxes64 / k_search_solo_boxes64 kernels only).  As admitted_box:
+	// the key is read and checked once against the shortest named column; the table's head (m and the columns' widths), the columns'
+	// addresses and the query's 2m cells come by scalar loads through the constant address space.  A column's width is
+	// wave-uniform, so a column costs a lane EITHER one 8-byte load OR one 4-byte load and the widening (host::label_widen) — the
+	// branch between them is scalar, and a narrow column is never read 8 bytes at a time.  Then m
+	// host::label_range64_cell_admits, (cell - lo) < count, are ANDed (host::label_box64_cells_admit is this loop).  A lane keeps
+	// its key and m widened cells.
+	__device__ __forceinline__ bool admitted_box64(uint32_t slot, uint32_t query) const {
+		const int64_t key = keys[slot];
+		if (key == 0x7FFFFFFFFFFFFFFFll)
+			return false;
+		if (key < 0 || (uint64_t)key >= (filter_bits & ~FILTER_FLAGS))
+			return false;
+		const auto *table = (const __attribute__((address_space(4))) unsigned long long *)filter;
+		const unsigned long long head = table[0];
+		const uint32_t m = host::label_box64_head_columns(head);
+		const auto *mine = table + host::label_box_query_cell(m, __builtin_amdgcn_readfirstlane(query));
+		uint64_t cell[host::LABEL_COLUMNS_MAX];
+#pragma unroll
+		for (uint32_t j = 0; j < host::LABEL_COLUMNS_MAX; ++j) {
+			cell[j] = 0;
+			if (j < m) {
+				if (host::label_box64_head_wide(head, j))
+					cell[j] = reinterpret_cast<const uint64_t *>(table[1 + j])[key];
+				else
+					cell[j] = host::label_widen(reinterpret_cast<const uint32_t *>(table[1 + j])[key]);
+			}
+		}
+		bool in = true;
+#pragma unroll
+		for (uint32_t j = 0; j < host::LABEL_COLUMNS_MAX; ++j)
+			if (j < m)
+				in &= host::label_range64_cell_admits(cell[j], mine[2 * j], mine[2 * j + 1]);
 		return in;
 	}
 
@@ -1215,12 +1261,15 @@ struct RowTouch {
 // PER_QUERY (TOMB): 1 (the *_groups kernels) the predicate is the one of the query being answered, GraphView::admitted_for;
 // 2 (the *_labels kernels) it is the query's wanted label, GraphView::admitted_label; 3 (the *_ranges kernels) the query's
 // label range, GraphView::admitted_range; 4 (the *_sets kernels) the query's label set, GraphView::admitted_set; 5 (the *_boxes
-// kernels) the query's box over several columns, GraphView::admitted_box
+// kernels) the query's box over several columns, GraphView::admitted_box; 6 (the *_boxes64 kernels) the query's box of 64-bit
+// ends over columns of either width, GraphView::admitted_box64
 // the admission test of a PER_QUERY value: what the kernel family compiles in, and nothing of the others
 template <int PER_QUERY>
 __device__ __forceinline__ bool admitted_as(const GraphView &gv, uint32_t slot, uint32_t query) {
-	static_assert(PER_QUERY >= 0 && PER_QUERY <= 5, "whole launch, groups, labels, ranges, sets, boxes");
-	if constexpr (PER_QUERY == 5)
+	static_assert(PER_QUERY >= 0 && PER_QUERY <= 6, "whole launch, groups, labels, ranges, sets, boxes, 64-bit boxes");
+	if constexpr (PER_QUERY == 6)
+		return gv.admitted_box64(slot, query);
+	else if constexpr (PER_QUERY == 5)
 		return gv.admitted_box(slot, query);
 	else if constexpr (PER_QUERY == 4)
 		return gv.admitted_set(slot, query);
@@ -2126,8 +2175,8 @@ __device__ __forceinline__ void crew_help(unsigned char *smem, const SearchArgs 
 constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS = 8)
 // GROUPS: the body of k_search_groups — a launch with one predicate per query (always a TOMB launch): the level search looks
 // the query's own bitmap up (1), compares the row's label with the query's (2: k_search_labels) or tests it against the query's
-// range (3: k_search_ranges), its set (4: k_search_sets) or its box (5: k_search_boxes), and the paths such a launch never takes
-// are not compiled.
+// range (3: k_search_ranges), its set (4: k_search_sets), its box (5: k_search_boxes) or its box of 64-bit ends
+// (6: k_search_boxes64), and the paths such a launch never takes are not compiled.
 template <int MT, int NCH, int R, int E, int THREADS, int GROUPS>
 __device__ __forceinline__ void search_engine(SearchArgs &a) {
 	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
@@ -2395,6 +2444,11 @@ template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search_boxes(SearchArgs a) {
 	search_engine<MT, NCH, R, E, THREADS, 5>(a);
 }
+// ... and with one box of 64-bit ends per query (vss_search_batch_by_label_box64)
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search_boxes64(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, 6>(a);
+}
 
 // =========================================================================================================
 // k_search_solo — the search engine's shape for FEW queries (the single-query probe of HNSW_INDEX_SCAN, reference
@@ -2532,6 +2586,10 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 template <int MT, int NCH, int R, int E, int T = 1>
 __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_boxes(SearchArgs a) {
 	search_solo<MT, NCH, R, E, T, 5>(a);
+}
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_boxes64(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, 6>(a);
 }
 
 // =========================================================================================================
@@ -2787,6 +2845,30 @@ __global__ __launch_bounds__(256) void k_resolve_label_boxes(ResolveBoxesArgs a)
 	if (i < (uint64_t)a.n_queries * a.m) {
 		const host::LabelRangeCells c = host::label_range_cells(a.boxes[2 * i], a.boxes[2 * i + 1]);
 		a.table[1 + a.m + 2 * i] = c.lo, a.table[2 + a.m + 2 * i] = c.width;
+	}
+}
+
+// Ahead of a launch with one box of 64-bit ends per query: the table GraphView::admitted_box64 reads (label_filter.h has the
+// layout next to label_box_table_cells).  `boxes` is the launch's n_queries x 4m matrix of 32-bit words, per named column lo then
+// hi, each end as (high word, low word), in DEVICE memory; a thread writes one column's pair of one query.
+struct ResolveBoxes64Args {
+	const uint32_t *columns[host::LABEL_COLUMNS_MAX]; // the named columns, in call order; [0, m) are used
+	const uint32_t *boxes;
+	uint32_t n_queries, m;
+	uint32_t wide_mask; // bit j: named column j has 64-bit cells
+	unsigned long long *table; // host::label_box_table_cells(m, n_queries) cells
+};
+
+__global__ __launch_bounds__(256) void k_resolve_label_boxes64(ResolveBoxes64Args a) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i == 0)
+		a.table[0] = host::label_box64_table_head(a.m, a.wide_mask);
+	if (i < a.m)
+		a.table[1 + i] = (unsigned long long)reinterpret_cast<uintptr_t>(a.columns[i]);
+	if (i < (uint64_t)a.n_queries * a.m) {
+		const host::LabelRange64Cells c =
+		    host::label_range64_cells(host::label_word64(a.boxes[4 * i], a.boxes[4 * i + 1]), host::label_word64(a.boxes[4 * i + 2], a.boxes[4 * i + 3]));
+		a.table[1 + a.m + 2 * i] = c.lo, a.table[2 + a.m + 2 * i] = c.count;
 	}
 }
 

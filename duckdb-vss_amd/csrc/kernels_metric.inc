@@ -4,41 +4,11 @@
 
 namespace vss {
 
-template <typename K>
-static hipError_t allow_big_lds(K kernel) {
-	// > 64 KiB of dynamic LDS must be requested explicitly; 160 KiB is the gfx950 per-CU total
-	return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-	                           160 * 1024);
-}
-
-#define VSS_LAUNCH_W(KERNEL, ARGS, WAVES)                                                                                      \
-	do {                                                                                                               \
-		auto kern = KERNEL;                                                                                            \
-		hipError_t e = allow_big_lds(kern);                                                                            \
-		if (e != hipSuccess)                                                                                           \
-			return e;                                                                                                  \
-		hipLaunchKernelGGL(kern, dim3(c.grid), dim3(64 * (WAVES)), c.lds, c.stream, ARGS);                             \
-		return hipGetLastError();                                                                                      \
-	} while (0)
-
-#define VSS_LAUNCH(KERNEL, ARGS) VSS_LAUNCH_W(KERNEL, ARGS, 1)
-
-#define VSS_LAUNCH_T(KERNEL, ARGS, THREADS)                                                                            \
-	do {                                                                                                               \
-		auto kern = KERNEL;                                                                                            \
-		hipError_t e = allow_big_lds(kern);                                                                            \
-		if (e != hipSuccess)                                                                                           \
-			return e;                                                                                                  \
-		hipLaunchKernelGGL(kern, dim3(c.grid), dim3(THREADS), c.lds, c.stream, ARGS);                                  \
-		return hipGetLastError();                                                                                      \
-	} while (0)
+#include "launch_macros.inc"
 
 // The search engine: c.threads / 64 waves per workgroup (walkers + scoring waves), 4 rows in flight per scoring pass
 // (<= 128 VGPRs, so that a 1024-thread workgroup fits a compute unit).  The candidate list takes 2, 4 or 8 registers per
 // lane, or lives in LDS (E = LDS_LIST_E: capacities of 513-4096) or in HBM (E = 0) for ef_search / k beyond 512.
-#ifndef VSS_SEARCH_R6
-#define VSS_SEARCH_R6 2 // 6 chunks per lane (dimension 1536): 4 rows in flight spill 72 bytes per lane beyond the 128 VGPRs
-#endif
 // launches with one predicate per query (GraphView::filter_bits carries FILTER_PER_QUERY): the *_groups kernels, same ladders
 // (such a launch is never pipelined: no 12-wave variant)
 template <int MT, int NCH, int R>
@@ -96,26 +66,9 @@ static hipError_t search_sets_e(const SearchArgs &a, const LaunchCfg &c) {
 		VSS_LAUNCH_T((k_search_sets<MT, NCH, RS, MAX_LIST_REGS>), a, c.threads);
 	VSS_LAUNCH_T((k_search_sets<MT, NCH, RS, 0>), a, c.threads);
 }
-// launches with one box per query (filter_bits carries FILTER_BY_RANGE and FILTER_BY_SET together): the *_boxes kernels, the
-// same ladders
-template <int MT, int NCH, int R>
-static hipError_t search_boxes_e(const SearchArgs &a, const LaunchCfg &c) {
-	constexpr int RS = NCH == 6 ? VSS_SEARCH_R6 : 4;
-	if (a.list_lds)
-		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, LDS_LIST_E>), a, c.threads);
-	if (c.regs <= 2)
-		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, 2>), a, c.threads);
-	if (c.regs <= 4)
-		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, 4>), a, c.threads);
-	if (c.regs <= MAX_LIST_REGS)
-		VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, MAX_LIST_REGS>), a, c.threads);
-	VSS_LAUNCH_T((k_search_boxes<MT, NCH, RS, 0>), a, c.threads);
-}
 template <int MT, int NCH, int R>
 static hipError_t search_e(const SearchArgs &a, const LaunchCfg &c) {
 	constexpr int RS = NCH == 6 ? VSS_SEARCH_R6 : 4;
-	if (filter_by_box(a.gv.filter_bits)) // (before either of its two bits alone)
-		return search_boxes_e<MT, NCH, R>(a, c);
 	if (a.gv.filter_bits & FILTER_BY_SET)
 		return search_sets_e<MT, NCH, R>(a, c);
 	if (a.gv.filter_bits & FILTER_BY_RANGE)
@@ -147,21 +100,7 @@ static hipError_t search_e(const SearchArgs &a, const LaunchCfg &c) {
 // waves of this kernel do not fit the register file.
 template <int MT, int NCH>
 static hipError_t search_team_e(const SearchArgs &a, const LaunchCfg &c) {
-#ifndef VSS_TEAM_R
-#define VSS_TEAM_R (VSS_TEAM_WAVES <= 4 ? 4 : 2) // (a level-0 list of 32 rows at 128 dims: 4 rows per wave; A/B builds)
-#endif
 	constexpr int T = VSS_TEAM_WAVES, RT = VSS_TEAM_R;
-	if (filter_by_box(a.gv.filter_bits)) {
-		if (c.regs <= 1)
-			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 1, T>), a, T);
-		if (c.regs <= 2)
-			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 2, T>), a, T);
-		if (c.regs <= 4)
-			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 4, T>), a, T);
-		if (c.regs <= MAX_LIST_REGS)
-			VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, MAX_LIST_REGS, T>), a, T);
-		VSS_LAUNCH_W((k_search_solo_boxes<MT, NCH, RT, 0, T>), a, T);
-	}
 	if (a.gv.filter_bits & FILTER_BY_SET) {
 		if (c.regs <= 1)
 			VSS_LAUNCH_W((k_search_solo_sets<MT, NCH, RT, 1, T>), a, T);
@@ -223,17 +162,6 @@ static hipError_t search_solo_e(const SearchArgs &a, const LaunchCfg &c) {
 			return search_team_e<MT, NCH>(a, c);
 	}
 	constexpr int RS = NCH == 1 ? 16 : (NCH == 6 || NCH == 4) ? 4 : 8;
-	if (filter_by_box(a.gv.filter_bits)) {
-		if (c.regs <= 1)
-			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 1>), a);
-		if (c.regs <= 2)
-			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 2>), a);
-		if (c.regs <= 4)
-			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 4>), a);
-		if (c.regs <= MAX_LIST_REGS)
-			VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, MAX_LIST_REGS>), a);
-		VSS_LAUNCH((k_search_solo_boxes<MT, NCH, RS, 0>), a);
-	}
 	if (a.gv.filter_bits & FILTER_BY_SET) {
 		if (c.regs <= 1)
 			VSS_LAUNCH((k_search_solo_sets<MT, NCH, RS, 1>), a);
@@ -299,24 +227,6 @@ static hipError_t phase_a_e(const BuildArgs &a, const LaunchCfg &c) {
 	VSS_LAUNCH((k_build_phase_a<MT, NCH, R, 0>), a);
 }
 
-// chunks per lane with unrolled instantiations: 1 (dimensions 4 .. 256 that fill a power-of-two group), 2 (512), 3 (768),
-// 4 (1024), 6 (1536); every other dimension takes the looping variant (0)
-#define VSS_BY_CHUNKS(FN, ...)                                                                                         \
-	switch (c.nch) {                                                                                                   \
-	case 1:                                                                                                            \
-		return FN<VSS_MT, 1, 8>(__VA_ARGS__);                                                                          \
-	case 2:                                                                                                            \
-		return FN<VSS_MT, 2, 8>(__VA_ARGS__);                                                                          \
-	case 3:                                                                                                            \
-		return FN<VSS_MT, 3, 8>(__VA_ARGS__);                                                                          \
-	case 4:                                                                                                            \
-		return FN<VSS_MT, 4, 4>(__VA_ARGS__);                                                                          \
-	case 6:                                                                                                            \
-		return FN<VSS_MT, 6, 4>(__VA_ARGS__);                                                                          \
-	default:                                                                                                           \
-		return FN<VSS_MT, 0, 4>(__VA_ARGS__);                                                                          \
-	}
-
 // Phase A with 4 instead of 8 rows in flight per wave at dim 768: a third wave per SIMD, and refine_'s early exit works
 // on passes of 4 kept neighbours instead of 8 (11 % fewer distances computed, same decisions): phase A -5.7 % at
 // 3M x 768.  Phase B measured 5 % slower that way and keeps 8.
@@ -354,10 +264,14 @@ static hipError_t rerank_e(const RerankArgs &a, const LaunchCfg &c) {
 
 template <>
 hipError_t launch_search<VSS_MT>(const SearchArgs &a, const LaunchCfg &c) {
+	if (filter_by_box(a.gv.filter_bits)) // (either box: before any of its bits alone; their walkers are units of their own)
+		return launch_search_boxes<VSS_MT>(a, c);
 	VSS_BY_CHUNKS(search_e, a, c)
 }
 template <>
 hipError_t launch_search_solo<VSS_MT>(const SearchArgs &a, const LaunchCfg &c) {
+	if (filter_by_box(a.gv.filter_bits))
+		return launch_search_solo_boxes<VSS_MT>(a, c);
 	VSS_BY_CHUNKS(search_solo_e, a, c)
 }
 template <>

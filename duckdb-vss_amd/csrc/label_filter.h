@@ -9,7 +9,9 @@
 // listing's forms of it and its groups are further down (host/label_range_check.cpp), and so are those of
 // vss_search_batch_by_label_set, which tests it against a short list of values per query (host/label_set_check.cpp).  The index
 // keeps LABEL_COLUMNS_MAX such columns — the one above is column 0 — and vss_search_batch_by_label_box tests up to four of them
-// against one range each per query: the last part (host/label_box_check.cpp).
+// against one range each per query (host/label_box_check.cpp).  A column's cells are 32 or 64 bits wide, and
+// vss_search_batch_by_label_box64 tests columns of either width against ranges with 64-bit ends: the last part
+// (host/label_box64_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -278,6 +280,125 @@ inline constexpr uint32_t label_box_bad_column(const uint32_t *columns, uint32_t
 				return j;
 	}
 	return m;
+}
+
+// ---- 64-bit columns and per-query boxes with 64-bit ends (vss_search_batch_by_label_box64): each of the LABEL_COLUMNS_MAX columns
+// has a WIDTH, 32 or 64 bits a cell (vss_set_label_column64 writes the wide ones; a column keeps one width until it is cleared).
+// The NULL cell of a wide column is NO_LABEL64.  A call names m distinct columns of either width, mixed, and query q brings one
+// range of 64-bit ends per named column.  A 32-bit cell is read ZERO-EXTENDED, and its NO_LABEL reads as NO_LABEL64
+// (label_widen), so one rule serves both widths: query q admits the live rows that label_range64_admits admits in EVERY named
+// column — the row id has a cell there, the widened cell is not NO_LABEL64, and lo <= cell <= hi, unsigned.  One empty range
+// empties the box; hi = NO_LABEL64 is "no upper bound" and still rejects the NULL cells.
+// Inside the engine a box travels as ONE row of 4m 32-bit words: per named column lo then hi, each 64-bit end as the pair (HIGH
+// word, low word) — label_box64_rows.  High word first, so that the lexicographic order of the rows as 32-bit words IS their
+// lexicographic order as 2m unsigned 64-bit words: label_set_groups' order is the contract's order, and everything that carries
+// rows of 32-bit words per query or per group (the plans, the compact batch of the graph-routed queries, the sharded exchange)
+// carries these unchanged.  The derived table: the distinct RAW rows, ascending, nothing canonicalised, are the groups; bitmap g
+// has bit r set iff label_box64_admits(..., r, row g); its n_bits is the smallest rows(c) of the named columns.
+constexpr uint64_t NO_LABEL64 = 0xFFFFFFFFFFFFFFFFull; // VSS_NO_LABEL64
+
+inline constexpr uint64_t label_widen(uint32_t cell) {
+	return cell == NO_LABEL ? NO_LABEL64 : (uint64_t)cell;
+}
+
+// One column of the index as the 64-bit rule reads it: `rows` cells, 32 bits wide (narrow) or 64 (wide); the other pointer is null.
+struct LabelColumn64 {
+	const uint32_t *narrow;
+	const uint64_t *wide;
+	uint64_t rows;
+};
+inline constexpr uint64_t label_cell64(const LabelColumn64 &c, uint64_t key) { // key < c.rows
+	return c.wide ? c.wide[key] : label_widen(c.narrow[key]);
+}
+
+inline constexpr bool label_range64_admits(const LabelColumn64 &c, int64_t key, uint64_t lo, uint64_t hi) {
+	if (key < 0 || (uint64_t)key >= c.rows)
+		return false;
+	const uint64_t cell = label_cell64(c, (uint64_t)key);
+	return cell != NO_LABEL64 && lo <= cell && cell <= hi;
+}
+
+// THE admission rule of a 64-bit box, but for the row being live.  index_columns[c]: column c of the index; box: 2m 64-bit words
+// (lo_0, hi_0, lo_1, hi_1, ...).  constexpr: the kernels' forms below are proven against this very code (host/label_box64_check.cpp).
+inline constexpr bool label_box64_admits(const LabelColumn64 *index_columns, const uint32_t *columns, uint32_t m, int64_t key,
+                                         const uint64_t *box) {
+	for (uint32_t j = 0; j != m; ++j)
+		if (!label_range64_admits(index_columns[columns[j]], key, box[2 * j], box[2 * j + 1]))
+			return false;
+	return true;
+}
+
+// a 64-bit end out of its (high word, low word) pair, and back
+inline constexpr uint64_t label_word64(const uint32_t *pair) {
+	return (uint64_t)pair[0] << 32 | pair[1];
+}
+inline constexpr uint64_t label_word64(uint32_t high, uint32_t low) {
+	return (uint64_t)high << 32 | low;
+}
+
+// The register form of the listing kernels: label[j] is the row's WIDENED cell in named column j, or NO_LABEL64 for "no cell at
+// all"; box: the group's 4m 32-bit words.  hi is cut below NO_LABEL64 as label_in_range cuts it below NO_LABEL.  No early exit.
+inline constexpr bool label64_in_range(uint64_t label, uint64_t lo, uint64_t hi) {
+	return lo <= label && label <= (hi == NO_LABEL64 ? NO_LABEL64 - 1 : hi);
+}
+template <uint32_t M>
+inline constexpr bool label_in_box64(const uint64_t (&label)[M], const uint32_t *box) {
+	bool in = true;
+	for (uint32_t j = 0; j != M; ++j)
+		in &= label64_in_range(label[j], label_word64(box + 4 * j), label_word64(box + 4 * j + 2));
+	return in;
+}
+
+// What the walker tests a row's widened cell with: two 64-bit cells per query and named column, {lo, count}, count the number of
+// admitted values: top = min(hi, NO_LABEL64 - 1), count = lo > top ? 0 : top - lo + 1 (at most 2^64 - 1: no wrap).  Admission is ONE
+// subtraction and ONE comparison, (cell - lo) < count, without a branch: the empty range has count 0, a cell below lo wraps to at
+// least 2^64 - lo > count, and the NO_LABEL64 cell gives 2^64 - 1 - lo >= count.  (The 32-bit box's {lo, width} form needs a
+// value beyond every cell for its empty range; 64 bits have none.)
+struct LabelRange64Cells {
+	uint64_t lo, count;
+};
+inline constexpr LabelRange64Cells label_range64_cells(uint64_t lo, uint64_t hi) {
+	const uint64_t top = hi == NO_LABEL64 ? NO_LABEL64 - 1 : hi;
+	return {lo, lo > top ? 0 : top - lo + 1};
+}
+inline constexpr bool label_range64_cell_admits(uint64_t cell, uint64_t cell_lo, uint64_t cell_count) {
+	return cell - cell_lo < cell_count;
+}
+
+// What the walker's table holds — label_box_table_cells(m, n_queries) cells, as the 32-bit box's: cell 0 is
+// label_box64_table_head: the number of named columns m in its low byte and from bit 8 on one bit per named column, set where the
+// column is 64 bits wide; cells 1 .. m the columns' addresses in call order; from cell 1 + m (label_box_query_cell) on 2m cells
+// per query, named column j's label_range64_cells pair at 2j and 2j + 1.
+inline constexpr uint64_t label_box64_table_head(uint32_t m, uint32_t wide_mask) {
+	return (uint64_t)m | (uint64_t)wide_mask << 8;
+}
+inline constexpr uint32_t label_box64_head_columns(uint64_t head) {
+	return (uint32_t)(head & 0xFF);
+}
+inline constexpr bool label_box64_head_wide(uint64_t head, uint32_t j) {
+	return (head >> (8 + j)) & 1;
+}
+// the walker's test of a row whose widened cells are label[0 .. m) against a query's 2m table cells
+inline constexpr bool label_box64_cells_admit(const uint64_t *label, const uint64_t *cells, uint32_t m) {
+	bool in = true;
+	for (uint32_t j = 0; j != m; ++j)
+		in &= label_range64_cell_admits(label[j], cells[2 * j], cells[2 * j + 1]);
+	return in;
+}
+
+// the n x 4m matrix of a call's boxes from its two n x m matrices of 64-bit ends
+inline void label_box64_rows(const uint64_t *lo, const uint64_t *hi, uint64_t n, uint32_t m, std::vector<uint32_t> &boxes) {
+	boxes.resize(4 * (size_t)m * n);
+	for (uint64_t i = 0; i != n * m; ++i) {
+		boxes[4 * i] = (uint32_t)(lo[i] >> 32), boxes[4 * i + 1] = (uint32_t)lo[i];
+		boxes[4 * i + 2] = (uint32_t)(hi[i] >> 32), boxes[4 * i + 3] = (uint32_t)hi[i];
+	}
+}
+
+// the distinct raw rows of `boxes` (n rows of 4m words), ascending — as 2m unsigned 64-bit words, see above — flattened into
+// `rows`, and the group of every query
+inline void label_box64_groups(const uint32_t *boxes, uint64_t n, uint32_t m, std::vector<uint32_t> &rows, std::vector<uint32_t> &group_of) {
+	label_set_groups(boxes, n, 4 * m, rows, group_of);
 }
 
 // vss_set_labels(first_rowid, n): what the range breaks, or NONE. Cells end at 2^32 (first_rowid + n == 2^32 is the last range

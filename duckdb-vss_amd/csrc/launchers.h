@@ -1,6 +1,8 @@
 // launchers.h — host-side launch functions of the templated kernels.  The kernels are instantiated per index metric
 // in three translation units (kernels_l2sq.hip / kernels_cosine.hip / kernels_ip.hip, all built from
-// kernels_metric.inc) so they compile in parallel; the engine picks the instantiation at run time.
+// kernels_metric.inc) so they compile in parallel; the engine picks the instantiation at run time.  The walkers of the launches
+// by label box (both boxes: filter_by_box()) are three more units, kernels_boxes_{l2sq,cosine,ip}.hip from kernels_boxes.inc:
+// launch_search / launch_search_solo hand such a launch to launch_search_boxes / launch_search_solo_boxes.
 #pragma once
 #include "exact_kernels.h"
 #include "hnsw_kernels.h"
@@ -21,6 +23,10 @@ hipError_t launch_search(const SearchArgs &a, const LaunchCfg &c);
 template <int MT>
 hipError_t launch_search_solo(const SearchArgs &a, const LaunchCfg &c);
 template <int MT>
+hipError_t launch_search_boxes(const SearchArgs &a, const LaunchCfg &c);
+template <int MT>
+hipError_t launch_search_solo_boxes(const SearchArgs &a, const LaunchCfg &c);
+template <int MT>
 hipError_t launch_phase_a(const BuildArgs &a, const LaunchCfg &c);
 template <int MT>
 hipError_t launch_phase_b(const LinkArgs &a, const LaunchCfg &c);
@@ -34,6 +40,10 @@ hipError_t launch_rerank(const RerankArgs &a, const LaunchCfg &c);
 	hipError_t launch_search<MT>(const SearchArgs &, const LaunchCfg &);                                               \
 	template <>                                                                                                        \
 	hipError_t launch_search_solo<MT>(const SearchArgs &, const LaunchCfg &);                                          \
+	template <>                                                                                                        \
+	hipError_t launch_search_boxes<MT>(const SearchArgs &, const LaunchCfg &);                                         \
+	template <>                                                                                                        \
+	hipError_t launch_search_solo_boxes<MT>(const SearchArgs &, const LaunchCfg &);                                    \
 	template <>                                                                                                        \
 	hipError_t launch_phase_a<MT>(const BuildArgs &, const LaunchCfg &);                                               \
 	template <>                                                                                                        \

@@ -126,7 +126,7 @@ static thread_local std::string tls_error;
 // What a search launch filters its results by.  The pointers are device memory for search_begin / search_launch and host
 // memory for search_host, which stages what they name and hands search_launch the staged copy.
 struct SearchPredicate {
-	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE, BY_SET, BY_BOX } kind = NONE;
+	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE, BY_SET, BY_BOX, BY_BOX64 } kind = NONE;
 	const uint64_t *bitmap = nullptr;                        // ONE_BITMAP: the whole launch's; bit set = row id admitted
 	FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES] = {}; // PER_QUERY: the table of every batch of the launch
 	uint64_t n_bits = 0;                                     // (BY_LABEL: the cells of the index's label column)
@@ -135,6 +135,7 @@ struct SearchPredicate {
 	const uint32_t *sets = nullptr;                          // BY_SET: `width` words per query, row-major
 	uint32_t width = 0;
 	const uint32_t *boxes = nullptr;                         // BY_BOX: 2 * n_columns words per query, (lo, hi) per named column
+	                                                         // BY_BOX64: 4 * n_columns words per query (label_box64_rows)
 	uint32_t n_columns = 0, columns[LABEL_COLUMNS_MAX] = {}; // BY_BOX: the label columns the call names (n_bits: the shortest one's cells)
 
 	// a launch of one batch against the index's label column: query q admits the rows labelled want[q]
@@ -163,6 +164,13 @@ struct SearchPredicate {
 		SearchPredicate p;
 		p.kind = BY_BOX, p.n_bits = shortest_rows, p.boxes = boxes, p.n_columns = m;
 		std::copy(columns, columns + m, p.columns);
+		return p;
+	}
+
+	// ... the same with 64-bit ends: 4m words per query, per named column lo then hi, each as (high word, low word)
+	static SearchPredicate by_box64(const uint32_t *boxes, const uint32_t *columns, uint32_t m, uint64_t shortest_rows) {
+		SearchPredicate p = by_box(boxes, columns, m, shortest_rows);
+		p.kind = BY_BOX64;
 		return p;
 	}
 
@@ -207,17 +215,24 @@ struct DeviceWords {
 	}
 };
 // The label columns a call by label box names, in call order, as the index holds them while the call runs (under its lock): their
-// numbers, their DEVICE cells and how many cells each has.
+// numbers, their DEVICE cells, how many cells each has and how wide a cell is (32 or 64 bits; a 64-bit cell is two words of `cells`).
 struct LabelBoxColumns {
 	uint32_t m = 0, columns[LABEL_COLUMNS_MAX] = {};
 	const uint32_t *cells[LABEL_COLUMNS_MAX] = {};
 	uint64_t rows[LABEL_COLUMNS_MAX] = {};
+	uint32_t width[LABEL_COLUMNS_MAX] = {};
+	uint32_t wide_mask() const { // bit j: named column j is 64 bits wide
+		uint32_t mask = 0;
+		for (uint32_t j = 0; j != m; ++j)
+			mask |= (uint32_t)(width[j] == 64) << j;
+		return mask;
+	}
 	uint64_t shortest_rows() const {
 		return *std::min_element(rows, rows + m);
 	}
 };
 
-// The groups the rows of a scan call are listed by, made by one of the five factories only.  Bitmaps: group g = the rows bitmap g
+// The groups the rows of a scan call are listed by, made by one of the six factories only.  Bitmaps: group g = the rows bitmap g
 // of a DEVICE table admits.  Labels: group g = the rows the index's label column gives values[g], the ascending distinct wanted
 // values (HOST memory); no bitmap exists.  Either way query q reads group group_of[q] (HOST memory; nullptr: all read group 0),
 // and the walk of the graph-routed queries reads the column's DEVICE twin: group numbers under bitmaps, wanted labels under labels.
@@ -228,6 +243,7 @@ struct LabelBoxColumns {
 // Boxes: group g = the rows whose cells in the call's m named label columns lie within the m pairs of rows[g], the ascending distinct
 // raw rows of 2m words (HOST memory, flattened; width = 2m); the walk reads every query's row of the DEVICE matrix d_sets likewise.
 // n_bits is the shortest named column's cells.
+// Boxes of 64-bit ends: the same with rows of 4m 32-bit words (label_box64_rows; width = 4m) over columns of either width.
 struct GroupedRows {
 	const uint64_t *d_table = nullptr;  // bitmaps: n_groups bitmaps of n_bits bits
 	uint64_t n_groups = 0, n_bits = 0;  // (labels: the distinct wanted values; the cells of the label column)
@@ -276,11 +292,18 @@ struct GroupedRows {
 		return g;
 	}
 
+	static GroupedRows boxes64(const std::vector<uint32_t> &rows, const LabelBoxColumns &box, HostWords group_of, DeviceWords d_boxes) {
+		GroupedRows g;
+		g.by_box64 = true, g.rows = rows.data(), g.width = 4 * box.m, g.box = box;
+		g.n_groups = rows.size() / g.width, g.n_bits = box.shortest_rows(), g.group_of = group_of.p, g.d_sets = d_boxes.p;
+		return g;
+	}
+
 	// words that name one used group to the list kernels: its table group, its wanted value, the two ends of its range, the
 	// words of its set, or the pairs of its box.  The walk of the graph-routed queries needs as many words per query gathered into
 	// the compact batch.
 	uint64_t group_cells() const {
-		return by_set || by_box ? width : by_range ? 2 : 1;
+		return by_set || by_box || by_box64 ? width : by_range ? 2 : 1;
 	}
 	// Those words beyond the one column k_route_gather takes along (d_group_of; under sets it takes none): `per` words a query,
 	// row-major from `words`, to word `at` of the compact batch's ng * group_cells() words — or words == nullptr, nothing more.
@@ -290,7 +313,7 @@ struct GroupedRows {
 		uint64_t at;
 	};
 	WalkWords more_walk_words(uint64_t ng) const {
-		if (by_set || by_box)
+		if (by_set || by_box || by_box64)
 			return {d_sets, width, 0};
 		if (by_range)
 			return {d_hi, 1, ng};
@@ -335,10 +358,21 @@ struct GroupedRows {
 		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
 		return a;
 	}
+	// ... and in the 64-bit box form: 4m words each, and the columns' widths
+	Box64ListArgs box64_list_args(const FilterListArgs &l) const {
+		Box64ListArgs a = {};
+		a.keys = l.keys, a.rows = l.rows, a.n_blocks = l.n_blocks;
+		for (uint32_t j = 0; j != box.m; ++j)
+			a.labels[j] = box.cells[j], a.labelled_rows[j] = box.rows[j];
+		a.wide = box.wide_mask();
+		a.boxes = l.groups, a.u_begin = l.u_begin, a.u_end = l.u_end;
+		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
+		return a;
+	}
 	// the cells of a plan's used groups, group_cells() words each: plan.groups, or their values / pairs / rows in `scratch` (which
 	// outlives the upload like plan.groups)
 	const uint32_t *used_group_cells(const ExactFilterPlan &plan, std::vector<uint32_t> &scratch) const {
-		if (by_set || by_box) {
+		if (by_set || by_box || by_box64) {
 			scratch.resize((size_t)width * plan.groups.size());
 			for (size_t u = 0; u != plan.groups.size(); ++u)
 				std::copy(rows + (size_t)plan.groups[u] * width, rows + ((size_t)plan.groups[u] + 1) * width, scratch.begin() + u * width);
@@ -374,6 +408,13 @@ struct GroupedRows {
 			case 3: hipLaunchKernelGGL(k_box_list_count<3>, grid, dim3(256), 0, stream, box_list_args(l)); break;
 			default: hipLaunchKernelGGL(k_box_list_count<4>, grid, dim3(256), 0, stream, box_list_args(l)); break;
 			}
+		else if (by_box64)
+			switch (box.m) {
+			case 1: hipLaunchKernelGGL(k_box64_list_count<1>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			case 2: hipLaunchKernelGGL(k_box64_list_count<2>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			case 3: hipLaunchKernelGGL(k_box64_list_count<3>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			default: hipLaunchKernelGGL(k_box64_list_count<4>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			}
 		else
 			hipLaunchKernelGGL(k_filter_list_count, grid, dim3(256), 0, stream, l);
 	}
@@ -393,6 +434,13 @@ struct GroupedRows {
 			case 3: hipLaunchKernelGGL(k_box_list_scatter<3>, grid, dim3(256), 0, stream, box_list_args(l)); break;
 			default: hipLaunchKernelGGL(k_box_list_scatter<4>, grid, dim3(256), 0, stream, box_list_args(l)); break;
 			}
+		else if (by_box64)
+			switch (box.m) {
+			case 1: hipLaunchKernelGGL(k_box64_list_scatter<1>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			case 2: hipLaunchKernelGGL(k_box64_list_scatter<2>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			case 3: hipLaunchKernelGGL(k_box64_list_scatter<3>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			default: hipLaunchKernelGGL(k_box64_list_scatter<4>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
+			}
 		else
 			hipLaunchKernelGGL(k_filter_list_scatter, grid, dim3(256), 0, stream, l);
 	}
@@ -400,6 +448,8 @@ struct GroupedRows {
 	// (k_route_gather's column first, more_walk_words() where it says)
 	SearchPredicate walk_predicate(const uint32_t *d_compact, uint64_t ng) const {
 		const uint32_t *d_compact_groups = d_compact;
+		if (by_box64)
+			return SearchPredicate::by_box64(d_compact, box.columns, box.m, n_bits);
 		if (by_box)
 			return SearchPredicate::by_box(d_compact, box.columns, box.m, n_bits);
 		if (by_set)
@@ -413,7 +463,7 @@ struct GroupedRows {
 	}
 
 private:
-	bool by_label = false, by_range = false, by_set = false, by_box = false;
+	bool by_label = false, by_range = false, by_set = false, by_box = false, by_box64 = false;
 	GroupedRows() = default;
 };
 
@@ -504,6 +554,10 @@ struct vss_index {
 	DevBuf<uint32_t> d_more_labels[LABEL_COLUMNS_MAX - 1];
 	uint64_t more_labelled_rows[LABEL_COLUMNS_MAX - 1] = {};
 	uint64_t label_column_bytes[LABEL_COLUMNS_MAX] = {};
+	// A column's cells are 32 bits wide or 64 (vss_set_label_column64): 0 while it is empty, then the width of the setter that made
+	// it, until it is cleared.  A 64-bit column keeps its cells in the same buffer, TWO words a cell (label_cells(c).n counts words),
+	// and only the search by label box64 reads it.
+	uint32_t label_width[LABEL_COLUMNS_MAX] = {};
 	std::atomic<uint64_t> label_bytes {0}; // every column's; vss_memory_usage (read without a lock)
 	DevBuf<uint32_t> &label_cells(uint32_t column) {
 		return column ? d_more_labels[column - 1] : d_labels;
@@ -841,6 +895,7 @@ struct vss_index {
 		box.m = (uint32_t)m;
 		for (uint32_t j = 0; j != box.m; ++j) {
 			box.columns[j] = columns[j], box.cells[j] = label_cells(columns[j]).p, box.rows[j] = label_rows(columns[j]);
+			box.width[j] = label_width[columns[j]];
 			if (!box.cells[j])
 				return false;
 		}
@@ -850,6 +905,7 @@ struct vss_index {
 	void clear_label_column(uint32_t column) {
 		label_cells(column).free();
 		label_rows(column) = 0;
+		label_width[column] = 0;
 		label_bytes.fetch_sub(label_column_bytes[column], std::memory_order_relaxed);
 		label_column_bytes[column] = 0;
 	}
@@ -859,12 +915,18 @@ struct vss_index {
 	}
 
 	// column `column`'s cells [first_rowid, first_rowid + n) = labels[0 .. n), from HOST or DEVICE memory; cells the write skips
-	// over become NO_LABEL.
+	// over become NO_LABEL.  cell_words: 1 for 32-bit cells, 2 for 64-bit cells (`labels` then holds uint64_t, and the skipped
+	// cells become NO_LABEL64); a column that has cells keeps their width.
 	// Under the exclusive lock.  The column grows into a NEW buffer, and the old one goes only once the new one holds its cells: a
 	// device without room fails this call and leaves the column as it was (nothing is visible before labelled_rows moves).
-	int set_labels(const char *what, uint32_t column, uint64_t first_rowid, const uint32_t *labels, uint64_t n, bool on_device) {
+	int set_labels(const char *what, uint32_t column, uint64_t first_rowid, const void *labels, uint64_t n, bool on_device,
+	               uint32_t cell_words = 1) {
 		if (column >= LABEL_COLUMNS_MAX)
 			return fail("%s: column %u is not below VSS_LABEL_COLUMNS_MAX (%u)", what, (unsigned)column, (unsigned)LABEL_COLUMNS_MAX);
+		if (label_cells(column).p && label_width[column] != 32 * cell_words)
+			return fail("%s: label column %u holds %u-bit cells and this call writes %u-bit cells (vss_clear_label_column it first)", what,
+			            (unsigned)column, (unsigned)label_width[column], (unsigned)(32 * cell_words));
+		const uint64_t cell_bytes = 4 * (uint64_t)cell_words;
 		// (these two shadow column 0's members on purpose: what follows is the one column's code, for whichever column)
 		DevBuf<uint32_t> &d_labels = label_cells(column);
 		uint64_t &labelled_rows = label_rows(column);
@@ -879,21 +941,21 @@ struct vss_index {
 		if (refuse_while_probing(what) != VSS_OK)
 			return VSS_ERROR;
 		const LabelWrite w = label_write(labelled_rows, first_rowid, n);
-		if (w.rows_after > d_labels.n) {
+		if (w.rows_after * cell_words > d_labels.n) {
 			// by halves, so that a column written chunk by chunk next to the appends is not copied once per chunk
 			const uint64_t roomy = std::min<uint64_t>(w.rows_after + w.rows_after / 2, LABEL_ROWS_MAX);
 			uint32_t *np = nullptr;
 			uint64_t got = roomy;
-			if (hipMalloc(&np, roomy * 4) != hipSuccess) {
+			if (hipMalloc(&np, roomy * cell_bytes) != hipSuccess) {
 				(void)hipGetLastError();
 				got = w.rows_after;
-				if (hipMalloc(&np, got * 4) != hipSuccess) {
+				if (hipMalloc(&np, got * cell_bytes) != hipSuccess) {
 					(void)hipGetLastError();
 					return fail("%s: no device memory for a label column of %llu rows (it keeps its %llu)", what,
 					            (unsigned long long)w.rows_after, (unsigned long long)labelled_rows);
 				}
 			}
-			hipError_t e = labelled_rows ? hipMemcpyAsync(np, d_labels.p, labelled_rows * 4, hipMemcpyDeviceToDevice, stream) : hipSuccess;
+			hipError_t e = labelled_rows ? hipMemcpyAsync(np, d_labels.p, labelled_rows * cell_bytes, hipMemcpyDeviceToDevice, stream) : hipSuccess;
 			if (e == hipSuccess)
 				e = hipStreamSynchronize(stream);
 			if (e != hipSuccess) {
@@ -901,15 +963,17 @@ struct vss_index {
 				throw HipError {e, "label column growth"};
 			}
 			d_labels.free();
-			d_labels.p = np, d_labels.n = got;
-			label_bytes.fetch_add(got * 4 - label_column_bytes[column], std::memory_order_relaxed);
-			label_column_bytes[column] = got * 4;
+			d_labels.p = np, d_labels.n = got * cell_words;
+			label_bytes.fetch_add(got * cell_bytes - label_column_bytes[column], std::memory_order_relaxed);
+			label_column_bytes[column] = got * cell_bytes;
 		}
 		if (w.gap_end > w.gap_begin)
-			HIP_TRY(hipMemsetAsync(d_labels.p + w.gap_begin, 0xFF, (w.gap_end - w.gap_begin) * 4, stream)); // NO_LABEL
-		HIP_TRY(hipMemcpyAsync(d_labels.p + first_rowid, labels, n * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipMemsetAsync(d_labels.p + w.gap_begin * cell_words, 0xFF, (w.gap_end - w.gap_begin) * cell_bytes, stream)); // NO_LABEL(64)
+		HIP_TRY(hipMemcpyAsync(d_labels.p + first_rowid * cell_words, labels, n * cell_bytes,
+		                       on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
 		HIP_TRY(hipStreamSynchronize(stream));
 		labelled_rows = w.rows_after;
+		label_width[column] = 32 * cell_words;
 		return VSS_OK;
 	}
 
@@ -1724,6 +1788,24 @@ struct vss_index {
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits = std::min<uint64_t>(box.shortest_rows(), FILTER_BY_SET - 1) | FILTER_PER_QUERY | FILTER_BY_BOX;
+		} else if (p.kind == SearchPredicate::BY_BOX64) {
+			// ... and by the *_boxes64 kernels (GraphView::admitted_box64): the head (the number of named columns and their
+			// widths), their addresses, then 2m cells per query.  No flag bit of its own either: all three BY_ bits together.
+			LabelBoxColumns box;
+			if (n_batches != 1 || !named_label_columns(p.columns, p.n_columns, box))
+				return fail("search by label box64: one batch per launch, over 1 to %u distinct label columns that have been set",
+				            (unsigned)LABEL_COLUMNS_MAX);
+			if (!c.d_group_bitmap.try_grow(label_box_table_cells(box.m, cap_q)))
+				return fail("search by label box64: no device memory for the boxes of %llu queries", (unsigned long long)cap_q);
+			count_group_tables(c);
+			ResolveBoxes64Args res = {};
+			std::copy(box.cells, box.cells + box.m, res.columns);
+			res.boxes = p.boxes, res.n_queries = (uint32_t)nq, res.m = box.m, res.wide_mask = box.wide_mask();
+			res.table = reinterpret_cast<unsigned long long *>(c.d_group_bitmap.p);
+			hipLaunchKernelGGL(k_resolve_label_boxes64, dim3((uint32_t)(nq * box.m / 256 + 1)), dim3(256), 0, c.stream, res);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits = std::min<uint64_t>(box.shortest_rows(), FILTER_BY_SET - 1) | FILTER_PER_QUERY | FILTER_BY_BOX64;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
@@ -1975,11 +2057,12 @@ struct vss_index {
 		return VSS_OK;
 	}
 	// the boxes of a call by label box (HOST memory), in the same buffer: the nq x 2m matrix as it is
-	int stage_label_boxes(SearchCtx &c, const uint32_t *boxes, uint32_t m, uint64_t nq) {
-		if (!c.d_group_of.try_grow(nq * 2 * m))
+	// (end_words: the 32-bit words of one end, 1, or 2 for the 64-bit ends of a call by label box64)
+	int stage_label_boxes(SearchCtx &c, const uint32_t *boxes, uint32_t m, uint64_t nq, uint32_t end_words = 1) {
+		if (!c.d_group_of.try_grow(nq * 2 * m * end_words))
 			return fail("search by label box: no device memory for the boxes of %llu queries", (unsigned long long)nq);
 		count_group_tables(c);
-		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, boxes, nq * 2 * m * 4, hipMemcpyHostToDevice, c.stream));
+		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, boxes, nq * 2 * m * end_words * 4, hipMemcpyHostToDevice, c.stream));
 		return VSS_OK;
 	}
 	// queries in, result buffers ensured ...
@@ -2090,6 +2173,10 @@ struct vss_index {
 				    if (const int rc = stage_label_boxes(c, filter.boxes, filter.n_columns, nq))
 					    return rc;
 				    staged = SearchPredicate::by_box(c.d_group_of.p, filter.columns, filter.n_columns, filter.n_bits);
+			    } else if (filter.kind == SearchPredicate::BY_BOX64) {
+				    if (const int rc = stage_label_boxes(c, filter.boxes, filter.n_columns, nq, 2))
+					    return rc;
+				    staged = SearchPredicate::by_box64(c.d_group_of.p, filter.columns, filter.n_columns, filter.n_bits);
 			    }
 			    return VSS_OK;
 		    },
@@ -2746,6 +2833,28 @@ struct vss_index {
 		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_boxes(c, boxes, box.m, hc.nq); },
 		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
 			    return by_box_launch(b, HostWords(boxes), box, DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
+		    });
+	}
+
+	// ------------------------------------------------------------------ search by label box64 (label_filter.h)
+	// The same with 64-bit ends: `boxes` is nq x 4m words (label_box64_rows), and the named columns may be of either width.
+	int by_box64_launch(const DeviceBatch &b, HostWords boxes, const LabelBoxColumns &box, DeviceWords d_boxes, uint64_t route_c,
+	                    const DeviceAnswers &out, std::vector<uint8_t> &route) {
+		std::vector<uint32_t> rows, group_of;
+		label_box64_groups(boxes.p, b.nq, box.m, rows, group_of);
+		const GroupedRows g = GroupedRows::boxes64(rows, box, HostWords(group_of.data()), d_boxes);
+		if (!d_boxes.p) {
+			route.assign(b.nq, FILTER_ROUTE_EXACT);
+			return exact_filtered_launch(b, g, out);
+		}
+		return filtered_auto(b, g, route_c, out, route);
+	}
+
+	int by_box64_host(const HostCall &hc, bool exact, const uint32_t *boxes, const LabelBoxColumns &box, uint64_t route_c) {
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_boxes(c, boxes, box.m, hc.nq, 2); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+			    return by_box64_launch(b, HostWords(boxes), box, DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
 		    });
 	}
 
@@ -4053,6 +4162,21 @@ int vss_clear_label_column(vss_index *h, uint32_t column) {
 	})
 }
 
+int vss_set_label_column64(vss_index *h, uint32_t column, uint64_t first_rowid, const uint64_t *labels, uint64_t n) {
+	VSS_GUARD(h, { return h->set_labels("vss_set_label_column64", column, first_rowid, labels, n, false, 2); })
+}
+
+int vss_set_label_column64_device(vss_index *h, uint32_t column, uint64_t first_rowid, const uint64_t *d_labels, uint64_t n) {
+	VSS_GUARD(h, { return h->set_labels("vss_set_label_column64_device", column, first_rowid, d_labels, n, true, 2); })
+}
+
+uint32_t vss_label_column_width(const vss_index *h, uint32_t column) {
+	if (!h || column >= LABEL_COLUMNS_MAX)
+		return 0;
+	std::shared_lock<std::shared_mutex> lk(const_cast<vss_index *>(h)->rw);
+	return h->label_width[column];
+}
+
 uint64_t vss_label_column_rows(const vss_index *h, uint32_t column) {
 	if (!h || column >= LABEL_COLUMNS_MAX)
 		return 0;
@@ -4067,6 +4191,8 @@ static int check_by_label(vss_index *h, const char *what, const float *Q, uint64
 		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
 	if (!h->d_labels.p)
 		return h->fail("%s: the index has no label column (call vss_set_labels first; vss_load and vss_clear_labels drop it)", what);
+	if (h->label_width[0] == 64)
+		return h->fail("%s: label column 0 holds 64-bit cells, which this call cannot read (vss_search_batch_by_label_box64 can)", what);
 	if (!Q || !want || !out || !out_counts)
 		return h->fail("%s: null query / wanted-label / row-id / count pointer", what);
 	if (nq > 0xFFFFFFFFull)
@@ -4122,6 +4248,8 @@ static int check_by_label_range(vss_index *h, const char *what, const float *Q, 
 		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
 	if (!h->d_labels.p)
 		return h->fail("%s: the index has no label column (call vss_set_labels first; vss_load and vss_clear_labels drop it)", what);
+	if (h->label_width[0] == 64)
+		return h->fail("%s: label column 0 holds 64-bit cells, which this call cannot read (vss_search_batch_by_label_box64 can)", what);
 	if (nq && (!lo || !hi))
 		return h->fail("%s: null lo / hi pointer for %llu queries", what, (unsigned long long)nq);
 	if (nq && (!Q || !out || !out_counts))
@@ -4189,6 +4317,8 @@ static int check_by_label_set(vss_index *h, const char *what, const float *Q, ui
 		return h->fail("%s: null sets pointer for %llu queries", what, (unsigned long long)nq);
 	if (!h->d_labels.p)
 		return h->fail("%s: the index has no label column (call vss_set_labels first; vss_load and vss_clear_labels drop it)", what);
+	if (h->label_width[0] == 64)
+		return h->fail("%s: label column 0 holds 64-bit cells, which this call cannot read (vss_search_batch_by_label_box64 can)", what);
 	if (nq && (!Q || !out || !out_counts))
 		return h->fail("%s: null query / row-id / count pointer", what);
 	if (nq > 0xFFFFFFFFull)
@@ -4241,9 +4371,10 @@ int vss_search_batch_by_label_set_device(vss_index *h, const float *Q, uint64_t 
 
 // ---- the search by label box: the mode is refused first, then the number of columns, a null `columns`, a column out of range or
 // named twice, null lo / hi — all before anything is launched or written — and a named column that was never set after them
+// (wide_ok: the call reads 64-bit columns too — the box64 calls; the box calls refuse such a column right after an unset one)
 static int check_by_label_box(vss_index *h, const char *what, const float *Q, uint64_t nq, const uint32_t *columns, uint64_t m,
-                              const uint32_t *lo, const uint32_t *hi, int mode, const int64_t *out, const uint32_t *out_counts,
-                              LabelBoxColumns &box) {
+                              const void *lo, const void *hi, int mode, const int64_t *out, const uint32_t *out_counts,
+                              LabelBoxColumns &box, bool wide_ok = false) {
 	if (mode != VSS_BY_LABEL_GRAPH && mode != VSS_BY_LABEL_EXACT && mode != VSS_BY_LABEL_AUTO)
 		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
 	if (m < 1 || m > VSS_LABEL_COLUMNS_MAX)
@@ -4261,6 +4392,10 @@ static int check_by_label_box(vss_index *h, const char *what, const float *Q, ui
 		if (!h->label_cells(columns[j]).p)
 			return h->fail("%s: the index has no label column %u (call vss_set_label_column first; vss_load, vss_clear_labels and "
 			               "vss_clear_label_column drop it)", what, (unsigned)columns[j]);
+	for (uint32_t j = 0; j != m && !wide_ok; ++j)
+		if (h->label_width[columns[j]] == 64)
+			return h->fail("%s: label column %u holds 64-bit cells, which this call cannot read (vss_search_batch_by_label_box64 can)", what,
+			               (unsigned)columns[j]);
 	if (nq && (!Q || !out || !out_counts))
 		return h->fail("%s: null query / row-id / count pointer", what);
 	if (nq > 0xFFFFFFFFull)
@@ -4320,6 +4455,67 @@ int vss_search_batch_by_label_box_device(vss_index *h, const float *Q, uint64_t 
 				return rc;
 		} else if (const int rc = h->by_box_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(boxes.data()), box,
 		                                           DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, {out, out_d, out_counts}, route))
+			return rc;
+		h->route_to_device(route, out_route);
+		return VSS_OK;
+	})
+}
+
+// ---- the search by label box64: the box call's checks in the box call's order (no width is refused), 64-bit ends
+int vss_search_batch_by_label_box64(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *columns,
+                                    uint64_t n_columns, const uint64_t *lo, const uint64_t *hi, int mode, uint64_t route_c, int64_t *out,
+                                    float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_by_label_box(h, "vss_search_batch_by_label_box64", Q, nq, columns, n_columns, lo, hi, mode, out, out_counts, box, true) !=
+		    VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		std::vector<uint32_t> boxes;
+		label_box64_rows(lo, hi, nq, box.m, boxes);
+		if (mode != VSS_BY_LABEL_GRAPH)
+			return h->by_box64_host({Q, nq, k, ef, out, out_d, out_counts, out_route}, mode == VSS_BY_LABEL_EXACT, boxes.data(), box, route_c);
+		if (out_route)
+			std::memset(out_route, FILTER_ROUTE_GRAPH, nq);
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false,
+		                      SearchPredicate::by_box64(boxes.data(), box.columns, box.m, box.shortest_rows()));
+	})
+}
+
+int vss_search_batch_by_label_box64_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, const uint32_t *columns,
+                                           uint64_t n_columns, const uint64_t *lo, const uint64_t *hi, int mode, uint64_t route_c,
+                                           int64_t *out, float *out_d, uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_by_label_box(h, "vss_search_batch_by_label_box64_device", Q, nq, columns, n_columns, lo, hi, mode, out, out_counts, box,
+		                       true) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		// the plans read the boxes on the host, and the walk reads them as ONE matrix of word pairs: both matrices come back
+		// (16 * n_columns bytes per query) and go to context 0 as label_box64_rows lays them out
+		const std::vector<uint32_t> lo_w = h->words_to_host(reinterpret_cast<const uint32_t *>(lo), 2 * nq * box.m),
+		                            hi_w = h->words_to_host(reinterpret_cast<const uint32_t *>(hi), 2 * nq * box.m);
+		std::vector<uint64_t> lo_h(nq * box.m), hi_h(nq * box.m);
+		std::memcpy(lo_h.data(), lo_w.data(), lo_h.size() * 8), std::memcpy(hi_h.data(), hi_w.data(), hi_h.size() * 8);
+		std::vector<uint32_t> boxes;
+		label_box64_rows(lo_h.data(), hi_h.data(), nq, box.m, boxes);
+		auto &c = h->context(0);
+		const bool exact = mode == VSS_BY_LABEL_EXACT;
+		if (!exact) {
+			if (const int rc = h->stage_label_boxes(c, boxes.data(), box.m, nq, 2))
+				return rc;
+			HIP_TRY(hipStreamSynchronize(c.stream)); // (`boxes` is pageable memory; the count kernels run on the index stream)
+		}
+		std::vector<uint8_t> route(nq, FILTER_ROUTE_GRAPH);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+			r.predicate = SearchPredicate::by_box64(c.d_group_of.p, box.columns, box.m, box.shortest_rows());
+			if (const int rc = h->search_launch(r))
+				return rc;
+		} else if (const int rc = h->by_box64_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(boxes.data()), box,
+		                                             DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, {out, out_d, out_counts}, route))
 			return rc;
 		h->route_to_device(route, out_route);
 		return VSS_OK;

@@ -307,6 +307,27 @@ public:
 			                                     counts, routes);
 		});
 	}
+	// The same chunk where a column of the predicate is 64 bits wide — ts a TIMESTAMP, tenant a BIGINT (INTEGRATION.md §5 maps them
+	// to unsigned 64 bits in order): lo and hi hold 64-bit ends, and the named columns may be of either width, mixed; a 32-bit
+	// column joins unchanged, its cells read zero-extended.  vss_search_batch_by_label_box64 does the rest.  hi = VSS_NO_LABEL64 is
+	// "no upper bound"; a NULL cell (VSS_NO_LABEL in a 32-bit column, VSS_NO_LABEL64 in a 64-bit one) is in no box.
+	idx_t ExecuteMultiScanBatchByLabelBox64(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit, const uint32_t *columns,
+	                                        idx_t n_columns, const uint64_t *lo, const uint64_t *hi, std::vector<uint32_t> *counts_out,
+	                                        std::vector<uint8_t> *routes_out = nullptr, int mode = VSS_BY_LABEL_AUTO, uint64_t route_c = 0) {
+		return ScanChunk(state_p, n_queries, limit, counts_out, routes_out, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *routes) {
+			return vss_search_batch_by_label_box64(index, queries, n_queries, limit, ef, columns, n_columns, lo, hi, mode, route_c, ids, nullptr,
+			                                       counts, routes);
+		});
+	}
+	// A label column of 64-bit cells (vss_set_label_column64): the column must be empty or 64 bits wide already; ClearLabelColumn
+	// forgets a column's width.  LabelColumnWidth: 0 (no cells), 32 or 64.
+	void SetLabelColumn64(uint32_t column, idx_t first_rowid, const uint64_t *labels, idx_t n) {
+		std::unique_lock<std::shared_mutex> lock(rwlock);
+		Check(vss_set_label_column64(index, column, first_rowid, labels, n), "label");
+	}
+	uint32_t LabelColumnWidth(uint32_t column) const {
+		return vss_label_column_width(index, column);
+	}
 	// Label columns 0 .. VSS_LABEL_COLUMNS_MAX - 1 (vss_set_label_column; column 0 is the column of SetLabels).  ClearLabels clears
 	// every column.  Not persisted: after LoadFromBlocks the owner writes them again from the table.
 	void SetLabelColumn(uint32_t column, idx_t first_rowid, const uint32_t *labels, idx_t n) {

@@ -540,6 +540,47 @@ public:
 			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
 		}
 	}
+	// A label column of 64-bit cells: every shard gets the whole column, as SetLabelColumn gives it.
+	void SetLabelColumn64(uint32_t column, idx_t first_rowid, const uint64_t *labels, idx_t n) {
+		for (auto &s : shards)
+			s.index->SetLabelColumn64(column, first_rowid, labels, n);
+	}
+	// SearchBatchByLabelBox with 64-bit ends over columns of either width (vss_search_batch_by_label_box64_device per shard; hi =
+	// VSS_NO_LABEL64: no upper bound).  Modes, shard_routes, exchange and merge are SearchBatchByLabelBox's; both matrices travel
+	// as UploadTables' group numbers, every 64-bit end as a PAIR of words in memory order, lo's 2 * n * n_columns words first —
+	// hi's then begin 8 * n * n_columns bytes in, aligned for the device to read them as 64-bit ends again.
+	void SearchBatchByLabelBox64(const float *queries, idx_t n, idx_t k, idx_t ef, const uint32_t *columns, idx_t n_columns, const uint64_t *lo,
+	                             const uint64_t *hi, int mode, uint64_t route_c, row_t *out_rowids, float *out_distances, uint32_t *out_counts,
+	                             std::vector<uint8_t> *shard_routes = nullptr) {
+		if (shard_routes)
+			shard_routes->assign(shards.size() * n, 0);
+		if (!n || !k)
+			return;
+		if (n_columns < 1 || n_columns > VSS_LABEL_COLUMNS_MAX || !columns)
+			throw InternalException("Failed to search the HNSW index: search by label box64 names 1 to 4 label columns");
+		if (!lo || !hi)
+			throw InternalException("Failed to search the HNSW index: search by label box64 needs both ends of every query's ranges");
+		Ensure(n, k);
+		const idx_t words = 2 * n * n_columns; // of one matrix
+		std::vector<uint32_t> ends(2 * words);
+		std::memcpy(ends.data(), lo, words * 4);
+		std::memcpy(ends.data() + words, hi, words * 4);
+		UploadTables(nullptr, 0, ends.data(), 2 * words);
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    const uint32_t *d_ends = bitmaps[s.bitmap].group_of;
+			    Vss(s, vss_search_batch_by_label_box64_device(s.index->Handle(), s.d_q, n, k, ef, columns, n_columns,
+			                                                  reinterpret_cast<const uint64_t *>(d_ends),
+			                                                  reinterpret_cast<const uint64_t *>(d_ends + words), mode, route_c, keys, dist, s.d_cnt,
+			                                                  s.d_route));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		for (size_t g = 0; shard_routes && g != shards.size(); ++g) {
+			Hip(hipSetDevice(shards[g].device), "hipSetDevice");
+			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
+		}
+	}
 	// Query q admits the live rows whose label is one of sets[q * width .. (q + 1) * width) (VSS_NO_LABEL pads a shorter list and
 	// equals nothing; a VSS_NO_LABEL cell is in no set): vss_search_batch_by_label_set_device per shard, every shard holding the
 	// whole column.  Modes, shard_routes, exchange and merge are SearchBatchByLabel's; the matrix travels as UploadTables' group

@@ -360,7 +360,7 @@ int vss_search_batch_by_label_set_device(vss_index *index, const float *d_querie
  * VSS_OK and writes nothing.
  * The _device form takes device pointers for everything but `columns` (d_out_distances and d_out_route may be NULL), copies d_lo
  * and d_hi back (8 * n_columns bytes per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin
- * forms; IN-lists or OR inside a box, 64-bit columns and more than four columns keep the bitmap calls. */
+ * forms; IN-lists or OR inside a box and more than four columns keep the bitmap calls; 64-bit columns have the box64 call below. */
 #define VSS_LABEL_COLUMNS_MAX 4
 int vss_set_label_column(vss_index *index, uint32_t column, uint64_t first_rowid, const uint32_t *labels, uint64_t n);
 int vss_set_label_column_device(vss_index *index, uint32_t column, uint64_t first_rowid, const uint32_t *d_labels, uint64_t n);
@@ -374,6 +374,44 @@ int vss_search_batch_by_label_box_device(vss_index *index, const float *d_querie
                                          const uint32_t *columns, uint64_t n_columns, const uint32_t *d_lo, const uint32_t *d_hi,
                                          int mode, uint64_t route_c, int64_t *d_out_rowids, float *d_out_distances,
                                          uint32_t *d_out_counts, uint8_t *d_out_route);
+/* ---- 64-bit label columns and boxes with 64-bit ends (csrc/label_filter.h) ------------------------------------------------------
+ * For `items.tenant = q.tenant AND items.ts >= q.since` where ts is a TIMESTAMP or an id a BIGINT (INTEGRATION.md §5 has the
+ * order-preserving maps to unsigned 64 bits).  Each of the VSS_LABEL_COLUMNS_MAX column slots has a WIDTH:
+ * vss_label_column_width is 0 for a column without cells (or a column number out of range), 32 for one written by
+ * vss_set_labels / vss_set_label_column, 64 for one written by vss_set_label_column64 / _device.  A wide column has one 64-bit
+ * cell per row id, VSS_NO_LABEL64 where nothing was set; growth, gap fill and the 2^32 row-id cap are those of the narrow
+ * columns, and vss_memory_usage counts 8 bytes a cell.  A column keeps its width while it has cells: a setter of the other width
+ * fails with a message that names both widths (column 0 and vss_set_labels included) until vss_clear_label_column, which forgets
+ * the width.  vss_clear_labels and vss_load clear wide columns like the others; none is persisted.  vss_search_batch_by_label,
+ * _range, _set and _box refuse a column that is 64 bits wide ("holds 64-bit cells") and are otherwise unchanged.
+ * The call: the arguments of vss_search_batch_by_label_box, but lo and hi are n_queries x n_columns matrices of uint64_t, and the
+ * named columns may be of either width, mixed.  A 32-bit cell is read zero-extended, and a VSS_NO_LABEL cell reads as
+ * VSS_NO_LABEL64: a 32-bit column joins a 64-bit box unchanged.  Query q admits a live row of id r iff for every j <
+ * n_columns, with c = columns[j]: r < vss_label_column_rows(c), the widened cell is not VSS_NO_LABEL64, and lo[q, j] <= cell <=
+ * hi[q, j], compared unsigned.  Any lo > hi empties the box; hi = 2^64 - 1 is "no upper bound" and still rejects NULLs; `=` is
+ * lo == hi.  mode, route_c, out_route, k and ef as for vss_search_batch_by_label_box.
+ * Contract: form the n_queries x 2 n_columns matrix of 64-bit words whose row q is (lo[q,0], hi[q,0], lo[q,1], hi[q,1], ...).
+ * Its distinct RAW rows, ascending lexicographically as unsigned 64-bit words and not canonicalised, are the groups b_0 < b_1 <
+ * ...; bitmap g = {r : the rule admits r for b_g}, n_bits = the smallest vss_label_column_rows(c) over the named columns, and
+ * group_of[q] = the index of query q's row.  The call returns cell for cell what the bitmap call of the same mode returns for
+ * that table — row ids, f32 distance bits, counts, routes — and leaves the same counters behind, as the box call does.  With
+ * every named column 32 bits wide and every end below 2^32 that is also, counters included, the answer of
+ * vss_search_batch_by_label_box.
+ * Errors: those of the box call, in its order, except that no width is refused.  The _device form copies d_lo and d_hi back
+ * (16 * n_columns bytes per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin forms; there is no
+ * 64-bit equality or set call of its own (a box with lo == hi is the equality). */
+#define VSS_NO_LABEL64 0xFFFFFFFFFFFFFFFFull
+int vss_set_label_column64(vss_index *index, uint32_t column, uint64_t first_rowid, const uint64_t *labels, uint64_t n);
+int vss_set_label_column64_device(vss_index *index, uint32_t column, uint64_t first_rowid, const uint64_t *d_labels, uint64_t n);
+uint32_t vss_label_column_width(const vss_index *index, uint32_t column);
+int vss_search_batch_by_label_box64(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                    const uint32_t *columns, uint64_t n_columns, const uint64_t *lo, const uint64_t *hi, int mode,
+                                    uint64_t route_c, int64_t *out_rowids, float *out_distances, uint32_t *out_counts,
+                                    uint8_t *out_route);
+int vss_search_batch_by_label_box64_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                           const uint32_t *columns, uint64_t n_columns, const uint64_t *d_lo, const uint64_t *d_hi,
+                                           int mode, uint64_t route_c, int64_t *d_out_rowids, float *d_out_distances,
+                                           uint32_t *d_out_counts, uint8_t *d_out_route);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
