@@ -27,11 +27,12 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 
 
 TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip",
-                     "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip"]
+                     "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip",
+                     "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip"]
 
 
 def build_library(force=False, extra_flags=(), out=None):
-    """hipcc cross-compiles the engine for gfx950 (works without a GPU): eight translation units in parallel, then a
+    """hipcc cross-compiles the engine for gfx950 (works without a GPU): eleven translation units in parallel, then a
     shared link.  Objects live in build/ (git-ignored)."""
     out = out or os.path.join(HERE, "libvssgpu.so")
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
@@ -121,6 +122,10 @@ SIGNATURES = {
     "vss_search_batch_by_label_box64": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_by_label_box64_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp,
                                                       _vp]),
+    "vss_search_batch_by_label_set_box": (_int, [_vp, _vp, _u64, _u64, _u64, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _int, _u64, _vp, _vp,
+                                                 _vp, _vp]),
+    "vss_search_batch_by_label_set_box_device": (_int, [_vp, _vp, _u64, _u64, _u64, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _int, _u64,
+                                                        _vp, _vp, _vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
@@ -602,6 +607,47 @@ class GpuIndex:
         self._check(self.lib.vss_search_batch_by_label_box64_device(self.h, d_Q, nq, k, ef, _p(columns), len(columns), d_lo, d_hi,
                                                                     self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
                                                                     d_counts, d_route))
+
+    def search_batch_by_label_set_box(self, Q, k, ef, set_column, sets, columns=(), lo=None, hi=None, mode="auto", route_c=0):
+        """vss_search_batch_by_label_set_box: query q admits the rows whose cell in `set_column` is one of the uint64 words of
+        sets[q] (NO_LABEL64 pads a shorter list) and whose cells in the range `columns` (0 to 3 of them) lie within lo[q] .. hi[q];
+        columns of either width, mixed.  sets: nq x width; lo and hi: nq x len(columns) matrices of uint64 (not needed without
+        range columns).  Returns (ids, distances, counts, route)."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        nq = len(Q)
+        sets = np.ascontiguousarray(sets, dtype=np.uint64)
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        if sets.ndim != 2 or sets.shape[0] != nq:
+            raise ValueError("sets must hold one row of uint64 words per query: %d queries, shape %r" % (nq, sets.shape))
+        if columns.ndim != 1:
+            raise ValueError("columns must be a list of column numbers, got shape %r" % (columns.shape,))
+        m = len(columns)
+        if m:
+            lo = np.ascontiguousarray(lo, dtype=np.uint64)
+            hi = np.ascontiguousarray(hi, dtype=np.uint64)
+            if lo.shape != (nq, m) or hi.shape != (nq, m):
+                raise ValueError("lo and hi must hold one range per query and range column: %d queries x %d columns, shapes %r and "
+                                 "%r" % (nq, m, lo.shape, hi.shape))
+        keys = np.full((nq, k), -1, dtype=np.int64)
+        d = np.full((nq, k), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        route = np.zeros(nq, dtype=np.uint8)
+        self._check(self.lib.vss_search_batch_by_label_set_box(self.h, _p(Q), nq, k, ef, set_column, _p(sets), sets.shape[1],
+                                                               _p(columns) if m else None, m, _p(lo) if m else None,
+                                                               _p(hi) if m else None, self.BY_LABEL_MODES.get(mode, mode), route_c,
+                                                               _p(keys), _p(d), _p(cnt), _p(route)))
+        return keys, d, cnt, route
+
+    def search_batch_by_label_set_box_device(self, d_Q, nq, k, ef, set_column, d_sets, width, columns, d_lo, d_hi, d_keys, d_dist,
+                                             d_counts, d_route=None, mode="auto", route_c=0):
+        """The same over raw device pointers (`columns` stays a host sequence; d_sets: nq x width uint64, d_lo and d_hi: nq x
+        len(columns) uint64, row-major, None without range columns; d_dist and d_route may be None); blocking."""
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        m = len(columns)
+        self._check(self.lib.vss_search_batch_by_label_set_box_device(self.h, d_Q, nq, k, ef, set_column, d_sets, width,
+                                                                      _p(columns) if m else None, m, d_lo, d_hi,
+                                                                      self.BY_LABEL_MODES.get(mode, mode), route_c, d_keys, d_dist,
+                                                                      d_counts, d_route))
 
     LABEL_SET_MAX = 32  # VSS_LABEL_SET_MAX
 

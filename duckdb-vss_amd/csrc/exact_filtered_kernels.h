@@ -6,8 +6,8 @@
 //              keys[slot] is read once per launch, however many groups the launch lists.  Ascending, so that position order in a
 //              list is slot order and ties come back by slot.  k_label_list_*, k_range_list_* and k_set_list_* make the same lists
 //              from the index's label column, for wanted values, label ranges and label sets, and k_box_list_* from up to four
-//              label columns, for a range on each, and k_box64_list_* the same for 64-bit ends over columns of either width
-//              (label_filter.h).
+//              label columns, for a range on each, and k_box64_list_* the same for 64-bit ends over columns of either width,
+//              and k_set_box_list_* for an IN-list on one column inside such a box (label_filter.h).
 //   scoring    k_exact_filtered_scores: k_exact_metric_scores with the rows gathered through a list — the same lane-to-component
 //              partition, accumulate4 / group_butterfly / finish_distance order, hence the bits k_exact_rerank computes.  One
 //              launch covers every group of a pass through the plan's tile table.
@@ -492,6 +492,91 @@ __global__ __launch_bounds__(256) void k_box64_list_scatter(Box64ListArgs a) {
 #pragma unroll
 		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
 			const bool in = host::label_in_box64<M>(label[s], box);
+			const unsigned long long m = __ballot(in);
+			if (in)
+				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;
+			at += __popcll(m);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same lists under an IN-LIST on one column inside a box of M ranges (vss_search_batch_by_label_set_box, label_filter.h): used
+// group u is a travelling row of 2 width + 4M 32-bit words, cells [(2 width + 4M) u, ...) of `rows`.  A wave reads keys[slot] and
+// the WIDENED cell of the set column and of each range column ONCE into registers, FL_KEYS_PER_LANE x (1 + M) 64-bit values a
+// lane (a column's width is launch-uniform: bit 0 of `wide` the set column, bit 1 + j range column j); a slot without a cell in a
+// column holds NO_LABEL64 there.  A group's words are wave-uniform; a group costs a slot `width` 64-bit register compares, one test
+// against NO_LABEL64 and 2M range compares (host::label_in_set_box).  The set width is a run-time argument.  Every
+// counts[u][block] cell is written: no zeroing.
+struct SetBoxListArgs {
+	const int64_t *keys;
+	uint32_t rows_n, n_blocks;
+	const uint32_t *labels[host::LABEL_COLUMNS_MAX]; // the set column, then the M range columns in call order
+	uint64_t labelled_rows[host::LABEL_COLUMNS_MAX];
+	uint32_t wide;                                   // bit j: column j of `labels` has 64-bit cells
+	const uint32_t *rows;                            // the used groups' travelling rows
+	uint32_t width;                                  // 1 .. host::LABEL_SET_MAX
+	uint32_t u_begin, u_end;                         // the used groups this launch lists
+	uint32_t *counts;
+	const uint32_t *list_base;
+	uint32_t *lists;
+};
+
+template <uint32_t M>
+__device__ __forceinline__ void set_box_list_labels(const SetBoxListArgs &a, uint32_t block, uint64_t (&label)[FL_KEYS_PER_LANE][M + 1]) {
+#pragma unroll
+	for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+		const uint32_t slot = block * FL_WAVE_SLOTS + s * 64 + lane_id();
+		const int64_t key = slot < a.rows_n ? a.keys[slot] : host::EXACT_FILTER_FREE_KEY;
+		const bool live = key != host::EXACT_FILTER_FREE_KEY && key >= 0;
+#pragma unroll
+		for (uint32_t j = 0; j < M + 1; ++j) {
+			label[s][j] = host::NO_LABEL64;
+			if (live && (uint64_t)key < a.labelled_rows[j]) {
+				if ((a.wide >> j) & 1)
+					label[s][j] = reinterpret_cast<const uint64_t *>(a.labels[j])[key];
+				else
+					label[s][j] = host::label_widen(a.labels[j][key]);
+			}
+		}
+	}
+}
+
+template <uint32_t M>
+__global__ __launch_bounds__(256) void k_set_box_list_count(SetBoxListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks) // (wave-uniform; no barrier below)
+		return;
+	uint64_t label[FL_KEYS_PER_LANE][M + 1];
+	set_box_list_labels<M>(a, block, label);
+	const uint32_t per = host::label_set_box_row_words(a.width, M);
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *row = a.rows + (size_t)u * per;
+		uint32_t n = 0;
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s)
+			n += __popcll(__ballot(host::label_in_set_box<M>(label[s], row, a.width)));
+		if (lane_id() == 0)
+			a.counts[(size_t)u * a.n_blocks + block] = n;
+	}
+}
+
+template <uint32_t M>
+__global__ __launch_bounds__(256) void k_set_box_list_scatter(SetBoxListArgs a) {
+	const uint32_t block = blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (block >= a.n_blocks)
+		return;
+	uint64_t label[FL_KEYS_PER_LANE][M + 1];
+	set_box_list_labels<M>(a, block, label);
+	const uint32_t per = host::label_set_box_row_words(a.width, M);
+	const int lane = lane_id();
+	for (uint32_t u = a.u_begin; u < a.u_end; ++u) {
+		const uint32_t *row = a.rows + (size_t)u * per;
+		// the rows this block found in the count pass (the index is read-locked in between: the same rows now)
+		uint32_t at = a.list_base[u] + a.counts[(size_t)u * a.n_blocks + block];
+#pragma unroll
+		for (uint32_t s = 0; s < FL_KEYS_PER_LANE; ++s) {
+			const bool in = host::label_in_set_box<M>(label[s], row, a.width);
 			const unsigned long long m = __ballot(in);
 			if (in)
 				a.lists[at + __popcll(m & lanes_below(lane))] = block * FL_WAVE_SLOTS + s * 64 + lane;

@@ -74,6 +74,15 @@ constexpr uint64_t FILTER_BY_BOX64 = FILTER_BY_LABEL | FILTER_BY_RANGE | FILTER_
 __host__ __device__ constexpr bool filter_by_box64(uint64_t filter_bits) {
 	return (filter_bits & FILTER_BY_BOX64) == FILTER_BY_BOX64;
 }
+// One IN-LIST on one column inside a box of ranges per query (vss_search_batch_by_label_set_box): no further bit either —
+// filter_bits carries FILTER_BY_LABEL and FILTER_BY_SET WITHOUT FILTER_BY_RANGE beside FILTER_PER_QUERY, a combination no other
+// launch sets, so the cut stays at 2^60 - 1.  The table is k_resolve_label_set_boxes' (host::label_set_box_table_head and what
+// follows it in label_filter.h).  Such launches run the k_search_set_boxes / k_search_solo_set_boxes kernels.  The launchers test for
+// it after both boxes and BEFORE FILTER_BY_SET or FILTER_BY_LABEL alone, which they test bit by bit.
+constexpr uint64_t FILTER_BY_SET_BOX = FILTER_BY_LABEL | FILTER_BY_SET;
+__host__ __device__ constexpr bool filter_by_set_box(uint64_t filter_bits) {
+	return (filter_bits & FILTER_BY_BOX64) == FILTER_BY_SET_BOX;
+}
 
 struct GraphView {
 	RowSpace sp;
@@ -223,6 +232,49 @@ struct GraphView {
 		for (uint32_t j = 0; j < host::LABEL_COLUMNS_MAX; ++j)
 			if (j < m)
 				in &= host::label_range64_cell_admits(cell[j], mine[2 * j], mine[2 * j + 1]);
+		return in;
+	}
+
+	// The same with one IN-list on one column inside a box of ranges per query (the k_search_set_boxes / k_search_solo_set_boxes
+	// kernels only).  Shaped as admitted_box64 and admitted_set: the key is read and checked once against the shortest of the set
+	// column and the range columns; the head (m, the padded set length, the widths), the 1 + m addresses, the query's set words and
+	// its 2m range cells come by scalar loads through the constant address space, the query's number through readfirstlane.  A
+	// column's width is a wave-uniform bit of the head, so a narrow column is never read 8 bytes at a time.  A lane keeps its key
+	// and 1 + m widened cells; the set loop is register compares against wave-uniform words, two 64-bit words (one aligned 16-byte
+	// chunk) a step, and no VGPR and no LDS holds the set (host::label_set_box_cells_admit is this test).
+	__device__ __forceinline__ bool admitted_set_box(uint32_t slot, uint32_t query) const {
+		typedef unsigned long long words2 __attribute__((ext_vector_type(2)));
+		const int64_t key = keys[slot];
+		if (key == 0x7FFFFFFFFFFFFFFFll)
+			return false;
+		if (key < 0 || (uint64_t)key >= (filter_bits & ~FILTER_FLAGS))
+			return false;
+		const auto *table = (const __attribute__((address_space(4))) unsigned long long *)filter;
+		const unsigned long long head = table[0];
+		const uint32_t m = host::label_set_box_head_ranges(head), padded = host::label_set_box_head_padded(head);
+		const auto *mine = table + host::label_set_box_query_cell(m, padded, __builtin_amdgcn_readfirstlane(query));
+		uint64_t cell[host::LABEL_COLUMNS_MAX];
+#pragma unroll
+		for (uint32_t j = 0; j < host::LABEL_COLUMNS_MAX; ++j) {
+			cell[j] = 0;
+			if (j <= m) {
+				if (host::label_set_box_head_wide(head, j))
+					cell[j] = reinterpret_cast<const uint64_t *>(table[1 + j])[key];
+				else
+					cell[j] = host::label_widen(reinterpret_cast<const uint32_t *>(table[1 + j])[key]);
+			}
+		}
+		const auto *chunk = (const __attribute__((address_space(4))) words2 *)mine;
+		bool hit = false;
+		for (uint32_t j = 0; j != padded / 2; ++j) {
+			const words2 w = chunk[j];
+			hit |= host::label64_hits2(cell[0], w.x, w.y);
+		}
+		bool in = hit & (cell[0] != host::NO_LABEL64);
+#pragma unroll
+		for (uint32_t j = 0; j < host::LABEL_SET_BOX_RANGES_MAX; ++j)
+			if (j < m)
+				in &= host::label_range64_cell_admits(cell[1 + j], mine[padded + 2 * j], mine[padded + 2 * j + 1]);
 		return in;
 	}
 
@@ -1262,12 +1314,15 @@ struct RowTouch {
 // 2 (the *_labels kernels) it is the query's wanted label, GraphView::admitted_label; 3 (the *_ranges kernels) the query's
 // label range, GraphView::admitted_range; 4 (the *_sets kernels) the query's label set, GraphView::admitted_set; 5 (the *_boxes
 // kernels) the query's box over several columns, GraphView::admitted_box; 6 (the *_boxes64 kernels) the query's box of 64-bit
-// ends over columns of either width, GraphView::admitted_box64
+// ends over columns of either width, GraphView::admitted_box64; 7 (the *_set_boxes kernels) the query's IN-list on one column
+// inside a box of ranges, GraphView::admitted_set_box
 // the admission test of a PER_QUERY value: what the kernel family compiles in, and nothing of the others
 template <int PER_QUERY>
 __device__ __forceinline__ bool admitted_as(const GraphView &gv, uint32_t slot, uint32_t query) {
-	static_assert(PER_QUERY >= 0 && PER_QUERY <= 6, "whole launch, groups, labels, ranges, sets, boxes, 64-bit boxes");
-	if constexpr (PER_QUERY == 6)
+	static_assert(PER_QUERY >= 0 && PER_QUERY <= 7, "whole launch, groups, labels, ranges, sets, boxes, 64-bit boxes, set boxes");
+	if constexpr (PER_QUERY == 7)
+		return gv.admitted_set_box(slot, query);
+	else if constexpr (PER_QUERY == 6)
 		return gv.admitted_box64(slot, query);
 	else if constexpr (PER_QUERY == 5)
 		return gv.admitted_box(slot, query);
@@ -2176,7 +2231,8 @@ constexpr int LDS_LIST_E = 64; // (no register list is that wide: MAX_LIST_REGS 
 // GROUPS: the body of k_search_groups — a launch with one predicate per query (always a TOMB launch): the level search looks
 // the query's own bitmap up (1), compares the row's label with the query's (2: k_search_labels) or tests it against the query's
 // range (3: k_search_ranges), its set (4: k_search_sets), its box (5: k_search_boxes) or its box of 64-bit ends
-// (6: k_search_boxes64), and the paths such a launch never takes are not compiled.
+// (6: k_search_boxes64) or its IN-list inside a box (7: k_search_set_boxes), and the paths such a launch never takes are not
+// compiled.
 template <int MT, int NCH, int R, int E, int THREADS, int GROUPS>
 __device__ __forceinline__ void search_engine(SearchArgs &a) {
 	static_assert(E == 0 || E == LDS_LIST_E || (E >= 1 && E <= MAX_LIST_REGS), "candidate list: registers, HBM or LDS");
@@ -2449,6 +2505,11 @@ template <int MT, int NCH, int R, int E, int THREADS = 1024>
 __global__ __launch_bounds__(THREADS) void k_search_boxes64(SearchArgs a) {
 	search_engine<MT, NCH, R, E, THREADS, 6>(a);
 }
+// ... and with one IN-list inside a box of ranges per query (vss_search_batch_by_label_set_box)
+template <int MT, int NCH, int R, int E, int THREADS = 1024>
+__global__ __launch_bounds__(THREADS) void k_search_set_boxes(SearchArgs a) {
+	search_engine<MT, NCH, R, E, THREADS, 7>(a);
+}
 
 // =========================================================================================================
 // k_search_solo — the search engine's shape for FEW queries (the single-query probe of HNSW_INDEX_SCAN, reference
@@ -2590,6 +2651,10 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) 
 template <int MT, int NCH, int R, int E, int T = 1>
 __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_boxes64(SearchArgs a) {
 	search_solo<MT, NCH, R, E, T, 6>(a);
+}
+template <int MT, int NCH, int R, int E, int T = 1>
+__global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search_solo_set_boxes(SearchArgs a) {
+	search_solo<MT, NCH, R, E, T, 7>(a);
 }
 
 // =========================================================================================================
@@ -2869,6 +2934,35 @@ __global__ __launch_bounds__(256) void k_resolve_label_boxes64(ResolveBoxes64Arg
 		const host::LabelRange64Cells c =
 		    host::label_range64_cells(host::label_word64(a.boxes[4 * i], a.boxes[4 * i + 1]), host::label_word64(a.boxes[4 * i + 2], a.boxes[4 * i + 3]));
 		a.table[1 + a.m + 2 * i] = c.lo, a.table[2 + a.m + 2 * i] = c.count;
+	}
+}
+
+// Ahead of a launch with one IN-list inside a box of ranges per query: the table GraphView::admitted_set_box reads (label_filter.h
+// has the layout next to label_set_box_table_head).  `rows` is the launch's n_queries x (2 width + 4m) matrix of travelling rows
+// (host::label_set_box_rows) in DEVICE memory; a thread writes one cell of one query, and the first ones the head and the addresses.
+struct ResolveSetBoxesArgs {
+	const uint32_t *columns[host::LABEL_COLUMNS_MAX]; // the set column, then the m range columns in call order
+	const uint32_t *rows;
+	uint32_t n_queries, width, m;
+	uint32_t wide_mask; // bit 0: the set column has 64-bit cells; bit 1 + j: range column j has
+	unsigned long long *table; // host::label_set_box_table_cells(m, padded, n_queries) cells
+};
+
+__global__ __launch_bounds__(256) void k_resolve_label_set_boxes(ResolveSetBoxesArgs a) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	const uint32_t padded = host::label_set_box_padded(a.width);
+	const uint32_t per = (uint32_t)host::label_set_box_query_cells(a.m, padded);
+	if (i == 0)
+		a.table[0] = host::label_set_box_table_head(a.m, padded, a.wide_mask);
+	if (i <= a.m)
+		a.table[1 + i] = (unsigned long long)reinterpret_cast<uintptr_t>(a.columns[i]);
+	if (i == a.m + 1 && 2 + a.m < host::label_set_box_query_base(a.m))
+		a.table[2 + a.m] = 0; // (the cell that keeps the per-query cells on an even index)
+	if (i < (uint64_t)a.n_queries * per) {
+		const uint64_t q = i / per;
+		const uint32_t j = (uint32_t)(i % per);
+		a.table[host::label_set_box_query_base(a.m) + i] =
+		    host::label_set_box_table_cell(a.rows + q * host::label_set_box_row_words(a.width, a.m), a.width, a.m, j);
 	}
 }
 

@@ -266,12 +266,16 @@ template <>
 hipError_t launch_search<VSS_MT>(const SearchArgs &a, const LaunchCfg &c) {
 	if (filter_by_box(a.gv.filter_bits)) // (either box: before any of its bits alone; their walkers are units of their own)
 		return launch_search_boxes<VSS_MT>(a, c);
+	if (filter_by_set_box(a.gv.filter_bits)) // (after both boxes, before FILTER_BY_SET and FILTER_BY_LABEL, which are tested singly)
+		return launch_search_set_boxes<VSS_MT>(a, c);
 	VSS_BY_CHUNKS(search_e, a, c)
 }
 template <>
 hipError_t launch_search_solo<VSS_MT>(const SearchArgs &a, const LaunchCfg &c) {
 	if (filter_by_box(a.gv.filter_bits))
 		return launch_search_solo_boxes<VSS_MT>(a, c);
+	if (filter_by_set_box(a.gv.filter_bits))
+		return launch_search_solo_set_boxes<VSS_MT>(a, c);
 	VSS_BY_CHUNKS(search_solo_e, a, c)
 }
 template <>

@@ -10,8 +10,9 @@
 // vss_search_batch_by_label_set, which tests it against a short list of values per query (host/label_set_check.cpp).  The index
 // keeps LABEL_COLUMNS_MAX such columns — the one above is column 0 — and vss_search_batch_by_label_box tests up to four of them
 // against one range each per query (host/label_box_check.cpp).  A column's cells are 32 or 64 bits wide, and
-// vss_search_batch_by_label_box64 tests columns of either width against ranges with 64-bit ends: the last part
-// (host/label_box64_check.cpp).
+// vss_search_batch_by_label_box64 tests columns of either width against ranges with 64-bit ends (host/label_box64_check.cpp).
+// vss_search_batch_by_label_set_box tests one column against a short list of 64-bit words per query and up to three more against
+// such ranges: the last part (host/label_set_box_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -399,6 +400,159 @@ inline void label_box64_rows(const uint64_t *lo, const uint64_t *hi, uint64_t n,
 // `rows`, and the group of every query
 inline void label_box64_groups(const uint32_t *boxes, uint64_t n, uint32_t m, std::vector<uint32_t> &rows, std::vector<uint32_t> &group_of) {
 	label_set_groups(boxes, n, 4 * m, rows, group_of);
+}
+
+// ---- per-query IN-LISTS on one column INSIDE a box of ranges (vss_search_batch_by_label_set_box): a call names one SET column and
+// m further distinct RANGE columns, 0 <= m <= 3, all of either width, mixed.  Query q brings `width` 64-bit words for the set column,
+// 1 <= width <= LABEL_SET_MAX (NO_LABEL64 pads a shorter list and equals nothing), and one range of 64-bit ends per range column.
+// Cells are read as the box64 call reads them (label_widen).  Query q admits the live rows whose row id has a cell in the set column
+// and in every range column, whose widened set cell is not NO_LABEL64 and equals one of the query's words, and which
+// label_range64_admits admits in every range column.  A row of words that is all padding is the empty predicate, and so is any
+// lo > hi; order and repeats among the words change nothing; a word of 2^32 or above matches no cell of a 32-bit column, and neither
+// does 0xFFFFFFFF there, because the cell it would match reads as NULL.  m == 0 is the set call over 64-bit words.
+// Inside the engine a predicate travels as ONE row of 2 width + 4m 32-bit words (label_set_box_rows): the set words first, then per
+// range column lo then hi, every 64-bit word as the pair (HIGH word, low word) — so the lexicographic order of the rows as 32-bit
+// words IS their order as width + 2m unsigned 64-bit words, label_set_groups' order is the contract's, and whatever carries rows of
+// 32-bit words per query or per group carries these unchanged.  The derived table: the distinct RAW rows, ascending, nothing
+// canonicalised (the same members in another order are another group), are the groups; bitmap g has bit r set iff
+// label_set_box_admits(..., r, row g); its n_bits is the smallest rows(c) over the set column and the range columns.
+constexpr uint32_t LABEL_SET_BOX_RANGES_MAX = LABEL_COLUMNS_MAX - 1;
+constexpr uint32_t LABEL_SET_BOX_ROW_WORDS_MAX = 2 * LABEL_SET_MAX + 4 * LABEL_SET_BOX_RANGES_MAX; // 76
+
+// THE admission rule, but for the row being live.  index_columns[c]: column c of the index; set: `width` 64-bit words; box: 2m 64-bit
+// words (lo_0, hi_0, ...) for the range columns columns[0 .. m).  constexpr: the kernels' forms below are proven against this very
+// code (host/label_set_box_check.cpp).
+inline constexpr bool label_set_box_admits(const LabelColumn64 *index_columns, uint32_t set_column, const uint64_t *set, uint32_t width,
+                                           const uint32_t *columns, uint32_t m, int64_t key, const uint64_t *box) {
+	const LabelColumn64 &sc = index_columns[set_column];
+	if (key < 0 || (uint64_t)key >= sc.rows)
+		return false;
+	for (uint32_t j = 0; j != m; ++j)
+		if (!label_range64_admits(index_columns[columns[j]], key, box[2 * j], box[2 * j + 1]))
+			return false;
+	const uint64_t cell = label_cell64(sc, (uint64_t)key);
+	if (cell == NO_LABEL64)
+		return false;
+	for (uint32_t j = 0; j != width; ++j)
+		if (cell == set[j])
+			return true;
+	return false;
+}
+
+// words of 32 bits in a travelling row, and where its range part begins
+inline constexpr uint32_t label_set_box_row_words(uint32_t width, uint32_t m) {
+	return 2 * width + 4 * m;
+}
+
+// The register form of the listing kernels: label[0] is the row's WIDENED cell in the set column, label[1 + j] in range column j,
+// each NO_LABEL64 for "no cell at all"; row: the group's travelling row.  No early exit: `width` 64-bit compares ORed, ONE test of
+// the set cell against NO_LABEL64 (which keeps the padding from matching the NULL cell), then label64_in_range per range column,
+// all ANDed.
+template <uint32_t M>
+inline constexpr bool label_in_set_box(const uint64_t (&label)[M + 1], const uint32_t *row, uint32_t width) {
+	bool hit = false;
+	for (uint32_t j = 0; j != width; ++j)
+		hit |= label[0] == label_word64(row + 2 * j);
+	bool in = hit & (label[0] != NO_LABEL64);
+	const uint32_t *box = row + 2 * width;
+	for (uint32_t j = 0; j != M; ++j)
+		in &= label64_in_range(label[1 + j], label_word64(box + 4 * j), label_word64(box + 4 * j + 2));
+	return in;
+}
+
+// What the walker's table holds.  Cell 0 is the head: the number of range columns m in its low byte, the PADDED set length in the
+// next byte — the words of a row padded with NO_LABEL64 to an even number, so that every query's words are whole, aligned 16-byte
+// chunks for two-word scalar loads — and from bit 16 on one bit per column, set where it is 64 bits wide: bit 16 the set column, bit
+// 17 + j range column j.  Cells 1 .. 1 + m hold the columns' addresses, the set column first.  The per-query cells begin at the next
+// EVEN cell (label_set_box_query_base): `padded` set words, then 2m cells, range column j's label_range64_cells pair at 2j, 2j + 1.
+inline constexpr uint32_t label_set_box_padded(uint32_t width) {
+	return (width + 1) & ~1u;
+}
+inline constexpr uint64_t label_set_box_table_head(uint32_t m, uint32_t padded, uint32_t wide_mask) {
+	return (uint64_t)m | (uint64_t)padded << 8 | (uint64_t)wide_mask << 16;
+}
+inline constexpr uint32_t label_set_box_head_ranges(uint64_t head) {
+	return (uint32_t)(head & 0xFF);
+}
+inline constexpr uint32_t label_set_box_head_padded(uint64_t head) {
+	return (uint32_t)(head >> 8 & 0xFF);
+}
+inline constexpr bool label_set_box_head_wide(uint64_t head, uint32_t j) { // j == 0: the set column; 1 + j: range column j
+	return (head >> (16 + j)) & 1;
+}
+inline constexpr uint64_t label_set_box_query_base(uint32_t m) {
+	return (2 + (uint64_t)m + 1) & ~1ull;
+}
+inline constexpr uint64_t label_set_box_query_cells(uint32_t m, uint32_t padded) {
+	return (uint64_t)padded + 2 * m;
+}
+inline constexpr uint64_t label_set_box_query_cell(uint32_t m, uint32_t padded, uint64_t query) { // the first of query's cells
+	return label_set_box_query_base(m) + label_set_box_query_cells(m, padded) * query;
+}
+inline constexpr uint64_t label_set_box_table_cells(uint32_t m, uint32_t padded, uint64_t n_queries) {
+	return label_set_box_query_cell(m, padded, n_queries);
+}
+// cell j < label_set_box_query_cells(m, padded) of a query whose travelling row is `row`
+inline constexpr uint64_t label_set_box_table_cell(const uint32_t *row, uint32_t width, uint32_t m, uint32_t j) {
+	const uint32_t padded = label_set_box_padded(width);
+	if (j < padded)
+		return j < width ? label_word64(row + 2 * j) : NO_LABEL64;
+	const uint32_t *pair = row + 2 * width + 4 * ((j - padded) / 2);
+	const LabelRange64Cells c = label_range64_cells(label_word64(pair), label_word64(pair + 2));
+	return (j - padded) & 1 ? c.count : c.lo;
+}
+// the walker's loop: one step tests the set cell against a chunk of two words
+inline constexpr bool label64_hits2(uint64_t label, uint64_t a, uint64_t b) {
+	return (label == a) | (label == b);
+}
+// the walker's test of a row whose widened cells are label[0] (set column) and label[1 .. 1 + m) against a query's cells
+inline constexpr bool label_set_box_cells_admit(const uint64_t *label, const uint64_t *cells, uint32_t m, uint32_t padded) {
+	bool hit = false;
+	for (uint32_t j = 0; j != padded; j += 2)
+		hit |= label64_hits2(label[0], cells[j], cells[j + 1]);
+	bool in = hit & (label[0] != NO_LABEL64);
+	for (uint32_t j = 0; j != m; ++j)
+		in &= label_range64_cell_admits(label[1 + j], cells[padded + 2 * j], cells[padded + 2 * j + 1]);
+	return in;
+}
+
+// the n x (2 width + 4m) matrix of a call's travelling rows from its three matrices (lo, hi: not read where m == 0)
+inline void label_set_box_rows(const uint64_t *sets, uint32_t width, const uint64_t *lo, const uint64_t *hi, uint64_t n, uint32_t m,
+                               std::vector<uint32_t> &rows) {
+	const uint32_t per = label_set_box_row_words(width, m);
+	rows.resize((size_t)per * n);
+	for (uint64_t q = 0; q != n; ++q) {
+		uint32_t *row = rows.data() + q * per;
+		for (uint32_t j = 0; j != width; ++j)
+			row[2 * j] = (uint32_t)(sets[q * width + j] >> 32), row[2 * j + 1] = (uint32_t)sets[q * width + j];
+		row += 2 * width;
+		for (uint32_t j = 0; j != m; ++j) {
+			const uint64_t l = lo[q * m + j], h = hi[q * m + j];
+			row[4 * j] = (uint32_t)(l >> 32), row[4 * j + 1] = (uint32_t)l;
+			row[4 * j + 2] = (uint32_t)(h >> 32), row[4 * j + 3] = (uint32_t)h;
+		}
+	}
+}
+
+// the distinct raw rows, ascending as width + 2m unsigned 64-bit words (see above), flattened, and the group of every query
+inline void label_set_box_groups(const uint32_t *rows_in, uint64_t n, uint32_t width, uint32_t m, std::vector<uint32_t> &rows,
+                                 std::vector<uint32_t> &group_of) {
+	label_set_groups(rows_in, n, label_set_box_row_words(width, m), rows, group_of);
+}
+
+// the columns of a call: which one breaks the rules, or m + 1 for none.  0: the set column is >= LABEL_COLUMNS_MAX.  1 + j: range
+// column j is >= LABEL_COLUMNS_MAX, was named before, or is the set column.
+inline constexpr uint32_t label_set_box_bad_column(uint32_t set_column, const uint32_t *columns, uint32_t m) {
+	if (set_column >= LABEL_COLUMNS_MAX)
+		return 0;
+	for (uint32_t j = 0; j != m; ++j) {
+		if (columns[j] >= LABEL_COLUMNS_MAX || columns[j] == set_column)
+			return 1 + j;
+		for (uint32_t i = 0; i != j; ++i)
+			if (columns[i] == columns[j])
+				return 1 + j;
+	}
+	return m + 1;
 }
 
 // vss_set_labels(first_rowid, n): what the range breaks, or NONE. Cells end at 2^32 (first_rowid + n == 2^32 is the last range

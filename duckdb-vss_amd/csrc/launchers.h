@@ -2,7 +2,9 @@
 // in three translation units (kernels_l2sq.hip / kernels_cosine.hip / kernels_ip.hip, all built from
 // kernels_metric.inc) so they compile in parallel; the engine picks the instantiation at run time.  The walkers of the launches
 // by label box (both boxes: filter_by_box()) are three more units, kernels_boxes_{l2sq,cosine,ip}.hip from kernels_boxes.inc:
-// launch_search / launch_search_solo hand such a launch to launch_search_boxes / launch_search_solo_boxes.
+// launch_search / launch_search_solo hand such a launch to launch_search_boxes / launch_search_solo_boxes.  The walkers of the
+// launches by label set box (filter_by_set_box()) are three more again, kernels_setboxes_{l2sq,cosine,ip}.hip from
+// kernels_setboxes.inc, behind launch_search_set_boxes / launch_search_solo_set_boxes.
 #pragma once
 #include "exact_kernels.h"
 #include "hnsw_kernels.h"
@@ -27,6 +29,10 @@ hipError_t launch_search_boxes(const SearchArgs &a, const LaunchCfg &c);
 template <int MT>
 hipError_t launch_search_solo_boxes(const SearchArgs &a, const LaunchCfg &c);
 template <int MT>
+hipError_t launch_search_set_boxes(const SearchArgs &a, const LaunchCfg &c);
+template <int MT>
+hipError_t launch_search_solo_set_boxes(const SearchArgs &a, const LaunchCfg &c);
+template <int MT>
 hipError_t launch_phase_a(const BuildArgs &a, const LaunchCfg &c);
 template <int MT>
 hipError_t launch_phase_b(const LinkArgs &a, const LaunchCfg &c);
@@ -44,6 +50,10 @@ hipError_t launch_rerank(const RerankArgs &a, const LaunchCfg &c);
 	hipError_t launch_search_boxes<MT>(const SearchArgs &, const LaunchCfg &);                                         \
 	template <>                                                                                                        \
 	hipError_t launch_search_solo_boxes<MT>(const SearchArgs &, const LaunchCfg &);                                    \
+	template <>                                                                                                        \
+	hipError_t launch_search_set_boxes<MT>(const SearchArgs &, const LaunchCfg &);                                     \
+	template <>                                                                                                        \
+	hipError_t launch_search_solo_set_boxes<MT>(const SearchArgs &, const LaunchCfg &);                                \
 	template <>                                                                                                        \
 	hipError_t launch_phase_a<MT>(const BuildArgs &, const LaunchCfg &);                                               \
 	template <>                                                                                                        \

@@ -126,7 +126,7 @@ static thread_local std::string tls_error;
 // What a search launch filters its results by.  The pointers are device memory for search_begin / search_launch and host
 // memory for search_host, which stages what they name and hands search_launch the staged copy.
 struct SearchPredicate {
-	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE, BY_SET, BY_BOX, BY_BOX64 } kind = NONE;
+	enum Kind { NONE, ONE_BITMAP, PER_QUERY, BY_LABEL, BY_RANGE, BY_SET, BY_BOX, BY_BOX64, BY_SET_BOX } kind = NONE;
 	const uint64_t *bitmap = nullptr;                        // ONE_BITMAP: the whole launch's; bit set = row id admitted
 	FilterGroupBatch batches[MAX_FILTER_GROUP_BATCHES] = {}; // PER_QUERY: the table of every batch of the launch
 	uint64_t n_bits = 0;                                     // (BY_LABEL: the cells of the index's label column)
@@ -136,6 +136,8 @@ struct SearchPredicate {
 	uint32_t width = 0;
 	const uint32_t *boxes = nullptr;                         // BY_BOX: 2 * n_columns words per query, (lo, hi) per named column
 	                                                         // BY_BOX64: 4 * n_columns words per query (label_box64_rows)
+	                                                         // BY_SET_BOX: the travelling rows (label_set_box_rows); `width` is the
+	                                                         // set's, columns[0] the set column, columns[1 ..] the range columns
 	uint32_t n_columns = 0, columns[LABEL_COLUMNS_MAX] = {}; // BY_BOX: the label columns the call names (n_bits: the shortest one's cells)
 
 	// a launch of one batch against the index's label column: query q admits the rows labelled want[q]
@@ -171,6 +173,14 @@ struct SearchPredicate {
 	static SearchPredicate by_box64(const uint32_t *boxes, const uint32_t *columns, uint32_t m, uint64_t shortest_rows) {
 		SearchPredicate p = by_box(boxes, columns, m, shortest_rows);
 		p.kind = BY_BOX64;
+		return p;
+	}
+
+	// ... query q admits what row q of `rows` (2 width + 4 (n - 1) words, label_set_box_rows) admits: columns[0] is the set column,
+	// columns[1 .. n) the range columns
+	static SearchPredicate by_set_box(const uint32_t *rows, uint32_t width, const uint32_t *columns, uint32_t n, uint64_t shortest_rows) {
+		SearchPredicate p = by_box(rows, columns, n, shortest_rows);
+		p.kind = BY_SET_BOX, p.width = width;
 		return p;
 	}
 
@@ -232,7 +242,7 @@ struct LabelBoxColumns {
 	}
 };
 
-// The groups the rows of a scan call are listed by, made by one of the six factories only.  Bitmaps: group g = the rows bitmap g
+// The groups the rows of a scan call are listed by, made by one of the seven factories only.  Bitmaps: group g = the rows bitmap g
 // of a DEVICE table admits.  Labels: group g = the rows the index's label column gives values[g], the ascending distinct wanted
 // values (HOST memory); no bitmap exists.  Either way query q reads group group_of[q] (HOST memory; nullptr: all read group 0),
 // and the walk of the graph-routed queries reads the column's DEVICE twin: group numbers under bitmaps, wanted labels under labels.
@@ -244,6 +254,8 @@ struct LabelBoxColumns {
 // raw rows of 2m words (HOST memory, flattened; width = 2m); the walk reads every query's row of the DEVICE matrix d_sets likewise.
 // n_bits is the shortest named column's cells.
 // Boxes of 64-bit ends: the same with rows of 4m 32-bit words (label_box64_rows; width = 4m) over columns of either width.
+// Set boxes: group g = the rows rows[g] admits, the ascending distinct travelling rows of 2 set_width + 4m words (label_set_box_rows;
+// width = that, at most 76); `box` names the set column FIRST and the m range columns after it.
 struct GroupedRows {
 	const uint64_t *d_table = nullptr;  // bitmaps: n_groups bitmaps of n_bits bits
 	uint64_t n_groups = 0, n_bits = 0;  // (labels: the distinct wanted values; the cells of the label column)
@@ -256,6 +268,7 @@ struct GroupedRows {
 	const uint32_t *d_sets = nullptr;   // sets: the call's n_queries x width matrix
 	uint32_t width = 0;                 // sets: words per row
 	LabelBoxColumns box;                // boxes: the named columns
+	uint32_t set_width = 0;             // set boxes: the words of a query's list
 
 	static GroupedRows bitmaps(const uint64_t *d_table, uint64_t n_groups, uint64_t n_bits, HostWords group_of, DeviceWords d_group_of) {
 		GroupedRows g;
@@ -299,11 +312,19 @@ struct GroupedRows {
 		return g;
 	}
 
+	static GroupedRows set_boxes(const std::vector<uint32_t> &rows, uint32_t set_width, const LabelBoxColumns &box, HostWords group_of,
+	                             DeviceWords d_rows) {
+		GroupedRows g;
+		g.by_set_box = true, g.rows = rows.data(), g.set_width = set_width, g.width = label_set_box_row_words(set_width, box.m - 1), g.box = box;
+		g.n_groups = rows.size() / g.width, g.n_bits = box.shortest_rows(), g.group_of = group_of.p, g.d_sets = d_rows.p;
+		return g;
+	}
+
 	// words that name one used group to the list kernels: its table group, its wanted value, the two ends of its range, the
 	// words of its set, or the pairs of its box.  The walk of the graph-routed queries needs as many words per query gathered into
 	// the compact batch.
 	uint64_t group_cells() const {
-		return by_set || by_box || by_box64 ? width : by_range ? 2 : 1;
+		return by_set || by_box || by_box64 || by_set_box ? width : by_range ? 2 : 1;
 	}
 	// Those words beyond the one column k_route_gather takes along (d_group_of; under sets it takes none): `per` words a query,
 	// row-major from `words`, to word `at` of the compact batch's ng * group_cells() words — or words == nullptr, nothing more.
@@ -313,7 +334,7 @@ struct GroupedRows {
 		uint64_t at;
 	};
 	WalkWords more_walk_words(uint64_t ng) const {
-		if (by_set || by_box || by_box64)
+		if (by_set || by_box || by_box64 || by_set_box)
 			return {d_sets, width, 0};
 		if (by_range)
 			return {d_hi, 1, ng};
@@ -369,10 +390,21 @@ struct GroupedRows {
 		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
 		return a;
 	}
+	// ... and in the set-box form: travelling rows, the set column first among the columns
+	SetBoxListArgs set_box_list_args(const FilterListArgs &l) const {
+		SetBoxListArgs a = {};
+		a.keys = l.keys, a.rows_n = l.rows, a.n_blocks = l.n_blocks;
+		for (uint32_t j = 0; j != box.m; ++j)
+			a.labels[j] = box.cells[j], a.labelled_rows[j] = box.rows[j];
+		a.wide = box.wide_mask();
+		a.rows = l.groups, a.width = set_width, a.u_begin = l.u_begin, a.u_end = l.u_end;
+		a.counts = l.counts, a.list_base = l.list_base, a.lists = l.lists;
+		return a;
+	}
 	// the cells of a plan's used groups, group_cells() words each: plan.groups, or their values / pairs / rows in `scratch` (which
 	// outlives the upload like plan.groups)
 	const uint32_t *used_group_cells(const ExactFilterPlan &plan, std::vector<uint32_t> &scratch) const {
-		if (by_set || by_box || by_box64) {
+		if (by_set || by_box || by_box64 || by_set_box) {
 			scratch.resize((size_t)width * plan.groups.size());
 			for (size_t u = 0; u != plan.groups.size(); ++u)
 				std::copy(rows + (size_t)plan.groups[u] * width, rows + ((size_t)plan.groups[u] + 1) * width, scratch.begin() + u * width);
@@ -415,6 +447,13 @@ struct GroupedRows {
 			case 3: hipLaunchKernelGGL(k_box64_list_count<3>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
 			default: hipLaunchKernelGGL(k_box64_list_count<4>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
 			}
+		else if (by_set_box) // (one kernel per number of range columns)
+			switch (box.m - 1) {
+			case 0: hipLaunchKernelGGL(k_set_box_list_count<0>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			case 1: hipLaunchKernelGGL(k_set_box_list_count<1>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			case 2: hipLaunchKernelGGL(k_set_box_list_count<2>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			default: hipLaunchKernelGGL(k_set_box_list_count<3>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			}
 		else
 			hipLaunchKernelGGL(k_filter_list_count, grid, dim3(256), 0, stream, l);
 	}
@@ -441,6 +480,13 @@ struct GroupedRows {
 			case 3: hipLaunchKernelGGL(k_box64_list_scatter<3>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
 			default: hipLaunchKernelGGL(k_box64_list_scatter<4>, grid, dim3(256), 0, stream, box64_list_args(l)); break;
 			}
+		else if (by_set_box)
+			switch (box.m - 1) {
+			case 0: hipLaunchKernelGGL(k_set_box_list_scatter<0>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			case 1: hipLaunchKernelGGL(k_set_box_list_scatter<1>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			case 2: hipLaunchKernelGGL(k_set_box_list_scatter<2>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			default: hipLaunchKernelGGL(k_set_box_list_scatter<3>, grid, dim3(256), 0, stream, set_box_list_args(l)); break;
+			}
 		else
 			hipLaunchKernelGGL(k_filter_list_scatter, grid, dim3(256), 0, stream, l);
 	}
@@ -448,6 +494,8 @@ struct GroupedRows {
 	// (k_route_gather's column first, more_walk_words() where it says)
 	SearchPredicate walk_predicate(const uint32_t *d_compact, uint64_t ng) const {
 		const uint32_t *d_compact_groups = d_compact;
+		if (by_set_box)
+			return SearchPredicate::by_set_box(d_compact, set_width, box.columns, box.m, n_bits);
 		if (by_box64)
 			return SearchPredicate::by_box64(d_compact, box.columns, box.m, n_bits);
 		if (by_box)
@@ -463,7 +511,7 @@ struct GroupedRows {
 	}
 
 private:
-	bool by_label = false, by_range = false, by_set = false, by_box = false, by_box64 = false;
+	bool by_label = false, by_range = false, by_set = false, by_box = false, by_box64 = false, by_set_box = false;
 	GroupedRows() = default;
 };
 
@@ -556,7 +604,7 @@ struct vss_index {
 	uint64_t label_column_bytes[LABEL_COLUMNS_MAX] = {};
 	// A column's cells are 32 bits wide or 64 (vss_set_label_column64): 0 while it is empty, then the width of the setter that made
 	// it, until it is cleared.  A 64-bit column keeps its cells in the same buffer, TWO words a cell (label_cells(c).n counts words),
-	// and only the search by label box64 reads it.
+	// and only the searches by label box64 and by label set box read it.
 	uint32_t label_width[LABEL_COLUMNS_MAX] = {};
 	std::atomic<uint64_t> label_bytes {0}; // every column's; vss_memory_usage (read without a lock)
 	DevBuf<uint32_t> &label_cells(uint32_t column) {
@@ -1806,6 +1854,27 @@ struct vss_index {
 			HIP_TRY(hipGetLastError());
 			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
 			a.gv.filter_bits = std::min<uint64_t>(box.shortest_rows(), FILTER_BY_SET - 1) | FILTER_PER_QUERY | FILTER_BY_BOX64;
+		} else if (p.kind == SearchPredicate::BY_SET_BOX) {
+			// ... and by the *_set_boxes kernels (GraphView::admitted_set_box): the head, the 1 + m addresses (set column first), then
+			// every query's padded set words and 2m range cells.  No flag bit of its own: FILTER_BY_LABEL and FILTER_BY_SET without
+			// FILTER_BY_RANGE.
+			LabelBoxColumns box;
+			if (n_batches != 1 || !named_label_columns(p.columns, p.n_columns, box) || p.width < 1 || p.width > LABEL_SET_MAX)
+				return fail("search by label set box: one batch per launch, over 1 to %u distinct label columns that have been set, set "
+				            "width 1 to %u", (unsigned)LABEL_COLUMNS_MAX, (unsigned)LABEL_SET_MAX);
+			const uint32_t m = box.m - 1, padded = label_set_box_padded(p.width);
+			if (!c.d_group_bitmap.try_grow(label_set_box_table_cells(m, padded, cap_q)))
+				return fail("search by label set box: no device memory for the predicates of %llu queries", (unsigned long long)cap_q);
+			count_group_tables(c);
+			ResolveSetBoxesArgs res = {};
+			std::copy(box.cells, box.cells + box.m, res.columns);
+			res.rows = p.boxes, res.n_queries = (uint32_t)nq, res.width = p.width, res.m = m, res.wide_mask = box.wide_mask();
+			res.table = reinterpret_cast<unsigned long long *>(c.d_group_bitmap.p);
+			hipLaunchKernelGGL(k_resolve_label_set_boxes, dim3((uint32_t)(nq * label_set_box_query_cells(m, padded) / 256 + 1)), dim3(256), 0,
+			                   c.stream, res);
+			HIP_TRY(hipGetLastError());
+			a.gv.filter = reinterpret_cast<const unsigned long long *>(c.d_group_bitmap.p);
+			a.gv.filter_bits = std::min<uint64_t>(box.shortest_rows(), FILTER_BY_SET - 1) | FILTER_PER_QUERY | FILTER_BY_SET_BOX;
 		}
 		for (uint64_t b = 0; b != MAX_COALESCED; ++b) {
 			const bool used = b < n_batches;
@@ -2065,6 +2134,14 @@ struct vss_index {
 		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, boxes, nq * 2 * m * end_words * 4, hipMemcpyHostToDevice, c.stream));
 		return VSS_OK;
 	}
+	// the travelling rows of a call by label set box (HOST memory), in the same buffer: the nq x row_words matrix as it is
+	int stage_label_set_boxes(SearchCtx &c, const uint32_t *rows, uint32_t row_words, uint64_t nq) {
+		if (!c.d_group_of.try_grow(nq * row_words))
+			return fail("search by label set box: no device memory for the predicates of %llu queries", (unsigned long long)nq);
+		count_group_tables(c);
+		HIP_TRY(hipMemcpyAsync(c.d_group_of.p, rows, nq * row_words * 4, hipMemcpyHostToDevice, c.stream));
+		return VSS_OK;
+	}
 	// queries in, result buffers ensured ...
 	void stage_queries(SearchCtx &c, const float *queries, uint64_t nq, uint64_t k) {
 		c.d_q.ensure(nq * dim, 0, c.stream), c.d_out_count.ensure(nq, 0, c.stream);
@@ -2177,6 +2254,10 @@ struct vss_index {
 				    if (const int rc = stage_label_boxes(c, filter.boxes, filter.n_columns, nq, 2))
 					    return rc;
 				    staged = SearchPredicate::by_box64(c.d_group_of.p, filter.columns, filter.n_columns, filter.n_bits);
+			    } else if (filter.kind == SearchPredicate::BY_SET_BOX) {
+				    if (const int rc = stage_label_set_boxes(c, filter.boxes, label_set_box_row_words(filter.width, filter.n_columns - 1), nq))
+					    return rc;
+				    staged = SearchPredicate::by_set_box(c.d_group_of.p, filter.width, filter.columns, filter.n_columns, filter.n_bits);
 			    }
 			    return VSS_OK;
 		    },
@@ -2855,6 +2936,30 @@ struct vss_index {
 		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_boxes(c, boxes, box.m, hc.nq, 2); },
 		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
 			    return by_box64_launch(b, HostWords(boxes), box, DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
+		    });
+	}
+
+	// ------------------------------------------------------------------ search by label set box (label_filter.h)
+	// An IN-list on one column inside a box of ranges: `rows` is nq travelling rows (label_set_box_rows), `box` names the set column
+	// first and the range columns after it.
+	int by_set_box_launch(const DeviceBatch &b, HostWords rows_in, uint32_t set_width, const LabelBoxColumns &box, DeviceWords d_rows,
+	                      uint64_t route_c, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+		std::vector<uint32_t> rows, group_of;
+		label_set_box_groups(rows_in.p, b.nq, set_width, box.m - 1, rows, group_of);
+		const GroupedRows g = GroupedRows::set_boxes(rows, set_width, box, HostWords(group_of.data()), d_rows);
+		if (!d_rows.p) {
+			route.assign(b.nq, FILTER_ROUTE_EXACT);
+			return exact_filtered_launch(b, g, out);
+		}
+		return filtered_auto(b, g, route_c, out, route);
+	}
+
+	int by_set_box_host(const HostCall &hc, bool exact, const uint32_t *rows, uint32_t set_width, const LabelBoxColumns &box, uint64_t route_c) {
+		const uint32_t row_words = label_set_box_row_words(set_width, box.m - 1);
+		return staged_call(
+		    hc, true, [&](SearchCtx &c) { return exact ? (int)VSS_OK : stage_label_set_boxes(c, rows, row_words, hc.nq); },
+		    [&](SearchCtx &c, const DeviceBatch &b, const DeviceAnswers &out, std::vector<uint8_t> &route) {
+			    return by_set_box_launch(b, HostWords(rows), set_width, box, DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, out, route);
 		    });
 	}
 
@@ -4516,6 +4621,118 @@ int vss_search_batch_by_label_box64_device(vss_index *h, const float *Q, uint64_
 				return rc;
 		} else if (const int rc = h->by_box64_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(boxes.data()), box,
 		                                             DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, {out, out_d, out_counts}, route))
+			return rc;
+		h->route_to_device(route, out_route);
+		return VSS_OK;
+	})
+}
+
+// ---- the search by label set box: the mode is refused first, then the set width, the number of range columns, null sets / lo / hi,
+// a column out of range, named twice or named beside the set column — all before anything is launched or written — then a column
+// that was never set, then the null pointers and the query count every call by label refuses.  `box` names the set column first.
+static int check_by_label_set_box(vss_index *h, const char *what, const float *Q, uint64_t nq, uint32_t set_column, const void *sets,
+                                  uint32_t set_width, const uint32_t *columns, uint64_t m, const void *lo, const void *hi, int mode,
+                                  const int64_t *out, const uint32_t *out_counts, LabelBoxColumns &box) {
+	if (mode != VSS_BY_LABEL_GRAPH && mode != VSS_BY_LABEL_EXACT && mode != VSS_BY_LABEL_AUTO)
+		return h->fail("%s: mode %d is none of VSS_BY_LABEL_GRAPH (0), _EXACT (1), _AUTO (2)", what, mode);
+	if (set_width < 1 || set_width > VSS_LABEL_SET_MAX)
+		return h->fail("%s: set_width %u is not within 1 .. VSS_LABEL_SET_MAX (%d); longer lists take the bitmap calls", what,
+		               (unsigned)set_width, VSS_LABEL_SET_MAX);
+	if (m > LABEL_SET_BOX_RANGES_MAX)
+		return h->fail("%s: n_columns %llu is not within 0 .. %u (the set column takes one of the VSS_LABEL_COLUMNS_MAX slots)", what,
+		               (unsigned long long)m, (unsigned)LABEL_SET_BOX_RANGES_MAX);
+	if (nq && !sets)
+		return h->fail("%s: null sets pointer for %llu queries", what, (unsigned long long)nq);
+	if (nq && m && (!lo || !hi))
+		return h->fail("%s: null lo / hi pointer for %llu queries", what, (unsigned long long)nq);
+	if (m && !columns)
+		return h->fail("%s: null columns pointer", what);
+	if (const uint32_t bad = label_set_box_bad_column(set_column, columns, (uint32_t)m); bad != m + 1) {
+		if (bad == 0)
+			return h->fail("%s: set column %u is not below VSS_LABEL_COLUMNS_MAX (%d)", what, (unsigned)set_column, VSS_LABEL_COLUMNS_MAX);
+		const uint32_t c = columns[bad - 1];
+		return c >= LABEL_COLUMNS_MAX ? h->fail("%s: column %u is not below VSS_LABEL_COLUMNS_MAX (%d)", what, (unsigned)c, VSS_LABEL_COLUMNS_MAX)
+		       : c == set_column      ? h->fail("%s: column %u is the set column and cannot carry a range too", what, (unsigned)c)
+		                              : h->fail("%s: column %u is named twice", what, (unsigned)c);
+	}
+	uint32_t all[LABEL_COLUMNS_MAX] = {set_column};
+	for (uint32_t j = 0; j != m; ++j)
+		all[1 + j] = columns[j];
+	for (uint32_t j = 0; j != m + 1; ++j)
+		if (!h->label_cells(all[j]).p)
+			return h->fail("%s: the index has no label column %u (call vss_set_label_column or vss_set_label_column64 first; vss_load, "
+			               "vss_clear_labels and vss_clear_label_column drop it)", what, (unsigned)all[j]);
+	if (nq && (!Q || !out || !out_counts))
+		return h->fail("%s: null query / row-id / count pointer", what);
+	if (nq > 0xFFFFFFFFull)
+		return h->fail("%s: at most 2^32 - 1 queries per call", what);
+	if (!h->named_label_columns(all, m + 1, box))
+		return h->fail("%s: the named label columns cannot be read", what);
+	return VSS_OK;
+}
+
+int vss_search_batch_by_label_set_box(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, uint32_t set_column,
+                                      const uint64_t *sets, uint32_t set_width, const uint32_t *columns, uint64_t n_columns,
+                                      const uint64_t *lo, const uint64_t *hi, int mode, uint64_t route_c, int64_t *out, float *out_d,
+                                      uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_by_label_set_box(h, "vss_search_batch_by_label_set_box", Q, nq, set_column, sets, set_width, columns, n_columns, lo, hi, mode,
+		                           out, out_counts, box) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		std::vector<uint32_t> rows;
+		label_set_box_rows(sets, set_width, lo, hi, nq, box.m - 1, rows);
+		if (mode != VSS_BY_LABEL_GRAPH)
+			return h->by_set_box_host({Q, nq, k, ef, out, out_d, out_counts, out_route}, mode == VSS_BY_LABEL_EXACT, rows.data(), set_width, box,
+			                          route_c);
+		if (out_route)
+			std::memset(out_route, FILTER_ROUTE_GRAPH, nq);
+		return h->search_host(Q, nq, k, ef, out, out_d, out_counts, false,
+		                      SearchPredicate::by_set_box(rows.data(), set_width, box.columns, box.m, box.shortest_rows()));
+	})
+}
+
+int vss_search_batch_by_label_set_box_device(vss_index *h, const float *Q, uint64_t nq, uint64_t k, uint64_t ef, uint32_t set_column,
+                                             const uint64_t *sets, uint32_t set_width, const uint32_t *columns, uint64_t n_columns,
+                                             const uint64_t *lo, const uint64_t *hi, int mode, uint64_t route_c, int64_t *out, float *out_d,
+                                             uint32_t *out_counts, uint8_t *out_route) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_by_label_set_box(h, "vss_search_batch_by_label_set_box_device", Q, nq, set_column, sets, set_width, columns, n_columns, lo,
+		                           hi, mode, out, out_counts, box) != VSS_OK)
+			return VSS_ERROR;
+		if (!nq || !k)
+			return VSS_OK;
+		// the plans read the predicates on the host, and the walk reads them as ONE matrix of travelling rows: the three matrices
+		// come back (8 * (set_width + 2 * n_columns) bytes per query) and go to context 0 as label_set_box_rows lays them out
+		const uint32_t m = box.m - 1;
+		const auto to_host = [&](const uint64_t *d_words, uint64_t n) {
+			const std::vector<uint32_t> w = h->words_to_host(reinterpret_cast<const uint32_t *>(d_words), 2 * n);
+			std::vector<uint64_t> v(n);
+			std::memcpy(v.data(), w.data(), n * 8);
+			return v;
+		};
+		const std::vector<uint64_t> sets_h = to_host(sets, nq * set_width);
+		const std::vector<uint64_t> lo_h = m ? to_host(lo, nq * m) : std::vector<uint64_t>(), hi_h = m ? to_host(hi, nq * m) : std::vector<uint64_t>();
+		std::vector<uint32_t> rows;
+		label_set_box_rows(sets_h.data(), set_width, lo_h.data(), hi_h.data(), nq, m, rows);
+		auto &c = h->context(0);
+		const bool exact = mode == VSS_BY_LABEL_EXACT;
+		if (!exact) {
+			if (const int rc = h->stage_label_set_boxes(c, rows.data(), label_set_box_row_words(set_width, m), nq))
+				return rc;
+			HIP_TRY(hipStreamSynchronize(c.stream)); // (`rows` is pageable memory; the count kernels run on the index stream)
+		}
+		std::vector<uint8_t> route(nq, FILTER_ROUTE_GRAPH);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			SearchRequest r = h->request(0, &Q, 1, nq, k, ef, &out, &out_d, &out_counts);
+			r.predicate = SearchPredicate::by_set_box(c.d_group_of.p, set_width, box.columns, box.m, box.shortest_rows());
+			if (const int rc = h->search_launch(r))
+				return rc;
+		} else if (const int rc = h->by_set_box_launch({0, Q, (uint32_t)h->dim, nq, k, ef}, HostWords(rows.data()), set_width, box,
+		                                               DeviceWords(exact ? nullptr : c.d_group_of.p), route_c, {out, out_d, out_counts}, route))
 			return rc;
 		h->route_to_device(route, out_route);
 		return VSS_OK;

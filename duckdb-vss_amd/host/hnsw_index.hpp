@@ -319,6 +319,19 @@ public:
 			                                       counts, routes);
 		});
 	}
+	// The same chunk under `items.grp IN (the groups this user may see) AND items.ts >= q.since [AND ...]`: an IN-list on one label
+	// column inside a box of ranges over up to three more (vss_search_batch_by_label_set_box).  sets: n_queries x set_width 64-bit
+	// words, a shorter list padded with VSS_NO_LABEL64; lo and hi: n_queries x n_columns 64-bit ends for the range columns (not read
+	// where n_columns == 0, which is the set call over 64-bit words).  Columns of either width, mixed.
+	idx_t ExecuteMultiScanBatchByLabelSetBox(IndexScanState &state_p, const float *queries, idx_t n_queries, idx_t limit, uint32_t set_column,
+	                                         const uint64_t *sets, uint32_t set_width, const uint32_t *columns, idx_t n_columns,
+	                                         const uint64_t *lo, const uint64_t *hi, std::vector<uint32_t> *counts_out,
+	                                         std::vector<uint8_t> *routes_out = nullptr, int mode = VSS_BY_LABEL_AUTO, uint64_t route_c = 0) {
+		return ScanChunk(state_p, n_queries, limit, counts_out, routes_out, [&](idx_t ef, row_t *ids, uint32_t *counts, uint8_t *routes) {
+			return vss_search_batch_by_label_set_box(index, queries, n_queries, limit, ef, set_column, sets, set_width, columns, n_columns, lo,
+			                                         hi, mode, route_c, ids, nullptr, counts, routes);
+		});
+	}
 	// A label column of 64-bit cells (vss_set_label_column64): the column must be empty or 64 bits wide already; ClearLabelColumn
 	// forgets a column's width.  LabelColumnWidth: 0 (no cells), 32 or 64.
 	void SetLabelColumn64(uint32_t column, idx_t first_rowid, const uint64_t *labels, idx_t n) {

@@ -581,6 +581,48 @@ public:
 			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
 		}
 	}
+	// An IN-list on one label column inside a box of ranges (vss_search_batch_by_label_set_box_device per shard, every shard over
+	// its own copy of the columns, the answers merged as SearchBatchByLabelBox64 merges them).  Modes, shard_routes, exchange and
+	// merge are SearchBatchByLabelBox64's; the three matrices travel as UploadTables' group numbers, every 64-bit word as a PAIR
+	// of words in memory order: the sets' 2 * n * set_width words first, then lo's and hi's 2 * n * n_columns each — every matrix
+	// begins a multiple of 8 bytes in, aligned for the device to read it as 64-bit words again.
+	void SearchBatchByLabelSetBox(const float *queries, idx_t n, idx_t k, idx_t ef, uint32_t set_column, const uint64_t *sets, uint32_t set_width,
+	                              const uint32_t *columns, idx_t n_columns, const uint64_t *lo, const uint64_t *hi, int mode, uint64_t route_c,
+	                              row_t *out_rowids, float *out_distances, uint32_t *out_counts, std::vector<uint8_t> *shard_routes = nullptr) {
+		if (shard_routes)
+			shard_routes->assign(shards.size() * n, 0);
+		if (!n || !k)
+			return;
+		if (set_width < 1 || set_width > VSS_LABEL_SET_MAX || !sets)
+			throw InternalException("Failed to search the HNSW index: search by label set box needs 1 to 32 words per query");
+		if (n_columns > VSS_LABEL_COLUMNS_MAX - 1 || (n_columns && (!columns || !lo || !hi)))
+			throw InternalException("Failed to search the HNSW index: search by label set box names 0 to 3 range columns with both ends of "
+			                        "every query's ranges");
+		Ensure(n, k);
+		const idx_t set_words = 2 * n * set_width, end_words = 2 * n * n_columns; // of one matrix
+		std::vector<uint32_t> words(set_words + 2 * end_words);
+		std::memcpy(words.data(), sets, set_words * 4);
+		if (end_words) {
+			std::memcpy(words.data() + set_words, lo, end_words * 4);
+			std::memcpy(words.data() + set_words + end_words, hi, end_words * 4);
+		}
+		UploadTables(nullptr, 0, words.data(), words.size());
+		Probe(
+		    queries, n, k, out_rowids, out_distances, out_counts,
+		    [&](Shard &s, row_t *keys, float *dist) {
+			    const uint32_t *d_words = bitmaps[s.bitmap].group_of;
+			    Vss(s, vss_search_batch_by_label_set_box_device(
+			               s.index->Handle(), s.d_q, n, k, ef, set_column, reinterpret_cast<const uint64_t *>(d_words), set_width, columns, n_columns,
+			               end_words ? reinterpret_cast<const uint64_t *>(d_words + set_words) : nullptr,
+			               end_words ? reinterpret_cast<const uint64_t *>(d_words + set_words + end_words) : nullptr, mode, route_c, keys, dist,
+			               s.d_cnt, s.d_route));
+		    },
+		    [&](Shard &s) { Vss(s, vss_synchronize(s.index->Handle())); });
+		for (size_t g = 0; shard_routes && g != shards.size(); ++g) {
+			Hip(hipSetDevice(shards[g].device), "hipSetDevice");
+			Hip(hipMemcpy(shard_routes->data() + g * n, shards[g].d_route, n, hipMemcpyDeviceToHost), "copy routes");
+		}
+	}
 	// Query q admits the live rows whose label is one of sets[q * width .. (q + 1) * width) (VSS_NO_LABEL pads a shorter list and
 	// equals nothing; a VSS_NO_LABEL cell is in no set): vss_search_batch_by_label_set_device per shard, every shard holding the
 	// whole column.  Modes, shard_routes, exchange and merge are SearchBatchByLabel's; the matrix travels as UploadTables' group

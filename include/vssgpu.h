@@ -360,7 +360,8 @@ int vss_search_batch_by_label_set_device(vss_index *index, const float *d_querie
  * VSS_OK and writes nothing.
  * The _device form takes device pointers for everything but `columns` (d_out_distances and d_out_route may be NULL), copies d_lo
  * and d_hi back (8 * n_columns bytes per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin
- * forms; IN-lists or OR inside a box and more than four columns keep the bitmap calls; 64-bit columns have the box64 call below. */
+ * forms; OR inside a box and more than four columns keep the bitmap calls; 64-bit columns have the box64 call below, and an IN-list
+ * inside a box the set_box call below that. */
 #define VSS_LABEL_COLUMNS_MAX 4
 int vss_set_label_column(vss_index *index, uint32_t column, uint64_t first_rowid, const uint32_t *labels, uint64_t n);
 int vss_set_label_column_device(vss_index *index, uint32_t column, uint64_t first_rowid, const uint32_t *d_labels, uint64_t n);
@@ -399,7 +400,8 @@ int vss_search_batch_by_label_box_device(vss_index *index, const float *d_querie
  * vss_search_batch_by_label_box.
  * Errors: those of the box call, in its order, except that no width is refused.  The _device form copies d_lo and d_hi back
  * (16 * n_columns bytes per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin forms; there is no
- * 64-bit equality or set call of its own (a box with lo == hi is the equality). */
+ * 64-bit equality call of its own (a box with lo == hi is the equality); the 64-bit set call is vss_search_batch_by_label_set_box
+ * with n_columns == 0, below. */
 #define VSS_NO_LABEL64 0xFFFFFFFFFFFFFFFFull
 int vss_set_label_column64(vss_index *index, uint32_t column, uint64_t first_rowid, const uint64_t *labels, uint64_t n);
 int vss_set_label_column64_device(vss_index *index, uint32_t column, uint64_t first_rowid, const uint64_t *d_labels, uint64_t n);
@@ -412,6 +414,44 @@ int vss_search_batch_by_label_box64_device(vss_index *index, const float *d_quer
                                            const uint32_t *columns, uint64_t n_columns, const uint64_t *d_lo, const uint64_t *d_hi,
                                            int mode, uint64_t route_c, int64_t *d_out_rowids, float *d_out_distances,
                                            uint32_t *d_out_counts, uint8_t *d_out_route);
+/* ---- an IN-list on one label column inside a box of ranges (csrc/label_filter.h) ------------------------------------------------
+ * For `items.grp IN (the groups this user may see) AND items.ts >= q.since [AND items.price BETWEEN ...]`.  set_column is one of
+ * the VSS_LABEL_COLUMNS_MAX column slots, of either width.  `sets` is a row-major n_queries x set_width matrix of uint64_t, 1 <=
+ * set_width <= VSS_LABEL_SET_MAX; a shorter list is padded with VSS_NO_LABEL64.  columns[0 .. n_columns) are the RANGE columns, 0
+ * <= n_columns <= 3, all distinct and none equal to set_column, of either width, mixed; lo and hi are n_queries x n_columns matrices
+ * of uint64_t as in the box64 call, and with n_columns == 0 they are not read and may be NULL — that is the set call over 64-bit
+ * words.  Cells are read as the box64 call reads them: a 32-bit cell zero-extended, its VSS_NO_LABEL as VSS_NO_LABEL64.
+ * Query q admits a live row of id r iff r < vss_label_column_rows(c) for the set column and every named range column; the widened
+ * cell of the set column is not VSS_NO_LABEL64 and equals sets[q, j] for some j < set_width; and for every range column j the
+ * widened cell is not VSS_NO_LABEL64 and lo[q, j] <= cell <= hi[q, j], compared unsigned.  A padding word equals nothing: a row of
+ * `sets` that is all padding is the empty predicate (count 0, ids -1), and so is any lo > hi.  Order and repeats within a row of
+ * `sets` change nothing of what it admits.  A word of 2^32 or above matches no cell of a 32-bit column, and neither does
+ * 0xFFFFFFFF there (the cell it would match reads as NULL).  hi == VSS_NO_LABEL64 is "no upper bound" and still rejects NULL cells.
+ * A column that is not named constrains nothing.  mode, route_c, out_route, k and ef as for vss_search_batch_by_label_box64.
+ * Contract: form the n_queries x (set_width + 2 n_columns) matrix of 64-bit words whose row q is (sets[q,0], ..., sets[q,w-1],
+ * lo[q,0], hi[q,0], lo[q,1], hi[q,1], ...).  Its distinct RAW rows, ascending lexicographically as unsigned 64-bit words and not
+ * canonicalised (the same members in another order are another group), are the groups; bitmap g = {r : the rule admits r for row
+ * g}, n_bits = the smallest vss_label_column_rows(c) over the set column and the named range columns, group_of[q] = the index of
+ * query q's row.  In each of the three modes the call returns cell for cell what the bitmap call of that mode returns for that
+ * table — row ids, f32 distance bits, counts, routes — and leaves the same counters behind.
+ * Errors, in this order: a mode other than the three; set_width 0 or above VSS_LABEL_SET_MAX; n_columns > 3; `sets` NULL with
+ * n_queries > 0, or lo / hi NULL with n_queries > 0 and n_columns > 0; a bad column (set_column or a named column >=
+ * VSS_LABEL_COLUMNS_MAX, a named column repeated or equal to set_column; the message names it); a column that was never set ("no
+ * label column" and its number); then the errors of the mode's own call.  n_queries == 0 or k == 0 returns VSS_OK having done
+ * nothing.  The _device form takes device pointers for everything but `columns` (d_out_distances and d_out_route may be NULL),
+ * copies d_sets, d_lo and d_hi back (8 * (set_width + 2 n_columns) bytes per query) and runs on context 0.  Not available in the
+ * pipelined / multi-batch _begin forms, and the columns are not persisted, as for its siblings.  More than one set term per
+ * predicate, OR across columns and lists beyond VSS_LABEL_SET_MAX values keep the bitmap calls; a query's list is neither
+ * canonicalised nor de-duplicated. */
+int vss_search_batch_by_label_set_box(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                      uint32_t set_column, const uint64_t *sets, uint32_t set_width, const uint32_t *columns,
+                                      uint64_t n_columns, const uint64_t *lo, const uint64_t *hi, int mode, uint64_t route_c,
+                                      int64_t *out_rowids, float *out_distances, uint32_t *out_counts, uint8_t *out_route);
+int vss_search_batch_by_label_set_box_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k, uint64_t ef,
+                                             uint32_t set_column, const uint64_t *d_sets, uint32_t set_width, const uint32_t *columns,
+                                             uint64_t n_columns, const uint64_t *d_lo, const uint64_t *d_hi, int mode,
+                                             uint64_t route_c, int64_t *d_out_rowids, float *d_out_distances,
+                                             uint32_t *d_out_counts, uint8_t *d_out_route);
 /* Pipelined form of vss_search_batch_device: `context` (0..3) names one of the index's independent search contexts —
  * the analogue of usearch's per-thread contexts (index.hpp:2213-2240) that let several ef_search calls run
  * concurrently under the reference's shared lock (hnsw_index.cpp:388).  _begin enqueues the probe on the context's own
