@@ -88,6 +88,8 @@ SIGNATURES = {
                                                              _vp]),
     "vss_search_multi_filtered_device_begin": (_int, [_vp, _int, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp,
                                                       _vp]),
+    "vss_search_by_label_device_begin": (_int, [_vp, _int, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_multi_by_label_device_begin": (_int, [_vp, _int, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_batch_end": (_int, [_vp, _int]),
     "vss_search_exact_batch": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "vss_search_exact_batch_device": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
@@ -204,6 +206,58 @@ def _p(a):
 
 class VssError(RuntimeError):
     pass
+
+
+class LabelPredicateStruct(C.Structure):
+    """vss_label_predicate of include/vssgpu.h"""
+    _fields_ = [("kind", _int), ("set_column", _u32), ("set_width", _u32), ("n_columns", _u32), ("columns", _u32 * 4),
+                ("d_want", _vp), ("d_sets", _vp), ("d_lo", _vp), ("d_hi", _vp)]
+
+
+class LabelPredicate:
+    """One batch's label predicate for search_by_label_begin / search_multi_by_label_begin: the kind and what the kind's blocking
+    _device call takes.  The per-query words are device tensors (anything with data_ptr()) or raw device addresses; the object
+    keeps the tensors alive, and `c` is the ctypes struct."""
+    KINDS = {"eq": 0, "range": 1, "set": 2, "box": 3, "box64": 4, "set_box": 5}
+
+    def __init__(self, kind, want=None, lo=None, hi=None, sets=None, set_width=0, columns=(), set_column=0):
+        self.kind = kind
+        self.keep = (want, lo, hi, sets)
+        columns = [int(c) for c in columns]
+        if len(columns) > 4:
+            raise ValueError("at most 4 label columns, got %d" % len(columns))
+        self.c = LabelPredicateStruct(self.KINDS.get(kind, kind), set_column, set_width, len(columns),
+                                      (_u32 * 4)(*columns), *[self._address(t) for t in (want, sets, lo, hi)])
+
+    @staticmethod
+    def _address(t):
+        if t is None:
+            return None
+        return int(t.data_ptr()) if hasattr(t, "data_ptr") else (int(t) or None)
+
+    @classmethod
+    def eq(cls, want):
+        return cls("eq", want=want)
+
+    @classmethod
+    def range(cls, lo, hi):
+        return cls("range", lo=lo, hi=hi)
+
+    @classmethod
+    def set(cls, sets, width):
+        return cls("set", sets=sets, set_width=width)
+
+    @classmethod
+    def box(cls, columns, lo, hi):
+        return cls("box", columns=columns, lo=lo, hi=hi)
+
+    @classmethod
+    def box64(cls, columns, lo, hi):
+        return cls("box64", columns=columns, lo=lo, hi=hi)
+
+    @classmethod
+    def set_box(cls, set_column, sets, width, columns=(), lo=None, hi=None):
+        return cls("set_box", set_column=set_column, sets=sets, set_width=width, columns=columns, lo=lo, hi=hi)
 
 
 class GpuIndex:
@@ -726,6 +780,26 @@ class GpuIndex:
         groups = (C.c_uint64 * n)(*[int(g) for g in n_groups]) if n_groups is not None else None
         self._check(self.lib.vss_search_multi_filtered_device_begin(self.h, context, n, tables[0], per_batch, k, ef, tables[1],
                                                                     groups, n_bits, tables[2], tables[3], tables[4], tables[5]))
+
+    def search_by_label_begin(self, context, d_Q, nq, k, ef, predicate, d_keys, d_dist, d_counts):
+        """search_begin under one label predicate per query (a LabelPredicate over device tensors or addresses): the walk of the
+        form's blocking _device call in mode graph, on the caller's context; search_end completes.  The predicate's device
+        memory stays untouched until then."""
+        self._check(self.lib.vss_search_by_label_device_begin(self.h, context, d_Q, nq, k, ef, C.byref(predicate.c), d_keys, d_dist,
+                                                              d_counts))
+
+    def search_multi_by_label_begin(self, context, d_Qs, per_batch, k, ef, predicates, d_keys, d_dists, d_counts):
+        """search_multi_begin where batch b brings predicates[b] (LabelPredicate): all of one kind, over the same columns, of the
+        same set width.  Lists with one entry per batch; d_dists[b] may be None."""
+        n = len(d_Qs)
+        for name, t in (("predicates", predicates), ("d_keys", d_keys), ("d_dists", d_dists), ("d_counts", d_counts)):
+            if t is not None and len(t) != n:
+                raise ValueError("%s has %d entries for %d batches" % (name, len(t), n))
+        tables = [(C.c_void_p * n)(*[int(p) if p else None for p in t]) if t is not None else None
+                  for t in (d_Qs, d_keys, d_dists, d_counts)]
+        preds =(LabelPredicateStruct * len(predicates))(*[p.c for p in predicates]) if predicates is not None else None
+        self._check(self.lib.vss_search_multi_by_label_device_begin(self.h, context, n, tables[0], per_batch, k, ef, preds, tables[1],
+                                                                    tables[2], tables[3]))
 
     def set_search_gating(self, on):
         self.set_option("search.gating", 1 if on else 0)

@@ -2966,6 +2966,41 @@ __global__ __launch_bounds__(256) void k_resolve_label_set_boxes(ResolveSetBoxes
 	}
 }
 
+// Ahead of a launch of SEVERAL batches by label (the pipelined and multi-batch _begin calls): the same six tables, written from every
+// batch's own matrices in DEVICE memory as the form's _device call takes them — nothing is interleaved on the host.  A thread writes
+// one unit (host::label_batches_query_units) of one launch-wide query, which is row q % per_batch of batch q / per_batch, and the
+// first threads the head; label_filter.h has the arithmetic, host/label_batches_check.cpp proves the cells equal to those of the six
+// kernels above.  The descriptors travel by value, as ResolveBatchesArgs' do (32 x 24 bytes).  Two kernels: the kinds whose words
+// are 32 bits wide (EQ, RANGE, SET, BOX) and those whose words are 64 (BOX64, SET_BOX).
+template <class W>
+struct ResolveLabelBatchesArgs {
+	host::LabelBatch<W> batch[host::LABEL_BATCHES_MAX];
+	host::LabelBatchShape shape;
+	host::LabelTableHead head;
+	uint32_t n_queries;
+	unsigned long long *table; // host::label_batches_table_cells(shape, n_queries) cells
+};
+
+__global__ __launch_bounds__(256) void k_resolve_label_batches(ResolveLabelBatchesArgs<uint32_t> a) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i < a.head.n)
+		a.table[i] = a.head.cell[i];
+	if (i >= (uint64_t)a.n_queries * host::label_batches_query_units(a.shape))
+		return;
+	if (a.shape.kind == host::LabelKind::SET)
+		reinterpret_cast<uint32_t *>(a.table + a.head.n)[i] = host::label_batches_set_word(a.batch, a.shape, i);
+	else
+		a.table[a.head.n + i] = host::label_batches_cell(a.batch, a.shape, i);
+}
+
+__global__ __launch_bounds__(256) void k_resolve_label_batches64(ResolveLabelBatchesArgs<uint64_t> a) {
+	const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (i < a.head.n)
+		a.table[i] = a.head.cell[i];
+	if (i < (uint64_t)a.n_queries * host::label_batches_query_units(a.shape))
+		a.table[a.head.n + i] = host::label_batches_cell64(a.batch, a.shape, i);
+}
+
 // Reused slots, before phase A: blank every list of the node (update() zeroes the node tape, index.hpp:2837-2840).
 // After phase A: move the parked new lists in.  One wave per batch node; appended nodes are skipped.
 __global__ __launch_bounds__(64) void k_reuse_lists(BuildArgs a, int commit) {

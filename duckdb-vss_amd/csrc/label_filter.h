@@ -555,6 +555,119 @@ inline constexpr uint32_t label_set_box_bad_column(uint32_t set_column, const ui
 	return m + 1;
 }
 
+// ---- SEVERAL BATCHES in one launch (vss_search_by_label_device_begin, vss_search_multi_by_label_device_begin): a launch carries 1 to
+// LABEL_BATCHES_MAX batches of per_batch queries each, all of one kind, over the same columns and of the same set width, and every
+// batch brings its OWN per-query words as the form's _device call takes them — separate matrices in DEVICE memory, no travelling
+// rows.  The launch numbers its queries q = batch * per_batch + row, and the walk table is the one of the single-batch forms above
+// over all n_batches * per_batch queries: query q's cells sit where the form's table puts query q, and each of them is what the
+// form's cell function makes of row `row` of batch `batch`'s matrices.  Everything here is constexpr: the resolve kernels and the
+// CPU check (host/label_batches_check.cpp) run this very code.
+constexpr uint32_t LABEL_BATCHES_MAX = 32; // the launch's batches (MAX_COALESCED of the engine)
+
+enum class LabelKind : uint32_t { EQ, RANGE, SET, BOX, BOX64, SET_BOX }; // VSS_LABEL_EQ .. VSS_LABEL_SET_BOX
+
+// launch-wide query -> (batch, row of the batch)
+struct LabelBatchAt {
+	uint64_t batch, row;
+};
+inline constexpr LabelBatchAt label_batch_at(uint64_t per_batch, uint64_t q) {
+	return {q / per_batch, q % per_batch};
+}
+
+// One batch's words, W = uint32_t for EQ / RANGE / SET / BOX and uint64_t for BOX64 / SET_BOX.  words: EQ's `want` (per_batch
+// values), SET's and SET_BOX's `sets` (per_batch x width); lo, hi: RANGE's ends (per_batch values), BOX's, BOX64's and SET_BOX's
+// matrices (per_batch x m).  What a kind does not use is not read.
+template <class W>
+struct LabelBatch {
+	const W *words, *lo, *hi;
+};
+
+// what all batches of a launch share.  width: the set's (SET, SET_BOX); m: the named columns of a BOX / BOX64, the RANGE columns of
+// a SET_BOX
+struct LabelBatchShape {
+	LabelKind kind;
+	uint32_t width, m, per_batch;
+};
+
+// A query's share of the table, in UNITS: 64-bit cells, but for SET, whose table is written by 32-bit words.  And the cell where
+// query 0's share begins — the head of the table ends there.
+inline constexpr uint64_t label_batches_query_units(const LabelBatchShape &s) {
+	return s.kind == LabelKind::EQ      ? 1
+	       : s.kind == LabelKind::RANGE ? 2
+	       : s.kind == LabelKind::SET   ? 4 * (uint64_t)label_set_chunks(s.width)
+	       : s.kind == LabelKind::SET_BOX ? label_set_box_query_cells(s.m, label_set_box_padded(s.width))
+	                                      : 2 * (uint64_t)s.m;
+}
+inline constexpr uint64_t label_batches_query_base(const LabelBatchShape &s) {
+	return s.kind == LabelKind::EQ || s.kind == LabelKind::RANGE ? 1
+	       : s.kind == LabelKind::SET                            ? 2
+	       : s.kind == LabelKind::SET_BOX                        ? label_set_box_query_base(s.m)
+	                                                             : label_box_query_cell(s.m, 0);
+}
+// the cells of the table of a launch of n_queries queries (the context's buffer holds this many for the largest launch it may carry)
+inline constexpr uint64_t label_batches_table_cells(const LabelBatchShape &s, uint64_t n_queries) {
+	const uint64_t units = label_batches_query_units(s) * n_queries;
+	return label_batches_query_base(s) + (s.kind == LabelKind::SET ? units / 2 : units);
+}
+
+// Unit i of the launch — unit i % units of launch-wide query i / units — for the kinds with 32-bit words whose table holds 64-bit
+// cells: EQ, RANGE (a box over one column) and BOX.
+inline constexpr uint64_t label_batches_cell(const LabelBatch<uint32_t> *batches, const LabelBatchShape &s, uint64_t i) {
+	const uint64_t units = label_batches_query_units(s);
+	const LabelBatchAt at = label_batch_at(s.per_batch, i / units);
+	const LabelBatch<uint32_t> &b = batches[at.batch];
+	if (s.kind == LabelKind::EQ)
+		return label_want_cell(b.words[at.row]);
+	const uint64_t j = i % units, end = at.row * (units / 2) + j / 2;
+	const LabelRangeCells c = label_range_cells(b.lo[end], b.hi[end]);
+	return j & 1 ? c.width : c.lo;
+}
+// ... for SET, whose units are the 32-bit words of the padded rows
+inline constexpr uint32_t label_batches_set_word(const LabelBatch<uint32_t> *batches, const LabelBatchShape &s, uint64_t i) {
+	const uint64_t units = label_batches_query_units(s);
+	const LabelBatchAt at = label_batch_at(s.per_batch, i / units);
+	return label_set_table_word(batches[at.batch].words + at.row * s.width, s.width, (uint32_t)(i % units));
+}
+// ... for the kinds with 64-bit words: BOX64 (no set words) and SET_BOX (the padded set words, then the range cells)
+inline constexpr uint64_t label_batches_cell64(const LabelBatch<uint64_t> *batches, const LabelBatchShape &s, uint64_t i) {
+	const uint64_t units = label_batches_query_units(s);
+	const LabelBatchAt at = label_batch_at(s.per_batch, i / units);
+	const LabelBatch<uint64_t> &b = batches[at.batch];
+	const uint64_t j = i % units, padded = s.kind == LabelKind::SET_BOX ? label_set_box_padded(s.width) : 0;
+	if (j < padded)
+		return j < s.width ? b.words[at.row * s.width + j] : NO_LABEL64;
+	const uint64_t end = at.row * s.m + (j - padded) / 2;
+	const LabelRange64Cells c = label_range64_cells(b.lo[end], b.hi[end]);
+	return (j - padded) & 1 ? c.count : c.lo;
+}
+
+// The head of the table, cells [0, label_batches_query_base): what the single-batch resolve kernels write ahead of query 0.
+// addresses: the columns' device addresses in table order — column 0 alone for EQ / RANGE / SET, the named columns for BOX / BOX64,
+// the set column and then the range columns for SET_BOX; wide_mask as the form's table head takes it.
+constexpr uint32_t LABEL_TABLE_HEAD_MAX = 6;
+struct LabelTableHead {
+	uint64_t cell[LABEL_TABLE_HEAD_MAX];
+	uint32_t n;
+};
+inline constexpr LabelTableHead label_batches_table_head(const LabelBatchShape &s, const uint64_t *addresses, uint32_t wide_mask) {
+	LabelTableHead h = {{0, 0, 0, 0, 0, 0}, (uint32_t)label_batches_query_base(s)};
+	if (s.kind == LabelKind::EQ || s.kind == LabelKind::RANGE || s.kind == LabelKind::SET) {
+		h.cell[0] = addresses[0];
+		if (s.kind == LabelKind::SET)
+			h.cell[1] = s.width;
+		return h;
+	}
+	const uint32_t n_addresses = s.kind == LabelKind::SET_BOX ? s.m + 1 : s.m;
+	h.cell[0] = s.kind == LabelKind::BOX     ? s.m
+	            : s.kind == LabelKind::BOX64 ? label_box64_table_head(s.m, wide_mask)
+	                                         : label_set_box_table_head(s.m, label_set_box_padded(s.width), wide_mask);
+	for (uint32_t j = 0; j != n_addresses; ++j)
+		h.cell[1 + j] = addresses[j];
+	return h; // (a SET_BOX's cell 2 + m, where there is one, stays 0: it keeps the per-query cells on an even index)
+}
+static_assert(1 + LABEL_COLUMNS_MAX <= LABEL_TABLE_HEAD_MAX && label_set_box_query_base(LABEL_SET_BOX_RANGES_MAX) <= LABEL_TABLE_HEAD_MAX,
+              "the head of every kind fits LabelTableHead");
+
 // vss_set_labels(first_rowid, n): what the range breaks, or NONE. Cells end at 2^32 (first_rowid + n == 2^32 is the last range
 // that fits); the sum is formed without wrapping.
 enum class LabelRangeFault { NONE, NO_LABELS, TOO_FAR };

@@ -139,6 +139,19 @@ struct SearchPredicate {
 	                                                         // BY_SET_BOX: the travelling rows (label_set_box_rows); `width` is the
 	                                                         // set's, columns[0] the set column, columns[1 ..] the range columns
 	uint32_t n_columns = 0, columns[LABEL_COLUMNS_MAX] = {}; // BY_BOX: the label columns the call names (n_bits: the shortest one's cells)
+	// The BY_ kinds of the _begin calls: every batch of the launch brings its own words, SEPARATE device matrices as the form's
+	// _device call takes them (label_filter.h, "several batches"), and want / lo / hi / sets / boxes above stay null.
+	bool by_batches = false;
+	struct LabelWords {
+		const void *words, *lo, *hi; // words: BY_LABEL's want, BY_SET's and BY_SET_BOX's sets
+	} label_words[MAX_FILTER_GROUP_BATCHES] = {};
+	// this BY_ predicate over `words`, one entry per batch of the launch
+	SearchPredicate with_batches(const LabelWords (&words)[MAX_FILTER_GROUP_BATCHES]) const {
+		SearchPredicate p = *this;
+		p.by_batches = true;
+		std::copy(words, words + MAX_FILTER_GROUP_BATCHES, p.label_words);
+		return p;
+	}
 
 	// a launch of one batch against the index's label column: query q admits the rows labelled want[q]
 	static SearchPredicate by_label(const uint32_t *want, uint64_t labelled_rows) {
@@ -1698,6 +1711,69 @@ struct vss_index {
 		return {slot, n_batches, per_batch, d_queries, d_keys_out, d_dist_out, d_count_out, (uint32_t)dim, k, ef};
 	}
 
+	// The predicate of a launch by label whose batches each bring their own words (SearchPredicate::by_batches) becomes the walkers'
+	// table HERE: one resolve kernel on the context's stream reads every batch's device matrices and writes the table of the kind
+	// — the one the single-batch branches of search_begin write — for all n_batches * per_batch queries, into the context's
+	// d_group_bitmap, sized for cap_q queries like the other per-query words.  Nothing is read back, copied or waited for.  The
+	// re-run rounds of search_end read the table again by launch-wide query number, so a re-run query keeps its batch's predicate.
+	// The six single-batch branches of search_begin keep their code for the blocking calls, so the choice of the flag bits and the
+	// cut of the rows is written there AND here: a change to one must be made to the other until the blocking calls are re-pointed
+	// at this path (the follow-up that also removes their host round trip).
+	int resolve_label_batches(SearchCtx &c, const SearchPredicate &p, uint64_t n_batches, uint64_t per_batch, uint64_t cap_q, GraphView &gv) {
+		LabelBatchShape s = {LabelKind::EQ, p.width, 0, (uint32_t)per_batch};
+		uint64_t addresses[LABEL_COLUMNS_MAX] = {}, rows = labelled_rows, flags = 0;
+		uint32_t wide_mask = 0;
+		if (p.kind == SearchPredicate::BY_LABEL || p.kind == SearchPredicate::BY_RANGE || p.kind == SearchPredicate::BY_SET) {
+			if (!d_labels.p || label_width[0] == 64 || (p.kind == SearchPredicate::BY_SET && (p.width < 1 || p.width > LABEL_SET_MAX)))
+				return fail("search by label: over an index whose 32-bit labels have been set, set width 1 to %u", (unsigned)LABEL_SET_MAX);
+			s.kind = p.kind == SearchPredicate::BY_LABEL ? LabelKind::EQ : p.kind == SearchPredicate::BY_RANGE ? LabelKind::RANGE : LabelKind::SET;
+			flags = p.kind == SearchPredicate::BY_LABEL ? FILTER_BY_LABEL : p.kind == SearchPredicate::BY_RANGE ? FILTER_BY_RANGE : FILTER_BY_SET;
+			addresses[0] = (uint64_t)reinterpret_cast<uintptr_t>(d_labels.p);
+		} else {
+			LabelBoxColumns box;
+			const bool set_box = p.kind == SearchPredicate::BY_SET_BOX;
+			if ((p.kind != SearchPredicate::BY_BOX && p.kind != SearchPredicate::BY_BOX64 && !set_box) ||
+			    !named_label_columns(p.columns, p.n_columns, box) || (set_box && (p.width < 1 || p.width > LABEL_SET_MAX)))
+				return fail("search by label box: over 1 to %u distinct label columns that have been set, set width 1 to %u",
+				            (unsigned)LABEL_COLUMNS_MAX, (unsigned)LABEL_SET_MAX);
+			wide_mask = box.wide_mask();
+			if (p.kind == SearchPredicate::BY_BOX && wide_mask)
+				return fail("search by label box: a named column holds 64-bit cells");
+			s.kind = set_box ? LabelKind::SET_BOX : p.kind == SearchPredicate::BY_BOX ? LabelKind::BOX : LabelKind::BOX64;
+			s.m = set_box ? box.m - 1 : box.m;
+			flags = set_box ? FILTER_BY_SET_BOX : p.kind == SearchPredicate::BY_BOX ? FILTER_BY_BOX : FILTER_BY_BOX64;
+			for (uint32_t j = 0; j != box.m; ++j)
+				addresses[j] = (uint64_t)reinterpret_cast<uintptr_t>(box.cells[j]);
+			rows = box.shortest_rows();
+		}
+		const uint64_t nq = n_batches * per_batch;
+		if (!c.d_group_bitmap.try_grow(label_batches_table_cells(s, cap_q)))
+			return fail("search by label: no device memory for the predicates of %llu queries", (unsigned long long)cap_q);
+		count_group_tables(c);
+		unsigned long long *table = reinterpret_cast<unsigned long long *>(c.d_group_bitmap.p);
+		const LabelTableHead head = label_batches_table_head(s, addresses, wide_mask);
+		const dim3 grid((uint32_t)(nq * label_batches_query_units(s) / 256 + 1));
+		if (s.kind == LabelKind::BOX64 || s.kind == LabelKind::SET_BOX) {
+			ResolveLabelBatchesArgs<uint64_t> res = {{}, s, head, (uint32_t)nq, table};
+			for (uint64_t b = 0; b != n_batches; ++b)
+				res.batch[b] = {static_cast<const uint64_t *>(p.label_words[b].words), static_cast<const uint64_t *>(p.label_words[b].lo),
+				                static_cast<const uint64_t *>(p.label_words[b].hi)};
+			hipLaunchKernelGGL(k_resolve_label_batches64, grid, dim3(256), 0, c.stream, res);
+		} else {
+			ResolveLabelBatchesArgs<uint32_t> res = {{}, s, head, (uint32_t)nq, table};
+			for (uint64_t b = 0; b != n_batches; ++b)
+				res.batch[b] = {static_cast<const uint32_t *>(p.label_words[b].words), static_cast<const uint32_t *>(p.label_words[b].lo),
+				                static_cast<const uint32_t *>(p.label_words[b].hi)};
+			hipLaunchKernelGGL(k_resolve_label_batches, grid, dim3(256), 0, c.stream, res);
+		}
+		HIP_TRY(hipGetLastError());
+		gv.filter = table;
+		// (the cut of the rows as the single-batch branches of search_begin make it: one bit lower per kind that took one)
+		const uint64_t cut = p.kind == SearchPredicate::BY_LABEL ? FILTER_BY_LABEL : p.kind == SearchPredicate::BY_RANGE ? FILTER_BY_RANGE : FILTER_BY_SET;
+		gv.filter_bits = std::min<uint64_t>(rows, cut - 1) | FILTER_PER_QUERY | flags;
+		return VSS_OK;
+	}
+
 	// Enqueue the probe batches of a request on its context (asynchronous); search_end() completes them.  ONE launch of the
 	// search engine answers all of them: its walkers take queries from every batch until none is left, so compute units that
 	// drew short queries in one batch go on with the next instead of idling until the slowest query of the batch is done.
@@ -1765,7 +1841,10 @@ struct vss_index {
 		const SearchPredicate &p = r.predicate;
 		a.gv.filter = p.kind == SearchPredicate::ONE_BITMAP ? reinterpret_cast<const unsigned long long *>(p.bitmap) : nullptr;
 		a.gv.filter_bits = std::min<uint64_t>(p.n_bits, FILTER_BY_SET - 1);
-		if (p.kind == SearchPredicate::PER_QUERY) {
+		if (p.by_batches) {
+			if (const int rc = resolve_label_batches(c, p, n_batches, per_batch, cap_q, a.gv))
+				return rc;
+		} else if (p.kind == SearchPredicate::PER_QUERY) {
 			// Descriptor b = batch b's table.  A small kernel ahead of the launch resolves every query's bitmap address; the walkers
 			// of the *_groups kernels read that (GraphView::admitted_for).  The descriptors go to it by value, so the launch path
 			// allocates, copies and waits for nothing once the address table has its size — cap_q, like the other per-query words.
@@ -4736,6 +4815,100 @@ int vss_search_batch_by_label_set_box_device(vss_index *h, const float *Q, uint6
 			return rc;
 		h->route_to_device(route, out_route);
 		return VSS_OK;
+	})
+}
+
+// ---- the six forms above in the pipelined and multi-batch launches: always the walk (mode graph), on the caller's context.
+// Everything is refused HERE, before search_begin waits at the gate or enqueues anything: first what makes the batches of a launch
+// differ (the message names the first batch that differs from batch 0), then, batch by batch, what the form's blocking call
+// refuses, in its words, with the batch named after the entry point.
+static_assert(VSS_LABEL_EQ == (int)LabelKind::EQ && VSS_LABEL_RANGE == (int)LabelKind::RANGE && VSS_LABEL_SET == (int)LabelKind::SET &&
+                  VSS_LABEL_BOX == (int)LabelKind::BOX && VSS_LABEL_BOX64 == (int)LabelKind::BOX64 && VSS_LABEL_SET_BOX == (int)LabelKind::SET_BOX,
+              "one numbering of the kinds, in the rule's header and in the C header");
+static int label_begin(vss_index *h, const char *entry, bool multi, int context, uint64_t n_batches, const float *const *Q,
+                       uint64_t per_batch, uint64_t k, uint64_t ef, const vss_label_predicate *preds, int64_t *const *out,
+                       float *const *out_d, uint32_t *const *out_counts) {
+	VSS_CHECK_CALLER_CONTEXT(h, context)
+	if (!Q || !out || !out_d || !out_counts || !preds)
+		return h->fail("%s: null table", entry);
+	if (n_batches < 1 || n_batches > MAX_COALESCED)
+		return h->fail("1 to %d batches per launch", MAX_COALESCED);
+	const vss_label_predicate &p0 = preds[0];
+	if (p0.kind < VSS_LABEL_EQ || p0.kind > VSS_LABEL_SET_BOX)
+		return h->fail("%s: kind %d is none of VSS_LABEL_EQ (0) .. VSS_LABEL_SET_BOX (5)", entry, p0.kind);
+	const bool has_set = p0.kind == VSS_LABEL_SET || p0.kind == VSS_LABEL_SET_BOX;
+	const bool has_columns = p0.kind == VSS_LABEL_BOX || p0.kind == VSS_LABEL_BOX64 || p0.kind == VSS_LABEL_SET_BOX;
+	for (uint64_t b = 1; b != n_batches; ++b) {
+		const vss_label_predicate &p = preds[b];
+		if (p.kind != p0.kind)
+			return h->fail("%s: batch %llu is of kind %d, batch 0 of kind %d: one kind per launch", entry, (unsigned long long)b, p.kind, p0.kind);
+		if (has_columns && (p.n_columns != p0.n_columns || (p0.kind == VSS_LABEL_SET_BOX && p.set_column != p0.set_column) ||
+		                    !std::equal(p.columns, p.columns + std::min<uint32_t>(p.n_columns, VSS_LABEL_COLUMNS_MAX), p0.columns)))
+			return h->fail("%s: batch %llu names other label columns than batch 0: the same columns, in the same order, per launch", entry,
+			               (unsigned long long)b);
+		if (has_set && p.set_width != p0.set_width)
+			return h->fail("%s: batch %llu has set width %u, batch 0 has %u: one set width per launch", entry, (unsigned long long)b,
+			               (unsigned)p.set_width, (unsigned)p0.set_width);
+	}
+	SearchRequest r = h->request(context, Q, n_batches, per_batch, k, ef, out, out_d, out_counts);
+	r.gate = true;
+	LabelBoxColumns box;
+	SearchPredicate::LabelWords words[MAX_FILTER_GROUP_BATCHES] = {};
+	// (as in the blocking calls, the checks do not depend on k, and with no queries only the pointers to them go unchecked)
+	for (uint64_t b = 0; b != n_batches; ++b) {
+		const vss_label_predicate &p = preds[b];
+		char what[96];
+		if (multi)
+			std::snprintf(what, sizeof what, "%s: batch %llu", entry, (unsigned long long)b);
+		else
+			std::snprintf(what, sizeof what, "%s", entry);
+		const int graph = VSS_BY_LABEL_GRAPH;
+		int rc = VSS_OK;
+		if (p.kind == VSS_LABEL_EQ)
+			rc = check_by_label(h, what, Q[b], per_batch, static_cast<const uint32_t *>(p.d_want), graph, out[b], out_counts[b]);
+		else if (p.kind == VSS_LABEL_RANGE)
+			rc = check_by_label_range(h, what, Q[b], per_batch, static_cast<const uint32_t *>(p.d_lo), static_cast<const uint32_t *>(p.d_hi),
+			                          graph, out[b], out_counts[b]);
+		else if (p.kind == VSS_LABEL_SET)
+			rc = check_by_label_set(h, what, Q[b], per_batch, static_cast<const uint32_t *>(p.d_sets), p.set_width, graph, out[b], out_counts[b]);
+		else if (p.kind == VSS_LABEL_SET_BOX)
+			rc = check_by_label_set_box(h, what, Q[b], per_batch, p.set_column, p.d_sets, p.set_width, p.columns, p.n_columns, p.d_lo, p.d_hi,
+			                            graph, out[b], out_counts[b], box);
+		else
+			rc = check_by_label_box(h, what, Q[b], per_batch, p.columns, p.n_columns, p.d_lo, p.d_hi, graph, out[b], out_counts[b], box,
+			                        p.kind == VSS_LABEL_BOX64);
+		if (rc != VSS_OK)
+			return rc;
+		words[b] = {p.kind == VSS_LABEL_EQ ? p.d_want : p.d_sets, p.d_lo, p.d_hi};
+	}
+	if (per_batch && k) {
+		if (p0.kind == VSS_LABEL_EQ)
+			r.predicate = SearchPredicate::by_label(nullptr, h->labelled_rows).with_batches(words);
+		else if (p0.kind == VSS_LABEL_RANGE)
+			r.predicate = SearchPredicate::by_range(nullptr, nullptr, h->labelled_rows).with_batches(words);
+		else if (p0.kind == VSS_LABEL_SET)
+			r.predicate = SearchPredicate::by_set(nullptr, p0.set_width, h->labelled_rows).with_batches(words);
+		else if (p0.kind == VSS_LABEL_BOX)
+			r.predicate = SearchPredicate::by_box(nullptr, box.columns, box.m, box.shortest_rows()).with_batches(words);
+		else if (p0.kind == VSS_LABEL_BOX64)
+			r.predicate = SearchPredicate::by_box64(nullptr, box.columns, box.m, box.shortest_rows()).with_batches(words);
+		else
+			r.predicate = SearchPredicate::by_set_box(nullptr, p0.set_width, box.columns, box.m, box.shortest_rows()).with_batches(words);
+	}
+	return h->search_begin(r);
+}
+
+int vss_search_by_label_device_begin(vss_index *h, int context, const float *Q, uint64_t nq, uint64_t k, uint64_t ef,
+                                     const vss_label_predicate *predicate, int64_t *out, float *out_d, uint32_t *out_counts) {
+	VSS_SHARED(h, { return label_begin(h, "vss_search_by_label_device_begin", false, context, 1, &Q, nq, k, ef, predicate, &out, &out_d, &out_counts); })
+}
+
+int vss_search_multi_by_label_device_begin(vss_index *h, int context, uint64_t n_batches, const float *const *Q, uint64_t per_batch,
+                                           uint64_t k, uint64_t ef, const vss_label_predicate *preds, int64_t *const *out,
+                                           float *const *out_d, uint32_t *const *out_counts) {
+	VSS_SHARED(h, {
+		return label_begin(h, "vss_search_multi_by_label_device_begin", true, context, n_batches, Q, per_batch, k, ef, preds, out, out_d,
+		                   out_counts);
 	})
 }
 

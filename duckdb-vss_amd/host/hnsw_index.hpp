@@ -332,6 +332,24 @@ public:
 			                                         hi, mode, route_c, ids, nullptr, counts, routes);
 		});
 	}
+	// SEVERAL join chunks with a label predicate each in ONE launch (vss_search_multi_by_label_device_begin, completed here): for
+	// an operator that keeps its chunks on the device.  Chunk b — per_chunk outer rows at d_queries[b] — is answered under
+	// predicates[b], whose per-row words are device memory laid out as the form's ExecuteMultiScanBatchByLabel* method above takes
+	// them; all chunks share the kind, the named columns and the set width.  Always the walk (mode VSS_BY_LABEL_GRAPH): the exact
+	// and auto routes plan on the host and keep the per-chunk methods.  Every chunk gets, cell for cell, what its own per-chunk
+	// call in mode graph gives it: `limit` row ids per outer row into d_rowids[b] (unused cells -1), the distances into
+	// d_distances[b] where that is not null, the counts into d_counts[b].  The three tables and `predicates` are host arrays of
+	// n_chunks (1 .. 32) entries.  context: one of the engine's caller contexts, 1 .. 3 for a pipeline thread of its own.
+	void ExecuteMultiScanChunksByLabel(IndexScanState &state_p, int context, idx_t n_chunks, const float *const *d_queries, idx_t per_chunk,
+	                                   idx_t limit, const vss_label_predicate *predicates, row_t *const *d_rowids, float *const *d_distances,
+	                                   uint32_t *const *d_counts) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::shared_lock<std::shared_mutex> lock(rwlock);
+		Check(vss_search_multi_by_label_device_begin(index, context, n_chunks, d_queries, per_chunk, limit, state.ef_search, predicates,
+		                                             d_rowids, d_distances, d_counts),
+		      "search");
+		Check(vss_search_batch_end(index, context), "search");
+	}
 	// A label column of 64-bit cells (vss_set_label_column64): the column must be empty or 64 bits wide already; ClearLabelColumn
 	// forgets a column's width.  LabelColumnWidth: 0 (no cells), 32 or 64.
 	void SetLabelColumn64(uint32_t column, idx_t first_rowid, const uint64_t *labels, idx_t n) {

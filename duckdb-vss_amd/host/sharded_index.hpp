@@ -457,6 +457,14 @@ public:
 			throw InternalException("Failed to search the HNSW index: search by label needs the wanted label of every query");
 		Ensure(n, k);
 		UploadTables(nullptr, 0, want, n);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			ProbeByLabelGraph(queries, n, k, ef, out_rowids, out_distances, out_counts, [&](Shard &s) {
+				vss_label_predicate p = {};
+				p.kind = VSS_LABEL_EQ, p.d_want = bitmaps[s.bitmap].group_of;
+				return p;
+			});
+			return;
+		}
 		Probe(
 		    queries, n, k, out_rowids, out_distances, out_counts,
 		    [&](Shard &s, row_t *keys, float *dist) {
@@ -485,6 +493,14 @@ public:
 		std::vector<uint32_t> ends(lo, lo + n);
 		ends.insert(ends.end(), hi, hi + n);
 		UploadTables(nullptr, 0, ends.data(), 2 * n);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			ProbeByLabelGraph(queries, n, k, ef, out_rowids, out_distances, out_counts, [&](Shard &s) {
+				vss_label_predicate p = {};
+				p.kind = VSS_LABEL_RANGE, p.d_lo = bitmaps[s.bitmap].group_of, p.d_hi = bitmaps[s.bitmap].group_of + n;
+				return p;
+			});
+			return;
+		}
 		Probe(
 		    queries, n, k, out_rowids, out_distances, out_counts,
 		    [&](Shard &s, row_t *keys, float *dist) {
@@ -527,6 +543,16 @@ public:
 		std::vector<uint32_t> ends(lo, lo + n * n_columns);
 		ends.insert(ends.end(), hi, hi + n * n_columns);
 		UploadTables(nullptr, 0, ends.data(), 2 * n * n_columns);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			ProbeByLabelGraph(queries, n, k, ef, out_rowids, out_distances, out_counts, [&](Shard &s) {
+				vss_label_predicate p = {};
+				p.kind = VSS_LABEL_BOX, p.n_columns = (uint32_t)n_columns;
+				std::copy(columns, columns + n_columns, p.columns);
+				p.d_lo = bitmaps[s.bitmap].group_of, p.d_hi = bitmaps[s.bitmap].group_of + n * n_columns;
+				return p;
+			});
+			return;
+		}
 		Probe(
 		    queries, n, k, out_rowids, out_distances, out_counts,
 		    [&](Shard &s, row_t *keys, float *dist) {
@@ -566,6 +592,16 @@ public:
 		std::memcpy(ends.data(), lo, words * 4);
 		std::memcpy(ends.data() + words, hi, words * 4);
 		UploadTables(nullptr, 0, ends.data(), 2 * words);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			ProbeByLabelGraph(queries, n, k, ef, out_rowids, out_distances, out_counts, [&](Shard &s) {
+				vss_label_predicate p = {};
+				p.kind = VSS_LABEL_BOX64, p.n_columns = (uint32_t)n_columns;
+				std::copy(columns, columns + n_columns, p.columns);
+				p.d_lo = bitmaps[s.bitmap].group_of, p.d_hi = bitmaps[s.bitmap].group_of + words;
+				return p;
+			});
+			return;
+		}
 		Probe(
 		    queries, n, k, out_rowids, out_distances, out_counts,
 		    [&](Shard &s, row_t *keys, float *dist) {
@@ -607,6 +643,18 @@ public:
 			std::memcpy(words.data() + set_words + end_words, hi, end_words * 4);
 		}
 		UploadTables(nullptr, 0, words.data(), words.size());
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			ProbeByLabelGraph(queries, n, k, ef, out_rowids, out_distances, out_counts, [&](Shard &s) {
+				const uint32_t *d_words = bitmaps[s.bitmap].group_of;
+				vss_label_predicate p = {};
+				p.kind = VSS_LABEL_SET_BOX, p.set_column = set_column, p.set_width = set_width, p.n_columns = (uint32_t)n_columns;
+				std::copy(columns, columns + n_columns, p.columns);
+				p.d_sets = d_words;
+				p.d_lo = end_words ? d_words + set_words : nullptr, p.d_hi = end_words ? d_words + set_words + end_words : nullptr;
+				return p;
+			});
+			return;
+		}
 		Probe(
 		    queries, n, k, out_rowids, out_distances, out_counts,
 		    [&](Shard &s, row_t *keys, float *dist) {
@@ -639,6 +687,14 @@ public:
 			throw InternalException("Failed to search the HNSW index: search by label set needs every query's row of labels");
 		Ensure(n, k);
 		UploadTables(nullptr, 0, sets, n * width);
+		if (mode == VSS_BY_LABEL_GRAPH) {
+			ProbeByLabelGraph(queries, n, k, ef, out_rowids, out_distances, out_counts, [&](Shard &s) {
+				vss_label_predicate p = {};
+				p.kind = VSS_LABEL_SET, p.set_width = (uint32_t)width, p.d_sets = bitmaps[s.bitmap].group_of;
+				return p;
+			});
+			return;
+		}
 		Probe(
 		    queries, n, k, out_rowids, out_distances, out_counts,
 		    [&](Shard &s, row_t *keys, float *dist) {
@@ -708,6 +764,17 @@ private:
 			DrainProbes();
 			throw;
 		}
+	}
+	// Mode VSS_BY_LABEL_GRAPH of the six calls by label: `predicate(shard)` names the shard's uploaded words, every shard is started
+	// through vss_search_by_label_device_begin before the first is waited for — all G walk at once, as under a bitmap — and
+	// vss_search_batch_end finishes each.  Every query walks in every shard: shard_routes stays all 0.
+	template <class Predicate>
+	void ProbeByLabelGraph(const float *queries, idx_t n, idx_t k, idx_t ef, row_t *out_rowids, float *out_distances, uint32_t *out_counts,
+	                       Predicate predicate) {
+		ProbeThroughBegin(queries, n, k, out_rowids, out_distances, out_counts, [&](Shard &s, row_t *keys, float *dist) {
+			const vss_label_predicate p = predicate(s);
+			Vss(s, vss_search_by_label_device_begin(s.index->Handle(), 0, s.d_q, n, k, ef, &p, keys, dist, s.d_cnt));
+		});
 	}
 	// An error between launch and finish of a filtered probe: every shard's probe is completed and its stream drained before the
 	// error leaves the call, so that no kernel (and no re-run round of vss_search_batch_end) still reads the tables in bitmaps[]

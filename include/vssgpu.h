@@ -268,7 +268,7 @@ uint64_t vss_labelled_rows(const vss_index *index);
  * vss_last_filter_route, vss_last_search_stats / _shape / _prescore values behind.
  * Errors: no column set; a mode other than the three (refused before anything is staged); those of the call of the mode.
  * The _device form takes device pointers (d_out_distances and d_out_route may be NULL), copies d_want back (4 bytes per
- * query) and runs on context 0.  Not available in the pipelined / multi-batch _begin forms. */
+ * query) and runs on context 0.  The pipelined / multi-batch forms: vss_search_by_label_device_begin, below. */
 enum { VSS_BY_LABEL_GRAPH = 0, VSS_BY_LABEL_EXACT = 1, VSS_BY_LABEL_AUTO = 2 };
 int vss_search_batch_by_label(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
                               const uint32_t *want, int mode, uint64_t route_c, int64_t *out_rowids, float *out_distances,
@@ -292,7 +292,7 @@ int vss_search_batch_by_label_device(vss_index *index, const float *d_queries, u
  * Errors: a mode other than the three (refused first, before anything is staged); no column set; lo or hi NULL with
  * n_queries > 0; those of the call of the mode.  n_queries == 0 or k == 0 returns VSS_OK.
  * The _device form takes device pointers (d_out_distances and d_out_route may be NULL), copies d_lo and d_hi back (8 bytes
- * per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin forms. */
+ * per query) and runs on context 0.  The pipelined / multi-batch forms: vss_search_by_label_device_begin, below. */
 int vss_search_batch_by_label_range(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
                                     const uint32_t *lo, const uint32_t *hi, int mode, uint64_t route_c, int64_t *out_rowids,
                                     float *out_distances, uint32_t *out_counts, uint8_t *out_route);
@@ -322,7 +322,7 @@ int vss_search_batch_by_label_range_device(vss_index *index, const float *d_quer
  * three before anything is launched or written); no column set; those of the call of the mode.  n_queries == 0 or k == 0
  * returns VSS_OK and writes nothing.
  * The _device form takes device pointers (d_out_distances and d_out_route may be NULL), copies d_sets back (4 * width bytes
- * per query) in modes exact and auto, and runs on context 0.  Not available in the pipelined / multi-batch _begin forms. */
+ * per query) in modes exact and auto, and runs on context 0.  The pipelined / multi-batch forms: vss_search_by_label_device_begin, below. */
 #define VSS_LABEL_SET_MAX 32
 int vss_search_batch_by_label_set(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
                                   const uint32_t *sets, uint64_t width, int mode, uint64_t route_c, int64_t *out_rowids,
@@ -359,8 +359,8 @@ int vss_search_batch_by_label_set_device(vss_index *index, const float *d_querie
  * that was never set ("no label column", with its number); those of the call of the mode.  n_queries == 0 or k == 0 returns
  * VSS_OK and writes nothing.
  * The _device form takes device pointers for everything but `columns` (d_out_distances and d_out_route may be NULL), copies d_lo
- * and d_hi back (8 * n_columns bytes per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin
- * forms; OR inside a box and more than four columns keep the bitmap calls; 64-bit columns have the box64 call below, and an IN-list
+ * and d_hi back (8 * n_columns bytes per query) and runs on context 0.  The pipelined / multi-batch forms: vss_search_by_label_device_begin, below;
+ * OR inside a box and more than four columns keep the bitmap calls; 64-bit columns have the box64 call below, and an IN-list
  * inside a box the set_box call below that. */
 #define VSS_LABEL_COLUMNS_MAX 4
 int vss_set_label_column(vss_index *index, uint32_t column, uint64_t first_rowid, const uint32_t *labels, uint64_t n);
@@ -399,7 +399,7 @@ int vss_search_batch_by_label_box_device(vss_index *index, const float *d_querie
  * every named column 32 bits wide and every end below 2^32 that is also, counters included, the answer of
  * vss_search_batch_by_label_box.
  * Errors: those of the box call, in its order, except that no width is refused.  The _device form copies d_lo and d_hi back
- * (16 * n_columns bytes per query) and runs on context 0.  Not available in the pipelined / multi-batch _begin forms; there is no
+ * (16 * n_columns bytes per query) and runs on context 0.  The pipelined / multi-batch forms: vss_search_by_label_device_begin, below; there is no
  * 64-bit equality call of its own (a box with lo == hi is the equality); the 64-bit set call is vss_search_batch_by_label_set_box
  * with n_columns == 0, below. */
 #define VSS_NO_LABEL64 0xFFFFFFFFFFFFFFFFull
@@ -439,8 +439,8 @@ int vss_search_batch_by_label_box64_device(vss_index *index, const float *d_quer
  * VSS_LABEL_COLUMNS_MAX, a named column repeated or equal to set_column; the message names it); a column that was never set ("no
  * label column" and its number); then the errors of the mode's own call.  n_queries == 0 or k == 0 returns VSS_OK having done
  * nothing.  The _device form takes device pointers for everything but `columns` (d_out_distances and d_out_route may be NULL),
- * copies d_sets, d_lo and d_hi back (8 * (set_width + 2 n_columns) bytes per query) and runs on context 0.  Not available in the
- * pipelined / multi-batch _begin forms, and the columns are not persisted, as for its siblings.  More than one set term per
+ * copies d_sets, d_lo and d_hi back (8 * (set_width + 2 n_columns) bytes per query) and runs on context 0.  The pipelined / multi-batch forms: vss_search_by_label_device_begin, below;
+ * the columns are not persisted, as for its siblings.  More than one set term per
  * predicate, OR across columns and lists beyond VSS_LABEL_SET_MAX values keep the bitmap calls; a query's list is neither
  * canonicalised nor de-duplicated. */
 int vss_search_batch_by_label_set_box(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k, uint64_t ef,
@@ -508,6 +508,51 @@ int vss_search_batch_filtered_groups_device_begin(vss_index *index, int context,
 int vss_search_multi_filtered_device_begin(vss_index *index, int context, uint64_t n_batches, const float *const *d_queries,
                                            uint64_t n_per_batch, uint64_t k, uint64_t ef, const uint64_t *const *d_allowed,
                                            const uint64_t *n_groups, uint64_t n_bits, const uint32_t *const *d_group_of,
+                                           int64_t *const *d_out_rowids, float *const *d_out_distances,
+                                           uint32_t *const *d_out_counts);
+/* ---- Label predicates in the pipelined and multi-batch launches --------------------------------------------------------------
+ * The six forms above on a caller's context (0..3), completed by vss_search_batch_end: a join's pipeline threads keep one context
+ * each, several join chunks ride in one launch.  Both calls WALK THE GRAPH — mode VSS_BY_LABEL_GRAPH; there is no mode argument.
+ * Modes exact and auto plan on the host (they read counts back) and stay blocking calls on context 0; label columns are still not
+ * persisted.
+ * vss_label_predicate names one form and carries what the form's _device call carries.  Layouts, element widths, padding words
+ * (VSS_NO_LABEL / VSS_NO_LABEL64), "no upper bound" and what a query admits are exactly those of that call:
+ *   VSS_LABEL_EQ       vss_search_batch_by_label_device          d_want (uint32_t)
+ *   VSS_LABEL_RANGE    vss_search_batch_by_label_range_device    d_lo, d_hi (uint32_t)
+ *   VSS_LABEL_SET      vss_search_batch_by_label_set_device      d_sets (uint32_t), set_width
+ *   VSS_LABEL_BOX      vss_search_batch_by_label_box_device      columns, n_columns, d_lo, d_hi (uint32_t)
+ *   VSS_LABEL_BOX64    vss_search_batch_by_label_box64_device    columns, n_columns, d_lo, d_hi (uint64_t)
+ *   VSS_LABEL_SET_BOX  vss_search_batch_by_label_set_box_device  set_column, d_sets (uint64_t), set_width, columns, n_columns, d_lo, d_hi
+ * Fields a kind does not use are ignored.  The struct and `columns` are host memory, read before the call returns; the d_ pointers
+ * are device memory, read on the device only — nothing is copied back, nothing is staged, the call does not wait — and they stay
+ * the caller's, valid and unchanged, until vss_search_batch_end(context) returns (its re-run rounds read the table made of them).
+ * Every query gets, bit for bit (row ids, f32 distance bits, count), what the form's _device call in mode VSS_BY_LABEL_GRAPH gives
+ * it, and a launch of one batch leaves the same vss_last_search_stats / _shape behind.
+ * vss_search_multi_by_label_device_begin: 1..32 batches of n_per_batch queries in ONE launch, as vss_search_multi_device_begin
+ * carries them; batch b brings predicates[b] with its own per-query words.  All batches of a launch share the kind, the named
+ * columns in the same order (and the set column), and the set width; a launch that mixes them is refused with a message naming the
+ * first batch that differs from batch 0.  d_out_distances[b] may be NULL.  The counters then cover all the batches.
+ * VSS_ERROR before anything is enqueued, nothing written to the outputs: context out of range or already in flight; n_batches
+ * outside 1..32; a NULL table; a kind other than the six; a mixed launch; and everything the form's blocking call refuses, in its
+ * words (for the multi call with "batch b" after the entry point's name).  These checks are made whatever n_queries and k are, as
+ * the blocking calls make them; with them passed, n_queries == 0 or k == 0: VSS_OK, nothing enqueued, nothing pending.  Both honour the pipelining gate below.  The writers of label columns are refused while such a probe is in
+ * flight, so the columns cannot move under a launch. */
+enum { VSS_LABEL_EQ = 0, VSS_LABEL_RANGE = 1, VSS_LABEL_SET = 2, VSS_LABEL_BOX = 3, VSS_LABEL_BOX64 = 4, VSS_LABEL_SET_BOX = 5 };
+typedef struct vss_label_predicate {
+	int kind;             /* VSS_LABEL_* */
+	uint32_t set_column;  /* SET_BOX */
+	uint32_t set_width;   /* SET, SET_BOX */
+	uint32_t n_columns;   /* BOX, BOX64: 1..4; SET_BOX: 0..3 */
+	uint32_t columns[4];  /* VSS_LABEL_COLUMNS_MAX entries, [0, n_columns) used */
+	const void *d_want;   /* EQ */
+	const void *d_sets;   /* SET, SET_BOX */
+	const void *d_lo, *d_hi; /* RANGE, BOX, BOX64, SET_BOX */
+} vss_label_predicate;
+int vss_search_by_label_device_begin(vss_index *index, int context, const float *d_queries, uint64_t n_queries, uint64_t k,
+                                     uint64_t ef, const vss_label_predicate *predicate, int64_t *d_out_rowids,
+                                     float *d_out_distances, uint32_t *d_out_counts);
+int vss_search_multi_by_label_device_begin(vss_index *index, int context, uint64_t n_batches, const float *const *d_queries,
+                                           uint64_t n_per_batch, uint64_t k, uint64_t ef, const vss_label_predicate *predicates,
                                            int64_t *const *d_out_rowids, float *const *d_out_distances,
                                            uint32_t *const *d_out_counts);
 int vss_search_batch_end(vss_index *index, int context);
