@@ -28,11 +28,13 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 
 TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip",
                      "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip",
-                     "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip"]
+                     "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip", "exact_split.hip"]
+# flags of single translation units: the split-bf16 score tile is built without packed f32 arithmetic
+TU_FLAGS = {"exact_split.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def build_library(force=False, extra_flags=(), out=None):
-    """hipcc cross-compiles the engine for gfx950 (works without a GPU): eleven translation units in parallel, then a
+    """hipcc cross-compiles the engine for gfx950 (works without a GPU): twelve translation units in parallel, then a
     shared link.  Objects live in build/ (git-ignored)."""
     out = out or os.path.join(HERE, "libvssgpu.so")
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
@@ -46,7 +48,7 @@ def build_library(force=False, extra_flags=(), out=None):
     for tu in TRANSLATION_UNITS:
         obj = os.path.join(objdir, tu.replace(".hip", ".o"))
         objs.append(obj)
-        procs.append(subprocess.Popen(["hipcc"] + flags + ["-c", os.path.join(CSRC, tu), "-o", obj]))
+        procs.append(subprocess.Popen(["hipcc"] + flags + TU_FLAGS.get(tu, []) + ["-c", os.path.join(CSRC, tu), "-o", obj]))
     for p in procs:
         if p.wait() != 0:
             raise RuntimeError("hipcc failed")
@@ -129,6 +131,7 @@ SIGNATURES = {
     "vss_search_batch_by_label_set_box_device": (_int, [_vp, _vp, _u64, _u64, _u64, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _int, _u64,
                                                         _vp, _vp, _vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
+    "vss_last_exact_scores": (_int, [_vp, _vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
     "vss_last_search_prescore": (_int, [_vp, _vp]),
@@ -837,6 +840,13 @@ class GpuIndex:
         """Queries of the last exact search that were answered again by brute force in the metric (their selection by ranking
         score could not be certified, csrc/exact_certificate.h)."""
         return int(self.lib.vss_last_exact_fallbacks(self.h))
+
+    def last_exact_scores(self):
+        """[score kind of the last exact search (0 = f32, 1 = split bf16: set_option("exact.split_bf16", 1)), its score launches,
+        the largest finite certificate bound E as a float, 0]."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.vss_last_exact_scores(self.h, _p(out)))
+        return [int(out[0]), int(out[1]), float(out[2:3].view(np.float64)[0]), int(out[3])]
 
     def timing(self, reset=False):
         out = np.zeros(6, dtype=np.float64)

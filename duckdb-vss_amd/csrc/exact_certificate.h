@@ -83,6 +83,76 @@ VSS_CERT_HD inline double exact_cert_error(int metric, uint32_t n, float qn2, fl
 	return E * (1.0 + 0x1p-20) + 0x1p-100;
 }
 
+// ---- the split-bf16 score (score kind 1: k_exact_scores_bf16x3, exact_split_kernels.h; split_bf16.h) --------------------
+// The tile's dot product is  dot3 = fl( sum_i qh_i xh_i + qh_i xl_i + ql_i xh_i ),  q_i = qh_i + ql_i + rq_i and likewise x_i,
+// w = 2^-8 the unit roundoff of bf16:  |q_i - qh_i| <= w |q_i|,  |ql_i| <= w (1 + w) |q_i|,  |rq_i| <= w^2 |q_i|.  Two parts:
+//   * SPLIT.  With qt_i = qh_i + ql_i:  q_i x_i = qt_i xt_i + rq_i x_i + qt_i rx_i, and qt_i xt_i is the three terms kept plus
+//     ql_i xl_i.  So per element
+//         |q_i x_i - (qh_i xh_i + qh_i xl_i + ql_i xh_i)| <= |ql_i xl_i| + |rq_i x_i| + |qt_i rx_i|
+//                                                        <= w^2 ((1 + w)^2 + 1 + (1 + w^2)) |q_i| |x_i|,
+//     and over the row, by Cauchy-Schwarz (sum |q_i| |x_i| <= A B):  c 2^-16 A B,  c = (1 + 2^-8)^2 + 2 + 2^-16 = 3.0078...
+//   * ACCUMULATION.  The 3 n products are exact in f32 (8 bits times 8 bits) and are added in an order the hardware chooses.
+//     How the matrix pipe rounds inside a 16-deep bf16 dot product is not documented as round-to-nearest, so — an ASSUMPTION
+//     about the hardware, checked by nothing but the contract tests — every addition is given a relative error of 2 u
+//     (u = 2^-24; this covers truncation), gamma2(m) = 2 m u / (1 - 2 m u):  any order of the 3 n terms is within
+//     gamma2(3 n) sum |terms|, and  sum |terms| <= (1 + w)^2 (1 + 2 w) A B  (|qh_i| <= (1 + w) |q_i|, |xl_i| <= w (1 + w) |x_i|).
+//   Together  |dot3 - q.x| <= sigma A B + F,   sigma = c 2^-16 + gamma2(3 n) (1 + 2^-8)^2 (1 + 2^-7),
+//   F = 2^-124 (sqrt(n) (A + B) + 3 n)  an absolute slack for operands and products below the normal range that the pipe may
+//   flush (each flushed hi, lo or product loses at most 2^-126 times its partner).
+// sigma >= gamma(n + 1), and sigma takes its place on the score side of every E above; the engine side (the wave-order metric,
+// |x|^2, |q|^2, the cosine's roots) and the range guards are the f32 form's, so a refusal depends on the norms only and happens
+// exactly where the f32 form refuses — a score that overflowed in bf16 belongs to norms the guards turn away:
+//   * l2sq:  xn2 and |q|^2 stay f32 sums of squares (gamma(n + 1) (A^2 + B^2) <= gamma(n + 1) (A + B)^2), the dot product
+//            enters twice, the score's own subtraction rounds a number of at most (1 + sigma) (B^2 + 2 A B):
+//                E = (gamma(n + 2) + gamma(n + 1) + u (1 + sigma)) (A + B)^2 + 2 sigma A B + 2 F
+//   * ip:        E = (gamma(n) + sigma) A B + u (1 + (1 + gamma(n)) A B) + F
+//   * cosine:    E = [engine, as above] + rs + (sigma + F / (A Bmin)) (1 + rs)
+// Each is at least the f32 form's E for the same arguments.
+VSS_CERT_HD inline double exact_cert_split_term() { // c 2^-16: the three kept terms against q.x, per unit of A B
+	const double w = 0x1p-8;
+	return ((1.0 + w) * (1.0 + w) + 2.0 + w * w) * w * w;
+}
+VSS_CERT_HD inline double exact_cert_split_sigma(uint32_t n) { // split and accumulation together, per unit of A B
+	const double u = 0x1p-24, w = 0x1p-8;
+	const double g2 = 6.0 * n * u / (1.0 - 6.0 * n * u);
+	return exact_cert_split_term() + g2 * (1.0 + w) * (1.0 + w) * (1.0 + 2.0 * w);
+}
+VSS_CERT_HD inline double exact_cert_split_flush(uint32_t n, double A, double B) { // F
+	return 0x1p-124 * (sqrt((double)n) * (A + B) + 3.0 * n);
+}
+
+VSS_CERT_HD inline double exact_cert_error_split(int metric, uint32_t n, float qn2, float xn2_max, float xn2_min) {
+	const double u = 0x1p-24, lo = 0x1p-80, hi = 0x1p80; // (the guards of exact_cert_error, unchanged)
+	const double a2 = qn2, b2 = xn2_max, b2min = xn2_min;
+	if (!(a2 >= 0.0 && a2 <= hi) || !(b2 >= 0.0 && b2 <= hi) || !((double)n * u < 0.01))
+		return (double)INFINITY;
+	if (metric == 1 && (!(a2 >= lo) || !(b2min >= lo)))
+		return (double)INFINITY;
+	const double gn = exact_cert_gamma(n), gn1 = exact_cert_gamma(n + 1.0), gn2 = exact_cert_gamma(n + 2.0);
+	const double A = sqrt(a2 / (1.0 - gn)), B = sqrt(b2 / (1.0 - gn));
+	const double sigma = exact_cert_split_sigma(n);
+	const double F = exact_cert_split_flush(n, A, B);
+	double E;
+	if (metric == 0)
+		E = (gn2 + gn1 + u * (1.0 + sigma)) * (A + B) * (A + B) + 2.0 * sigma * A * B + 2.0 * F;
+	else if (metric == 2)
+		E = (gn + sigma) * A * B + u * (1.0 + (1.0 + gn) * A * B) + F;
+	else {
+		const double h = 1.0 / sqrt(1.0 - gn) - 1.0;
+		const double rd = (1.0 + h) * (1.0 + h) * (1.0 + 2.0 * u) * (1.0 + 2.0 * u) * (1.0 + u) - 1.0, r = rd / (1.0 - rd);
+		const double rs = (1.0 + 4.0 * u) * (1.0 + h) * (1.0 + h) * (1.0 + u) - 1.0;
+		const double Bmin = sqrt(b2min) / (1.0 + h); // (a lower bound of the smallest real row norm)
+		E = (gn + r + u) * (1.0 + r) * (1.0 + u) * (1.0 + u) + 2.0 * u + rs + (sigma + F / (A * Bmin)) * (1.0 + rs);
+	}
+	return E * (1.0 + 0x1p-20) + 0x1p-100;
+}
+
+// E of the score kind a launch ran with: 0 = the f32 tiles, 1 = the split-bf16 tile
+VSS_CERT_HD inline double exact_cert_error_of(int score_kind, int metric, uint32_t n, float qn2, float xn2_max, float xn2_min) {
+	return score_kind == 1 ? exact_cert_error_split(metric, n, qn2, xn2_max, xn2_min)
+	                       : exact_cert_error(metric, n, qn2, xn2_max, xn2_min);
+}
+
 // FLOOR: no live row outside the kept set has an engine distance below it (-inf = no certificate).  tau_s = the largest
 // score of the (full) kept set, E = exact_cert_error of this query.
 VSS_CERT_HD inline double exact_cert_floor_given(int metric, float tau_s, float qn2, double E) {

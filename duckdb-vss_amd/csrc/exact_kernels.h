@@ -4,6 +4,8 @@
 //   k_exact_scores     S[B x C] = f(Q . X^T) on MFMA f32 (v_mfma_f32_32x32x2_f32), LDS-staged 128x128x32 tiles.
 //                      Replaces the distance loop of usearch search_exact_ (index.hpp:4004-4019) for a whole
 //                      batch of queries at once; scores are RANKING scores (|x|^2 - 2 q.x, -q.x/|x|, -q.x).
+//   k_exact_scores_bf16x3  the same scores from a two-way bf16 split of both operands on v_mfma_f32_32x32x16_bf16
+//                      (exact_split_kernels.h; option exact.split_bf16)
 //   k_exact_select     per query: fold one chunk of scores into a running top-K' (K' = k + slack)
 //   k_exact_rerank     per query: recompute the K' survivors with the exact wave-order metric, sort, emit k; decides whether
 //                      the selection by score provably kept the metric's top-k (exact_certificate.h)
@@ -57,6 +59,7 @@ __global__ void k_row_norms(const float4 *vectors, uint32_t V, uint32_t G, uint3
 // ds_read_b128 plus register-staged prefetch (two LDS buffers / one barrier, or one buffer), a K step of 16 with and
 // without a second LDS buffer and the next step's loads in flight during the MFMAs, and software-pipelined operand reads
 // inside the wave (sched_group_barrier: reads of step k+1 ahead of the MFMAs of step k).
+#endif // VSS_ENGINE_TU (the tile's types and arguments are shared with exact_split.hip)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #ifndef VSS_EXACT_WAVES
@@ -94,6 +97,7 @@ struct ExactArgs {
 	float *cand_s;      // n_queries x cand_cap
 	uint32_t *cand_i;
 };
+#ifdef VSS_ENGINE_TU
 
 // Register budget pinned to 4 waves per SIMD (128 registers, accumulators included): left alone the compiler takes 92
 // VGPRs + 64 AGPRs = 3 waves per SIMD, i.e. three of the four workgroups the LDS admits per CU; with four, 0.73-0.745 of
@@ -753,6 +757,7 @@ __device__ __forceinline__ void glds16(uint32_t lds_dst, uint32_t lane_offset, c
 	             : "memory");
 }
 
+#endif // VSS_ENGINE_TU
 template <int MT>
 __device__ __forceinline__ float exact_score(float dot, float xn2, float rs) {
 	if (MT == 0)
@@ -761,6 +766,7 @@ __device__ __forceinline__ float exact_score(float dot, float xn2, float rs) {
 		return -dot;
 	return xn2 > 0.f ? -dot * rs : 0.f;
 }
+#ifdef VSS_ENGINE_TU
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_exact_scores_v4(ExactArgs a) {
 	constexpr int TN = 2;
@@ -1301,6 +1307,8 @@ struct RerankArgs {
 	const float *best_s;
 	const uint32_t *norm_ext; // bit patterns of the largest and the smallest |x|^2 over the live rows (k_norm_extrema)
 	uint32_t *certified;
+	int score_kind;            // which tile produced best_s, hence which E holds: 0 = f32, 1 = split bf16 (exact_cert_error_of)
+	unsigned long long *e_max; // bit pattern of the largest finite E used (doubles >= 0 order like their bits); NULL = not asked for
 	// the redo: workgroup b answers query query_map[b] from row b of best_i (NULL = identity)
 	const uint32_t *query_map;
 };
@@ -1330,8 +1338,10 @@ __global__ __launch_bounds__(64) void k_exact_rerank(RerankArgs a) {
 	if (a.certified) {
 		// every live row outside the kept set has a distance >= floor; a kept set that is not full holds every live row (within
 		// the model's range of norms, where no score reaches the select's 3e38 cut)
-		const double E = exact_cert_error(MT, a.gv.sp.V * 4u, qa2, __uint_as_float(a.norm_ext[0]), __uint_as_float(a.norm_ext[1]));
+		const double E = exact_cert_error_of(a.score_kind, MT, a.gv.sp.V * 4u, qa2, __uint_as_float(a.norm_ext[0]), __uint_as_float(a.norm_ext[1]));
 		const bool model = E < (double)__builtin_inff();
+		if (a.e_max && model && lane == 0)
+			atomicMax(a.e_max, (unsigned long long)__double_as_longlong(E));
 		const double floor_d = exact_cert_floor_given(MT, a.best_s[(size_t)bq * a.KP + a.KP - 1], qa2, E);
 		int below = 0;
 		for (int off = 0; off < n; off += 64)
@@ -1587,3 +1597,5 @@ __global__ __launch_bounds__(64) void k_merge_topk(const float *in_d, const int6
 #endif // VSS_ENGINE_TU
 
 } // namespace vss
+
+#include "exact_split_kernels.h" // k_exact_scores_bf16x3: the 128 x 128 tile on the bf16 matrix pipe (option exact.split_bf16)

@@ -821,6 +821,14 @@ struct vss_index {
 	uint64_t last_exact_fallbacks = 0; // queries of the last exact call that were redone
 	bool exact_filter = true; // the select folded into the score tile's epilogue from the second chunk on (VSS_EXACT_FILTER=0: A/B)
 	uint64_t norms_valid_for = ~0ull; // value of `mutations` the norms were computed at
+	// exact.split_bf16 (exact_split_kernels.h): the first pass's score launches run k_exact_scores_bf16x3 where the padded
+	// dimension is a multiple of 32, and the re-rank certifies with the split score's E.  Off by default.  d_q_hi / d_q_lo: the
+	// query block split once per call (eight bf16 per cell); last_exact_scores: vss_last_exact_scores.
+	bool exact_split_bf16 = false;
+	DevBuf<uint4> d_q_hi, d_q_lo;
+	DevBuf<uint64_t> d_e_max;
+	uint64_t last_exact_scores[4] = {0, 0, 0, 0};
+	std::atomic<uint64_t> exact_split_bytes {0}; // of d_q_hi and d_q_lo (vss_memory_usage, read without a lock)
 	// vss_search_exact_batch_filtered_groups (exact_filtered_kernels.h), under exact_mu like the rest: the lists of one pass, the
 	// block counts of the groups in use, and the small tables of the plan.  exact_filter_budget = B, the entries the lists of
 	// one pass may hold where that is more than the index has rows (VSS_EXACT_FILTER_LIST_ENTRIES).
@@ -888,6 +896,7 @@ struct vss_index {
 		d_global_hash.free(), d_row_norm2.free(), d_q_norm2.free(), d_scores.free(), d_best_s.free(), d_qpad.free();
 		d_best_i.free(), d_cand_s.free(), d_cand_cnt.free(), d_cand_i.free();
 		d_norm_ext.free(), d_certified.free(), d_redo_map.free();
+		d_q_hi.free(), d_q_lo.free(), d_e_max.free();
 		d_xf_lists.free(), d_xf_counts.free(), d_xf_tables.free();
 		exact_filter_bytes.store(0, std::memory_order_relaxed);
 		if (h_counters)
@@ -2358,6 +2367,7 @@ struct vss_index {
 			return VSS_OK;
 		std::lock_guard<std::mutex> exact_lock(exact_mu); // score tiles, norms and the index stream are shared
 		last_exact_fallbacks = 0;
+		std::fill(last_exact_scores, last_exact_scores + 4, 0);
 		// Contract: for finite inputs the answer is the brute force of the wave-order metric over the live rows,
 		// ordered by (distance, slot).  Rows are SELECTED by an MFMA ranking score, the survivors re-scored with the metric; the
 		// re-rank certifies per query that the selection cannot have lost a row (csrc/exact_certificate.h), and the queries it
@@ -2398,6 +2408,18 @@ struct vss_index {
 		                         hipMemcpyDeviceToDevice, stream));
 		hipLaunchKernelGGL(k_row_norms, dim3(256), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V,
 		                   G, logG, (uint32_t)nq, d_q_norm2.p);
+		// exact.split_bf16: the score tile on the bf16 matrix pipe, where a row is a whole number of 128-byte steps (and, as for
+		// the LDS-DMA tile, a tile's rows lie within 32-bit offsets); other shapes keep the f32 tile.  The queries are split once.
+		const bool split = exact_split_bf16 && V % 8 == 0 && 128ull * V * 16 < (1ull << 31);
+		const int score_kind = split ? 1 : 0;
+		uint64_t score_launches = 0;
+		if (split) {
+			const uint64_t n8 = nq * (uint64_t)V / 2; // cells of eight bf16
+			d_q_hi.ensure(n8, 0, stream);
+			d_q_lo.ensure(n8, 0, stream);
+			exact_split_bytes.store((d_q_hi.n + d_q_lo.n) * sizeof(uint4), std::memory_order_relaxed);
+			HIP_TRY(launch_split_queries(reinterpret_cast<const float4 *>(d_qpad.p), n8, d_q_hi.p, d_q_lo.p, stream));
+		}
 		// Round 4: from the second chunk on the select is folded into the score tile's epilogue — only scores that beat a
 		// query's K'-th best so far are kept (as survivors in a small per-query buffer), and the running top-K' is refreshed
 		// from those buffers once per launch of eight chunks' worth of rows instead of from 128 KiB of scores per query after
@@ -2412,7 +2434,7 @@ struct vss_index {
 		// behind one chunk would fill a quarter of the buffer — the plain way is taken from the start (the first
 		// window of eight chunks used to overflow almost surely for k above ~248, and the whole pass was then repeated).
 		const uint64_t CAND_CAP = SEL_CAP, SELECT_EVERY = 8;
-		const bool want_filter = exact_filter && (exact_kernel == 2 || exact_kernel >= 4) && rows > CH && 8 * KP <= CAND_CAP;
+		const bool want_filter = exact_filter && (split || exact_kernel == 2 || exact_kernel >= 4) && rows > CH && 8 * KP <= CAND_CAP;
 		if (want_filter) {
 			d_cand_cnt.ensure(nq + 1, 0, stream); // [nq] = the overflow flag
 			d_cand_s.ensure(nq * CAND_CAP, 0, stream);
@@ -2446,7 +2468,12 @@ struct vss_index {
 				e.best_s = d_best_s.p, e.best_i = d_best_i.p, e.KP = (uint32_t)KP, e.cand_cap = (uint32_t)CAND_CAP;
 				e.cand_cnt = filter_this ? d_cand_cnt.p : nullptr;
 				e.cand_s = d_cand_s.p, e.cand_i = d_cand_i.p;
-				if (exact_kernel >= 4) { // round 5: the 128 x 128 tile as persistent workgroups, two per compute unit
+				++score_launches;
+				if (split) { // the persistent 128 x 128 tile on v_mfma_f32_32x32x16_bf16, two workgroups per compute unit
+					const uint64_t tiles = ((r1 - r0 + 127) / 128) * ((nq + 127) / 128);
+					const uint32_t grid = (uint32_t)std::min<uint64_t>(2ull * n_cus, tiles);
+					HIP_TRY(launch_exact_scores_bf16x3(e, d_q_hi.p, d_q_lo.p, grid, stream));
+				} else if (exact_kernel >= 4) { // round 5: the 128 x 128 tile as persistent workgroups, two per compute unit
 					const uint64_t tiles = ((r1 - r0 + 127) / 128) * ((nq + 127) / 128);
 					const uint32_t grid = (uint32_t)std::min<uint64_t>(2ull * n_cus, tiles);
 					// operands by LDS-DMA (5, the default) where a row is a whole number of 128-byte steps and a tile's rows lie within
@@ -2488,7 +2515,10 @@ struct vss_index {
 				r0 = r1;
 			}
 		};
+		ensure_events();
+		HIP_TRY(hipEventRecord(ev[0], stream));
 		run(want_filter);
+		HIP_TRY(hipEventRecord(ev[1], stream)); // (score tiles and selects of the first pass: timing[0] below)
 		if (want_filter) {
 			uint32_t overflowed = 0;
 			HIP_TRY(hipMemcpyAsync(&overflowed, d_cand_cnt.p + nq, 4, hipMemcpyDeviceToHost, stream));
@@ -2511,13 +2541,25 @@ struct vss_index {
 		r.norm_ext = d_norm_ext.p;
 		r.certified = d_certified.p;
 		r.query_map = nullptr;
+		d_e_max.ensure(1, 0, stream);
+		HIP_TRY(hipMemsetAsync(d_e_max.p, 0, 8, stream));
+		r.score_kind = score_kind;
+		r.e_max = reinterpret_cast<unsigned long long *>(d_e_max.p);
 		const uint32_t lds = align16(V * 16) + 2 * align16((uint32_t)KP * 4);
 		launch_by_metric<RerankArgs>(launch_rerank<0>, launch_rerank<1>, launch_rerank<2>, r,
 		                             launch_cfg((uint32_t)nq, lds, 64));
 		// the queries the re-rank could not certify: redone with the metric itself as the score
 		std::vector<uint32_t> flags(nq), redo;
 		HIP_TRY(hipMemcpyAsync(flags.data(), d_certified.p, nq * 4, hipMemcpyDeviceToHost, stream));
+		last_exact_scores[0] = (uint64_t)score_kind, last_exact_scores[1] = score_launches;
+		HIP_TRY(hipMemcpyAsync(&last_exact_scores[2], d_e_max.p, 8, hipMemcpyDeviceToHost, stream));
 		HIP_TRY(hipStreamSynchronize(stream));
+		{
+			float ms = 0;
+			HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+			std::lock_guard<std::mutex> lk(stats_mu);
+			timing[0] = ms;
+		}
 		for (uint64_t i = 0; i != nq; ++i)
 			if (!flags[i] || exact_certify == 2)
 				redo.push_back((uint32_t)i);
@@ -2571,7 +2613,7 @@ struct vss_index {
 			s.overflow = nullptr;
 			hipLaunchKernelGGL(k_exact_select, dim3((uint32_t)nb), dim3(SEL_THREADS), 0, stream, s);
 		}
-		r.certified = nullptr; // (the kept set is the metric's own top-K': nothing left to prove)
+		r.certified = nullptr, r.e_max = nullptr; // (the kept set is the metric's own top-K': nothing left to prove)
 		r.query_map = d_redo_map.p;
 		launch_by_metric<RerankArgs>(launch_rerank<0>, launch_rerank<1>, launch_rerank<2>, r,
 		                             launch_cfg((uint32_t)nb, lds, 64));
@@ -2760,6 +2802,7 @@ struct vss_index {
 		r.out_d = out.dist;
 		r.out_count = out.count;
 		r.best_s = nullptr, r.norm_ext = nullptr, r.certified = nullptr;
+		r.score_kind = 0, r.e_max = nullptr;
 		r.query_map = d_xf_tables.p + at_order;
 		const uint32_t lds = align16(V * 16) + 2 * align16((uint32_t)KP * 4);
 		launch_by_metric<RerankArgs>(launch_rerank<0>, launch_rerank<1>, launch_rerank<2>, r, launch_cfg((uint32_t)nq, lds, 64));
@@ -3741,6 +3784,8 @@ const OptionRule OPTION_RULES[] = {
      "at most 256, 2 in every pipelined launch"},
     {"search.prescore_descent", 0, 1, [](vss_index *h, int64_t v) { h->search_prescore_descent = v != 0; },
      "in launches that filter on row codes, the greedy descent's rows are bounded against its closest distance too"},
+    {"exact.split_bf16", 0, 1, [](vss_index *h, int64_t v) { h->exact_split_bf16 = v != 0; },
+     "exact search selects rows by a split-bf16 score on the bf16 matrix pipe (dimensions whose padding is a multiple of 32)"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {
@@ -4943,6 +4988,14 @@ uint64_t vss_last_exact_fallbacks(vss_index *h) {
 	return h->last_exact_fallbacks;
 }
 
+int vss_last_exact_scores(vss_index *h, uint64_t *out4) {
+	if (!h || !out4)
+		return VSS_ERROR;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	std::memcpy(out4, h->last_exact_scores, sizeof h->last_exact_scores);
+	return VSS_OK;
+}
+
 int vss_last_search_shape(vss_index *h, uint32_t *out8) {
 	VSS_SHARED(h, {
 		std::lock_guard<std::mutex> lk(h->stats_mu);
@@ -5059,7 +5112,8 @@ uint64_t vss_memory_usage(vss_index *h) {
 	const uint64_t group_tables = h->group_table_bytes.load(std::memory_order_relaxed);
 	return h->d_vectors.n * 4 + h->d_links0.n * 4 + h->d_links_up.n * 4 + h->d_upper_off.n * 4 + h->d_levels.n +
 	       h->d_keys.n * 8 + h->d_list_owner.n * 4 + h->d_codes.n * sizeof(uint32_t) + h->d_code_meta.n * sizeof(RowCodeMeta) +
-	       group_tables + h->exact_filter_bytes.load(std::memory_order_relaxed) + h->label_bytes.load(std::memory_order_relaxed);
+	       group_tables + h->exact_filter_bytes.load(std::memory_order_relaxed) + h->label_bytes.load(std::memory_order_relaxed) +
+	       h->exact_split_bytes.load(std::memory_order_relaxed);
 }
 
 int vss_level_stats(vss_index *h, uint64_t level, uint64_t *out4) {

@@ -122,6 +122,9 @@ int vss_set_build_reorder(vss_index *index, int on);
  *   search.prescore_descent (0/1) in the launches that filter on row codes, the greedy descent's rows are bounded too, against the
  *                                descent's closest distance (default 1; 0: the descent scores every row it gathers);
  *                                vss_last_search_prescore_descent reports it
+ *   exact.split_bf16 (0/1)       vss_search_exact_batch* selects rows by a split-bf16 score on the bf16 matrix pipe instead of
+ *                                the f32 one (default 0; dimensions whose padding is no multiple of 32 keep the f32 tile);
+ *                                answers do not depend on it, vss_last_exact_fallbacks may; vss_last_exact_scores reports it
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -578,6 +581,13 @@ int vss_search_exact_batch_device(vss_index *index, const float *d_queries, uint
  * because their selection by score could not be certified (diagnostics and tests; results never depend on it; 0 on data
  * whose nearest neighbours are further apart than the f32 scores' rounding error, e.g. the benchmark's). */
 uint64_t vss_last_exact_fallbacks(vss_index *index);
+/* Which score tile the last vss_search_exact_batch* call selected rows with: out4[0] = the score kind, 0 = f32
+ * (v_mfma_f32_32x32x2_f32), 1 = split bf16 (vss_set_option "exact.split_bf16" = 1 and a dimension whose padding is a multiple
+ * of 32: q.x ~ qh.xh + qh.xl + ql.xh on v_mfma_f32_32x32x16_bf16, csrc/exact_split_kernels.h); [1] = its score launches;
+ * [2] = the bit pattern of the largest finite error bound E (a double, csrc/exact_certificate.h) the re-rank certified with,
+ * 0 if none was finite; [3] = 0.  Answers never depend on the option — the certificate carries the bound of the kind that ran,
+ * and what it cannot prove is redone in the metric — vss_last_exact_fallbacks may. */
+int vss_last_exact_scores(vss_index *index, uint64_t *out4);
 /* Work counters of the last vss_search_batch* call, summed over its queries (usearch's
  * search_result_t::computed_distances / visited_members, index.hpp:2566-2571):
  * out[0] = computed distances, out[1] = expanded nodes, out[2] = queries, out[3] = retried queries. */
