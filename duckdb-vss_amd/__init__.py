@@ -28,13 +28,16 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 
 TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip",
                      "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip",
-                     "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip", "exact_split.hip"]
-# flags of single translation units: the split-bf16 score tile is built without packed f32 arithmetic
-TU_FLAGS = {"exact_split.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                     "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip", "exact_split.hip",
+                     "exact_range.hip"]
+# flags of single translation units: the split-bf16 score tile and the range search are built without packed f32 arithmetic
+NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+TU_FLAGS = {"exact_split.hip": NO_PACKED_F32, "exact_range.hip": NO_PACKED_F32}
+RANGE_ROW_CHUNK = 8192  # rows per launch of the range search's candidate tile (csrc/exact_range.h)
 
 
 def build_library(force=False, extra_flags=(), out=None):
-    """hipcc cross-compiles the engine for gfx950 (works without a GPU): twelve translation units in parallel, then a
+    """hipcc cross-compiles the engine for gfx950 (works without a GPU): thirteen translation units in parallel, then a
     shared link.  Objects live in build/ (git-ignored)."""
     out = out or os.path.join(HERE, "libvssgpu.so")
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
@@ -132,6 +135,9 @@ SIGNATURES = {
                                                         _vp, _vp, _vp, _vp]),
     "vss_last_exact_fallbacks": (_u64, [_vp]),
     "vss_last_exact_scores": (_int, [_vp, _vp]),
+    "vss_search_range_batch": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_range_batch_device": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "vss_last_range": (_int, [_vp, _vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
     "vss_last_search_prescore": (_int, [_vp, _vp]),
@@ -847,6 +853,54 @@ class GpuIndex:
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_exact_scores(self.h, _p(out)))
         return [int(out[0]), int(out[1]), float(out[2:3].view(np.float64)[0]), int(out[3])]
+
+    def search_range_batch(self, Q, radii, capacity=None, sort=False):
+        """vss_search_range_batch: every live row within radii[q] of query q (the metric's own units, d <= r).  Returns
+        (offsets, row ids, distances, total): query q's matches are cells offsets[q]:offsets[q + 1], in no particular order
+        unless sort=True (by distance, then row id, on the host).  capacity=None counts first and then fills exactly; with a
+        capacity the cells come back empty when the total exceeds it (read the total and call again); capacity=0 only counts."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        radii = np.ascontiguousarray(radii, dtype=np.float32)
+        nq = len(Q)
+        if radii.shape != (nq,):
+            raise ValueError("radii must hold one radius per query: %d queries, shape %r" % (nq, radii.shape))
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        total = _u64(0)
+
+        def call(cells, ids, d):
+            self._check(self.lib.vss_search_range_batch(self.h, _p(Q), nq, _p(radii), cells, _p(offsets), _p(ids), _p(d),
+                                                        C.byref(total)))
+        if capacity is None:
+            call(0, None, None)
+            capacity = total.value
+        ids = np.full(capacity, -1, dtype=np.int64)
+        d = np.full(capacity, np.inf, dtype=np.float32)
+        if capacity:
+            call(capacity, ids, d)
+        else:
+            call(0, None, None)
+        if total.value > capacity:
+            return offsets, ids[:0], d[:0], total.value
+        ids, d = ids[:total.value], d[:total.value]
+        if sort:
+            for q in range(nq):
+                lo, hi = int(offsets[q]), int(offsets[q + 1])
+                order = np.lexsort((ids[lo:hi], d[lo:hi]))
+                ids[lo:hi], d[lo:hi] = ids[lo:hi][order], d[lo:hi][order]
+        return offsets, ids, d, total.value
+
+    def search_range_batch_device(self, d_Q, nq, d_radii, capacity, d_offsets, d_rowids, d_dist, d_total):
+        """The same over raw device pointers (d_offsets: nq + 1 uint64, d_total: one uint64; d_rowids / d_dist may be None
+        iff capacity == 0); blocking."""
+        self._check(self.lib.vss_search_range_batch_device(self.h, d_Q, nq, d_radii, capacity, d_offsets, d_rowids, d_dist,
+                                                           d_total))
+
+    def last_range(self):
+        """[pairs the score tile proposed, matches, queries without a finite error bound, bytes of scratch held] of the last
+        search_range_batch call."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.vss_last_range(self.h, _p(out)))
+        return out
 
     def timing(self, reset=False):
         out = np.zeros(6, dtype=np.float64)

@@ -29,6 +29,7 @@
 #include "filter_groups.h"
 #include "label_filter.h"
 #include "exact_filtered_kernels.h"
+#include "exact_range_kernels.h"
 #include "filter_route_kernels.h"
 #include "row_codes.h"
 
@@ -837,6 +838,16 @@ struct vss_index {
 	uint64_t last_exact_filtered[4] = {0, 0, 0, 0}; // vss_last_exact_filtered
 	uint64_t last_filter_route[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // vss_last_filter_route (under exact_mu too)
 	std::atomic<uint64_t> exact_filter_bytes {0};   // of the three buffers (vss_memory_usage, read without a lock)
+	// vss_search_range_batch (exact_range_kernels.h), under exact_mu like the rest: thresholds, counts and cursors per query, the
+	// fixed candidate buffer of one tile launch with a counter word per launch, the match scratch (16 bytes per cell of the
+	// caller's capacity, at most queries x rows), and the staging of the host-pointer form.
+	DevBuf<float> d_rg_theta, d_rg_m_dist, d_rg_radii, d_rg_q, d_rg_out_d;
+	DevBuf<uint32_t> d_rg_counts, d_rg_cand_count, d_rg_m_query;
+	DevBuf<uint2> d_rg_cand;
+	DevBuf<int64_t> d_rg_m_rowid, d_rg_out_ids;
+	DevBuf<uint64_t> d_rg_stats, d_rg_offsets;
+	uint64_t last_range[4] = {0, 0, 0, 0};        // vss_last_range
+	std::atomic<uint64_t> exact_range_bytes {0}; // of the buffers above (vss_memory_usage, read without a lock)
 	uint64_t mutations = 0;
 
 	int fail(const char *fmt, ...) {
@@ -899,6 +910,10 @@ struct vss_index {
 		d_q_hi.free(), d_q_lo.free(), d_e_max.free();
 		d_xf_lists.free(), d_xf_counts.free(), d_xf_tables.free();
 		exact_filter_bytes.store(0, std::memory_order_relaxed);
+		d_rg_theta.free(), d_rg_m_dist.free(), d_rg_radii.free(), d_rg_q.free(), d_rg_out_d.free(), d_rg_counts.free();
+		d_rg_cand_count.free(), d_rg_m_query.free(), d_rg_cand.free(), d_rg_m_rowid.free(), d_rg_out_ids.free();
+		d_rg_stats.free(), d_rg_offsets.free();
+		exact_range_bytes.store(0, std::memory_order_relaxed);
 		if (h_counters)
 			(void)hipHostFree(h_counters);
 		h_counters = nullptr;
@@ -2360,6 +2375,20 @@ struct vss_index {
 	}
 
 	// ------------------------------------------------------------------ exact search
+	// |x|^2 of every stored row and the certificate's largest / smallest live |x|^2, cached until the index changes (under
+	// exact_mu; the caller has ensured d_row_norm2 and d_norm_ext)
+	void refresh_row_norms(uint64_t rows) {
+		if (norms_valid_for == mutations)
+			return;
+		hipLaunchKernelGGL(k_row_norms, dim3(2048), dim3(256), 0, stream,
+		                   reinterpret_cast<const float4 *>(d_vectors.p), V, G, logG, (uint32_t)rows, d_row_norm2.p);
+		HIP_TRY(hipMemsetAsync(d_norm_ext.p, 0, 4, stream));
+		HIP_TRY(hipMemsetAsync(d_norm_ext.p + 1, 0xFF, 4, stream));
+		hipLaunchKernelGGL(k_norm_extrema, dim3((uint32_t)std::min<uint64_t>((rows + 255) / 256, 1024)), dim3(256), 0, stream,
+		                   d_row_norm2.p, d_keys.p, (uint32_t)rows, d_norm_ext.p);
+		norms_valid_for = mutations;
+	}
+
 	int exact_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, uint64_t k, int64_t *d_keys_out,
 	                 float *d_dist_out, uint32_t *d_count_out) {
 		const uint64_t rows = count;
@@ -2393,16 +2422,7 @@ struct vss_index {
 		d_best_i.ensure(nq * KP, 0, stream);
 		d_norm_ext.ensure(2, 0, stream);
 		d_certified.ensure(nq, 0, stream);
-		if (norms_valid_for != mutations) {
-			hipLaunchKernelGGL(k_row_norms, dim3(2048), dim3(256), 0, stream,
-			                   reinterpret_cast<const float4 *>(d_vectors.p), V, G, logG, (uint32_t)rows, d_row_norm2.p);
-			// the certificate's largest / smallest live |x|^2, cached with the norms
-			HIP_TRY(hipMemsetAsync(d_norm_ext.p, 0, 4, stream));
-			HIP_TRY(hipMemsetAsync(d_norm_ext.p + 1, 0xFF, 4, stream));
-			hipLaunchKernelGGL(k_norm_extrema, dim3((uint32_t)std::min<uint64_t>((rows + 255) / 256, 1024)), dim3(256), 0, stream,
-			                   d_row_norm2.p, d_keys.p, (uint32_t)rows, d_norm_ext.p);
-			norms_valid_for = mutations;
-		}
+		refresh_row_norms(rows);
 		HIP_TRY(hipMemsetAsync(d_qpad.p, 0, nq * stride * 4, stream));
 		HIP_TRY(hipMemcpy2DAsync(d_qpad.p, stride * 4, d_queries, (size_t)q_stride * 4, dim * 4, nq,
 		                         hipMemcpyDeviceToDevice, stream));
@@ -2619,6 +2639,123 @@ struct vss_index {
 		                             launch_cfg((uint32_t)nb, lds, 64));
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(stream));
+		return VSS_OK;
+	}
+
+	// ------------------------------------------------------------------ exact range search
+	// Contract (include/vssgpu.h): query q matches the live rows whose wave-order metric distance is <= radii[q].
+	// Rows are PROPOSED by the MFMA ranking score against a per-query threshold that no matching row can exceed (exact_range.h:
+	// the certificate's E pointed at the radius) and DECIDED by the metric itself, so nothing is certified and nothing redone.
+	// The caller holds exact_mu; every pointer is device memory; d_rowids / d_dist may be NULL iff cells == 0.
+	int range_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, const float *d_radii, uint64_t cells,
+	                 uint64_t *d_offsets, int64_t *d_rowids, float *d_dist, uint64_t *d_total) {
+		const uint64_t rows = count;
+		std::fill(last_range, last_range + 3, 0);
+		if (!nq || !rows) {
+			HIP_TRY(hipMemsetAsync(d_offsets, 0, (nq + 1) * 8, stream));
+			HIP_TRY(hipMemsetAsync(d_total, 0, 8, stream));
+			HIP_TRY(hipStreamSynchronize(stream));
+			return VSS_OK;
+		}
+		const uint64_t stride = (uint64_t)V * 4;
+		const uint64_t row_chunks = (rows + RANGE_ROW_CHUNK - 1) / RANGE_ROW_CHUNK, query_blocks = (nq + RANGE_QUERY_BLOCK - 1) / RANGE_QUERY_BLOCK;
+		const uint64_t match_cells = std::min(cells, nq * rows);
+		d_row_norm2.ensure(capacity, 0, stream);
+		d_norm_ext.ensure(2, 0, stream);
+		d_qpad.ensure(nq * stride, 0, stream);
+		d_q_norm2.ensure(nq, 0, stream);
+		d_rg_theta.ensure(nq, 0, stream);
+		d_rg_counts.ensure(2 * nq, 0, stream); // counts, then the scatter's cursors
+		d_rg_stats.ensure(4, 0, stream);
+		d_rg_cand_count.ensure(row_chunks * query_blocks, 0, stream);
+		// every pair of one tile launch fits: no overflow path
+		d_rg_cand.ensure(std::min<uint64_t>(nq, RANGE_QUERY_BLOCK) * std::min<uint64_t>(rows, RANGE_ROW_CHUNK), 0, stream);
+		if (match_cells) {
+			d_rg_m_query.ensure(match_cells, 0, stream);
+			d_rg_m_rowid.ensure(match_cells, 0, stream);
+			d_rg_m_dist.ensure(match_cells, 0, stream);
+		}
+		count_range_bytes();
+		refresh_row_norms(rows);
+		HIP_TRY(hipMemsetAsync(d_qpad.p, 0, nq * stride * 4, stream));
+		HIP_TRY(hipMemcpy2DAsync(d_qpad.p, stride * 4, d_queries, (size_t)q_stride * 4, dim * 4, nq, hipMemcpyDeviceToDevice, stream));
+		// (the wave-order |q|^2: the value k_exact_rerank's wave_query_norm computes, and the cosine distance's own)
+		hipLaunchKernelGGL(k_row_norms, dim3(256), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V, G, logG,
+		                   (uint32_t)nq, d_q_norm2.p);
+		HIP_TRY(hipMemsetAsync(d_rg_stats.p, 0, 4 * 8, stream));
+		HIP_TRY(hipMemsetAsync(d_rg_cand_count.p, 0, row_chunks * query_blocks * 4, stream));
+		RangeStats *stats = reinterpret_cast<RangeStats *>(d_rg_stats.p);
+		RangePrepareArgs p;
+		p.metric = metric, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
+		p.radii = d_radii, p.query_norm2 = d_q_norm2.p, p.norm_ext = d_norm_ext.p;
+		p.theta = d_rg_theta.p, p.counts = d_rg_counts.p, p.cursors = d_rg_counts.p + nq, p.stats = stats;
+		HIP_TRY(launch_range_prepare(p, stream));
+		RangeTileArgs t;
+		t.queries = reinterpret_cast<const float4 *>(d_qpad.p), t.vectors = reinterpret_cast<const float4 *>(d_vectors.p);
+		t.row_norm2 = d_row_norm2.p, t.keys = d_keys.p, t.theta = d_rg_theta.p, t.V = V, t.metric = metric, t.cand = d_rg_cand.p;
+		RangeRescoreArgs r;
+		r.sp = view().sp, r.keys = d_keys.p, r.queries = t.queries, r.query_norm2 = d_q_norm2.p, r.radii = d_radii;
+		r.cand = d_rg_cand.p, r.counts = d_rg_counts.p, r.stats = stats, r.capacity = match_cells;
+		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p;
+		uint32_t *launch_word = d_rg_cand_count.p;
+		// row chunks outside: a chunk's rows are read from HBM once and serve every query block out of the cache
+		for (uint64_t r0 = 0; r0 < rows; r0 += RANGE_ROW_CHUNK)
+			for (uint64_t q0 = 0; q0 < nq; q0 += RANGE_QUERY_BLOCK, ++launch_word) {
+				t.row_begin = (uint32_t)r0, t.row_end = (uint32_t)std::min<uint64_t>(rows, r0 + RANGE_ROW_CHUNK);
+				t.q_begin = (uint32_t)q0, t.q_end = (uint32_t)std::min<uint64_t>(nq, q0 + RANGE_QUERY_BLOCK);
+				t.cand_count = launch_word, r.cand_count = launch_word;
+				HIP_TRY(launch_range_candidates(t, stream));
+				HIP_TRY(launch_range_rescore(r, n_cus, stream));
+			}
+		RangeLayoutArgs l;
+		l.n_queries = (uint32_t)nq, l.counts = d_rg_counts.p, l.cursors = d_rg_counts.p + nq, l.stats = stats, l.capacity = match_cells;
+		l.offsets = reinterpret_cast<unsigned long long *>(d_offsets), l.total = reinterpret_cast<unsigned long long *>(d_total);
+		l.m_query = d_rg_m_query.p, l.m_rowid = d_rg_m_rowid.p, l.m_dist = d_rg_m_dist.p;
+		l.out_rowids = d_rowids, l.out_dist = d_dist;
+		HIP_TRY(launch_range_layout(l, n_cus, stream));
+		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		return VSS_OK;
+	}
+	void count_range_bytes() {
+		const uint64_t bytes = (d_rg_theta.n + d_rg_m_dist.n + d_rg_radii.n + d_rg_q.n + d_rg_out_d.n + d_rg_counts.n + d_rg_cand_count.n + d_rg_m_query.n) * 4 +
+		                       (d_rg_cand.n + d_rg_m_rowid.n + d_rg_out_ids.n + d_rg_stats.n + d_rg_offsets.n) * 8;
+		exact_range_bytes.store(bytes, std::memory_order_relaxed);
+		last_range[3] = bytes;
+	}
+	int range_device(const float *d_queries, uint64_t nq, const float *d_radii, uint64_t cells, uint64_t *d_offsets,
+	                 int64_t *d_rowids, float *d_dist, uint64_t *d_total) {
+		std::lock_guard<std::mutex> exact_lock(exact_mu);
+		return range_launch(d_queries, (uint32_t)dim, nq, d_radii, cells, d_offsets, d_rowids, d_dist, d_total);
+	}
+	// the host-pointer form: queries and radii in, offsets, total and — where the total fits — the cells out
+	int range_host(const float *queries, uint64_t nq, const float *radii, uint64_t cells, uint64_t *out_offsets, int64_t *out_rowids,
+	               float *out_d, uint64_t *out_total) {
+		std::lock_guard<std::mutex> exact_lock(exact_mu);
+		const uint64_t out_cells = std::min(cells, nq * (uint64_t)count); // (more can never be written)
+		d_rg_q.ensure(std::max<uint64_t>(nq * dim, 1), 0, stream);
+		d_rg_radii.ensure(std::max<uint64_t>(nq, 1), 0, stream);
+		d_rg_offsets.ensure(nq + 2, 0, stream); // offsets, then the total
+		d_rg_out_ids.ensure(out_cells, 0, stream);
+		d_rg_out_d.ensure(out_cells, 0, stream);
+		count_range_bytes();
+		if (nq) {
+			HIP_TRY(hipMemcpyAsync(d_rg_q.p, queries, nq * dim * 4, hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipMemcpyAsync(d_rg_radii.p, radii, nq * 4, hipMemcpyHostToDevice, stream));
+		}
+		if (const int rc = range_launch(d_rg_q.p, (uint32_t)dim, nq, d_rg_radii.p, out_cells, d_rg_offsets.p, d_rg_out_ids.p, d_rg_out_d.p,
+		                                d_rg_offsets.p + nq + 1))
+			return rc;
+		uint64_t total = 0;
+		HIP_TRY(hipMemcpyAsync(out_offsets, d_rg_offsets.p, (nq + 1) * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&total, d_rg_offsets.p + nq + 1, 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		*out_total = total;
+		if (total && total <= cells) {
+			HIP_TRY(hipMemcpyAsync(out_rowids, d_rg_out_ids.p, total * 8, hipMemcpyDeviceToHost, stream));
+			HIP_TRY(hipMemcpyAsync(out_d, d_rg_out_d.p, total * 4, hipMemcpyDeviceToHost, stream));
+			HIP_TRY(hipStreamSynchronize(stream));
+		}
 		return VSS_OK;
 	}
 
@@ -4245,6 +4382,46 @@ int vss_search_exact_batch_device(vss_index *h, const float *Q, uint64_t nq, uin
 	VSS_SHARED(h, { return h->exact_launch(Q, (uint32_t)h->dim, nq, k, out, out_d, out_counts); })
 }
 
+// Exact range search: every live row within radii[q] of query q, as offsets + cells (exact_range_kernels.h)
+static int check_range(vss_index *h, const char *what, const float *Q, uint64_t nq, const float *radii, uint64_t cells,
+                       const uint64_t *out_offsets, const int64_t *out_rowids, const float *out_d, const uint64_t *out_total) {
+	if (!out_offsets || !out_total)
+		return h->fail("%s: null offsets / total pointer", what);
+	if (nq && (!Q || !radii))
+		return h->fail("%s: null query / radius pointer", what);
+	if (cells && (!out_rowids || !out_d))
+		return h->fail("%s: null row-id / distance pointer with a capacity of %llu cells", what, (unsigned long long)cells);
+	if (nq > 0xFFFFFFFFull)
+		return h->fail("%s: at most 2^32 - 1 queries per call", what);
+	return VSS_OK;
+}
+
+int vss_search_range_batch(vss_index *h, const float *Q, uint64_t nq, const float *radii, uint64_t capacity, uint64_t *out_offsets,
+                           int64_t *out_rowids, float *out_d, uint64_t *out_total) {
+	VSS_SHARED(h, {
+		if (check_range(h, "vss_search_range_batch", Q, nq, radii, capacity, out_offsets, out_rowids, out_d, out_total) != VSS_OK)
+			return VSS_ERROR;
+		return h->range_host(Q, nq, radii, capacity, out_offsets, out_rowids, out_d, out_total);
+	})
+}
+
+int vss_search_range_batch_device(vss_index *h, const float *Q, uint64_t nq, const float *radii, uint64_t capacity,
+                                  uint64_t *out_offsets, int64_t *out_rowids, float *out_d, uint64_t *out_total) {
+	VSS_SHARED(h, {
+		if (check_range(h, "vss_search_range_batch_device", Q, nq, radii, capacity, out_offsets, out_rowids, out_d, out_total) != VSS_OK)
+			return VSS_ERROR;
+		return h->range_device(Q, nq, radii, capacity, out_offsets, out_rowids, out_d, out_total);
+	})
+}
+
+int vss_last_range(vss_index *h, uint64_t *out4) {
+	if (!h || !out4)
+		return VSS_ERROR;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	std::memcpy(out4, h->last_range, sizeof h->last_range);
+	return VSS_OK;
+}
+
 // Exact top-k under per-query predicates: only the rows a query's group admits are scored (exact_filtered_kernels.h).  The table
 // and the admission rule are vss_search_batch_filtered_groups'; group_of == NULL gives every query bitmap 0.
 static int check_exact_filtered(vss_index *h, const char *what, const float *Q, uint64_t nq, const FilterGroupBatch &table,
@@ -5113,7 +5290,7 @@ uint64_t vss_memory_usage(vss_index *h) {
 	return h->d_vectors.n * 4 + h->d_links0.n * 4 + h->d_links_up.n * 4 + h->d_upper_off.n * 4 + h->d_levels.n +
 	       h->d_keys.n * 8 + h->d_list_owner.n * 4 + h->d_codes.n * sizeof(uint32_t) + h->d_code_meta.n * sizeof(RowCodeMeta) +
 	       group_tables + h->exact_filter_bytes.load(std::memory_order_relaxed) + h->label_bytes.load(std::memory_order_relaxed) +
-	       h->exact_split_bytes.load(std::memory_order_relaxed);
+	       h->exact_split_bytes.load(std::memory_order_relaxed) + h->exact_range_bytes.load(std::memory_order_relaxed);
 }
 
 int vss_level_stats(vss_index *h, uint64_t level, uint64_t *out4) {

@@ -245,6 +245,36 @@ public:
 			                                              counts);
 		});
 	}
+	// A chunk of a similarity join or a threshold filter (`... ON array_cosine_distance(a.v, items.v) < 0.2`): every live row within
+	// radii[q] of outer row q, exactly (vss_search_range_batch; INTEGRATION.md §5 maps the SQL threshold to the radius and says
+	// which survivors the operator re-checks).  Counts first, then fills exactly.  Row ids are appended query after query, in no
+	// particular order inside a query; offsets_out (optional) receives the n_queries + 1 offsets of this chunk's ids, distances_out
+	// (optional) the distances in the metric's own units.  Returns the ids appended.
+	idx_t ExecuteRangeScanBatch(IndexScanState &state_p, const float *queries, idx_t n_queries, const float *radii,
+	                            std::vector<uint64_t> *offsets_out = nullptr, std::vector<float> *distances_out = nullptr) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::vector<uint64_t> offsets(n_queries + 1);
+		std::vector<row_t> ids;
+		std::vector<float> distances;
+		uint64_t total = 0;
+		{
+			// (one shared lock over both calls: no row may come or go between the count and the fill)
+			std::shared_lock<std::shared_mutex> lock(rwlock);
+			Check(vss_search_range_batch(index, queries, n_queries, radii, 0, offsets.data(), nullptr, nullptr, &total), "range-search");
+			ids.resize(total), distances.resize(total);
+			if (total)
+				Check(vss_search_range_batch(index, queries, n_queries, radii, total, offsets.data(), ids.data(), distances.data(), &total),
+				      "range-search");
+			if (total > ids.size())
+				throw InternalException("Failed to range-search the HNSW index: the match count changed between two calls");
+		}
+		state.row_ids.insert(state.row_ids.end(), ids.begin(), ids.end());
+		if (offsets_out)
+			*offsets_out = std::move(offsets);
+		if (distances_out)
+			*distances_out = std::move(distances);
+		return total;
+	}
 	// The same chunk with every group answered by the cheaper of the two calls above (vss_search_batch_filtered_groups_auto): the
 	// engine counts the live rows each predicate admits and decides per group — the call for an operator that has bitmaps and
 	// no idea how selective each is.  group_of may be nullptr; route_c = 0 takes the engine's constant;

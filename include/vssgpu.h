@@ -588,6 +588,32 @@ uint64_t vss_last_exact_fallbacks(vss_index *index);
  * 0 if none was finite; [3] = 0.  Answers never depend on the option — the certificate carries the bound of the kind that ran,
  * and what it cannot prove is redone in the metric — vss_last_exact_fallbacks may. */
 int vss_last_exact_scores(vss_index *index, uint64_t *out4);
+/* Exact RANGE search — the predicate of a similarity join or a threshold filter (`array_cosine_distance(a.v, items.v) < 0.2`;
+ * INTEGRATION.md §5 maps SQL thresholds to radii): query q matches every live row whose distance d satisfies d <= radii[q], a
+ * plain f32 compare; d = the engine's f32 metric in the index's own units (squared L2, 1 - cos, 1 - q.x), the bits
+ * vss_search_batch reports for that pair.  A NaN radius matches nothing, a negative one matches nothing under l2sq and cosine,
+ * +inf matches every live row whose distance is finite.  Inputs are taken to be finite numbers otherwise.
+ * out_offsets (n_queries + 1 cells) and *out_total are always written: out_offsets[q + 1] - out_offsets[q] = the matches of
+ * query q, *out_total = out_offsets[n_queries].  If *out_total <= capacity, cells [out_offsets[q], out_offsets[q + 1]) of
+ * out_rowids / out_distances hold query q's matches, in no particular order (a predicate, not a ranking); otherwise NO cell is
+ * written and the call still returns VSS_OK: read *out_total and call again.  capacity == 0 is the count-only call, and only
+ * then may out_rowids and out_distances be NULL.  n_queries == 0 and an empty index answer zeros.  At most 2^32 - 1 queries.
+ * Rows are proposed by an f32 MFMA score tile against a per-query threshold that provably keeps every matching row
+ * (csrc/exact_range.h, from the error bound of csrc/exact_certificate.h) and decided by the metric itself; answers depend on no
+ * option (exact.split_bf16 is not consulted).  The _device form takes device pointers for every argument, runs on the index's
+ * stream and returns with the results valid.  Takes the reader lock and the exact path's mutex, as vss_search_exact_batch.
+ * Device scratch, kept for the next call and counted by vss_memory_usage: at most 64 MiB of candidates (fixed: 1024 queries x
+ * 8192 rows per launch, 8 bytes a pair) + 16 bytes per cell of min(capacity, n_queries x rows) + 12 bytes per query; the host
+ * form stages queries, radii and min(capacity, n_queries x rows) result cells (12 bytes each) on top. */
+int vss_search_range_batch(vss_index *index, const float *queries, uint64_t n_queries, const float *radii, uint64_t capacity,
+                           uint64_t *out_offsets, int64_t *out_rowids, float *out_distances, uint64_t *out_total);
+int vss_search_range_batch_device(vss_index *index, const float *d_queries, uint64_t n_queries, const float *d_radii,
+                                  uint64_t capacity, uint64_t *d_out_offsets, int64_t *d_out_rowids, float *d_out_distances,
+                                  uint64_t *d_out_total);
+/* The last vss_search_range_batch* call on this index (diagnostics and tests; results never depend on it): out4[0] = (query, row)
+ * pairs the score tile proposed, [1] = matches, [2] = queries that had no finite error bound (norms outside 2^-40 .. 2^40 or
+ * values that are not finite: every live row was re-scored for them), [3] = bytes of range-search scratch the index holds. */
+int vss_last_range(vss_index *index, uint64_t *out4);
 /* Work counters of the last vss_search_batch* call, summed over its queries (usearch's
  * search_result_t::computed_distances / visited_members, index.hpp:2566-2571):
  * out[0] = computed distances, out[1] = expanded nodes, out[2] = queries, out[3] = retried queries. */
