@@ -138,6 +138,9 @@ SIGNATURES = {
     "vss_search_range_batch": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_range_batch_device": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_range": (_int, [_vp, _vp]),
+    "vss_search_range_batch_by_label_box64": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "vss_search_range_batch_by_label_box64_device": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "vss_last_range_filtered": (_int, [_vp, _vp]),
     "vss_last_search_stats": (_int, [_vp, _vp]),
     "vss_last_search_shape": (_int, [_vp, _vp]),
     "vss_last_search_prescore": (_int, [_vp, _vp]),
@@ -900,6 +903,61 @@ class GpuIndex:
         search_range_batch call."""
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_range(self.h, _p(out)))
+        return out
+
+    def search_range_batch_by_label_box64(self, Q, radii, columns, lo, hi, capacity=None, sort=False):
+        """vss_search_range_batch_by_label_box64: search_range_batch over the live rows that query q's box admits only (the box
+        rule of search_batch_by_label_box64: lo and hi are nq x len(columns) matrices of uint64).  Same returns, same capacity
+        protocol: counts first, then fills."""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        radii = np.ascontiguousarray(radii, dtype=np.float32)
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        hi = np.ascontiguousarray(hi, dtype=np.uint64)
+        nq = len(Q)
+        if radii.shape != (nq,):
+            raise ValueError("radii must hold one radius per query: %d queries, shape %r" % (nq, radii.shape))
+        if columns.ndim != 1 or lo.shape != (nq, len(columns)) or hi.shape != (nq, len(columns)):
+            raise ValueError("lo and hi must hold one range per query and named column: %d queries x %r columns, shapes %r and %r"
+                             % (nq, columns.shape, lo.shape, hi.shape))
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        total = _u64(0)
+
+        def call(cells, ids, d):
+            self._check(self.lib.vss_search_range_batch_by_label_box64(self.h, _p(Q), nq, _p(radii), _p(columns), len(columns), _p(lo),
+                                                                       _p(hi), cells, _p(offsets), _p(ids), _p(d), C.byref(total)))
+        if capacity is None:
+            call(0, None, None)
+            capacity = total.value
+        ids = np.full(capacity, -1, dtype=np.int64)
+        d = np.full(capacity, np.inf, dtype=np.float32)
+        if capacity:
+            call(capacity, ids, d)
+        else:
+            call(0, None, None)
+        if total.value > capacity:
+            return offsets, ids[:0], d[:0], total.value
+        ids, d = ids[:total.value], d[:total.value]
+        if sort:
+            for q in range(nq):
+                b, e = int(offsets[q]), int(offsets[q + 1])
+                order = np.lexsort((ids[b:e], d[b:e]))
+                ids[b:e], d[b:e] = ids[b:e][order], d[b:e][order]
+        return offsets, ids, d, total.value
+
+    def search_range_batch_by_label_box64_device(self, d_Q, nq, d_radii, columns, d_lo, d_hi, capacity, d_offsets, d_rowids, d_dist,
+                                                 d_total):
+        """The same over raw device pointers (`columns` stays a host sequence; d_lo, d_hi: nq x len(columns) uint64; the outputs
+        as search_range_batch_device's); blocking."""
+        columns = np.ascontiguousarray(columns, dtype=np.uint32)
+        self._check(self.lib.vss_search_range_batch_by_label_box64_device(self.h, d_Q, nq, d_radii, _p(columns), len(columns), d_lo, d_hi,
+                                                                          capacity, d_offsets, d_rowids, d_dist, d_total))
+
+    def last_range_filtered(self):
+        """[rows listed over the distinct boxes in use, (query, row) pairs the tile scored, tile launches, bytes of list and plan
+        scratch held] of the last search_range_batch_by_label_box64 call; last_range() holds for it too."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.vss_last_range_filtered(self.h, _p(out)))
         return out
 
     def timing(self, reset=False):

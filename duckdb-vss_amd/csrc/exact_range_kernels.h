@@ -5,6 +5,10 @@
 //   k_range_candidates   one launch per (query block, row chunk): Q . X^T on v_mfma_f32_32x32x2_f32, 128 queries x 128 rows per
 //                        workgroup; the epilogue keeps the (query, slot) pairs with !(score > theta_q), compacts them in LDS and
 //                        appends them to the launch's candidate buffer with ONE global atomic per workgroup
+//   k_range_candidates_lists   the same tile with its B operand GATHERED through a list of slots, for the range search under
+//                        per-query label boxes (vss_search_range_batch_by_label_box64): one workgroup per tile of a plan
+//                        (range_filtered_plan.h) and run of list positions, in two shapes, 128 queries x 128 listed rows and
+//                        32 queries x 256 listed rows
 //   k_range_rescore      64 / G candidates side by side per wave, four deep: the wave-order metric itself (accumulate4,
 //                        group_butterfly, finish_distance: the bits of k_exact_rerank), d <= r, the per-query count, and the
 //                        (query, row id, d) triple into the match scratch while the caller's capacity lasts
@@ -19,6 +23,7 @@
 #pragma once
 #include "exact_kernels.h"
 #include "exact_range.h"
+#include "range_filtered_plan.h"
 
 namespace vss {
 
@@ -50,6 +55,24 @@ struct RangeTileArgs {
 	int metric;
 	uint2 *cand;          // (query, slot)
 	uint32_t *cand_count; // this launch's own word, zero before it
+};
+
+// one launch of a plan (host::RangeFilterLaunch) in one of its two shapes: workgroup row y takes tile tiles[tile_index[y]]
+struct RangeListTileArgs {
+	const float4 *queries; // n_queries x V float4 (zero padded), by ORIGINAL query index
+	const float4 *vectors;
+	const float *row_norm2;
+	const float *theta;    // by original query index
+	const uint32_t *order; // the group order: position -> original query index
+	const uint32_t *lists; // the pass's lists of live admitted slots
+	const host::ExactFilterTile *tiles;
+	const uint32_t *tile_index;
+	uint32_t n_tiles;
+	uint32_t V;
+	uint32_t pos_begin, pos_end; // of every tile's list; sum over the tiles of n_queries x positions <= the cells of `cand`
+	int metric;
+	uint2 *cand;          // (original query index, slot)
+	uint32_t *cand_count; // this launch's own word, zero before its first shape
 };
 
 struct RangeRescoreArgs {
@@ -85,6 +108,7 @@ struct RangeLayoutArgs {
 
 hipError_t launch_range_prepare(const RangePrepareArgs &a, hipStream_t stream);
 hipError_t launch_range_candidates(const RangeTileArgs &a, hipStream_t stream);
+hipError_t launch_range_candidates_lists(const RangeListTileArgs &a, bool small, hipStream_t stream); // small: the 32-query shape
 hipError_t launch_range_rescore(const RangeRescoreArgs &a, uint32_t n_cus, hipStream_t stream);
 hipError_t launch_range_layout(const RangeLayoutArgs &a, uint32_t n_cus, hipStream_t stream); // offsets, then the scatter
 
@@ -286,6 +310,210 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The gathered candidate tile: the tile above with row r of the B operand = row lists[list_offset + pos] of the index, one
+// indirection per row (a row is 16 V contiguous bytes: whole cache lines still), and query t of the A operand = query
+// order[first_query + t].  A loading thread reads its list entries, and a lane of the epilogue its columns' |x|^2, ahead of the
+// K loop.  Listed rows are live (the listing kernels skip FREE_KEY); positions from the end of the list or of the launch's run,
+// and queries from n_queries, are padding: col_live = false, theta = -inf.  Staging, swizzle, double buffering, the single
+// barrier per step, loads two steps ahead, the half-wave K split and the zero staging past V are the dense tile's.
+// Two shapes, one launch each over its own tile-index array (the accumulator counts differ):
+//   QH = 128  2 x 2 waves of 64 x 64: 128 queries x 128 listed rows, 2 x (16 + 16) KiB of operand images
+//   QH = 32   four waves side by side along the list, 32 queries x 64 rows each (1 x 2 accumulators): 32 queries x 256 listed
+//             rows, 2 x (4 + 32) KiB — a tile of a few queries wastes at most 31 query rows of MFMA instead of 127, at a
+//             quarter of the flops per staged B byte
+// Either way two workgroups fit a compute unit's 160 KiB.  The epilogue's code is query in tile << LOG_W | row in tile (7 + 7
+// or 5 + 8 bits); the original query index and the slot of a surviving pair are read through order / lists when it is written.
+template <int QH>
+struct RangeListShape {
+	static constexpr uint32_t W = QH == 128 ? 128 : 256, LOG_W = QH == 128 ? 7 : 8; // listed rows per workgroup
+	static constexpr int WN = QH == 128 ? 2 : 4;                                     // waves along the list (4 / WN along the queries)
+	static constexpr int AI = QH == 128 ? 2 : 1;                                     // accumulators of a wave along the queries (two along the list)
+	static constexpr int PA = QH / 32, PB = W / 32;                                  // float4 a loading thread stages per step and operand
+	static constexpr uint32_t A_BYTES = QH * 128, BUF_BYTES = (QH + W) * 128, LDS_BYTES = 2 * BUF_BYTES;
+};
+
+template <int MT, int QH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_range_candidates_lists(RangeListTileArgs a) {
+	using S = RangeListShape<QH>;
+	extern __shared__ __attribute__((aligned(16))) unsigned char rt_smem[];
+	__shared__ float theta_l[QH];
+	__shared__ uint32_t n_staged, g_base;
+	const host::ExactFilterTile tile = a.tiles[a.tile_index[blockIdx.y]];
+	const uint32_t end = tile.list_length < a.pos_end ? tile.list_length : a.pos_end; // of this tile's positions in the launch
+	const uint32_t p0 = a.pos_begin + blockIdx.x * S::W;
+	if (p0 >= end) // (uniform over the workgroup) the grid follows the launch's longest list
+		return;
+	const int tid = threadIdx.x;
+	const int lane = tid & 63, wave = tid >> 6;
+	const int wm = wave / S::WN, wn = wave % S::WN;
+	const uint32_t *order = a.order + tile.first_query, *list = a.lists + tile.list_offset;
+	if (tid < QH)
+		theta_l[tid] = (uint32_t)tid < tile.n_queries ? a.theta[order[tid]] : -__builtin_inff();
+	if (tid == 0)
+		n_staged = 0u;
+
+	f32x16 acc[S::AI][2];
+#pragma unroll
+	for (int i = 0; i < S::AI; ++i)
+#pragma unroll
+		for (int j = 0; j < 2; ++j)
+#pragma unroll
+			for (int e = 0; e < 16; ++e)
+				acc[i][j][e] = 0.f;
+
+	// the load side: thread -> chunk f of the step's eight, rows rr + 32 p of both operands (rows beyond the edge re-read the last)
+	const uint32_t f = (uint32_t)tid & 7u, rr = (uint32_t)tid >> 3;
+	const float4 *qsrc[S::PA], *xsrc[S::PB];
+#pragma unroll
+	for (int p = 0; p < S::PA; ++p) {
+		const uint32_t t = rr + 32u * p;
+		qsrc[p] = a.queries + (size_t)order[t < tile.n_queries ? t : tile.n_queries - 1u] * a.V;
+	}
+#pragma unroll
+	for (int p = 0; p < S::PB; ++p) {
+		const uint32_t pos = p0 + rr + 32u * p;
+		xsrc[p] = a.vectors + (size_t)list[pos < end ? pos : end - 1u] * a.V;
+	}
+	const uint32_t steps = (a.V + 7u) / 8u;
+	float4 qa[S::PA], xb[S::PB];
+	auto load_step = [&](uint32_t step) { // unconditional (clamped chunk, zeroed afterwards): guarded loads are waited for one by one
+		const uint32_t c = step * 8u + f, cc = c < a.V ? c : a.V - 1u;
+#pragma unroll
+		for (int p = 0; p < S::PA; ++p)
+			qa[p] = qsrc[p][cc];
+#pragma unroll
+		for (int p = 0; p < S::PB; ++p)
+			xb[p] = xsrc[p][cc];
+		if (c >= a.V) {
+#pragma unroll
+			for (int p = 0; p < S::PA; ++p)
+				qa[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+			for (int p = 0; p < S::PB; ++p)
+				xb[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+		}
+	};
+	const uint32_t st_off = rr * 128u + ((f ^ (rr & 7u)) << 4); // (rows rr + 32 p: the same row & 7)
+	auto store_step = [&](int buf) {
+		unsigned char *A = rt_smem + buf * S::BUF_BYTES, *B = A + S::A_BYTES;
+#pragma unroll
+		for (int p = 0; p < S::PA; ++p)
+			*reinterpret_cast<float4 *>(A + st_off + p * 32 * 128) = qa[p];
+#pragma unroll
+		for (int p = 0; p < S::PB; ++p)
+			*reinterpret_cast<float4 *>(B + st_off + p * 32 * 128) = xb[p];
+	};
+	// the MFMA side: row lane & 31 of each 32-row tile, chunk 2 g + (lane >> 5) of k-group g
+	const uint32_t a_row = (uint32_t)(wm * 64 + (lane & 31)) * 128u, b_row = S::A_BYTES + (uint32_t)(wn * 64 + (lane & 31)) * 128u;
+	uint32_t pos[4];
+#pragma unroll
+	for (int g = 0; g < 4; ++g)
+		pos[g] = (((uint32_t)(2 * g) + ((uint32_t)lane >> 5)) ^ ((uint32_t)lane & 7u)) << 4;
+	auto read_group = [&](int buf, int g, float4 (&av)[S::AI], float4 (&bv)[2]) {
+		const unsigned char *I = rt_smem + buf * S::BUF_BYTES;
+#pragma unroll
+		for (int i = 0; i < S::AI; ++i)
+			av[i] = *reinterpret_cast<const float4 *>(I + a_row + i * 32 * 128 + pos[g]);
+#pragma unroll
+		for (int j = 0; j < 2; ++j)
+			bv[j] = *reinterpret_cast<const float4 *>(I + b_row + j * 32 * 128 + pos[g]);
+	};
+	auto mfma_group = [&](const float4 (&av)[S::AI], const float4 (&bv)[2]) {
+#pragma unroll
+		for (int i = 0; i < S::AI; ++i)
+#pragma unroll
+			for (int j = 0; j < 2; ++j)
+				acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].x, bv[j].x, acc[i][j], 0, 0, 0);
+#pragma unroll
+		for (int i = 0; i < S::AI; ++i)
+#pragma unroll
+			for (int j = 0; j < 2; ++j)
+				acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].y, bv[j].y, acc[i][j], 0, 0, 0);
+#pragma unroll
+		for (int i = 0; i < S::AI; ++i)
+#pragma unroll
+			for (int j = 0; j < 2; ++j)
+				acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].z, bv[j].z, acc[i][j], 0, 0, 0);
+#pragma unroll
+		for (int i = 0; i < S::AI; ++i)
+#pragma unroll
+			for (int j = 0; j < 2; ++j)
+				acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i].w, bv[j].w, acc[i][j], 0, 0, 0);
+	};
+
+	load_step(0);
+	store_step(0);
+	if (steps > 1)
+		load_step(1);
+	// what the epilogue reads from memory, asked for ahead of the loop: this lane's two columns
+	float col_n2[2];
+	bool col_live[2];
+#pragma unroll
+	for (int j = 0; j < 2; ++j) {
+		const uint32_t col = p0 + wn * 64 + j * 32 + (lane & 31);
+		col_n2[j] = a.row_norm2[list[col < end ? col : end - 1u]];
+		col_live[j] = col < end;
+	}
+	__syncthreads();
+	for (uint32_t k = 0; k < steps; ++k) {
+		const int buf = (int)(k & 1u);
+		float4 av0[S::AI], bv0[2], av1[S::AI], bv1[2];
+		read_group(buf, 0, av0, bv0);
+		if (k + 1 < steps)
+			store_step(buf ^ 1); // step k + 1, loaded a whole step ago; the idle buffer's readers passed the last barrier
+		read_group(buf, 1, av1, bv1);
+		if (k + 2 < steps)
+			load_step(k + 2);
+		mfma_group(av0, bv0);
+		read_group(buf, 2, av0, bv0);
+		mfma_group(av1, bv1);
+		read_group(buf, 3, av1, bv1);
+		mfma_group(av0, bv0);
+		mfma_group(av1, bv1);
+		__syncthreads();
+	}
+
+	// ---- epilogue: C[row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)][col = lane & 31]; the operand images are dead, and QH x W
+	// 16-bit codes (32 or 16 KiB) fit them
+	uint16_t *staged = reinterpret_cast<uint16_t *>(rt_smem);
+#pragma unroll
+	for (int j = 0; j < 2; ++j) {
+		const uint32_t cl = wn * 64 + j * 32 + (lane & 31);
+		const float xn2 = col_n2[j], rs = MT == 1 ? rsqrtf(xn2) : 0.f;
+#pragma unroll
+		for (int i = 0; i < S::AI; ++i) {
+#pragma unroll
+			for (int e = 0; e < 16; ++e) {
+				const uint32_t ql = wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * ((uint32_t)lane >> 5);
+				const float s = exact_score<MT>(acc[i][j][e], xn2, rs);
+				const bool keep = col_live[j] && ql < tile.n_queries && !(s > theta_l[ql]);
+				const unsigned long long m = __ballot(keep);
+				if (m) { // (wave-uniform)
+					uint32_t base = 0;
+					if (lane == 0)
+						base = atomicAdd(&n_staged, (uint32_t)__popcll(m));
+					base = __shfl(base, 0);
+					if (keep)
+						staged[base + __popcll(m & lanes_below(lane))] = (uint16_t)(ql << S::LOG_W | cl);
+				}
+			}
+		}
+	}
+	__syncthreads();
+	const uint32_t n = n_staged;
+	if (n == 0)
+		return;
+	if (tid == 0)
+		g_base = atomicAdd(a.cand_count, n);
+	__syncthreads();
+	uint2 *out = a.cand + g_base;
+	for (uint32_t t = tid; t < n; t += 256) {
+		const uint32_t code = staged[t];
+		out[t] = make_uint2(order[code >> S::LOG_W], list[p0 + (code & (S::W - 1u))]);
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // The re-score: lane group g of G lanes takes chunks g, g + G, ... of its candidate's row and query — the partition, fma order
 // and butterfly of wave_distance_one — RR candidates deep so that their loads are in flight together.
 constexpr int RANGE_RR = 4;
@@ -407,6 +635,29 @@ hipError_t launch_range_candidates(const RangeTileArgs &a, hipStream_t stream) {
 	else
 		hipLaunchKernelGGL(k_range_candidates<2>, grid, dim3(256), RT_LDS_BYTES, stream, a);
 	return hipGetLastError();
+}
+
+template <int MT, int QH>
+static hipError_t launch_range_candidates_lists_as(const RangeListTileArgs &a, hipStream_t stream) {
+	using S = RangeListShape<QH>;
+	if (const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_range_candidates_lists<MT, QH>),
+	                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES))
+		return e;
+	const dim3 grid((a.pos_end - a.pos_begin + S::W - 1u) / S::W, a.n_tiles);
+	hipLaunchKernelGGL((k_range_candidates_lists<MT, QH>), grid, dim3(256), S::LDS_BYTES, stream, a);
+	return hipGetLastError();
+}
+
+hipError_t launch_range_candidates_lists(const RangeListTileArgs &a, bool small, hipStream_t stream) {
+	if (!a.n_tiles || a.pos_begin >= a.pos_end)
+		return hipSuccess;
+	if (small)
+		return a.metric == 0   ? launch_range_candidates_lists_as<0, 32>(a, stream)
+		       : a.metric == 1 ? launch_range_candidates_lists_as<1, 32>(a, stream)
+		                       : launch_range_candidates_lists_as<2, 32>(a, stream);
+	return a.metric == 0   ? launch_range_candidates_lists_as<0, 128>(a, stream)
+	       : a.metric == 1 ? launch_range_candidates_lists_as<1, 128>(a, stream)
+	                       : launch_range_candidates_lists_as<2, 128>(a, stream);
 }
 
 hipError_t launch_range_rescore(const RangeRescoreArgs &a, uint32_t n_cus, hipStream_t stream) {

@@ -847,6 +847,10 @@ struct vss_index {
 	DevBuf<int64_t> d_rg_m_rowid, d_rg_out_ids;
 	DevBuf<uint64_t> d_rg_stats, d_rg_offsets;
 	uint64_t last_range[4] = {0, 0, 0, 0};        // vss_last_range
+	// vss_search_range_batch_by_label_box64: the tile-index arrays of its plan (range_filtered_plan.h); lists, block counts and the
+	// plan's tables are the exact filtered search's (d_xf_*)
+	DevBuf<uint32_t> d_rg_tile_index;
+	uint64_t last_range_filtered[4] = {0, 0, 0, 0}; // vss_last_range_filtered
 	std::atomic<uint64_t> exact_range_bytes {0}; // of the buffers above (vss_memory_usage, read without a lock)
 	uint64_t mutations = 0;
 
@@ -912,7 +916,7 @@ struct vss_index {
 		exact_filter_bytes.store(0, std::memory_order_relaxed);
 		d_rg_theta.free(), d_rg_m_dist.free(), d_rg_radii.free(), d_rg_q.free(), d_rg_out_d.free(), d_rg_counts.free();
 		d_rg_cand_count.free(), d_rg_m_query.free(), d_rg_cand.free(), d_rg_m_rowid.free(), d_rg_out_ids.free();
-		d_rg_stats.free(), d_rg_offsets.free();
+		d_rg_stats.free(), d_rg_offsets.free(), d_rg_tile_index.free();
 		exact_range_bytes.store(0, std::memory_order_relaxed);
 		if (h_counters)
 			(void)hipHostFree(h_counters);
@@ -2718,7 +2722,8 @@ struct vss_index {
 		return VSS_OK;
 	}
 	void count_range_bytes() {
-		const uint64_t bytes = (d_rg_theta.n + d_rg_m_dist.n + d_rg_radii.n + d_rg_q.n + d_rg_out_d.n + d_rg_counts.n + d_rg_cand_count.n + d_rg_m_query.n) * 4 +
+		const uint64_t bytes = (d_rg_theta.n + d_rg_m_dist.n + d_rg_radii.n + d_rg_q.n + d_rg_out_d.n + d_rg_counts.n + d_rg_cand_count.n + d_rg_m_query.n +
+		                        d_rg_tile_index.n) * 4 +
 		                       (d_rg_cand.n + d_rg_m_rowid.n + d_rg_out_ids.n + d_rg_stats.n + d_rg_offsets.n) * 8;
 		exact_range_bytes.store(bytes, std::memory_order_relaxed);
 		last_range[3] = bytes;
@@ -2729,8 +2734,9 @@ struct vss_index {
 		return range_launch(d_queries, (uint32_t)dim, nq, d_radii, cells, d_offsets, d_rowids, d_dist, d_total);
 	}
 	// the host-pointer form: queries and radii in, offsets, total and — where the total fits — the cells out
+	// (g: nullptr, or the groups of the call under label boxes — range_filtered_launch)
 	int range_host(const float *queries, uint64_t nq, const float *radii, uint64_t cells, uint64_t *out_offsets, int64_t *out_rowids,
-	               float *out_d, uint64_t *out_total) {
+	               float *out_d, uint64_t *out_total, const GroupedRows *g = nullptr) {
 		std::lock_guard<std::mutex> exact_lock(exact_mu);
 		const uint64_t out_cells = std::min(cells, nq * (uint64_t)count); // (more can never be written)
 		d_rg_q.ensure(std::max<uint64_t>(nq * dim, 1), 0, stream);
@@ -2743,8 +2749,10 @@ struct vss_index {
 			HIP_TRY(hipMemcpyAsync(d_rg_q.p, queries, nq * dim * 4, hipMemcpyHostToDevice, stream));
 			HIP_TRY(hipMemcpyAsync(d_rg_radii.p, radii, nq * 4, hipMemcpyHostToDevice, stream));
 		}
-		if (const int rc = range_launch(d_rg_q.p, (uint32_t)dim, nq, d_rg_radii.p, out_cells, d_rg_offsets.p, d_rg_out_ids.p, d_rg_out_d.p,
-		                                d_rg_offsets.p + nq + 1))
+		if (const int rc = g ? range_filtered_launch(d_rg_q.p, (uint32_t)dim, nq, d_rg_radii.p, *g, out_cells, d_rg_offsets.p, d_rg_out_ids.p,
+		                                             d_rg_out_d.p, d_rg_offsets.p + nq + 1)
+		                     : range_launch(d_rg_q.p, (uint32_t)dim, nq, d_rg_radii.p, out_cells, d_rg_offsets.p, d_rg_out_ids.p, d_rg_out_d.p,
+		                                    d_rg_offsets.p + nq + 1))
 			return rc;
 		uint64_t total = 0;
 		HIP_TRY(hipMemcpyAsync(out_offsets, d_rg_offsets.p, (nq + 1) * 8, hipMemcpyDeviceToHost, stream));
@@ -2757,6 +2765,140 @@ struct vss_index {
 			HIP_TRY(hipStreamSynchronize(stream));
 		}
 		return VSS_OK;
+	}
+
+	// ------------------------------------------------------------------ exact range search under per-query label boxes
+	// Contract (include/vssgpu.h): query q matches the live rows its group of `g` admits whose metric distance is
+	// <= radii[q].  Carries out range_filtered_plan.h: the queries in group order, the groups' lists of live admitted slots
+	// (the listing of the exact filtered search, its scratch and its count step), and per launch of the plan the gathered
+	// candidate tile in its two shapes, then the range search's own re-score; its layout kernels finish.  Only listed rows are
+	// ever scored.  The thresholds are range_launch's: the norm extrema over ALL live rows bound those of any subset, so the E
+	// of exact_cert_error, and with it range_score_threshold, stays valid for every list.  Queries of an unknown group, of a
+	// group that admits nothing or of an empty box are in no tile: k_range_prepare's zero counts answer them.
+	// The caller holds exact_mu; every pointer is device memory; d_rowids / d_dist may be NULL iff cells == 0.
+	int range_filtered_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, const float *d_radii, const GroupedRows &g,
+	                          uint64_t cells, uint64_t *d_offsets, int64_t *d_rowids, float *d_dist, uint64_t *d_total) {
+		const uint64_t rows = count;
+		std::fill(last_range, last_range + 3, 0);
+		std::fill(last_range_filtered, last_range_filtered + 3, 0);
+		if (!nq || !rows) {
+			HIP_TRY(hipMemsetAsync(d_offsets, 0, (nq + 1) * 8, stream));
+			HIP_TRY(hipMemsetAsync(d_total, 0, 8, stream));
+			HIP_TRY(hipStreamSynchronize(stream));
+			return VSS_OK;
+		}
+		ExactFilterPlan plan;
+		exact_filter_order(g.group_of, nq, g.n_groups, plan);
+		std::vector<uint32_t> lengths;
+		if (const int rc = exact_filtered_count(plan, nq, 1, g, lengths)) // (ends synchronised)
+			return rc;
+		exact_filter_pack(lengths.data(), std::max<uint64_t>(exact_filter_budget, rows), RANGE_LIST_QT, plan);
+		RangeFilterPlan rp;
+		range_filter_plan(plan, rp);
+		const uint64_t nu = plan.groups.size(), n_index = rp.small.size() + rp.tall.size();
+		const ExactFilterTables t(nu, nq, g.group_cells());
+		uint64_t entries_max = 0;
+		for (const ExactFilterPass &pass : plan.passes)
+			entries_max = std::max(entries_max, pass.entries);
+		if (!d_xf_lists.try_grow(std::max<uint64_t>(entries_max, 1)) || !d_rg_tile_index.try_grow(std::max<uint64_t>(n_index, 1)))
+			return fail("range search under label boxes: no device memory for lists of %llu rows", (unsigned long long)entries_max);
+		count_exact_filter_scratch();
+		const uint64_t stride = (uint64_t)V * 4;
+		const uint64_t match_cells = std::min(cells, plan.distances); // (no query can match more rows than its list holds)
+		d_row_norm2.ensure(capacity, 0, stream);
+		d_norm_ext.ensure(2, 0, stream);
+		d_qpad.ensure(nq * stride, 0, stream);
+		d_q_norm2.ensure(nq, 0, stream);
+		d_rg_theta.ensure(nq, 0, stream);
+		d_rg_counts.ensure(2 * nq, 0, stream); // counts, then the scatter's cursors
+		d_rg_stats.ensure(4, 0, stream);
+		d_rg_cand_count.ensure(std::max<uint64_t>(rp.launches.size(), 1), 0, stream);
+		// every pair of the plan's largest launch fits (at most RANGE_QUERY_BLOCK x RANGE_ROW_CHUNK): no overflow path
+		d_rg_cand.ensure(std::max<uint64_t>(rp.largest, 1), 0, stream);
+		if (match_cells) {
+			d_rg_m_query.ensure(match_cells, 0, stream);
+			d_rg_m_rowid.ensure(match_cells, 0, stream);
+			d_rg_m_dist.ensure(match_cells, 0, stream);
+		}
+		count_range_bytes();
+		last_range_filtered[0] = plan.listed, last_range_filtered[1] = rp.pairs;
+		last_range_filtered[3] = (d_xf_lists.n + d_xf_counts.n + d_xf_tables.n + d_rg_tile_index.n) * 4;
+		{
+			// the plan's tables, where the listing and the tile read them: list_base and order, the cut tiles, the index arrays
+			std::vector<uint32_t> up(t.at_offset - t.at_base), index(rp.small);
+			std::copy(plan.list_base.begin(), plan.list_base.begin() + nu, up.begin());
+			std::copy(plan.order.begin(), plan.order.end(), up.begin() + (t.at_order - t.at_base));
+			index.insert(index.end(), rp.tall.begin(), rp.tall.end());
+			HIP_TRY(hipMemcpyAsync(d_xf_tables.p + t.at_base, up.data(), up.size() * 4, hipMemcpyHostToDevice, stream));
+			if (!rp.tiles.empty()) // (at most one per known query: they fit the 5 nq words behind at_tiles)
+				HIP_TRY(hipMemcpyAsync(d_xf_tables.p + t.at_tiles, rp.tiles.data(), rp.tiles.size() * sizeof(ExactFilterTile),
+				                       hipMemcpyHostToDevice, stream));
+			if (n_index)
+				HIP_TRY(hipMemcpyAsync(d_rg_tile_index.p, index.data(), n_index * 4, hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipStreamSynchronize(stream)); // (pageable memory: the copies have left it before it goes)
+		}
+		refresh_row_norms(rows);
+		HIP_TRY(hipMemsetAsync(d_qpad.p, 0, nq * stride * 4, stream));
+		HIP_TRY(hipMemcpy2DAsync(d_qpad.p, stride * 4, d_queries, (size_t)q_stride * 4, dim * 4, nq, hipMemcpyDeviceToDevice, stream));
+		hipLaunchKernelGGL(k_row_norms, dim3(256), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V, G, logG,
+		                   (uint32_t)nq, d_q_norm2.p);
+		HIP_TRY(hipMemsetAsync(d_rg_stats.p, 0, 4 * 8, stream));
+		HIP_TRY(hipMemsetAsync(d_rg_cand_count.p, 0, std::max<uint64_t>(rp.launches.size(), 1) * 4, stream));
+		RangeStats *stats = reinterpret_cast<RangeStats *>(d_rg_stats.p);
+		RangePrepareArgs p;
+		p.metric = metric, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
+		p.radii = d_radii, p.query_norm2 = d_q_norm2.p, p.norm_ext = d_norm_ext.p;
+		p.theta = d_rg_theta.p, p.counts = d_rg_counts.p, p.cursors = d_rg_counts.p + nq, p.stats = stats;
+		HIP_TRY(launch_range_prepare(p, stream));
+		FilterListArgs l = exact_filter_list_args(g, nu, t);
+		l.lists = d_xf_lists.p;
+		RangeListTileArgs c;
+		c.queries = reinterpret_cast<const float4 *>(d_qpad.p), c.vectors = reinterpret_cast<const float4 *>(d_vectors.p);
+		c.row_norm2 = d_row_norm2.p, c.theta = d_rg_theta.p, c.order = d_xf_tables.p + t.at_order, c.lists = d_xf_lists.p;
+		c.tiles = reinterpret_cast<const ExactFilterTile *>(d_xf_tables.p + t.at_tiles);
+		c.V = V, c.metric = metric, c.cand = d_rg_cand.p;
+		RangeRescoreArgs r;
+		r.sp = view().sp, r.keys = d_keys.p, r.queries = c.queries, r.query_norm2 = d_q_norm2.p, r.radii = d_radii;
+		r.cand = d_rg_cand.p, r.counts = d_rg_counts.p, r.stats = stats, r.capacity = match_cells;
+		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p;
+		uint32_t listed_pass = UINT32_MAX;
+		for (size_t i = 0; i != rp.launches.size(); ++i) {
+			const RangeFilterLaunch &rl = rp.launches[i];
+			if (rl.pass != listed_pass) { // (stream order: the previous pass's launches have read their lists)
+				l.u_begin = plan.passes[rl.pass].group_begin, l.u_end = plan.passes[rl.pass].group_end;
+				g.launch_scatter(l, stream);
+				listed_pass = rl.pass;
+			}
+			c.pos_begin = rl.pos_begin, c.pos_end = rl.pos_end;
+			c.cand_count = d_rg_cand_count.p + i, r.cand_count = c.cand_count; // one word and one re-score for both shapes
+			c.tile_index = d_rg_tile_index.p + rl.small_begin, c.n_tiles = rl.small_end - rl.small_begin;
+			HIP_TRY(launch_range_candidates_lists(c, true, stream));
+			last_range_filtered[2] += c.n_tiles != 0;
+			c.tile_index = d_rg_tile_index.p + rp.small.size() + rl.tall_begin, c.n_tiles = rl.tall_end - rl.tall_begin;
+			HIP_TRY(launch_range_candidates_lists(c, false, stream));
+			last_range_filtered[2] += c.n_tiles != 0;
+			HIP_TRY(launch_range_rescore(r, n_cus, stream));
+		}
+		RangeLayoutArgs y;
+		y.n_queries = (uint32_t)nq, y.counts = d_rg_counts.p, y.cursors = d_rg_counts.p + nq, y.stats = stats, y.capacity = match_cells;
+		y.offsets = reinterpret_cast<unsigned long long *>(d_offsets), y.total = reinterpret_cast<unsigned long long *>(d_total);
+		y.m_query = d_rg_m_query.p, y.m_rowid = d_rg_m_rowid.p, y.m_dist = d_rg_m_dist.p;
+		y.out_rowids = d_rowids, y.out_dist = d_dist;
+		HIP_TRY(launch_range_layout(y, n_cus, stream));
+		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		return VSS_OK;
+	}
+	// the two forms: `boxes` is nq x 4m words (label_box64_rows, HOST); the groups are its distinct raw rows
+	int range_by_box64(bool host_form, const float *queries, uint64_t nq, const float *radii, const uint32_t *boxes, const LabelBoxColumns &box,
+	                   uint64_t cells, uint64_t *offsets, int64_t *rowids, float *dist, uint64_t *total) {
+		std::vector<uint32_t> rows, group_of;
+		label_box64_groups(boxes, nq, box.m, rows, group_of);
+		const GroupedRows g = GroupedRows::boxes64(rows, box, HostWords(group_of.data()), DeviceWords(nullptr));
+		if (host_form)
+			return range_host(queries, nq, radii, cells, offsets, rowids, dist, total, &g);
+		std::lock_guard<std::mutex> exact_lock(exact_mu);
+		return range_filtered_launch(queries, (uint32_t)dim, nq, radii, g, cells, offsets, rowids, dist, total);
 	}
 
 	// ------------------------------------------------------------------ exact search under per-query predicates
@@ -4926,6 +5068,61 @@ int vss_search_batch_by_label_box64_device(vss_index *h, const float *Q, uint64_
 		h->route_to_device(route, out_route);
 		return VSS_OK;
 	})
+}
+
+// ---- the range search under label boxes of 64-bit ends: what vss_search_range_batch refuses first (check_range), then what the
+// box64 call refuses about columns and ends (check_by_label_box; it has no mode and no per-query cells of its own to refuse: the
+// exact mode and the offsets stand in for them)
+static int check_range_by_label_box64(vss_index *h, const char *what, const float *Q, uint64_t nq, const float *radii,
+                                      const uint32_t *columns, uint64_t m, const void *lo, const void *hi, uint64_t cells,
+                                      const uint64_t *out_offsets, const int64_t *out_rowids, const float *out_d, const uint64_t *out_total,
+                                      LabelBoxColumns &box) {
+	if (check_range(h, what, Q, nq, radii, cells, out_offsets, out_rowids, out_d, out_total) != VSS_OK)
+		return VSS_ERROR;
+	return check_by_label_box(h, what, Q, nq, columns, m, lo, hi, VSS_BY_LABEL_EXACT, reinterpret_cast<const int64_t *>(out_offsets),
+	                          reinterpret_cast<const uint32_t *>(out_offsets), box, true);
+}
+
+int vss_search_range_batch_by_label_box64(vss_index *h, const float *Q, uint64_t nq, const float *radii, const uint32_t *columns,
+                                          uint64_t n_columns, const uint64_t *lo, const uint64_t *hi, uint64_t capacity,
+                                          uint64_t *out_offsets, int64_t *out_rowids, float *out_d, uint64_t *out_total) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_range_by_label_box64(h, "vss_search_range_batch_by_label_box64", Q, nq, radii, columns, n_columns, lo, hi, capacity,
+		                               out_offsets, out_rowids, out_d, out_total, box) != VSS_OK)
+			return VSS_ERROR;
+		std::vector<uint32_t> boxes;
+		label_box64_rows(lo, hi, nq, box.m, boxes);
+		return h->range_by_box64(true, Q, nq, radii, boxes.data(), box, capacity, out_offsets, out_rowids, out_d, out_total);
+	})
+}
+
+int vss_search_range_batch_by_label_box64_device(vss_index *h, const float *Q, uint64_t nq, const float *radii, const uint32_t *columns,
+                                                 uint64_t n_columns, const uint64_t *lo, const uint64_t *hi, uint64_t capacity,
+                                                 uint64_t *out_offsets, int64_t *out_rowids, float *out_d, uint64_t *out_total) {
+	VSS_SHARED(h, {
+		LabelBoxColumns box;
+		if (check_range_by_label_box64(h, "vss_search_range_batch_by_label_box64_device", Q, nq, radii, columns, n_columns, lo, hi, capacity,
+		                               out_offsets, out_rowids, out_d, out_total, box) != VSS_OK)
+			return VSS_ERROR;
+		// the plan reads the boxes on the host: both matrices come back (16 * n_columns bytes per query)
+		const std::vector<uint32_t> lo_w = h->words_to_host(reinterpret_cast<const uint32_t *>(lo), 2 * nq * box.m),
+		                            hi_w = h->words_to_host(reinterpret_cast<const uint32_t *>(hi), 2 * nq * box.m);
+		std::vector<uint64_t> lo_h(nq * box.m), hi_h(nq * box.m);
+		if (nq)
+			std::memcpy(lo_h.data(), lo_w.data(), lo_h.size() * 8), std::memcpy(hi_h.data(), hi_w.data(), hi_h.size() * 8);
+		std::vector<uint32_t> boxes;
+		label_box64_rows(lo_h.data(), hi_h.data(), nq, box.m, boxes);
+		return h->range_by_box64(false, Q, nq, radii, boxes.data(), box, capacity, out_offsets, out_rowids, out_d, out_total);
+	})
+}
+
+int vss_last_range_filtered(vss_index *h, uint64_t *out4) {
+	if (!h || !out4)
+		return VSS_ERROR;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	std::memcpy(out4, h->last_range_filtered, sizeof h->last_range_filtered);
+	return VSS_OK;
 }
 
 // ---- the search by label set box: the mode is refused first, then the set width, the number of range columns, null sets / lo / hi,

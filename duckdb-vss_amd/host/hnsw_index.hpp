@@ -275,6 +275,39 @@ public:
 			*distances_out = std::move(distances);
 		return total;
 	}
+	// The same chunk of a similarity join with a per-outer-row predicate on resident label columns (`... < r AND items.tenant =
+	// a.tenant AND items.ts >= a.since`): every live row that outer row q's box (lo[q, .], hi[q, .] over `columns`, the rule of
+	// ExecuteMultiScanBatchByLabelBox64) admits AND that lies within radii[q] (vss_search_range_batch_by_label_box64; only
+	// admitted rows are scored).  Counts first, then fills exactly; outputs as ExecuteRangeScanBatch.  Returns the ids appended.
+	idx_t ExecuteRangeScanBatchByLabelBox64(IndexScanState &state_p, const float *queries, idx_t n_queries, const float *radii,
+	                                        const uint32_t *columns, idx_t n_columns, const uint64_t *lo, const uint64_t *hi,
+	                                        std::vector<uint64_t> *offsets_out = nullptr, std::vector<float> *distances_out = nullptr) {
+		auto &state = static_cast<MultiScanState &>(state_p);
+		std::vector<uint64_t> offsets(n_queries + 1);
+		std::vector<row_t> ids;
+		std::vector<float> distances;
+		uint64_t total = 0;
+		{
+			// (one shared lock over both calls: no row or label may come or go between the count and the fill)
+			std::shared_lock<std::shared_mutex> lock(rwlock);
+			Check(vss_search_range_batch_by_label_box64(index, queries, n_queries, radii, columns, n_columns, lo, hi, 0, offsets.data(),
+			                                            nullptr, nullptr, &total),
+			      "range-search by label box");
+			ids.resize(total), distances.resize(total);
+			if (total)
+				Check(vss_search_range_batch_by_label_box64(index, queries, n_queries, radii, columns, n_columns, lo, hi, total,
+				                                            offsets.data(), ids.data(), distances.data(), &total),
+				      "range-search by label box");
+			if (total > ids.size())
+				throw InternalException("Failed to range-search the HNSW index by label box: the match count changed between two calls");
+		}
+		state.row_ids.insert(state.row_ids.end(), ids.begin(), ids.end());
+		if (offsets_out)
+			*offsets_out = std::move(offsets);
+		if (distances_out)
+			*distances_out = std::move(distances);
+		return total;
+	}
 	// The same chunk with every group answered by the cheaper of the two calls above (vss_search_batch_filtered_groups_auto): the
 	// engine counts the live rows each predicate admits and decides per group — the call for an operator that has bitmaps and
 	// no idea how selective each is.  group_of may be nullptr; route_c = 0 takes the engine's constant;

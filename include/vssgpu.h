@@ -614,6 +614,39 @@ int vss_search_range_batch_device(vss_index *index, const float *d_queries, uint
  * pairs the score tile proposed, [1] = matches, [2] = queries that had no finite error bound (norms outside 2^-40 .. 2^40 or
  * values that are not finite: every live row was re-scored for them), [3] = bytes of range-search scratch the index holds. */
 int vss_last_range(vss_index *index, uint64_t *out4);
+/* Exact range search UNDER PER-QUERY LABEL BOXES — the filtered similarity join (`... < r AND items.tenant = a.tenant AND
+ * items.ts >= a.since`): query q matches a live row iff (1) the box rule of vss_search_batch_by_label_box64 admits the row for
+ * (lo[q, .], hi[q, .]) — `columns` names 1 .. VSS_LABEL_COLUMNS_MAX distinct label columns of either width for the whole call,
+ * both ends inclusive and unsigned, a NULL cell (VSS_NO_LABEL / VSS_NO_LABEL64) or a row beyond a named column is in no box, any
+ * lo > hi empties the box, hi = VSS_NO_LABEL64 is no upper bound — and (2) its distance d satisfies d <= radii[q]: the compare
+ * and the distance bits of vss_search_range_batch.  Only the rows a query's box admits are scored: the distinct boxes of the
+ * call become lists of live admitted rows, and an f32 MFMA tile gathers its rows through them.
+ * Everything else is vss_search_range_batch's, word for word: out_offsets and *out_total are always written, the cells only if
+ * *out_total <= capacity (otherwise none, and VSS_OK), in no particular order inside a query; capacity == 0 is the count-only
+ * call, and only then may out_rowids / out_distances be NULL; NaN, negative and +inf radii; n_queries == 0 and the empty index
+ * answer zeros; the reader lock and the exact path's mutex.  Writers of label columns are excluded while it runs, as for the
+ * blocking calls by label.  The box of 64-bit ends is the only predicate form here because it covers equality (lo == hi),
+ * intervals and conjunctions over 1 - 4 columns of either width; the other five predicate kinds (bitmap groups, one label, one
+ * range, IN-list, IN-list inside a box) have no range form.
+ * Errors (VSS_ERROR, nothing written): what vss_search_range_batch refuses, then what vss_search_batch_by_label_box64 refuses
+ * about columns and ends (n_columns outside 1 .. 4, a null, repeated or out-of-range column, null lo / hi, a column never set).
+ * The _device form takes device pointers for queries, radii, lo, hi and every output (`columns` stays in host memory); lo and hi
+ * are copied back, because the plan reads them on the host.
+ * Scratch, kept and counted by vss_memory_usage: vss_search_range_batch's, with min(capacity, sum over q of the rows q's box
+ * admits) match cells, plus the lists and tables of the exact filtered search and 4 bytes per tile of the plan. */
+int vss_search_range_batch_by_label_box64(vss_index *index, const float *queries, uint64_t n_queries, const float *radii,
+                                          const uint32_t *columns, uint64_t n_columns, const uint64_t *lo, const uint64_t *hi,
+                                          uint64_t capacity, uint64_t *out_offsets, int64_t *out_rowids, float *out_distances,
+                                          uint64_t *out_total);
+int vss_search_range_batch_by_label_box64_device(vss_index *index, const float *d_queries, uint64_t n_queries, const float *d_radii,
+                                                 const uint32_t *columns, uint64_t n_columns, const uint64_t *d_lo, const uint64_t *d_hi,
+                                                 uint64_t capacity, uint64_t *d_out_offsets, int64_t *d_out_rowids,
+                                                 float *d_out_distances, uint64_t *d_out_total);
+/* The last vss_search_range_batch_by_label_box64* call on this index (vss_last_range keeps its meaning for it: proposed pairs,
+ * matches, queries without a bound, bytes): out4[0] = rows listed, summed over the distinct boxes in use, [1] = (query, row)
+ * pairs the tile scored = the sum over the queries of the live rows their boxes admit, [2] = launches of the tile, [3] = bytes of
+ * list and plan scratch the index holds. */
+int vss_last_range_filtered(vss_index *index, uint64_t *out4);
 /* Work counters of the last vss_search_batch* call, summed over its queries (usearch's
  * search_result_t::computed_distances / visited_members, index.hpp:2566-2571):
  * out[0] = computed distances, out[1] = expanded nodes, out[2] = queries, out[3] = retried queries. */
