@@ -138,6 +138,7 @@ SIGNATURES = {
     "vss_search_range_batch": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_range_batch_device": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_range": (_int, [_vp, _vp]),
+    "vss_last_range_scores": (_int, [_vp, _vp]),
     "vss_search_range_batch_by_label_box64": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_range_batch_by_label_box64_device": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_range_filtered": (_int, [_vp, _vp]),
@@ -904,6 +905,13 @@ class GpuIndex:
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_range(self.h, _p(out)))
         return out
+
+    def last_range_scores(self):
+        """(score kind of the last range search of either form (0 = f32, 1 = split bf16: set_option("range.split_bf16", 1)), its
+        candidate-tile launches, the largest finite error bound E its thresholds were built from as a float, 0)."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.vss_last_range_scores(self.h, _p(out)))
+        return int(out[0]), int(out[1]), float(out[2:3].view(np.float64)[0]), int(out[3])
 
     def search_range_batch_by_label_box64(self, Q, radii, columns, lo, hi, capacity=None, sort=False):
         """vss_search_range_batch_by_label_box64: search_range_batch over the live rows that query q's box admits only (the box

@@ -9,6 +9,8 @@
 //                        per-query label boxes (vss_search_range_batch_by_label_box64): one workgroup per tile of a plan
 //                        (range_filtered_plan.h) and run of list positions, in two shapes, 128 queries x 128 listed rows and
 //                        32 queries x 256 listed rows
+//   k_range_candidates_bf16x3, k_range_candidates_lists_bf16x3   both tiles on the bf16 matrix pipe (option range.split_bf16,
+//                        score kind 1: exact_range_split_kernels.h)
 //   k_range_rescore      64 / G candidates side by side per wave, four deep: the wave-order metric itself (accumulate4,
 //                        group_butterfly, finish_distance: the bits of k_exact_rerank), d <= r, the per-query count, and the
 //                        (query, row id, d) triple into the match scratch while the caller's capacity lasts
@@ -29,10 +31,12 @@ namespace vss {
 
 struct RangeStats { // device words of one call
 	unsigned long long candidates, matches, no_bound;
+	unsigned long long e_max; // bit pattern of the largest finite E of k_range_prepare (non-negative doubles order as their bits)
 };
 
 struct RangePrepareArgs {
 	int metric;
+	int score_kind;          // whose error bound the thresholds carry: 0 = the f32 tiles, 1 = the split-bf16 tiles
 	uint32_t n;              // padded dimension
 	uint32_t n_queries;
 	const float *radii;
@@ -119,11 +123,13 @@ __global__ __launch_bounds__(256) void k_range_prepare(RangePrepareArgs a) {
 	if (q >= a.n_queries)
 		return;
 	const float qn2 = a.query_norm2[q];
-	const double E = exact_cert_error(a.metric, a.n, qn2, __uint_as_float(a.norm_ext[0]), __uint_as_float(a.norm_ext[1]));
+	const double E = exact_cert_error_of(a.score_kind, a.metric, a.n, qn2, __uint_as_float(a.norm_ext[0]), __uint_as_float(a.norm_ext[1]));
 	a.theta[q] = range_score_threshold(a.metric, a.radii[q], qn2, E);
 	a.counts[q] = 0u, a.cursors[q] = 0u;
 	if (!(E < (double)__builtin_inff()))
 		atomicAdd(&a.stats->no_bound, 1ull);
+	else
+		atomicMax(&a.stats->e_max, (unsigned long long)__double_as_longlong(E));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -681,3 +687,5 @@ hipError_t launch_range_layout(const RangeLayoutArgs &a, uint32_t n_cus, hipStre
 #endif // VSS_EXACT_RANGE_TU
 
 } // namespace vss
+
+#include "exact_range_split_kernels.h" // both candidate tiles on the bf16 matrix pipe (option range.split_bf16)

@@ -23,7 +23,9 @@ hipError_t launch_split_queries(const float4 *queries, uint64_t n8, uint4 *q_hi,
 // one score launch over e.row_begin .. e.row_end: `grid` persistent workgroups (two per compute unit, at most one per tile)
 hipError_t launch_exact_scores_bf16x3(const ExactArgs &e, const uint4 *q_hi, const uint4 *q_lo, uint32_t grid, hipStream_t stream);
 
-#ifdef VSS_EXACT_SPLIT_TU
+// The inline device helpers, for this tile's translation unit and for the range search's (exact_range_split_kernels.h: both are
+// built without packed f32 arithmetic).
+#if defined(VSS_EXACT_SPLIT_TU) || defined(VSS_EXACT_RANGE_TU)
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -44,6 +46,13 @@ __device__ __forceinline__ void split_chunk(const float4 x0, const float4 x1, ui
 	split_pair(x1.x, x1.y, hi.z, lo.z);
 	split_pair(x1.z, x1.w, hi.w, lo.w);
 }
+// where chunk c of row r sits in a bf16 image of 64-byte rows: position c ^ xs_swizzle(r) (the tile's comment below says why)
+__device__ __forceinline__ uint32_t xs_swizzle(uint32_t row) {
+	return (((row >> 1) ^ (row >> 3)) & 1u) | ((row >> 1) & 2u);
+}
+#endif
+
+#ifdef VSS_EXACT_SPLIT_TU
 
 // n8 groups of eight floats (the zero-padded query block: n_queries x 4 V floats, V even) -> hi / lo, 16 bytes per group each
 __global__ __launch_bounds__(256) void k_split_queries(const float4 *q, uint64_t n8, uint4 *hi, uint4 *lo) {
@@ -75,10 +84,6 @@ __global__ __launch_bounds__(256) void k_split_queries(const float4 *q, uint64_t
 //   * One LDS barrier per step, placed before the step's second block: the first operands of the next step are read right
 //     behind it, under those MFMAs.
 // Needs V % 8 == 0 (whole steps), as v4.
-__device__ __forceinline__ uint32_t xs_swizzle(uint32_t row) {
-	return (((row >> 1) ^ (row >> 3)) & 1u) | ((row >> 1) & 2u);
-}
-
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 k_exact_scores_bf16x3(ExactArgs a, const uint4 *q_hi, const uint4 *q_lo) {
 	constexpr int TN = 2;

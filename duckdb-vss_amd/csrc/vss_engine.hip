@@ -847,6 +847,12 @@ struct vss_index {
 	DevBuf<int64_t> d_rg_m_rowid, d_rg_out_ids;
 	DevBuf<uint64_t> d_rg_stats, d_rg_offsets;
 	uint64_t last_range[4] = {0, 0, 0, 0};        // vss_last_range
+	// range.split_bf16 (exact_range_split_kernels.h): where the padded dimension is a multiple of 32 every candidate launch of a
+	// range call runs the bf16x3 tiles (score kind 1) and k_range_prepare builds the thresholds from the split score's E.  Off by
+	// default.  d_rg_q_hi / d_rg_q_lo: the query block split once per call (eight bf16 per cell), allocated by the first such call.
+	bool range_split_bf16 = false;
+	DevBuf<uint4> d_rg_q_hi, d_rg_q_lo;
+	uint64_t last_range_scores[4] = {0, 0, 0, 0}; // vss_last_range_scores
 	// vss_search_range_batch_by_label_box64: the tile-index arrays of its plan (range_filtered_plan.h); lists, block counts and the
 	// plan's tables are the exact filtered search's (d_xf_*)
 	DevBuf<uint32_t> d_rg_tile_index;
@@ -916,7 +922,7 @@ struct vss_index {
 		exact_filter_bytes.store(0, std::memory_order_relaxed);
 		d_rg_theta.free(), d_rg_m_dist.free(), d_rg_radii.free(), d_rg_q.free(), d_rg_out_d.free(), d_rg_counts.free();
 		d_rg_cand_count.free(), d_rg_m_query.free(), d_rg_cand.free(), d_rg_m_rowid.free(), d_rg_out_ids.free();
-		d_rg_stats.free(), d_rg_offsets.free(), d_rg_tile_index.free();
+		d_rg_stats.free(), d_rg_offsets.free(), d_rg_tile_index.free(), d_rg_q_hi.free(), d_rg_q_lo.free();
 		exact_range_bytes.store(0, std::memory_order_relaxed);
 		if (h_counters)
 			(void)hipHostFree(h_counters);
@@ -2651,10 +2657,23 @@ struct vss_index {
 	// Rows are PROPOSED by the MFMA ranking score against a per-query threshold that no matching row can exceed (exact_range.h:
 	// the certificate's E pointed at the radius) and DECIDED by the metric itself, so nothing is certified and nothing redone.
 	// The caller holds exact_mu; every pointer is device memory; d_rowids / d_dist may be NULL iff cells == 0.
+	// The score kind of a range call over the nq padded queries of d_qpad: 1 iff range.split_bf16 is set and a row is a whole
+	// number of 128-byte steps.  Kind 1 splits the queries, once per call, into scratch that is kept for the next one.
+	int range_score_kind(uint64_t nq) {
+		if (!range_split_bf16 || V % 8 != 0)
+			return 0;
+		const uint64_t n8 = nq * (uint64_t)V / 2; // cells of eight bf16
+		d_rg_q_hi.ensure(n8, 0, stream);
+		d_rg_q_lo.ensure(n8, 0, stream);
+		count_range_bytes();
+		HIP_TRY(launch_split_queries(reinterpret_cast<const float4 *>(d_qpad.p), n8, d_rg_q_hi.p, d_rg_q_lo.p, stream));
+		return 1;
+	}
 	int range_launch(const float *d_queries, uint32_t q_stride, uint64_t nq, const float *d_radii, uint64_t cells,
 	                 uint64_t *d_offsets, int64_t *d_rowids, float *d_dist, uint64_t *d_total) {
 		const uint64_t rows = count;
 		std::fill(last_range, last_range + 3, 0);
+		std::fill(last_range_scores, last_range_scores + 4, 0);
 		if (!nq || !rows) {
 			HIP_TRY(hipMemsetAsync(d_offsets, 0, (nq + 1) * 8, stream));
 			HIP_TRY(hipMemsetAsync(d_total, 0, 8, stream));
@@ -2688,9 +2707,10 @@ struct vss_index {
 		                   (uint32_t)nq, d_q_norm2.p);
 		HIP_TRY(hipMemsetAsync(d_rg_stats.p, 0, 4 * 8, stream));
 		HIP_TRY(hipMemsetAsync(d_rg_cand_count.p, 0, row_chunks * query_blocks * 4, stream));
+		const int score_kind = range_score_kind(nq);
 		RangeStats *stats = reinterpret_cast<RangeStats *>(d_rg_stats.p);
 		RangePrepareArgs p;
-		p.metric = metric, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
+		p.metric = metric, p.score_kind = score_kind, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
 		p.radii = d_radii, p.query_norm2 = d_q_norm2.p, p.norm_ext = d_norm_ext.p;
 		p.theta = d_rg_theta.p, p.counts = d_rg_counts.p, p.cursors = d_rg_counts.p + nq, p.stats = stats;
 		HIP_TRY(launch_range_prepare(p, stream));
@@ -2708,9 +2728,11 @@ struct vss_index {
 				t.row_begin = (uint32_t)r0, t.row_end = (uint32_t)std::min<uint64_t>(rows, r0 + RANGE_ROW_CHUNK);
 				t.q_begin = (uint32_t)q0, t.q_end = (uint32_t)std::min<uint64_t>(nq, q0 + RANGE_QUERY_BLOCK);
 				t.cand_count = launch_word, r.cand_count = launch_word;
-				HIP_TRY(launch_range_candidates(t, stream));
+				HIP_TRY(score_kind ? launch_range_candidates_bf16x3(t, d_rg_q_hi.p, d_rg_q_lo.p, stream) : launch_range_candidates(t, stream));
 				HIP_TRY(launch_range_rescore(r, n_cus, stream));
+				++last_range_scores[1];
 			}
+		last_range_scores[0] = (uint64_t)score_kind;
 		RangeLayoutArgs l;
 		l.n_queries = (uint32_t)nq, l.counts = d_rg_counts.p, l.cursors = d_rg_counts.p + nq, l.stats = stats, l.capacity = match_cells;
 		l.offsets = reinterpret_cast<unsigned long long *>(d_offsets), l.total = reinterpret_cast<unsigned long long *>(d_total);
@@ -2718,13 +2740,15 @@ struct vss_index {
 		l.out_rowids = d_rowids, l.out_dist = d_dist;
 		HIP_TRY(launch_range_layout(l, n_cus, stream));
 		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&last_range_scores[2], d_rg_stats.p + 3, 8, hipMemcpyDeviceToHost, stream));
 		HIP_TRY(hipStreamSynchronize(stream));
 		return VSS_OK;
 	}
 	void count_range_bytes() {
 		const uint64_t bytes = (d_rg_theta.n + d_rg_m_dist.n + d_rg_radii.n + d_rg_q.n + d_rg_out_d.n + d_rg_counts.n + d_rg_cand_count.n + d_rg_m_query.n +
 		                        d_rg_tile_index.n) * 4 +
-		                       (d_rg_cand.n + d_rg_m_rowid.n + d_rg_out_ids.n + d_rg_stats.n + d_rg_offsets.n) * 8;
+		                       (d_rg_cand.n + d_rg_m_rowid.n + d_rg_out_ids.n + d_rg_stats.n + d_rg_offsets.n) * 8 +
+		                       (d_rg_q_hi.n + d_rg_q_lo.n) * sizeof(uint4);
 		exact_range_bytes.store(bytes, std::memory_order_relaxed);
 		last_range[3] = bytes;
 	}
@@ -2780,6 +2804,7 @@ struct vss_index {
 	                          uint64_t cells, uint64_t *d_offsets, int64_t *d_rowids, float *d_dist, uint64_t *d_total) {
 		const uint64_t rows = count;
 		std::fill(last_range, last_range + 3, 0);
+		std::fill(last_range_scores, last_range_scores + 4, 0);
 		std::fill(last_range_filtered, last_range_filtered + 3, 0);
 		if (!nq || !rows) {
 			HIP_TRY(hipMemsetAsync(d_offsets, 0, (nq + 1) * 8, stream));
@@ -2844,9 +2869,10 @@ struct vss_index {
 		                   (uint32_t)nq, d_q_norm2.p);
 		HIP_TRY(hipMemsetAsync(d_rg_stats.p, 0, 4 * 8, stream));
 		HIP_TRY(hipMemsetAsync(d_rg_cand_count.p, 0, std::max<uint64_t>(rp.launches.size(), 1) * 4, stream));
+		const int score_kind = range_score_kind(nq);
 		RangeStats *stats = reinterpret_cast<RangeStats *>(d_rg_stats.p);
 		RangePrepareArgs p;
-		p.metric = metric, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
+		p.metric = metric, p.score_kind = score_kind, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
 		p.radii = d_radii, p.query_norm2 = d_q_norm2.p, p.norm_ext = d_norm_ext.p;
 		p.theta = d_rg_theta.p, p.counts = d_rg_counts.p, p.cursors = d_rg_counts.p + nq, p.stats = stats;
 		HIP_TRY(launch_range_prepare(p, stream));
@@ -2861,6 +2887,10 @@ struct vss_index {
 		r.sp = view().sp, r.keys = d_keys.p, r.queries = c.queries, r.query_norm2 = d_q_norm2.p, r.radii = d_radii;
 		r.cand = d_rg_cand.p, r.counts = d_rg_counts.p, r.stats = stats, r.capacity = match_cells;
 		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p;
+		auto lists_tile = [&](bool small) { // one shape of the gathered tile, of the call's score kind
+			return score_kind ? launch_range_candidates_lists_bf16x3(c, small, d_rg_q_hi.p, d_rg_q_lo.p, stream)
+			                  : launch_range_candidates_lists(c, small, stream);
+		};
 		uint32_t listed_pass = UINT32_MAX;
 		for (size_t i = 0; i != rp.launches.size(); ++i) {
 			const RangeFilterLaunch &rl = rp.launches[i];
@@ -2872,13 +2902,14 @@ struct vss_index {
 			c.pos_begin = rl.pos_begin, c.pos_end = rl.pos_end;
 			c.cand_count = d_rg_cand_count.p + i, r.cand_count = c.cand_count; // one word and one re-score for both shapes
 			c.tile_index = d_rg_tile_index.p + rl.small_begin, c.n_tiles = rl.small_end - rl.small_begin;
-			HIP_TRY(launch_range_candidates_lists(c, true, stream));
+			HIP_TRY(lists_tile(true));
 			last_range_filtered[2] += c.n_tiles != 0;
 			c.tile_index = d_rg_tile_index.p + rp.small.size() + rl.tall_begin, c.n_tiles = rl.tall_end - rl.tall_begin;
-			HIP_TRY(launch_range_candidates_lists(c, false, stream));
+			HIP_TRY(lists_tile(false));
 			last_range_filtered[2] += c.n_tiles != 0;
 			HIP_TRY(launch_range_rescore(r, n_cus, stream));
 		}
+		last_range_scores[0] = (uint64_t)score_kind, last_range_scores[1] = last_range_filtered[2];
 		RangeLayoutArgs y;
 		y.n_queries = (uint32_t)nq, y.counts = d_rg_counts.p, y.cursors = d_rg_counts.p + nq, y.stats = stats, y.capacity = match_cells;
 		y.offsets = reinterpret_cast<unsigned long long *>(d_offsets), y.total = reinterpret_cast<unsigned long long *>(d_total);
@@ -2886,6 +2917,7 @@ struct vss_index {
 		y.out_rowids = d_rowids, y.out_dist = d_dist;
 		HIP_TRY(launch_range_layout(y, n_cus, stream));
 		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&last_range_scores[2], d_rg_stats.p + 3, 8, hipMemcpyDeviceToHost, stream));
 		HIP_TRY(hipStreamSynchronize(stream));
 		return VSS_OK;
 	}
@@ -4065,6 +4097,8 @@ const OptionRule OPTION_RULES[] = {
      "in launches that filter on row codes, the greedy descent's rows are bounded against its closest distance too"},
     {"exact.split_bf16", 0, 1, [](vss_index *h, int64_t v) { h->exact_split_bf16 = v != 0; },
      "exact search selects rows by a split-bf16 score on the bf16 matrix pipe (dimensions whose padding is a multiple of 32)"},
+    {"range.split_bf16", 0, 1, [](vss_index *h, int64_t v) { h->range_split_bf16 = v != 0; },
+     "range search proposes rows by a split-bf16 score on the bf16 matrix pipe (dimensions whose padding is a multiple of 32)"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {
@@ -4561,6 +4595,14 @@ int vss_last_range(vss_index *h, uint64_t *out4) {
 		return VSS_ERROR;
 	std::lock_guard<std::mutex> lk(h->exact_mu);
 	std::memcpy(out4, h->last_range, sizeof h->last_range);
+	return VSS_OK;
+}
+
+int vss_last_range_scores(vss_index *h, uint64_t *out4) {
+	if (!h || !out4)
+		return VSS_ERROR;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	std::memcpy(out4, h->last_range_scores, sizeof h->last_range_scores);
 	return VSS_OK;
 }
 

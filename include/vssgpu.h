@@ -125,6 +125,10 @@ int vss_set_build_reorder(vss_index *index, int on);
  *   exact.split_bf16 (0/1)       vss_search_exact_batch* selects rows by a split-bf16 score on the bf16 matrix pipe instead of
  *                                the f32 one (default 0; dimensions whose padding is no multiple of 32 keep the f32 tile);
  *                                answers do not depend on it, vss_last_exact_fallbacks may; vss_last_exact_scores reports it
+ *   range.split_bf16 (0/1)       vss_search_range_batch* and vss_search_range_batch_by_label_box64* propose rows by the split-bf16
+ *                                score, against thresholds built from its error bound (default 0; dimensions whose padding is
+ *                                no multiple of 32 keep the f32 tiles); answers do not depend on it, the number of proposed
+ *                                pairs (vss_last_range) may; vss_last_range_scores reports it
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -600,7 +604,9 @@ int vss_last_exact_scores(vss_index *index, uint64_t *out4);
  * then may out_rowids and out_distances be NULL.  n_queries == 0 and an empty index answer zeros.  At most 2^32 - 1 queries.
  * Rows are proposed by an f32 MFMA score tile against a per-query threshold that provably keeps every matching row
  * (csrc/exact_range.h, from the error bound of csrc/exact_certificate.h) and decided by the metric itself; answers depend on no
- * option (exact.split_bf16 is not consulted).  The _device form takes device pointers for every argument, runs on the index's
+ * option (exact.split_bf16 is not consulted).  With vss_set_option "range.split_bf16" = 1 and a dimension whose padding is a
+ * multiple of 32 the tile is the split-bf16 one and the threshold carries its wider bound (vss_last_range_scores); the query
+ * block split into bf16 halves, 4 bytes per padded query float, then joins the scratch below.  The _device form takes device pointers for every argument, runs on the index's
  * stream and returns with the results valid.  Takes the reader lock and the exact path's mutex, as vss_search_exact_batch.
  * Device scratch, kept for the next call and counted by vss_memory_usage: at most 64 MiB of candidates (fixed: 1024 queries x
  * 8192 rows per launch, 8 bytes a pair) + 16 bytes per cell of min(capacity, n_queries x rows) + 12 bytes per query; the host
@@ -614,6 +620,14 @@ int vss_search_range_batch_device(vss_index *index, const float *d_queries, uint
  * pairs the score tile proposed, [1] = matches, [2] = queries that had no finite error bound (norms outside 2^-40 .. 2^40 or
  * values that are not finite: every live row was re-scored for them), [3] = bytes of range-search scratch the index holds. */
 int vss_last_range(vss_index *index, uint64_t *out4);
+/* Which candidate tiles the last range call of either form (vss_search_range_batch*, vss_search_range_batch_by_label_box64*) on
+ * this index proposed rows with: out4[0] = the score kind, 0 = f32 (v_mfma_f32_32x32x2_f32), 1 = split bf16 (vss_set_option
+ * "range.split_bf16" = 1 and a dimension whose padding is a multiple of 32: q.x ~ qh.xh + qh.xl + ql.xh on
+ * v_mfma_f32_32x32x16_bf16, csrc/exact_range_split_kernels.h); [1] = its candidate-tile launches; [2] = the bit pattern of the
+ * largest finite error bound E (a double, csrc/exact_certificate.h) its thresholds were built from, 0 if none was finite;
+ * [3] = 0.  Diagnostics and tests: answers never depend on the option, because the threshold carries the bound of the kind that
+ * ran and the metric decides every proposed pair. */
+int vss_last_range_scores(vss_index *index, uint64_t *out4);
 /* Exact range search UNDER PER-QUERY LABEL BOXES — the filtered similarity join (`... < r AND items.tenant = a.tenant AND
  * items.ts >= a.since`): query q matches a live row iff (1) the box rule of vss_search_batch_by_label_box64 admits the row for
  * (lo[q, .], hi[q, .]) — `columns` names 1 .. VSS_LABEL_COLUMNS_MAX distinct label columns of either width for the whole call,
@@ -621,6 +635,8 @@ int vss_last_range(vss_index *index, uint64_t *out4);
  * lo > hi empties the box, hi = VSS_NO_LABEL64 is no upper bound — and (2) its distance d satisfies d <= radii[q]: the compare
  * and the distance bits of vss_search_range_batch.  Only the rows a query's box admits are scored: the distinct boxes of the
  * call become lists of live admitted rows, and an f32 MFMA tile gathers its rows through them.
+ * vss_set_option "range.split_bf16" = 1 puts every launch of that tile, in both its shapes, on the split-bf16 score, as it does
+ * for vss_search_range_batch.
  * Everything else is vss_search_range_batch's, word for word: out_offsets and *out_total are always written, the cells only if
  * *out_total <= capacity (otherwise none, and VSS_OK), in no particular order inside a query; capacity == 0 is the count-only
  * call, and only then may out_rowids / out_distances be NULL; NaN, negative and +inf radii; n_queries == 0 and the empty index

@@ -4,7 +4,9 @@ graph (M 8, ef_construction 16: only the exact paths are measured), 1024 queries
 range call (count-only and with the cells filled) and of the exact top-100 call, each between two hipEvents on the index's
 stream, five repeats after one warm-up, and candidates / matches from vss_last_range: how many rows the score threshold hands
 to the re-score per row that matches (set by the certificate's E: 1.8e-4 for cosine at 768 dimensions).
-    python tools/probe_range.py [rows [dim [metric [neighbour]]]]"""
+--split measures the range calls under option range.split_bf16 = 0 and = 1 in turn (the f32 and the split-bf16 candidate tiles),
+ten repeats each, with vss_last_range_scores' kind and E beside the candidates.
+    python tools/probe_range.py [--split] [rows [dim [metric [neighbour]]]]"""
 import os
 import sys
 
@@ -17,11 +19,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
 import bench  # noqa: E402
 from __graft_entry__ import load_package  # noqa: E402
 
+SPLIT = "--split" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--split"]
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 dim = int(sys.argv[2]) if len(sys.argv) > 2 else 768
 metric = sys.argv[3] if len(sys.argv) > 3 else "cosine"
 K = int(sys.argv[4]) if len(sys.argv) > 4 else 100
-B, REPEATS = 1024, 5
+B, REPEATS = 1024, 10 if SPLIT else 5
 pkg = load_package()
 dev = torch.device("cuda", 0)
 gen = bench.Mixture(rows, dim, metric != "l2sq", dev)
@@ -66,18 +70,30 @@ radii = dist[:, K - 1].contiguous()
 offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
 total = torch.zeros(1, dtype=torch.int64, device=dev)
 torch.cuda.synchronize()
-print("range call ms, count only  %s" % timed(lambda: idx.search_range_batch_device(Q.data_ptr(), B, radii.data_ptr(), 0, offsets.data_ptr(),
-                                                                                    None, None, total.data_ptr())), flush=True)
-n = int(total.item())
-r_ids = torch.empty(n, dtype=torch.int64, device=dev)
-r_d = torch.empty(n, dtype=torch.float32, device=dev)
-torch.cuda.synchronize()
-print("range call ms, %d cells    %s" % (n, timed(lambda: idx.search_range_batch_device(Q.data_ptr(), B, radii.data_ptr(), n, offsets.data_ptr(),
-                                                                                         r_ids.data_ptr(), r_d.data_ptr(), total.data_ptr()))),
-      flush=True)
-stats = idx.last_range()
-per_query = (offsets[1:] - offsets[:-1]).cpu().numpy()
-print("candidates %d  matches %d  candidates / matches %.2f  queries without a bound %d  scratch %.1f MB"
-      % (stats[0], stats[1], stats[0] / max(1, stats[1]), stats[2], stats[3] / 1e6))
-print("matches per query: min %d median %d max %d; the top-%d's rows are among them: %s"
-      % (per_query.min(), np.median(per_query), per_query.max(), K, bool((per_query >= K).all())))
+
+
+def range_calls():
+    print("range call ms, count only  %s" % timed(lambda: idx.search_range_batch_device(Q.data_ptr(), B, radii.data_ptr(), 0, offsets.data_ptr(),
+                                                                                        None, None, total.data_ptr())), flush=True)
+    n = int(total.item())
+    r_ids = torch.empty(n, dtype=torch.int64, device=dev)
+    r_d = torch.empty(n, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    print("range call ms, %d cells    %s" % (n, timed(lambda: idx.search_range_batch_device(Q.data_ptr(), B, radii.data_ptr(), n, offsets.data_ptr(),
+                                                                                             r_ids.data_ptr(), r_d.data_ptr(), total.data_ptr()))),
+          flush=True)
+    stats = idx.last_range()
+    per_query = (offsets[1:] - offsets[:-1]).cpu().numpy()
+    print("candidates %d  matches %d  candidates / matches %.2f  queries without a bound %d  scratch %.1f MB"
+          % (stats[0], stats[1], stats[0] / max(1, stats[1]), stats[2], stats[3] / 1e6))
+    print("matches per query: min %d median %d max %d; the top-%d's rows are among them: %s"
+          % (per_query.min(), np.median(per_query), per_query.max(), K, bool((per_query >= K).all())), flush=True)
+
+
+if not SPLIT:
+    range_calls()
+for kind in ((0, 1, 0, 1) if SPLIT else ()):  # (each kind twice, in turn: how far two equal runs lie apart is part of the answer)
+    idx.set_option("range.split_bf16", kind)
+    print("range.split_bf16 = %d" % kind)
+    range_calls()
+    print("score kind %d, %d tile launches, E %.3g" % idx.last_range_scores()[:3], flush=True)

@@ -9,7 +9,9 @@ reports it) — about 10 matches per query.  Per T, interleaved, 10 repeats afte
   dense device  vss_search_range_batch_device between two hipEvents, same radii
 and the pairs scored with the whole-call rate 2 x dim x pairs / device time of the new and of the dense call (a call's rate, not
 the tile kernel's: that takes a kernel trace in a run of its own).  The answers of the two routes are compared.
-    python tools/probe_range_filtered.py [rows [dim [metric]]]"""
+--split adds two legs to the same interleaved rounds: the device form and the dense device call under option range.split_bf16 = 1
+(the split-bf16 candidate tiles), and prints the pairs the split score proposed beside the f32 score's.
+    python tools/probe_range_filtered.py [--split] [rows [dim [metric]]]"""
 import os
 import sys
 import time
@@ -23,6 +25,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
 import bench  # noqa: E402
 from __graft_entry__ import load_package  # noqa: E402
 
+SPLIT = "--split" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--split"]
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 dim = int(sys.argv[2]) if len(sys.argv) > 2 else 768
 metric = sys.argv[3] if len(sys.argv) > 3 else "cosine"
@@ -101,8 +105,20 @@ for T in (1, 16, 256):
         idx.search_range_batch_device(d_Q.data_ptr(), B, d_radii.data_ptr(), n_old, d_off.data_ptr(), d_ids.data_ptr(), d_d.data_ptr(),
                                       d_total.data_ptr())
 
+    def split(clock):  # the same clock around a call under range.split_bf16 = 1 (set and reset outside the timed part)
+        def timed(call):
+            idx.set_option("range.split_bf16", 1)
+            t = clock(call)
+            proposed_split[0] = int(idx.last_range()[0])
+            idx.set_option("range.split_bf16", 0)
+            return t
+        return timed
+
+    proposed_split = [0]
     legs = [("device form", events, new_device), ("host form", wall, new_host), ("old route", wall, old_route),
             ("dense device", events, dense_device)]
+    if SPLIT:
+        legs += [("dense split", split(events), dense_device), ("device split", split(events), new_device)]
     ms = {name: [] for name, _, _ in legs}
     for rep in range(REPEATS + 1):  # (the first round warms up: scratch allocations, the row norms)
         for name, clock, call in legs:
@@ -123,6 +139,8 @@ for T in (1, 16, 256):
           % (T, n_new, n_old, listed, pairs, proposed, launches, bool(same)), flush=True)
     for name, _, _ in legs:
         print("  %-13s ms  %s" % (name, summary(ms[name])), flush=True)
+    if SPLIT:
+        print("  device split proposed %d pairs (f32: %d) for %d matches" % (proposed_split[0], proposed, n_new), flush=True)
     new_ms, dense_ms = float(np.median(ms["device form"])), float(np.median(ms["dense device"]))
     print("  whole-call rate: new %.1f TFLOP/s over %d pairs, dense %.1f TFLOP/s over %d pairs"
           % (2.0 * dim * pairs / new_ms / 1e9, pairs, 2.0 * dim * B * rows / dense_ms / 1e9, B * rows), flush=True)
