@@ -29,15 +29,15 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip",
                      "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip",
                      "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip", "exact_split.hip",
-                     "exact_range.hip"]
+                     "exact_range.hip", "exact_range_codes.hip"]
 # flags of single translation units: the split-bf16 score tile and the range search are built without packed f32 arithmetic
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-TU_FLAGS = {"exact_split.hip": NO_PACKED_F32, "exact_range.hip": NO_PACKED_F32}
+TU_FLAGS = {"exact_split.hip": NO_PACKED_F32, "exact_range.hip": NO_PACKED_F32, "exact_range_codes.hip": NO_PACKED_F32}
 RANGE_ROW_CHUNK = 8192  # rows per launch of the range search's candidate tile (csrc/exact_range.h)
 
 
 def build_library(force=False, extra_flags=(), out=None):
-    """hipcc cross-compiles the engine for gfx950 (works without a GPU): thirteen translation units in parallel, then a
+    """hipcc cross-compiles the engine for gfx950 (works without a GPU): fourteen translation units in parallel, then a
     shared link.  Objects live in build/ (git-ignored)."""
     out = out or os.path.join(HERE, "libvssgpu.so")
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
@@ -907,8 +907,9 @@ class GpuIndex:
         return out
 
     def last_range_scores(self):
-        """(score kind of the last range search of either form (0 = f32, 1 = split bf16: set_option("range.split_bf16", 1)), its
-        candidate-tile launches, the largest finite error bound E its thresholds were built from as a float, 0)."""
+        """(score kind of the last range search of either form (0 = f32, 1 = split bf16: set_option("range.split_bf16", 1),
+        2 = int8 row codes: set_option("range.codes_i8", 1)), its candidate-tile launches, the largest finite error bound E its
+        thresholds were built from as a float — under kind 2 the largest finite per-query slack of the codes' pair test —, 0)."""
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_range_scores(self.h, _p(out)))
         return int(out[0]), int(out[1]), float(out[2:3].view(np.float64)[0]), int(out[3])

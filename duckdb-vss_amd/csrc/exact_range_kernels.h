@@ -11,7 +11,9 @@
 //                        32 queries x 256 listed rows
 //   k_range_candidates_bf16x3, k_range_candidates_lists_bf16x3   both tiles on the bf16 matrix pipe (option range.split_bf16,
 //                        score kind 1: exact_range_split_kernels.h)
-//   k_range_rescore      64 / G candidates side by side per wave, four deep: the wave-order metric itself (accumulate4,
+//   k_range_candidates_i8, k_range_candidates_lists_i8   both tiles on the int8 matrix pipe over the 8-bit row codes (option
+//                        range.codes_i8, score kind 2: exact_range_codes_kernels.h, defined in exact_range_codes.hip)
+//   k_range_rescore     64 / G candidates side by side per wave, four deep: the wave-order metric itself (accumulate4,
 //                        group_butterfly, finish_distance: the bits of k_exact_rerank), d <= r, the per-query count, and the
 //                        (query, row id, d) triple into the match scratch while the caller's capacity lasts
 //   k_range_offsets      counts -> offsets (one workgroup, 64-bit)
@@ -689,3 +691,4 @@ hipError_t launch_range_layout(const RangeLayoutArgs &a, uint32_t n_cus, hipStre
 } // namespace vss
 
 #include "exact_range_split_kernels.h" // both candidate tiles on the bf16 matrix pipe (option range.split_bf16)
+#include "exact_range_codes_kernels.h" // both candidate tiles on the int8 matrix pipe, over the row codes (option range.codes_i8)

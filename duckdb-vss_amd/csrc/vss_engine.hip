@@ -732,6 +732,9 @@ struct vss_index {
 	// search.prescore, VSS_SEARCH_PRESCORE: 0 off (no codes held), 1 where it was measured to gain — limits of at most 256, the
 	// 16-wave kernels —, 2 every pipelined launch (the 12-wave kernels of limits 257-512 too: measured SLOWER there)
 	uint32_t search_prescore = 1;
+	// range.codes_i8 (exact_range_codes_kernels.h): where the padded dimension is a multiple of 32 and the codes of every live
+	// row are valid, every candidate launch of a range call runs the int8 tiles over them (score kind 2).  Off by default.
+	bool range_codes_i8 = false;
 	// search.prescore_descent, VSS_SEARCH_PRESCORE_DESCENT: the greedy descent's jobs carry closest_dist as their bound in the
 	// launches that filter at all (1, the default); 0: they carry +inf, as every job of the descent did before
 	bool search_prescore_descent = true;
@@ -747,6 +750,11 @@ struct vss_index {
 		const uint32_t nch = (G == 64 && V % 64 == 0 && !force_looping) ? V / 64 : 0;
 		return search_prescore && (nch == 2 || nch == 3 || nch == 4 || nch == 6);
 	}
+	// the second reason to hold codes: range.codes_i8 (below), at every dimension whose padding is a multiple of 32.  The graph
+	// search's own eligibility stays codes_wanted(): its kernels are instantiated for those four row shapes only.
+	bool codes_held() const {
+		return codes_wanted() || (range_codes_i8 && V % 8 == 0);
+	}
 	void free_codes() {
 		d_codes.free(), d_code_meta.free();
 		codes_stale.clear();
@@ -756,7 +764,7 @@ struct vss_index {
 	// the call waits).  may_allocate: only under the exclusive index lock — a search never replaces buffers another search
 	// may be reading; it finds them too small (a reserve() since) and runs unfiltered.  No room on the device: no filter, no error.
 	bool ensure_codes(hipStream_t s, bool may_allocate) {
-		if (!codes_wanted() || !capacity)
+		if (!codes_held() || !capacity)
 			return false;
 		std::lock_guard<std::mutex> lk(codes_mu);
 		if (d_codes.n < capacity * V || d_code_meta.n < capacity) {
@@ -852,6 +860,11 @@ struct vss_index {
 	// default.  d_rg_q_hi / d_rg_q_lo: the query block split once per call (eight bf16 per cell), allocated by the first such call.
 	bool range_split_bf16 = false;
 	DevBuf<uint4> d_rg_q_hi, d_rg_q_lo;
+	// range.codes_i8: the query block coded once per call by k_encode_rows, exactly as a row is (one plane), and the constants
+	// of the pair test per query (k_range_prepare_codes); allocated by the first such call, kept for the next one
+	DevBuf<uint32_t> d_rg_q_codes;
+	DevBuf<RowCodeMeta> d_rg_q_meta;
+	DevBuf<RangeCodesQuery> d_rg_qc;
 	uint64_t last_range_scores[4] = {0, 0, 0, 0}; // vss_last_range_scores
 	// vss_search_range_batch_by_label_box64: the tile-index arrays of its plan (range_filtered_plan.h); lists, block counts and the
 	// plan's tables are the exact filtered search's (d_xf_*)
@@ -1616,7 +1629,7 @@ struct vss_index {
 		// pre-scoring on row codes (search.prescore), where the plan wants it and the codes can be had
 		a.prescore = PrescoreView {nullptr, nullptr, nullptr};
 		bool codes_ready = false;
-		if (plan.wants_prescore) {
+		if (plan.wants_prescore && codes_wanted()) { // (codes held for range.codes_i8 alone are not the graph search's)
 			try {
 				codes_ready = ensure_codes(c.stream, false);
 			} catch (const HipError &) { // (optional derived data: the search runs unfiltered, the slots stay marked)
@@ -2657,9 +2670,31 @@ struct vss_index {
 	// Rows are PROPOSED by the MFMA ranking score against a per-query threshold that no matching row can exceed (exact_range.h:
 	// the certificate's E pointed at the radius) and DECIDED by the metric itself, so nothing is certified and nothing redone.
 	// The caller holds exact_mu; every pointer is device memory; d_rowids / d_dist may be NULL iff cells == 0.
-	// The score kind of a range call over the nq padded queries of d_qpad: 1 iff range.split_bf16 is set and a row is a whole
-	// number of 128-byte steps.  Kind 1 splits the queries, once per call, into scratch that is kept for the next one.
+	// The score kind of a range call over the nq padded queries of d_qpad.  2 iff range.codes_i8 is set, a row is a whole number
+	// of 32-dimension MFMA blocks and the codes of every live row are valid — ensure_codes under the reader lock: it encodes stale
+	// slots and never allocates; without codes (no room on the device, a reserve() since) the call silently takes another kind.
+	// Kind 2 codes the queries, once per call, with the rows' own encoder.  Else 1 iff range.split_bf16 is set and a row is a
+	// whole number of 128-byte steps: kind 1 splits the queries, once per call.  Either scratch is kept for the next call.
 	int range_score_kind(uint64_t nq) {
+		if (range_codes_i8 && V % 8 == 0) {
+			bool codes_ready = false;
+			try {
+				codes_ready = ensure_codes(stream, false);
+			} catch (const HipError &) { // (optional derived data: the slots stay marked, the call runs another tile)
+				(void)hipGetLastError();
+			}
+			if (codes_ready) {
+				d_rg_q_codes.ensure(nq * V, 0, stream);
+				d_rg_q_meta.ensure(nq, 0, stream);
+				d_rg_qc.ensure(nq, 0, stream);
+				count_range_bytes();
+				const uint32_t grid = (uint32_t)std::min<uint64_t>((nq + 3) / 4, (uint64_t)n_cus * 16);
+				hipLaunchKernelGGL(k_encode_rows, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V,
+				                   (uint64_t)0, nq, d_rg_q_codes.p, d_rg_q_meta.p);
+				HIP_TRY(hipGetLastError());
+				return 2;
+			}
+		}
 		if (!range_split_bf16 || V % 8 != 0)
 			return 0;
 		const uint64_t n8 = nq * (uint64_t)V / 2; // cells of eight bf16
@@ -2713,7 +2748,8 @@ struct vss_index {
 		p.metric = metric, p.score_kind = score_kind, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
 		p.radii = d_radii, p.query_norm2 = d_q_norm2.p, p.norm_ext = d_norm_ext.p;
 		p.theta = d_rg_theta.p, p.counts = d_rg_counts.p, p.cursors = d_rg_counts.p + nq, p.stats = stats;
-		HIP_TRY(launch_range_prepare(p, stream));
+		HIP_TRY(score_kind == 2 ? range_prepare_codes(p) : launch_range_prepare(p, stream));
+		const RangeCodesView cv = range_codes_view(score_kind);
 		RangeTileArgs t;
 		t.queries = reinterpret_cast<const float4 *>(d_qpad.p), t.vectors = reinterpret_cast<const float4 *>(d_vectors.p);
 		t.row_norm2 = d_row_norm2.p, t.keys = d_keys.p, t.theta = d_rg_theta.p, t.V = V, t.metric = metric, t.cand = d_rg_cand.p;
@@ -2728,7 +2764,9 @@ struct vss_index {
 				t.row_begin = (uint32_t)r0, t.row_end = (uint32_t)std::min<uint64_t>(rows, r0 + RANGE_ROW_CHUNK);
 				t.q_begin = (uint32_t)q0, t.q_end = (uint32_t)std::min<uint64_t>(nq, q0 + RANGE_QUERY_BLOCK);
 				t.cand_count = launch_word, r.cand_count = launch_word;
-				HIP_TRY(score_kind ? launch_range_candidates_bf16x3(t, d_rg_q_hi.p, d_rg_q_lo.p, stream) : launch_range_candidates(t, stream));
+				HIP_TRY(score_kind == 2   ? launch_range_candidates_i8(t, cv, stream)
+				        : score_kind == 1 ? launch_range_candidates_bf16x3(t, d_rg_q_hi.p, d_rg_q_lo.p, stream)
+				                          : launch_range_candidates(t, stream));
 				HIP_TRY(launch_range_rescore(r, n_cus, stream));
 				++last_range_scores[1];
 			}
@@ -2744,11 +2782,24 @@ struct vss_index {
 		HIP_TRY(hipStreamSynchronize(stream));
 		return VSS_OK;
 	}
+	// kind 2's prepare step and operands: the queries' code records in the place of their norms, the index's resident row codes
+	hipError_t range_prepare_codes(const RangePrepareArgs &p) {
+		RangeCodesPrepareArgs a;
+		a.metric = p.metric, a.n = p.n, a.n_queries = p.n_queries, a.radii = p.radii, a.q_meta = d_rg_q_meta.p, a.norm_ext = p.norm_ext;
+		a.qc = d_rg_qc.p, a.counts = p.counts, a.cursors = p.cursors, a.stats = p.stats;
+		return launch_range_prepare_codes(a, stream);
+	}
+	RangeCodesView range_codes_view(int score_kind) const {
+		if (score_kind != 2)
+			return RangeCodesView {nullptr, nullptr, nullptr, nullptr};
+		return RangeCodesView {d_rg_q_codes.p, d_rg_qc.p, d_codes.p, d_code_meta.p};
+	}
 	void count_range_bytes() {
 		const uint64_t bytes = (d_rg_theta.n + d_rg_m_dist.n + d_rg_radii.n + d_rg_q.n + d_rg_out_d.n + d_rg_counts.n + d_rg_cand_count.n + d_rg_m_query.n +
 		                        d_rg_tile_index.n) * 4 +
 		                       (d_rg_cand.n + d_rg_m_rowid.n + d_rg_out_ids.n + d_rg_stats.n + d_rg_offsets.n) * 8 +
-		                       (d_rg_q_hi.n + d_rg_q_lo.n) * sizeof(uint4);
+		                       (d_rg_q_hi.n + d_rg_q_lo.n) * sizeof(uint4) + d_rg_q_codes.n * 4 +
+		                       d_rg_q_meta.n * sizeof(RowCodeMeta) + d_rg_qc.n * sizeof(RangeCodesQuery);
 		exact_range_bytes.store(bytes, std::memory_order_relaxed);
 		last_range[3] = bytes;
 	}
@@ -2875,7 +2926,8 @@ struct vss_index {
 		p.metric = metric, p.score_kind = score_kind, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
 		p.radii = d_radii, p.query_norm2 = d_q_norm2.p, p.norm_ext = d_norm_ext.p;
 		p.theta = d_rg_theta.p, p.counts = d_rg_counts.p, p.cursors = d_rg_counts.p + nq, p.stats = stats;
-		HIP_TRY(launch_range_prepare(p, stream));
+		HIP_TRY(score_kind == 2 ? range_prepare_codes(p) : launch_range_prepare(p, stream));
+		const RangeCodesView cv = range_codes_view(score_kind);
 		FilterListArgs l = exact_filter_list_args(g, nu, t);
 		l.lists = d_xf_lists.p;
 		RangeListTileArgs c;
@@ -2888,8 +2940,9 @@ struct vss_index {
 		r.cand = d_rg_cand.p, r.counts = d_rg_counts.p, r.stats = stats, r.capacity = match_cells;
 		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p;
 		auto lists_tile = [&](bool small) { // one shape of the gathered tile, of the call's score kind
-			return score_kind ? launch_range_candidates_lists_bf16x3(c, small, d_rg_q_hi.p, d_rg_q_lo.p, stream)
-			                  : launch_range_candidates_lists(c, small, stream);
+			return score_kind == 2   ? launch_range_candidates_lists_i8(c, small, cv, stream)
+			       : score_kind == 1 ? launch_range_candidates_lists_bf16x3(c, small, d_rg_q_hi.p, d_rg_q_lo.p, stream)
+			                         : launch_range_candidates_lists(c, small, stream);
 		};
 		uint32_t listed_pass = UINT32_MAX;
 		for (size_t i = 0; i != rp.launches.size(); ++i) {
@@ -4086,8 +4139,9 @@ const OptionRule OPTION_RULES[] = {
     {"search.prescore", 0, 2,
      [](vss_index *h, int64_t v) {
 	     h->search_prescore = (uint32_t)v;
-	     if (!h->search_prescore)
-		     h->free_codes(); // 0: no codes are held, every job's bound is +inf — the path without the filter, exactly
+	     if (!h->codes_held())
+		     h->free_codes(); // 0: no codes are held (unless range.codes_i8 holds them), every job's bound is +inf — the path
+		                      // without the filter, exactly
 	     else if (h->stream)
 		     h->refresh_codes();
      },
@@ -4099,6 +4153,16 @@ const OptionRule OPTION_RULES[] = {
      "exact search selects rows by a split-bf16 score on the bf16 matrix pipe (dimensions whose padding is a multiple of 32)"},
     {"range.split_bf16", 0, 1, [](vss_index *h, int64_t v) { h->range_split_bf16 = v != 0; },
      "range search proposes rows by a split-bf16 score on the bf16 matrix pipe (dimensions whose padding is a multiple of 32)"},
+    {"range.codes_i8", 0, 1,
+     [](vss_index *h, int64_t v) {
+	     h->range_codes_i8 = v != 0;
+	     if (!h->codes_held())
+		     h->free_codes();
+	     else if (h->stream)
+		     h->refresh_codes(); // (exclusive lock: the only places code buffers are allocated are here and after mutations)
+     },
+     "range search proposes rows by the integer dot product of 8-bit row codes on the int8 matrix pipe, under the codes' own "
+     "residual bound (dimensions whose padding is a multiple of 32; before range.split_bf16 where both are set)"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {

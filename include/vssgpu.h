@@ -129,6 +129,12 @@ int vss_set_build_reorder(vss_index *index, int on);
  *                                score, against thresholds built from its error bound (default 0; dimensions whose padding is
  *                                no multiple of 32 keep the f32 tiles); answers do not depend on it, the number of proposed
  *                                pairs (vss_last_range) may; vss_last_range_scores reports it
+ *   range.codes_i8 (0/1)         the same calls propose rows by the INTEGER dot product of 8-bit codes of query and row on the
+ *                                int8 matrix pipe, under the codes' own residual bound (default 0; dimensions whose padding is
+ *                                no multiple of 32, and an index whose device has no room for row codes, keep the rule above;
+ *                                where both options are set this one runs); the index then holds row codes (one byte per
+ *                                padded float and 16 bytes per row, counted by vss_memory_usage) whatever search.prescore
+ *                                says; answers do not depend on it, the number of proposed pairs may
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -606,7 +612,10 @@ int vss_last_exact_scores(vss_index *index, uint64_t *out4);
  * (csrc/exact_range.h, from the error bound of csrc/exact_certificate.h) and decided by the metric itself; answers depend on no
  * option (exact.split_bf16 is not consulted).  With vss_set_option "range.split_bf16" = 1 and a dimension whose padding is a
  * multiple of 32 the tile is the split-bf16 one and the threshold carries its wider bound (vss_last_range_scores); the query
- * block split into bf16 halves, 4 bytes per padded query float, then joins the scratch below.  The _device form takes device pointers for every argument, runs on the index's
+ * block split into bf16 halves, 4 bytes per padded query float, then joins the scratch below.  With "range.codes_i8" = 1 (and
+ * such a dimension, and valid row codes) the tile is the int8 one over the row codes and a per-pair test takes the threshold's
+ * place (csrc/exact_range_codes.h); the query block's codes, 1 byte per padded query float and 32 bytes per query, join the
+ * scratch as well.  The _device form takes device pointers for every argument, runs on the index's
  * stream and returns with the results valid.  Takes the reader lock and the exact path's mutex, as vss_search_exact_batch.
  * Device scratch, kept for the next call and counted by vss_memory_usage: at most 64 MiB of candidates (fixed: 1024 queries x
  * 8192 rows per launch, 8 bytes a pair) + 16 bytes per cell of min(capacity, n_queries x rows) + 12 bytes per query; the host
@@ -623,9 +632,12 @@ int vss_last_range(vss_index *index, uint64_t *out4);
 /* Which candidate tiles the last range call of either form (vss_search_range_batch*, vss_search_range_batch_by_label_box64*) on
  * this index proposed rows with: out4[0] = the score kind, 0 = f32 (v_mfma_f32_32x32x2_f32), 1 = split bf16 (vss_set_option
  * "range.split_bf16" = 1 and a dimension whose padding is a multiple of 32: q.x ~ qh.xh + qh.xl + ql.xh on
- * v_mfma_f32_32x32x16_bf16, csrc/exact_range_split_kernels.h); [1] = its candidate-tile launches; [2] = the bit pattern of the
- * largest finite error bound E (a double, csrc/exact_certificate.h) its thresholds were built from, 0 if none was finite;
- * [3] = 0.  Diagnostics and tests: answers never depend on the option, because the threshold carries the bound of the kind that
+ * v_mfma_f32_32x32x16_bf16, csrc/exact_range_split_kernels.h), 2 = int8 row codes (vss_set_option "range.codes_i8" = 1, such a
+ * dimension and valid codes of every live row: sum cq_i cx_i on v_mfma_i32_32x32x32_i8, csrc/exact_range_codes_kernels.h);
+ * [1] = its candidate-tile launches; [2] = the bit pattern of the largest finite error bound E (a double,
+ * csrc/exact_certificate.h) its thresholds were built from, 0 if none was finite — under kind 2, where the bound depends on the
+ * row as well, of the largest finite per-query SLACK: the distance the pair test gives away at a row of the largest live norm
+ * whose residual is half a code step in every component (csrc/exact_range_codes.h); [3] = 0.  Diagnostics and tests: answers never depend on the option, because the threshold carries the bound of the kind that
  * ran and the metric decides every proposed pair. */
 int vss_last_range_scores(vss_index *index, uint64_t *out4);
 /* Exact range search UNDER PER-QUERY LABEL BOXES — the filtered similarity join (`... < r AND items.tenant = a.tenant AND
@@ -636,7 +648,7 @@ int vss_last_range_scores(vss_index *index, uint64_t *out4);
  * and the distance bits of vss_search_range_batch.  Only the rows a query's box admits are scored: the distinct boxes of the
  * call become lists of live admitted rows, and an f32 MFMA tile gathers its rows through them.
  * vss_set_option "range.split_bf16" = 1 puts every launch of that tile, in both its shapes, on the split-bf16 score, as it does
- * for vss_search_range_batch.
+ * for vss_search_range_batch, and "range.codes_i8" = 1 on the int8 tiles over the row codes, gathered through the same lists.
  * Everything else is vss_search_range_batch's, word for word: out_offsets and *out_total are always written, the cells only if
  * *out_total <= capacity (otherwise none, and VSS_OK), in no particular order inside a query; capacity == 0 is the count-only
  * call, and only then may out_rowids / out_distances be NULL; NaN, negative and +inf radii; n_queries == 0 and the empty index

@@ -6,7 +6,9 @@ stream, five repeats after one warm-up, and candidates / matches from vss_last_r
 to the re-score per row that matches (set by the certificate's E: 1.8e-4 for cosine at 768 dimensions).
 --split measures the range calls under option range.split_bf16 = 0 and = 1 in turn (the f32 and the split-bf16 candidate tiles),
 ten repeats each, with vss_last_range_scores' kind and E beside the candidates.
-    python tools/probe_range.py [--split] [rows [dim [metric [neighbour]]]]"""
+--codes-i8 measures them under kinds 0, 1 and 2 in turn, twice (range.codes_i8 = 1 for the int8 tiles over the row codes; the
+figure beside kind 2 is the largest per-query slack of its pair test, not an E).
+    python tools/probe_range.py [--split | --codes-i8] [rows [dim [metric [neighbour]]]]"""
 import os
 import sys
 
@@ -19,13 +21,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
 import bench  # noqa: E402
 from __graft_entry__ import load_package  # noqa: E402
 
-SPLIT = "--split" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--split"]
+SPLIT, CODES = "--split" in sys.argv, "--codes-i8" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--split", "--codes-i8")]
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 dim = int(sys.argv[2]) if len(sys.argv) > 2 else 768
 metric = sys.argv[3] if len(sys.argv) > 3 else "cosine"
 K = int(sys.argv[4]) if len(sys.argv) > 4 else 100
-B, REPEATS = 1024, 10 if SPLIT else 5
+B, REPEATS = 1024, 10 if SPLIT or CODES else 5
 pkg = load_package()
 dev = torch.device("cuda", 0)
 gen = bench.Mixture(rows, dim, metric != "l2sq", dev)
@@ -90,10 +92,12 @@ def range_calls():
           % (per_query.min(), np.median(per_query), per_query.max(), K, bool((per_query >= K).all())), flush=True)
 
 
-if not SPLIT:
+if not SPLIT and not CODES:
     range_calls()
-for kind in ((0, 1, 0, 1) if SPLIT else ()):  # (each kind twice, in turn: how far two equal runs lie apart is part of the answer)
-    idx.set_option("range.split_bf16", kind)
-    print("range.split_bf16 = %d" % kind)
+# (each kind twice, in turn: how far two equal runs lie apart is part of the answer)
+for kind in ((0, 1, 2, 0, 1, 2) if CODES else (0, 1, 0, 1) if SPLIT else ()):
+    idx.set_option("range.split_bf16", int(kind == 1))
+    idx.set_option("range.codes_i8", int(kind == 2))
+    print("range.split_bf16 = %d, range.codes_i8 = %d" % (kind == 1, kind == 2))
     range_calls()
     print("score kind %d, %d tile launches, E %.3g" % idx.last_range_scores()[:3], flush=True)
