@@ -29,15 +29,16 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip",
                      "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip",
                      "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip", "exact_split.hip",
-                     "exact_range.hip", "exact_range_codes.hip"]
+                     "exact_range.hip", "exact_range_codes.hip", "exact_codes.hip"]
 # flags of single translation units: the split-bf16 score tile and the range search are built without packed f32 arithmetic
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-TU_FLAGS = {"exact_split.hip": NO_PACKED_F32, "exact_range.hip": NO_PACKED_F32, "exact_range_codes.hip": NO_PACKED_F32}
+TU_FLAGS = {"exact_split.hip": NO_PACKED_F32, "exact_range.hip": NO_PACKED_F32, "exact_range_codes.hip": NO_PACKED_F32,
+            "exact_codes.hip": NO_PACKED_F32}
 RANGE_ROW_CHUNK = 8192  # rows per launch of the range search's candidate tile (csrc/exact_range.h)
 
 
 def build_library(force=False, extra_flags=(), out=None):
-    """hipcc cross-compiles the engine for gfx950 (works without a GPU): fourteen translation units in parallel, then a
+    """hipcc cross-compiles the engine for gfx950 (works without a GPU): fifteen translation units in parallel, then a
     shared link.  Objects live in build/ (git-ignored)."""
     out = out or os.path.join(HERE, "libvssgpu.so")
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
@@ -852,8 +853,11 @@ class GpuIndex:
         return int(self.lib.vss_last_exact_fallbacks(self.h))
 
     def last_exact_scores(self):
-        """[score kind of the last exact search (0 = f32, 1 = split bf16: set_option("exact.split_bf16", 1)), its score launches,
-        the largest finite certificate bound E as a float, 0]."""
+        """[score kind of the last exact search (0 = f32, 1 = split bf16: set_option("exact.split_bf16", 1), 2 = by bounds from
+        the int8 row codes: set_option("exact.codes_i8", 1)), its score launches (kind 2: the bound-tile launches of the first
+        pass), the largest finite certificate bound E as a float (kind 2: the largest finite per-query slack of the codes), the
+        (query, row) pairs re-scored in the metric under kind 2, else 0].  A call under exact.codes_i8 whose candidates did not
+        fit max(1024, 4 k) cells per query reports the kind that answered it instead."""
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_exact_scores(self.h, _p(out)))
         return [int(out[0]), int(out[1]), float(out[2:3].view(np.float64)[0]), int(out[3])]

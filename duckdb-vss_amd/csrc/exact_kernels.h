@@ -6,7 +6,9 @@
 //                      batch of queries at once; scores are RANKING scores (|x|^2 - 2 q.x, -q.x/|x|, -q.x).
 //   k_exact_scores_bf16x3  the same scores from a two-way bf16 split of both operands on v_mfma_f32_32x32x16_bf16
 //                      (exact_split_kernels.h; option exact.split_bf16)
-//   k_exact_select     per query: fold one chunk of scores into a running top-K' (K' = k + slack)
+//   k_exact_bounds_i8  upper bounds of the distances from the 8-bit row codes on v_mfma_i32_32x32x32_i8, for an exact top-k by
+//                      bounds (exact_codes_kernels.h; option exact.codes_i8)
+//   k_exact_select    per query: fold one chunk of scores into a running top-K' (K' = k + slack)
 //   k_exact_rerank     per query: recompute the K' survivors with the exact wave-order metric, sort, emit k; decides whether
 //                      the selection by score provably kept the metric's top-k (exact_certificate.h)
 //   k_norm_extrema     largest / smallest |x|^2 over the live rows (cached with the norms; the certificate's E)
@@ -1599,3 +1601,4 @@ __global__ __launch_bounds__(64) void k_merge_topk(const float *in_d, const int6
 } // namespace vss
 
 #include "exact_split_kernels.h" // k_exact_scores_bf16x3: the 128 x 128 tile on the bf16 matrix pipe (option exact.split_bf16)
+#include "exact_codes_kernels.h" // k_exact_bounds_i8: the 128 x 128 bound tile on the int8 matrix pipe (option exact.codes_i8)

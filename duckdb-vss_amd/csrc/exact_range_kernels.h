@@ -95,6 +95,7 @@ struct RangeRescoreArgs {
 	uint32_t *m_query;
 	int64_t *m_rowid;
 	float *m_dist;
+	bool slots = false; // m_rowid takes the match's SLOT, not its row id: the exact search by bounds (exact_codes_kernels.h) ranks by slot
 };
 
 struct RangeLayoutArgs {
@@ -573,7 +574,7 @@ __global__ __launch_bounds__(256) void k_range_rescore(RangeRescoreArgs a) {
 				atomicAdd(&a.counts[c[r].x], 1u);
 				if (at < a.capacity) {
 					a.m_query[at] = c[r].x;
-					a.m_rowid[at] = a.keys[c[r].y];
+					a.m_rowid[at] = a.slots ? (int64_t)c[r].y : a.keys[c[r].y];
 					a.m_dist[at] = d;
 				}
 			}

@@ -735,6 +735,10 @@ struct vss_index {
 	// range.codes_i8 (exact_range_codes_kernels.h): where the padded dimension is a multiple of 32 and the codes of every live
 	// row are valid, every candidate launch of a range call runs the int8 tiles over them (score kind 2).  Off by default.
 	bool range_codes_i8 = false;
+	// exact.codes_i8 (exact_codes_kernels.h): under the same conditions an exact call is answered by bounds (score kind 2) — the
+	// int8 bound tiles give every query the k-th smallest UPPER bound of its distances, the range search of kind 2 under that
+	// radius re-scores the rows whose LOWER bound is not above it, and the top k of those matches is the answer.  Off by default.
+	bool exact_codes_i8 = false;
 	// search.prescore_descent, VSS_SEARCH_PRESCORE_DESCENT: the greedy descent's jobs carry closest_dist as their bound in the
 	// launches that filter at all (1, the default); 0: they carry +inf, as every job of the descent did before
 	bool search_prescore_descent = true;
@@ -752,8 +756,9 @@ struct vss_index {
 	}
 	// the second reason to hold codes: range.codes_i8 (below), at every dimension whose padding is a multiple of 32.  The graph
 	// search's own eligibility stays codes_wanted(): its kernels are instantiated for those four row shapes only.
+	// The third: exact.codes_i8 (exact_codes_kernels.h), at the same dimensions.
 	bool codes_held() const {
-		return codes_wanted() || (range_codes_i8 && V % 8 == 0);
+		return codes_wanted() || ((range_codes_i8 || exact_codes_i8) && V % 8 == 0);
 	}
 	void free_codes() {
 		d_codes.free(), d_code_meta.free();
@@ -865,6 +870,9 @@ struct vss_index {
 	DevBuf<uint32_t> d_rg_q_codes;
 	DevBuf<RowCodeMeta> d_rg_q_meta;
 	DevBuf<RangeCodesQuery> d_rg_qc;
+	// exact.codes_i8: the constants of the upper bound per query (k_exact_prepare_codes); the coded query block, the radii and
+	// the matches of its second pass are the range search's buffers above, counted with them
+	DevBuf<ExactCodesQuery> d_xc_qc;
 	uint64_t last_range_scores[4] = {0, 0, 0, 0}; // vss_last_range_scores
 	// vss_search_range_batch_by_label_box64: the tile-index arrays of its plan (range_filtered_plan.h); lists, block counts and the
 	// plan's tables are the exact filtered search's (d_xf_*)
@@ -935,7 +943,7 @@ struct vss_index {
 		exact_filter_bytes.store(0, std::memory_order_relaxed);
 		d_rg_theta.free(), d_rg_m_dist.free(), d_rg_radii.free(), d_rg_q.free(), d_rg_out_d.free(), d_rg_counts.free();
 		d_rg_cand_count.free(), d_rg_m_query.free(), d_rg_cand.free(), d_rg_m_rowid.free(), d_rg_out_ids.free();
-		d_rg_stats.free(), d_rg_offsets.free(), d_rg_tile_index.free(), d_rg_q_hi.free(), d_rg_q_lo.free();
+		d_rg_stats.free(), d_rg_offsets.free(), d_rg_tile_index.free(), d_rg_q_hi.free(), d_rg_q_lo.free(), d_xc_qc.free();
 		exact_range_bytes.store(0, std::memory_order_relaxed);
 		if (h_counters)
 			(void)hipHostFree(h_counters);
@@ -2428,7 +2436,7 @@ struct vss_index {
 		// exact=true), its k is bounded by the select kernel's LDS
 		if (k + 8 > SEL_KP_MAX)
 			return fail("exact search supports k <= %d", SEL_KP_MAX - 8);
-		const uint64_t KP = k + 8;
+		uint64_t KP = k + 8; // (k itself while the call runs by bounds: exact.codes_i8, below)
 		if (!rows) {
 			HIP_TRY(hipMemsetAsync(d_keys_out, 0xFF, nq * k * 8, stream));
 			HIP_TRY(hipMemsetAsync(d_count_out, 0, nq * 4, stream));
@@ -2454,15 +2462,20 @@ struct vss_index {
 		// exact.split_bf16: the score tile on the bf16 matrix pipe, where a row is a whole number of 128-byte steps (and, as for
 		// the LDS-DMA tile, a tile's rows lie within 32-bit offsets); other shapes keep the f32 tile.  The queries are split once.
 		const bool split = exact_split_bf16 && V % 8 == 0 && 128ull * V * 16 < (1ull << 31);
-		const int score_kind = split ? 1 : 0;
+		// exact.codes_i8: the call is answered by bounds where the int8 tiles' condition holds (range_score_kind's rule); it goes
+		// before exact.split_bf16, and a call whose candidates do not fit is answered from the start by the kind below
+		const bool by_bounds = exact_codes_i8 && codes_tiles_ready(nq, false);
+		int score_kind = by_bounds ? 2 : split ? 1 : 0;
 		uint64_t score_launches = 0;
-		if (split) {
+		auto split_queries = [&]() {
 			const uint64_t n8 = nq * (uint64_t)V / 2; // cells of eight bf16
 			d_q_hi.ensure(n8, 0, stream);
 			d_q_lo.ensure(n8, 0, stream);
 			exact_split_bytes.store((d_q_hi.n + d_q_lo.n) * sizeof(uint4), std::memory_order_relaxed);
 			HIP_TRY(launch_split_queries(reinterpret_cast<const float4 *>(d_qpad.p), n8, d_q_hi.p, d_q_lo.p, stream));
-		}
+		};
+		if (split && !by_bounds)
+			split_queries();
 		// Round 4: from the second chunk on the select is folded into the score tile's epilogue — only scores that beat a
 		// query's K'-th best so far are kept (as survivors in a small per-query buffer), and the running top-K' is refreshed
 		// from those buffers once per launch of eight chunks' worth of rows instead of from 128 KiB of scores per query after
@@ -2478,7 +2491,8 @@ struct vss_index {
 		// window of eight chunks used to overflow almost surely for k above ~248, and the whole pass was then repeated).
 		const uint64_t CAND_CAP = SEL_CAP, SELECT_EVERY = 8;
 		const bool want_filter = exact_filter && (split || exact_kernel == 2 || exact_kernel >= 4) && rows > CH && 8 * KP <= CAND_CAP;
-		if (want_filter) {
+		const bool bounds_filter = by_bounds && exact_filter && rows > CH && 8 * k <= CAND_CAP; // (pass A keeps a running top-k: K' = k)
+		if (want_filter || bounds_filter) {
 			d_cand_cnt.ensure(nq + 1, 0, stream); // [nq] = the overflow flag
 			d_cand_s.ensure(nq * CAND_CAP, 0, stream);
 			d_cand_i.ensure(nq * CAND_CAP, 0, stream);
@@ -2512,7 +2526,11 @@ struct vss_index {
 				e.cand_cnt = filter_this ? d_cand_cnt.p : nullptr;
 				e.cand_s = d_cand_s.p, e.cand_i = d_cand_i.p;
 				++score_launches;
-				if (split) { // the persistent 128 x 128 tile on v_mfma_f32_32x32x16_bf16, two workgroups per compute unit
+				if (score_kind == 2) { // pass A of the search by bounds: the persistent 128 x 128 tile on v_mfma_i32_32x32x32_i8, its score an upper bound
+					const uint64_t tiles = ((r1 - r0 + 127) / 128) * ((nq + 127) / 128);
+					const uint32_t grid = (uint32_t)std::min<uint64_t>(2ull * n_cus, tiles);
+					HIP_TRY(launch_exact_bounds_i8(e, ExactCodesView {d_rg_q_codes.p, d_xc_qc.p, d_codes.p, d_code_meta.p}, grid, stream));
+				} else if (split) { // the persistent 128 x 128 tile on v_mfma_f32_32x32x16_bf16, two workgroups per compute unit
 					const uint64_t tiles = ((r1 - r0 + 127) / 128) * ((nq + 127) / 128);
 					const uint32_t grid = (uint32_t)std::min<uint64_t>(2ull * n_cus, tiles);
 					HIP_TRY(launch_exact_scores_bf16x3(e, d_q_hi.p, d_q_lo.p, grid, stream));
@@ -2560,6 +2578,43 @@ struct vss_index {
 		};
 		ensure_events();
 		HIP_TRY(hipEventRecord(ev[0], stream));
+		if (by_bounds) {
+			// pass A: tau_q = best_s[q][k - 1], the k-th smallest upper bound; pass B and the answer: exact_codes_answer
+			KP = k;
+			d_xc_qc.ensure(nq, 0, stream);
+			d_e_max.ensure(1, 0, stream);
+			count_range_bytes(false);
+			HIP_TRY(hipMemsetAsync(d_e_max.p, 0, 8, stream));
+			ExactCodesPrepareArgs pa;
+			pa.metric = metric, pa.n = (uint32_t)stride, pa.n_queries = (uint32_t)nq, pa.q_meta = d_rg_q_meta.p, pa.norm_ext = d_norm_ext.p;
+			pa.qc = d_xc_qc.p, pa.e_max = reinterpret_cast<unsigned long long *>(d_e_max.p);
+			HIP_TRY(launch_exact_prepare_codes(pa, stream));
+			run(bounds_filter);
+			if (bounds_filter) {
+				uint32_t overflowed = 0;
+				HIP_TRY(hipMemcpyAsync(&overflowed, d_cand_cnt.p + nq, 4, hipMemcpyDeviceToHost, stream));
+				HIP_TRY(hipStreamSynchronize(stream));
+				if (overflowed)
+					run(false);
+			}
+			bool answered = false;
+			if (const int rc = exact_codes_answer(nq, k, d_keys_out, d_dist_out, d_count_out, answered))
+				return rc;
+			if (answered) {
+				last_exact_scores[0] = 2, last_exact_scores[1] = score_launches;
+				float ms = 0;
+				HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+				std::lock_guard<std::mutex> lk(stats_mu);
+				timing[0] = ms;
+				return VSS_OK;
+			}
+			// data the codes cannot separate: the call is answered from the start by the kind it would have taken without the option
+			KP = k + 8, score_kind = split ? 1 : 0, score_launches = 0;
+			std::fill(last_exact_scores, last_exact_scores + 4, 0);
+			if (split)
+				split_queries();
+			HIP_TRY(hipEventRecord(ev[0], stream));
+		}
 		run(want_filter);
 		HIP_TRY(hipEventRecord(ev[1], stream)); // (score tiles and selects of the first pass: timing[0] below)
 		if (want_filter) {
@@ -2665,6 +2720,43 @@ struct vss_index {
 		return VSS_OK;
 	}
 
+	// Pass B of the exact search by bounds (exact.codes_i8; the caller is exact_launch after pass A: d_best_s[q][k - 1] = tau_q,
+	// the queries padded, coded and their norms taken).  The range search of kind 2 under the radii tau_q re-scores, in the
+	// metric, every live row whose lower bound is not above tau_q — the true top-k among them — into a match capacity of
+	// max(1024, 4 k) cells per query; if the total fits, the k smallest (distance, slot) of each query's matches are the answer
+	// (answered = true; vss_last_exact_scores [2], [3] are filled in, ev[1] is recorded).  If it does not, nothing is written.
+	int exact_codes_answer(uint64_t nq, uint64_t k, int64_t *d_keys_out, float *d_dist_out, uint32_t *d_count_out, bool &answered) {
+		const uint64_t rows = count;
+		const uint64_t match_cells = std::min(nq * std::max<uint64_t>(1024, 4 * k), nq * rows);
+		range_scratch(nq, rows, match_cells, false);
+		d_rg_radii.ensure(nq, 0, stream);
+		d_rg_offsets.ensure(nq + 2, 0, stream); // offsets, then the total
+		d_rg_out_ids.ensure(match_cells, 0, stream);
+		d_rg_out_d.ensure(match_cells, 0, stream);
+		count_range_bytes(false);
+		HIP_TRY(launch_exact_codes_radii(d_best_s.p, (uint32_t)k, (uint32_t)nq, d_rg_radii.p, stream));
+		uint64_t launches = 0;
+		if (const int rc = range_pairs(nq, d_rg_radii.p, match_cells, 2, true, d_rg_offsets.p, d_rg_out_ids.p, d_rg_out_d.p,
+		                               d_rg_offsets.p + nq + 1, launches))
+			return rc;
+		uint64_t total = 0, rescored = 0;
+		HIP_TRY(hipMemcpyAsync(&total, d_rg_offsets.p + nq + 1, 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&rescored, d_rg_stats.p, 8, hipMemcpyDeviceToHost, stream)); // RangeStats::candidates
+		HIP_TRY(hipStreamSynchronize(stream));
+		answered = total <= match_cells;
+		if (!answered)
+			return VSS_OK;
+		ExactCodesTopkArgs t;
+		t.k = (uint32_t)k, t.offsets = reinterpret_cast<const unsigned long long *>(d_rg_offsets.p), t.slots = d_rg_out_ids.p, t.dist = d_rg_out_d.p;
+		t.keys = d_keys.p, t.out_keys = d_keys_out, t.out_d = d_dist_out, t.out_count = d_count_out;
+		HIP_TRY(launch_exact_codes_topk(t, (uint32_t)nq, stream));
+		HIP_TRY(hipEventRecord(ev[1], stream));
+		HIP_TRY(hipMemcpyAsync(&last_exact_scores[2], d_e_max.p, 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		last_exact_scores[3] = rescored;
+		return VSS_OK;
+	}
+
 	// ------------------------------------------------------------------ exact range search
 	// Contract (include/vssgpu.h): query q matches the live rows whose wave-order metric distance is <= radii[q].
 	// Rows are PROPOSED by the MFMA ranking score against a per-query threshold that no matching row can exceed (exact_range.h:
@@ -2675,26 +2767,31 @@ struct vss_index {
 	// slots and never allocates; without codes (no room on the device, a reserve() since) the call silently takes another kind.
 	// Kind 2 codes the queries, once per call, with the rows' own encoder.  Else 1 iff range.split_bf16 is set and a row is a
 	// whole number of 128-byte steps: kind 1 splits the queries, once per call.  Either scratch is kept for the next call.
-	int range_score_kind(uint64_t nq) {
-		if (range_codes_i8 && V % 8 == 0) {
-			bool codes_ready = false;
-			try {
-				codes_ready = ensure_codes(stream, false);
-			} catch (const HipError &) { // (optional derived data: the slots stay marked, the call runs another tile)
-				(void)hipGetLastError();
-			}
-			if (codes_ready) {
-				d_rg_q_codes.ensure(nq * V, 0, stream);
-				d_rg_q_meta.ensure(nq, 0, stream);
-				d_rg_qc.ensure(nq, 0, stream);
-				count_range_bytes();
-				const uint32_t grid = (uint32_t)std::min<uint64_t>((nq + 3) / 4, (uint64_t)n_cus * 16);
-				hipLaunchKernelGGL(k_encode_rows, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V,
-				                   (uint64_t)0, nq, d_rg_q_codes.p, d_rg_q_meta.p);
-				HIP_TRY(hipGetLastError());
-				return 2;
-			}
+	// the int8 tiles' condition (range.codes_i8 and exact.codes_i8 alike); true: the nq padded queries of d_qpad are coded too
+	bool codes_tiles_ready(uint64_t nq, bool report_bytes) {
+		if (V % 8 != 0)
+			return false;
+		bool codes_ready = false;
+		try {
+			codes_ready = ensure_codes(stream, false);
+		} catch (const HipError &) { // (optional derived data: the slots stay marked, the call runs another tile)
+			(void)hipGetLastError();
 		}
+		if (!codes_ready)
+			return false;
+		d_rg_q_codes.ensure(nq * V, 0, stream);
+		d_rg_q_meta.ensure(nq, 0, stream);
+		d_rg_qc.ensure(nq, 0, stream);
+		count_range_bytes(report_bytes);
+		const uint32_t grid = (uint32_t)std::min<uint64_t>((nq + 3) / 4, (uint64_t)n_cus * 16);
+		hipLaunchKernelGGL(k_encode_rows, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V, (uint64_t)0, nq,
+		                   d_rg_q_codes.p, d_rg_q_meta.p);
+		HIP_TRY(hipGetLastError());
+		return true;
+	}
+	int range_score_kind(uint64_t nq) {
+		if (range_codes_i8 && codes_tiles_ready(nq, true))
+			return 2;
 		if (!range_split_bf16 || V % 8 != 0)
 			return 0;
 		const uint64_t n8 = nq * (uint64_t)V / 2; // cells of eight bf16
@@ -2716,12 +2813,30 @@ struct vss_index {
 			return VSS_OK;
 		}
 		const uint64_t stride = (uint64_t)V * 4;
-		const uint64_t row_chunks = (rows + RANGE_ROW_CHUNK - 1) / RANGE_ROW_CHUNK, query_blocks = (nq + RANGE_QUERY_BLOCK - 1) / RANGE_QUERY_BLOCK;
 		const uint64_t match_cells = std::min(cells, nq * rows);
 		d_row_norm2.ensure(capacity, 0, stream);
 		d_norm_ext.ensure(2, 0, stream);
 		d_qpad.ensure(nq * stride, 0, stream);
 		d_q_norm2.ensure(nq, 0, stream);
+		range_scratch(nq, rows, match_cells, true);
+		refresh_row_norms(rows);
+		HIP_TRY(hipMemsetAsync(d_qpad.p, 0, nq * stride * 4, stream));
+		HIP_TRY(hipMemcpy2DAsync(d_qpad.p, stride * 4, d_queries, (size_t)q_stride * 4, dim * 4, nq, hipMemcpyDeviceToDevice, stream));
+		// (the wave-order |q|^2: the value k_exact_rerank's wave_query_norm computes, and the cosine distance's own)
+		hipLaunchKernelGGL(k_row_norms, dim3(256), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V, G, logG,
+		                   (uint32_t)nq, d_q_norm2.p);
+		const int score_kind = range_score_kind(nq);
+		if (const int rc = range_pairs(nq, d_radii, match_cells, score_kind, false, d_offsets, d_rowids, d_dist, d_total, last_range_scores[1]))
+			return rc;
+		last_range_scores[0] = (uint64_t)score_kind;
+		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&last_range_scores[2], d_rg_stats.p + 3, 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		return VSS_OK;
+	}
+	// the per-call scratch of the dense range search over nq queries and `rows` rows, match_cells cells of matches
+	void range_scratch(uint64_t nq, uint64_t rows, uint64_t match_cells, bool report_bytes) {
+		const uint64_t row_chunks = (rows + RANGE_ROW_CHUNK - 1) / RANGE_ROW_CHUNK, query_blocks = (nq + RANGE_QUERY_BLOCK - 1) / RANGE_QUERY_BLOCK;
 		d_rg_theta.ensure(nq, 0, stream);
 		d_rg_counts.ensure(2 * nq, 0, stream); // counts, then the scatter's cursors
 		d_rg_stats.ensure(4, 0, stream);
@@ -2733,16 +2848,18 @@ struct vss_index {
 			d_rg_m_rowid.ensure(match_cells, 0, stream);
 			d_rg_m_dist.ensure(match_cells, 0, stream);
 		}
-		count_range_bytes();
-		refresh_row_norms(rows);
-		HIP_TRY(hipMemsetAsync(d_qpad.p, 0, nq * stride * 4, stream));
-		HIP_TRY(hipMemcpy2DAsync(d_qpad.p, stride * 4, d_queries, (size_t)q_stride * 4, dim * 4, nq, hipMemcpyDeviceToDevice, stream));
-		// (the wave-order |q|^2: the value k_exact_rerank's wave_query_norm computes, and the cosine distance's own)
-		hipLaunchKernelGGL(k_row_norms, dim3(256), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V, G, logG,
-		                   (uint32_t)nq, d_q_norm2.p);
+		count_range_bytes(report_bytes);
+	}
+	// The dense range search proper, for range_launch and for the exact search by bounds (exact_codes_answer): prepare, candidate
+	// tiles and re-scores per (row chunk, query block), layout.  The queries are padded in d_qpad with their norms in d_q_norm2,
+	// the row norms are fresh, range_scratch has run, and for kind 2 the queries are coded (codes_tiles_ready).  slots: the cells
+	// of d_rowids take the matches' slots.  Touches no diagnostics of the public range calls but `launches`; does not wait.
+	int range_pairs(uint64_t nq, const float *d_radii, uint64_t match_cells, int score_kind, bool slots, uint64_t *d_offsets,
+	                int64_t *d_rowids, float *d_dist, uint64_t *d_total, uint64_t &launches) {
+		const uint64_t rows = count, stride = (uint64_t)V * 4;
+		const uint64_t row_chunks = (rows + RANGE_ROW_CHUNK - 1) / RANGE_ROW_CHUNK, query_blocks = (nq + RANGE_QUERY_BLOCK - 1) / RANGE_QUERY_BLOCK;
 		HIP_TRY(hipMemsetAsync(d_rg_stats.p, 0, 4 * 8, stream));
 		HIP_TRY(hipMemsetAsync(d_rg_cand_count.p, 0, row_chunks * query_blocks * 4, stream));
-		const int score_kind = range_score_kind(nq);
 		RangeStats *stats = reinterpret_cast<RangeStats *>(d_rg_stats.p);
 		RangePrepareArgs p;
 		p.metric = metric, p.score_kind = score_kind, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
@@ -2756,7 +2873,7 @@ struct vss_index {
 		RangeRescoreArgs r;
 		r.sp = view().sp, r.keys = d_keys.p, r.queries = t.queries, r.query_norm2 = d_q_norm2.p, r.radii = d_radii;
 		r.cand = d_rg_cand.p, r.counts = d_rg_counts.p, r.stats = stats, r.capacity = match_cells;
-		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p;
+		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p, r.slots = slots;
 		uint32_t *launch_word = d_rg_cand_count.p;
 		// row chunks outside: a chunk's rows are read from HBM once and serve every query block out of the cache
 		for (uint64_t r0 = 0; r0 < rows; r0 += RANGE_ROW_CHUNK)
@@ -2768,18 +2885,14 @@ struct vss_index {
 				        : score_kind == 1 ? launch_range_candidates_bf16x3(t, d_rg_q_hi.p, d_rg_q_lo.p, stream)
 				                          : launch_range_candidates(t, stream));
 				HIP_TRY(launch_range_rescore(r, n_cus, stream));
-				++last_range_scores[1];
+				++launches;
 			}
-		last_range_scores[0] = (uint64_t)score_kind;
 		RangeLayoutArgs l;
 		l.n_queries = (uint32_t)nq, l.counts = d_rg_counts.p, l.cursors = d_rg_counts.p + nq, l.stats = stats, l.capacity = match_cells;
 		l.offsets = reinterpret_cast<unsigned long long *>(d_offsets), l.total = reinterpret_cast<unsigned long long *>(d_total);
 		l.m_query = d_rg_m_query.p, l.m_rowid = d_rg_m_rowid.p, l.m_dist = d_rg_m_dist.p;
 		l.out_rowids = d_rowids, l.out_dist = d_dist;
 		HIP_TRY(launch_range_layout(l, n_cus, stream));
-		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
-		HIP_TRY(hipMemcpyAsync(&last_range_scores[2], d_rg_stats.p + 3, 8, hipMemcpyDeviceToHost, stream));
-		HIP_TRY(hipStreamSynchronize(stream));
 		return VSS_OK;
 	}
 	// kind 2's prepare step and operands: the queries' code records in the place of their norms, the index's resident row codes
@@ -2794,14 +2907,15 @@ struct vss_index {
 			return RangeCodesView {nullptr, nullptr, nullptr, nullptr};
 		return RangeCodesView {d_rg_q_codes.p, d_rg_qc.p, d_codes.p, d_code_meta.p};
 	}
-	void count_range_bytes() {
+	void count_range_bytes(bool report = true) { // report: into vss_last_range [3] too (not from an exact call)
 		const uint64_t bytes = (d_rg_theta.n + d_rg_m_dist.n + d_rg_radii.n + d_rg_q.n + d_rg_out_d.n + d_rg_counts.n + d_rg_cand_count.n + d_rg_m_query.n +
 		                        d_rg_tile_index.n) * 4 +
 		                       (d_rg_cand.n + d_rg_m_rowid.n + d_rg_out_ids.n + d_rg_stats.n + d_rg_offsets.n) * 8 +
 		                       (d_rg_q_hi.n + d_rg_q_lo.n) * sizeof(uint4) + d_rg_q_codes.n * 4 +
-		                       d_rg_q_meta.n * sizeof(RowCodeMeta) + d_rg_qc.n * sizeof(RangeCodesQuery);
+		                       d_rg_q_meta.n * sizeof(RowCodeMeta) + d_rg_qc.n * sizeof(RangeCodesQuery) + d_xc_qc.n * sizeof(ExactCodesQuery);
 		exact_range_bytes.store(bytes, std::memory_order_relaxed);
-		last_range[3] = bytes;
+		if (report)
+			last_range[3] = bytes;
 	}
 	int range_device(const float *d_queries, uint64_t nq, const float *d_radii, uint64_t cells, uint64_t *d_offsets,
 	                 int64_t *d_rowids, float *d_dist, uint64_t *d_total) {
@@ -4140,7 +4254,7 @@ const OptionRule OPTION_RULES[] = {
      [](vss_index *h, int64_t v) {
 	     h->search_prescore = (uint32_t)v;
 	     if (!h->codes_held())
-		     h->free_codes(); // 0: no codes are held (unless range.codes_i8 holds them), every job's bound is +inf — the path
+		     h->free_codes(); // 0: no codes are held (unless range.codes_i8 or exact.codes_i8 holds them), every job's bound is +inf — the path
 		                      // without the filter, exactly
 	     else if (h->stream)
 		     h->refresh_codes();
@@ -4163,6 +4277,17 @@ const OptionRule OPTION_RULES[] = {
      },
      "range search proposes rows by the integer dot product of 8-bit row codes on the int8 matrix pipe, under the codes' own "
      "residual bound (dimensions whose padding is a multiple of 32; before range.split_bf16 where both are set)"},
+    {"exact.codes_i8", 0, 1,
+     [](vss_index *h, int64_t v) {
+	     h->exact_codes_i8 = v != 0;
+	     if (!h->codes_held())
+		     h->free_codes();
+	     else if (h->stream)
+		     h->refresh_codes(); // (exclusive lock, as range.codes_i8)
+     },
+     "exact search answers by bounds from the integer dot product of 8-bit row codes on the int8 matrix pipe: the k-th smallest "
+     "upper bound per query, then the metric over the rows whose lower bound is not above it (dimensions whose padding is a "
+     "multiple of 32; before exact.split_bf16 where both are set; calls whose candidates do not fit run the other tiles)"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {

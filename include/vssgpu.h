@@ -135,6 +135,11 @@ int vss_set_build_reorder(vss_index *index, int on);
  *                                where both options are set this one runs); the index then holds row codes (one byte per
  *                                padded float and 16 bytes per row, counted by vss_memory_usage) whatever search.prescore
  *                                says; answers do not depend on it, the number of proposed pairs may
+ *   exact.codes_i8 (0/1)         vss_search_exact_batch* answers BY BOUNDS from the same codes on the int8 matrix pipe: the k-th
+ *                                smallest upper bound of a query's distances, then the metric over the rows whose lower bound is
+ *                                not above it (default 0; same dimensions, same row codes held as range.codes_i8; goes before
+ *                                exact.split_bf16 where both are set; a call whose candidates do not fit is answered by the
+ *                                other tiles); answers do not depend on it; vss_last_exact_scores reports it
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -582,7 +587,17 @@ int vss_search_batch_end(vss_index *index, int context);
  * Rows are selected by MFMA ranking scores and the survivors re-scored; a query for which the engine cannot prove that this
  * selection lost no row (csrc/exact_certificate.h) is answered again by brute force in the metric itself.
  * Limits: k <= 4088; a live row whose distance is not below 3e38 (an f32 sum that overflowed: outside "finite inputs" in
- * effect) is never returned; rows wider than 10 240 dimensions cannot be answered again and fail the call (VSS_ERROR). */
+ * effect) is never returned; rows wider than 10 240 dimensions cannot be answered again and fail the call (VSS_ERROR).
+ * With vss_set_option "exact.codes_i8" = 1, a dimension whose padding is a multiple of 32 and valid codes of every live row, the
+ * call is answered by bounds instead (csrc/exact_codes_bound.h, csrc/exact_codes_kernels.h): pass A gives every query tau_q, the
+ * k-th smallest UPPER bound of its distances from the integer dot products of the 8-bit codes (no row of the top-k is farther);
+ * pass B is the range search of kind 2 under the radii tau_q, which re-scores in the metric every row whose LOWER bound is not
+ * above tau_q; the k smallest (distance, slot) of those matches are the answer — the same cells, nothing certified or redone.
+ * The matches have max(1024, 4 k) cells per query in all; if they do not fit (data the codes cannot separate) the call is
+ * answered from the start by the kind it would have used without the option, at the cost of the int8 pass.  Extra scratch,
+ * counted with the range search's by vss_memory_usage: the coded query block (one byte per padded query float, 32 bytes per
+ * query), the range search's scratch for that capacity (28 bytes per match cell, its candidate buffer of at most 64 MiB) and
+ * 40 bytes per query. */
 int vss_search_exact_batch(vss_index *index, const float *queries, uint64_t n_queries, uint64_t k,
                            int64_t *out_rowids, float *out_distances, uint32_t *out_counts);
 int vss_search_exact_batch_device(vss_index *index, const float *d_queries, uint64_t n_queries, uint64_t k,
@@ -596,7 +611,11 @@ uint64_t vss_last_exact_fallbacks(vss_index *index);
  * of 32: q.x ~ qh.xh + qh.xl + ql.xh on v_mfma_f32_32x32x16_bf16, csrc/exact_split_kernels.h); [1] = its score launches;
  * [2] = the bit pattern of the largest finite error bound E (a double, csrc/exact_certificate.h) the re-rank certified with,
  * 0 if none was finite; [3] = 0.  Answers never depend on the option — the certificate carries the bound of the kind that ran,
- * and what it cannot prove is redone in the metric — vss_last_exact_fallbacks may. */
+ * and what it cannot prove is redone in the metric — vss_last_exact_fallbacks may.
+ * Kind 2 = by bounds from the int8 row codes (vss_set_option "exact.codes_i8" = 1, v_mfma_i32_32x32x32_i8): [1] = the bound-tile
+ * launches of pass A, [2] = the bit pattern of the largest finite per-query slack of the codes (as vss_last_range_scores [2]
+ * under its kind 2), [3] = the (query, row) pairs re-scored in the metric; vss_last_exact_fallbacks is 0.  A call under that
+ * option that fell back reports the kind that answered it. */
 int vss_last_exact_scores(vss_index *index, uint64_t *out4);
 /* Exact RANGE search — the predicate of a similarity join or a threshold filter (`array_cosine_distance(a.v, items.v) < 0.2`;
  * INTEGRATION.md §5 maps SQL thresholds to radii): query q matches every live row whose distance d satisfies d <= radii[q], a
