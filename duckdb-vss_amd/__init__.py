@@ -29,16 +29,16 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 TRANSLATION_UNITS = ["vss_engine.hip", "vss_exchange.hip", "kernels_l2sq.hip", "kernels_cosine.hip", "kernels_ip.hip",
                      "kernels_boxes_l2sq.hip", "kernels_boxes_cosine.hip", "kernels_boxes_ip.hip",
                      "kernels_setboxes_l2sq.hip", "kernels_setboxes_cosine.hip", "kernels_setboxes_ip.hip", "exact_split.hip",
-                     "exact_range.hip", "exact_range_codes.hip", "exact_codes.hip"]
+                     "exact_range.hip", "exact_range_codes.hip", "exact_codes.hip", "exact_filtered_codes.hip"]
 # flags of single translation units: the split-bf16 score tile and the range search are built without packed f32 arithmetic
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 TU_FLAGS = {"exact_split.hip": NO_PACKED_F32, "exact_range.hip": NO_PACKED_F32, "exact_range_codes.hip": NO_PACKED_F32,
-            "exact_codes.hip": NO_PACKED_F32}
+            "exact_codes.hip": NO_PACKED_F32, "exact_filtered_codes.hip": NO_PACKED_F32}
 RANGE_ROW_CHUNK = 8192  # rows per launch of the range search's candidate tile (csrc/exact_range.h)
 
 
 def build_library(force=False, extra_flags=(), out=None):
-    """hipcc cross-compiles the engine for gfx950 (works without a GPU): fifteen translation units in parallel, then a
+    """hipcc cross-compiles the engine for gfx950 (works without a GPU): sixteen translation units in parallel, then a
     shared link.  Objects live in build/ (git-ignored)."""
     out = out or os.path.join(HERE, "libvssgpu.so")
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
@@ -102,6 +102,7 @@ SIGNATURES = {
     "vss_search_exact_batch_filtered_groups": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "vss_search_exact_batch_filtered_groups_device": (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "vss_last_exact_filtered": (_int, [_vp, _vp]),
+    "vss_last_exact_filtered_scores": (_int, [_vp, _vp]),
     "vss_search_batch_filtered_groups_auto": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp,
                                                      _vp]),
     "vss_search_batch_filtered_groups_auto_device": (_int, [_vp, _vp, _u64, _u64, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _vp,
@@ -467,6 +468,15 @@ class GpuIndex:
         out = np.zeros(4, dtype=np.uint64)
         self._check(self.lib.vss_last_exact_filtered(self.h, _p(out)))
         return out
+
+    def last_exact_filtered_scores(self):
+        """[kind that answered the exact part of the last filtered call (0 = the metric kernel, 2 = bounds from the int8 row
+        codes gathered through the lists: set_option("exact.filtered_codes_i8", 1)), bound-tile launches of its
+        first pass, the largest finite per-query slack of the codes as a float, (query, row) pairs re-scored in the metric];
+        [1:] are 0 under kind 0."""
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.vss_last_exact_filtered_scores(self.h, _p(out)))
+        return [int(out[0]), int(out[1]), float(out[2:3].view(np.float64)[0]), int(out[3])]
 
     def search_batch_filtered_groups_auto(self, Q, k, ef, bitmaps, n_bits, group_of=None, route_c=0):
         """vss_search_batch_filtered_groups_auto: every group answered by the cheaper of search_batch_filtered_groups and

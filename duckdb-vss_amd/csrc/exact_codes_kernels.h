@@ -45,13 +45,16 @@ struct ExactCodesTopkArgs {
 	int64_t *out_keys; // n_queries x k, as k_exact_rerank writes them
 	float *out_d;
 	uint32_t *out_count;
+	const uint32_t *query_map = nullptr; // workgroup b answers query query_map[b] from segment query_map[b] (NULL = identity)
 };
 
 hipError_t launch_exact_prepare_codes(const ExactCodesPrepareArgs &a, hipStream_t stream);
 // one bound launch over e.row_begin .. e.row_end: `grid` persistent workgroups.  ExactArgs: queries, vectors, row_norm2 and
 // query_norm2 are not read.  Needs V % 8 == 0.
 hipError_t launch_exact_bounds_i8(const ExactArgs &e, const ExactCodesView &c, uint32_t grid, hipStream_t stream);
-hipError_t launch_exact_codes_radii(const float *best_s, uint32_t k, uint32_t n_queries, float *radii, hipStream_t stream);
+// query_map: row t of best_s is the running list of query query_map[t] (the filtered search's group order); NULL = identity
+hipError_t launch_exact_codes_radii(const float *best_s, uint32_t k, uint32_t n_queries, float *radii, hipStream_t stream,
+                                    const uint32_t *query_map = nullptr);
 hipError_t launch_exact_codes_topk(const ExactCodesTopkArgs &a, uint32_t n_queries, hipStream_t stream);
 
 #ifdef VSS_EXACT_CODES_TU
@@ -342,12 +345,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // tau_q -> the radius of pass B.  A k-th best that was never written (the memset's 3.39e38) or is +inf: fewer than k rows had a
 // finite bound, and every live row has to be looked at
-__global__ __launch_bounds__(256) void k_exact_codes_radii(const float *best_s, uint32_t k, uint32_t n_queries, float *radii) {
+__global__ __launch_bounds__(256) void k_exact_codes_radii(const float *best_s, uint32_t k, uint32_t n_queries, float *radii,
+                                                           const uint32_t *query_map) {
 	const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
 	if (q >= n_queries)
 		return;
 	const float tau = best_s[(size_t)q * k + k - 1];
-	radii[q] = tau < 3.0e38f ? tau : __builtin_inff();
+	radii[query_map ? query_map[q] : q] = tau < 3.0e38f ? tau : __builtin_inff();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -362,7 +366,7 @@ constexpr uint32_t XC_TOPK_LDS = 1024;
 __global__ __launch_bounds__(256) void k_exact_codes_topk(ExactCodesTopkArgs a) {
 	__shared__ float sd[XC_TOPK_LDS];
 	__shared__ uint32_t ss[XC_TOPK_LDS];
-	const uint32_t q = blockIdx.x, tid = threadIdx.x;
+	const uint32_t q = a.query_map ? a.query_map[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
 	const unsigned long long lo = a.offsets[q], n = a.offsets[q + 1] - lo;
 	const uint32_t count = n < a.k ? (uint32_t)n : a.k;
 	const int64_t *slots = a.slots + lo;
@@ -411,8 +415,9 @@ hipError_t launch_exact_bounds_i8(const ExactArgs &e, const ExactCodesView &c, u
 	hipLaunchKernelGGL(k_exact_bounds_i8, dim3(grid), dim3(256), XC_LDS_BYTES, stream, e, c);
 	return hipGetLastError();
 }
-hipError_t launch_exact_codes_radii(const float *best_s, uint32_t k, uint32_t n_queries, float *radii, hipStream_t stream) {
-	hipLaunchKernelGGL(k_exact_codes_radii, dim3((n_queries + 255u) / 256u), dim3(256), 0, stream, best_s, k, n_queries, radii);
+hipError_t launch_exact_codes_radii(const float *best_s, uint32_t k, uint32_t n_queries, float *radii, hipStream_t stream,
+                                    const uint32_t *query_map) {
+	hipLaunchKernelGGL(k_exact_codes_radii, dim3((n_queries + 255u) / 256u), dim3(256), 0, stream, best_s, k, n_queries, radii, query_map);
 	return hipGetLastError();
 }
 hipError_t launch_exact_codes_topk(const ExactCodesTopkArgs &a, uint32_t n_queries, hipStream_t stream) {

@@ -30,6 +30,7 @@
 #include "label_filter.h"
 #include "exact_filtered_kernels.h"
 #include "exact_range_kernels.h"
+#include "exact_filtered_codes_kernels.h"
 #include "filter_route_kernels.h"
 #include "row_codes.h"
 
@@ -739,6 +740,9 @@ struct vss_index {
 	// int8 bound tiles give every query the k-th smallest UPPER bound of its distances, the range search of kind 2 under that
 	// radius re-scores the rows whose LOWER bound is not above it, and the top k of those matches is the answer.  Off by default.
 	bool exact_codes_i8 = false;
+	// exact.filtered_codes_i8 (exact_filtered_codes_kernels.h): the same answer by bounds for the exact search under per-query
+	// predicates — every call that ends in exact_filtered_score — with both passes gathered through the lists.  Off by default.
+	bool exact_filtered_codes_i8 = false;
 	// search.prescore_descent, VSS_SEARCH_PRESCORE_DESCENT: the greedy descent's jobs carry closest_dist as their bound in the
 	// launches that filter at all (1, the default); 0: they carry +inf, as every job of the descent did before
 	bool search_prescore_descent = true;
@@ -756,9 +760,9 @@ struct vss_index {
 	}
 	// the second reason to hold codes: range.codes_i8 (below), at every dimension whose padding is a multiple of 32.  The graph
 	// search's own eligibility stays codes_wanted(): its kernels are instantiated for those four row shapes only.
-	// The third: exact.codes_i8 (exact_codes_kernels.h), at the same dimensions.
+	// The third: exact.codes_i8 (exact_codes_kernels.h) and exact.filtered_codes_i8, at the same dimensions.
 	bool codes_held() const {
-		return codes_wanted() || ((range_codes_i8 || exact_codes_i8) && V % 8 == 0);
+		return codes_wanted() || ((range_codes_i8 || exact_codes_i8 || exact_filtered_codes_i8) && V % 8 == 0);
 	}
 	void free_codes() {
 		d_codes.free(), d_code_meta.free();
@@ -849,6 +853,7 @@ struct vss_index {
 	DevBuf<uint32_t> d_xf_lists, d_xf_counts, d_xf_tables;
 	uint64_t exact_filter_budget = EXACT_FILTER_LIST_ENTRIES;
 	uint64_t last_exact_filtered[4] = {0, 0, 0, 0}; // vss_last_exact_filtered
+	uint64_t last_exact_filtered_scores[4] = {0, 0, 0, 0}; // vss_last_exact_filtered_scores
 	uint64_t last_filter_route[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // vss_last_filter_route (under exact_mu too)
 	std::atomic<uint64_t> exact_filter_bytes {0};   // of the three buffers (vss_memory_usage, read without a lock)
 	// vss_search_range_batch (exact_range_kernels.h), under exact_mu like the rest: thresholds, counts and cursors per query, the
@@ -2993,24 +2998,8 @@ struct vss_index {
 		if (!d_xf_lists.try_grow(std::max<uint64_t>(entries_max, 1)) || !d_rg_tile_index.try_grow(std::max<uint64_t>(n_index, 1)))
 			return fail("range search under label boxes: no device memory for lists of %llu rows", (unsigned long long)entries_max);
 		count_exact_filter_scratch();
-		const uint64_t stride = (uint64_t)V * 4;
 		const uint64_t match_cells = std::min(cells, plan.distances); // (no query can match more rows than its list holds)
-		d_row_norm2.ensure(capacity, 0, stream);
-		d_norm_ext.ensure(2, 0, stream);
-		d_qpad.ensure(nq * stride, 0, stream);
-		d_q_norm2.ensure(nq, 0, stream);
-		d_rg_theta.ensure(nq, 0, stream);
-		d_rg_counts.ensure(2 * nq, 0, stream); // counts, then the scatter's cursors
-		d_rg_stats.ensure(4, 0, stream);
-		d_rg_cand_count.ensure(std::max<uint64_t>(rp.launches.size(), 1), 0, stream);
-		// every pair of the plan's largest launch fits (at most RANGE_QUERY_BLOCK x RANGE_ROW_CHUNK): no overflow path
-		d_rg_cand.ensure(std::max<uint64_t>(rp.largest, 1), 0, stream);
-		if (match_cells) {
-			d_rg_m_query.ensure(match_cells, 0, stream);
-			d_rg_m_rowid.ensure(match_cells, 0, stream);
-			d_rg_m_dist.ensure(match_cells, 0, stream);
-		}
-		count_range_bytes();
+		range_filtered_scratch(nq, rp, match_cells, true);
 		last_range_filtered[0] = plan.listed, last_range_filtered[1] = rp.pairs;
 		last_range_filtered[3] = (d_xf_lists.n + d_xf_counts.n + d_xf_tables.n + d_rg_tile_index.n) * 4;
 		{
@@ -3027,14 +3016,60 @@ struct vss_index {
 				HIP_TRY(hipMemcpyAsync(d_rg_tile_index.p, index.data(), n_index * 4, hipMemcpyHostToDevice, stream));
 			HIP_TRY(hipStreamSynchronize(stream)); // (pageable memory: the copies have left it before it goes)
 		}
-		refresh_row_norms(rows);
+		range_filtered_queries(d_queries, q_stride, nq);
+		const int score_kind = range_score_kind(nq);
+		if (const int rc = range_filtered_pairs(plan, rp, exact_filter_list_args(g, nu, t), g, nq, d_radii, match_cells, score_kind, false,
+		                                        UINT32_MAX, d_offsets, d_rowids, d_dist, d_total, last_range_filtered[2]))
+			return rc;
+		last_range_scores[0] = (uint64_t)score_kind, last_range_scores[1] = last_range_filtered[2];
+		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&last_range_scores[2], d_rg_stats.p + 3, 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		return VSS_OK;
+	}
+	// the per-call scratch of the range search over the launches of a plan: nq queries, match_cells cells of matches
+	void range_filtered_scratch(uint64_t nq, const RangeFilterPlan &rp, uint64_t match_cells, bool report_bytes) {
+		const uint64_t stride = (uint64_t)V * 4;
+		d_row_norm2.ensure(capacity, 0, stream);
+		d_norm_ext.ensure(2, 0, stream);
+		d_qpad.ensure(nq * stride, 0, stream);
+		d_q_norm2.ensure(nq, 0, stream);
+		d_rg_theta.ensure(nq, 0, stream);
+		d_rg_counts.ensure(2 * nq, 0, stream); // counts, then the scatter's cursors
+		d_rg_stats.ensure(4, 0, stream);
+		d_rg_cand_count.ensure(std::max<uint64_t>(rp.launches.size(), 1), 0, stream);
+		// every pair of the plan's largest launch fits (at most RANGE_QUERY_BLOCK x RANGE_ROW_CHUNK): no overflow path
+		d_rg_cand.ensure(std::max<uint64_t>(rp.largest, 1), 0, stream);
+		if (match_cells) {
+			d_rg_m_query.ensure(match_cells, 0, stream);
+			d_rg_m_rowid.ensure(match_cells, 0, stream);
+			d_rg_m_dist.ensure(match_cells, 0, stream);
+		}
+		count_range_bytes(report_bytes);
+	}
+	// fresh row norms; the nq queries padded into d_qpad, their wave-order norms in d_q_norm2
+	void range_filtered_queries(const float *d_queries, uint32_t q_stride, uint64_t nq) {
+		const uint64_t stride = (uint64_t)V * 4;
+		refresh_row_norms(count);
 		HIP_TRY(hipMemsetAsync(d_qpad.p, 0, nq * stride * 4, stream));
 		HIP_TRY(hipMemcpy2DAsync(d_qpad.p, stride * 4, d_queries, (size_t)q_stride * 4, dim * 4, nq, hipMemcpyDeviceToDevice, stream));
 		hipLaunchKernelGGL(k_row_norms, dim3(256), dim3(256), 0, stream, reinterpret_cast<const float4 *>(d_qpad.p), V, G, logG,
 		                   (uint32_t)nq, d_q_norm2.p);
+	}
+	// The range search over lists proper, for range_filtered_launch and for the filtered exact search by bounds
+	// (exact_filtered_bounds): prepare, per launch of `rp` the gathered candidate tile in its two shapes and the re-score, layout.
+	// range_filtered_scratch and range_filtered_queries have run over the nq queries, the plan's tables are in d_xf_tables with
+	// rp.tiles behind at_tiles, rp.small then rp.tall lead d_rg_tile_index, and for kind 2 the queries are coded
+	// (codes_tiles_ready).  l: the listing arguments of the plan's groups; listed_pass: the pass whose lists are in d_xf_lists
+	// already, or UINT32_MAX.  slots: the cells of d_rowids take the matches' slots.  Touches no diagnostics of the public range
+	// calls but `launches`; does not wait.
+	int range_filtered_pairs(const ExactFilterPlan &plan, const RangeFilterPlan &rp, FilterListArgs l, const GroupedRows &g, uint64_t nq,
+	                         const float *d_radii, uint64_t match_cells, int score_kind, bool slots, uint32_t listed_pass, uint64_t *d_offsets,
+	                         int64_t *d_rowids, float *d_dist, uint64_t *d_total, uint64_t &launches) {
+		const uint64_t stride = (uint64_t)V * 4;
+		const ExactFilterTables t(plan.groups.size(), plan.order.size(), g.group_cells());
 		HIP_TRY(hipMemsetAsync(d_rg_stats.p, 0, 4 * 8, stream));
 		HIP_TRY(hipMemsetAsync(d_rg_cand_count.p, 0, std::max<uint64_t>(rp.launches.size(), 1) * 4, stream));
-		const int score_kind = range_score_kind(nq);
 		RangeStats *stats = reinterpret_cast<RangeStats *>(d_rg_stats.p);
 		RangePrepareArgs p;
 		p.metric = metric, p.score_kind = score_kind, p.n = (uint32_t)stride, p.n_queries = (uint32_t)nq;
@@ -3042,7 +3077,6 @@ struct vss_index {
 		p.theta = d_rg_theta.p, p.counts = d_rg_counts.p, p.cursors = d_rg_counts.p + nq, p.stats = stats;
 		HIP_TRY(score_kind == 2 ? range_prepare_codes(p) : launch_range_prepare(p, stream));
 		const RangeCodesView cv = range_codes_view(score_kind);
-		FilterListArgs l = exact_filter_list_args(g, nu, t);
 		l.lists = d_xf_lists.p;
 		RangeListTileArgs c;
 		c.queries = reinterpret_cast<const float4 *>(d_qpad.p), c.vectors = reinterpret_cast<const float4 *>(d_vectors.p);
@@ -3052,13 +3086,12 @@ struct vss_index {
 		RangeRescoreArgs r;
 		r.sp = view().sp, r.keys = d_keys.p, r.queries = c.queries, r.query_norm2 = d_q_norm2.p, r.radii = d_radii;
 		r.cand = d_rg_cand.p, r.counts = d_rg_counts.p, r.stats = stats, r.capacity = match_cells;
-		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p;
+		r.m_query = d_rg_m_query.p, r.m_rowid = d_rg_m_rowid.p, r.m_dist = d_rg_m_dist.p, r.slots = slots;
 		auto lists_tile = [&](bool small) { // one shape of the gathered tile, of the call's score kind
 			return score_kind == 2   ? launch_range_candidates_lists_i8(c, small, cv, stream)
 			       : score_kind == 1 ? launch_range_candidates_lists_bf16x3(c, small, d_rg_q_hi.p, d_rg_q_lo.p, stream)
 			                         : launch_range_candidates_lists(c, small, stream);
 		};
-		uint32_t listed_pass = UINT32_MAX;
 		for (size_t i = 0; i != rp.launches.size(); ++i) {
 			const RangeFilterLaunch &rl = rp.launches[i];
 			if (rl.pass != listed_pass) { // (stream order: the previous pass's launches have read their lists)
@@ -3070,22 +3103,18 @@ struct vss_index {
 			c.cand_count = d_rg_cand_count.p + i, r.cand_count = c.cand_count; // one word and one re-score for both shapes
 			c.tile_index = d_rg_tile_index.p + rl.small_begin, c.n_tiles = rl.small_end - rl.small_begin;
 			HIP_TRY(lists_tile(true));
-			last_range_filtered[2] += c.n_tiles != 0;
+			launches += c.n_tiles != 0;
 			c.tile_index = d_rg_tile_index.p + rp.small.size() + rl.tall_begin, c.n_tiles = rl.tall_end - rl.tall_begin;
 			HIP_TRY(lists_tile(false));
-			last_range_filtered[2] += c.n_tiles != 0;
+			launches += c.n_tiles != 0;
 			HIP_TRY(launch_range_rescore(r, n_cus, stream));
 		}
-		last_range_scores[0] = (uint64_t)score_kind, last_range_scores[1] = last_range_filtered[2];
 		RangeLayoutArgs y;
 		y.n_queries = (uint32_t)nq, y.counts = d_rg_counts.p, y.cursors = d_rg_counts.p + nq, y.stats = stats, y.capacity = match_cells;
 		y.offsets = reinterpret_cast<unsigned long long *>(d_offsets), y.total = reinterpret_cast<unsigned long long *>(d_total);
 		y.m_query = d_rg_m_query.p, y.m_rowid = d_rg_m_rowid.p, y.m_dist = d_rg_m_dist.p;
 		y.out_rowids = d_rowids, y.out_dist = d_dist;
 		HIP_TRY(launch_range_layout(y, n_cus, stream));
-		HIP_TRY(hipMemcpyAsync(last_range, d_rg_stats.p, 3 * 8, hipMemcpyDeviceToHost, stream));
-		HIP_TRY(hipMemcpyAsync(&last_range_scores[2], d_rg_stats.p + 3, 8, hipMemcpyDeviceToHost, stream));
-		HIP_TRY(hipStreamSynchronize(stream));
 		return VSS_OK;
 	}
 	// the two forms: `boxes` is nq x 4m words (label_box64_rows, HOST); the groups are its distinct raw rows
@@ -3187,6 +3216,7 @@ struct vss_index {
 		if (!qt)
 			return fail("exact filtered search: a row of %llu dimensions does not fit the scoring kernel's LDS", (unsigned long long)dim);
 		const uint64_t KP = k + 8, CH = 32768, rows = count, nq = plan.order.size(), nu = plan.groups.size();
+		std::fill(last_exact_filtered_scores, last_exact_filtered_scores + 4, 0);
 		if (!nq)
 			return VSS_OK;
 		const ExactFilterTables t(nu, nq, g.group_cells());
@@ -3194,8 +3224,6 @@ struct vss_index {
 		if (!d_xf_tables.try_grow(t.words) || !d_scores.try_grow(nq * CH) || !d_best_s.try_grow(nq * KP) || !d_best_i.try_grow(nq * KP))
 			return fail("exact filtered search: no device memory for %llu queries over %llu groups in use", (unsigned long long)nq,
 			            (unsigned long long)nu);
-		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, nq * KP * 4, stream)); // 0x7F7F7F7F = 3.39e38 (acts as +inf)
-		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, nq * KP * 4, stream));
 		FilterListArgs l = exact_filter_list_args(g, nu, t);
 		std::vector<uint32_t> values;
 		if (taken_counts) {
@@ -3203,6 +3231,17 @@ struct vss_index {
 			if (nu) // (plan.groups and `values` outlive the copy: this step ends synchronised)
 				upload_used_groups(plan, g, values);
 		}
+		// exact.filtered_codes_i8: the call is answered by bounds where the int8 tiles' condition holds; a call whose matches do
+		// not fit is answered from the start by the metric kernel below
+		if (exact_filtered_codes_i8 && V % 8 == 0 && rows) {
+			bool answered = false;
+			if (const int rc = exact_filtered_bounds(plan, lengths, l, b, g, out, answered))
+				return rc;
+			if (answered)
+				return VSS_OK;
+		}
+		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, nq * KP * 4, stream)); // 0x7F7F7F7F = 3.39e38 (acts as +inf)
+		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, nq * KP * 4, stream));
 		exact_filter_pack(lengths.data(), std::max<uint64_t>(exact_filter_budget, rows), qt, plan);
 		uint64_t entries_max = 0;
 		for (const ExactFilterPass &pass : plan.passes)
@@ -3293,6 +3332,148 @@ struct vss_index {
 			std::lock_guard<std::mutex> lk(stats_mu);
 			timing[0] = ms;
 		}
+		return VSS_OK;
+	}
+
+	// The filtered exact search by bounds (exact.filtered_codes_i8; the caller is exact_filtered_score: its tables are grown, the
+	// groups' cells and scanned block counts are where `l` names them).  One plan serves both passes: the lists packed with the
+	// range search's tall tile, cut into its launches (range_filtered_plan.h).
+	//   pass A  per pass and 32 768-position chunk the gathered int8 BOUND tile in its two shapes, then k_exact_select_lists with
+	//           K' = k: best_s[t][k - 1] = tau of position t, the k-th smallest upper bound over its list
+	//   pass B  the gathered int8 range search under the radii tau (range_filtered_pairs), matches as (distance, slot), into
+	//           max(1024, 4 k) cells per answered query; k_exact_codes_topk writes the k smallest of each query of plan.order
+	// Queries are addressed by their index in the batch throughout, so all b.nq of them are padded and coded; only the cells of
+	// plan.order's queries are written.  answered = false (and nothing written): no valid codes, or the matches do not fit.
+	int exact_filtered_bounds(ExactFilterPlan &plan, const std::vector<uint32_t> &lengths, FilterListArgs l, const DeviceBatch &b,
+	                          const GroupedRows &g, const DeviceAnswers &out, bool &answered) {
+		const uint64_t k = b.k, CH = 32768, rows = count, np = plan.order.size(), nu = plan.groups.size(), nq = b.nq;
+		exact_filter_pack(lengths.data(), std::max<uint64_t>(exact_filter_budget, rows), RANGE_LIST_QT, plan);
+		RangeFilterPlan rp;
+		range_filter_plan(plan, rp);
+		const uint64_t match_cells = std::min(np * std::max<uint64_t>(1024, 4 * k), plan.distances);
+		// the tile-index runs: pass B's launches (rp.small, rp.tall), then per pass of the plan its small and its tall tiles
+		struct Run {
+			uint32_t small_begin, n_small, tall_begin, n_tall;
+		};
+		std::vector<uint32_t> index(rp.small), tall;
+		index.insert(index.end(), rp.tall.begin(), rp.tall.end());
+		std::vector<Run> runs(plan.passes.size());
+		uint64_t entries_max = 0;
+		for (size_t ps = 0, ti = 0; ps != plan.passes.size(); ++ps) { // (the cut tiles are in order of first_query, as the passes are)
+			Run &run = runs[ps];
+			run.small_begin = (uint32_t)index.size();
+			tall.clear();
+			for (; ti != rp.tiles.size() && rp.tiles[ti].first_query < plan.passes[ps].query_end; ++ti)
+				(rp.tiles[ti].n_queries <= RANGE_LIST_SMALL_QUERIES ? index : tall).push_back((uint32_t)ti);
+			run.n_small = (uint32_t)index.size() - run.small_begin, run.tall_begin = (uint32_t)index.size(), run.n_tall = (uint32_t)tall.size();
+			index.insert(index.end(), tall.begin(), tall.end());
+			entries_max = std::max(entries_max, plan.passes[ps].entries);
+		}
+		if (!d_xf_lists.try_grow(std::max<uint64_t>(entries_max, 1)) || !d_rg_tile_index.try_grow(std::max<uint64_t>(index.size(), 1)))
+			return fail("exact filtered search: no device memory for lists of %llu rows", (unsigned long long)entries_max);
+		count_exact_filter_scratch();
+		range_filtered_scratch(nq, rp, match_cells, false);
+		d_rg_radii.ensure(nq, 0, stream);
+		d_rg_offsets.ensure(nq + 2, 0, stream); // offsets, then the total
+		d_rg_out_ids.ensure(std::max<uint64_t>(match_cells, 1), 0, stream);
+		d_rg_out_d.ensure(std::max<uint64_t>(match_cells, 1), 0, stream);
+		d_xc_qc.ensure(nq, 0, stream);
+		d_e_max.ensure(1, 0, stream);
+		range_filtered_queries(b.d_queries, b.q_stride, nq);
+		if (!codes_tiles_ready(nq, false)) // (counts the range search's bytes)
+			return VSS_OK;
+		last_exact_filtered[0] = plan.listed, last_exact_filtered[1] = plan.distances, last_exact_filtered[2] = plan.passes.size();
+		const ExactFilterTables t(nu, np, g.group_cells());
+		{
+			std::vector<uint32_t> up(t.at_tiles - t.at_base);
+			std::copy(plan.list_base.begin(), plan.list_base.begin() + nu, up.begin());
+			std::copy(plan.order.begin(), plan.order.end(), up.begin() + (t.at_order - t.at_base));
+			std::copy(plan.query_offset.begin(), plan.query_offset.end(), up.begin() + (t.at_offset - t.at_base));
+			std::copy(plan.query_length.begin(), plan.query_length.end(), up.begin() + (t.at_length - t.at_base));
+			HIP_TRY(hipMemcpyAsync(d_xf_tables.p + t.at_base, up.data(), up.size() * 4, hipMemcpyHostToDevice, stream));
+			if (!rp.tiles.empty()) // (at most one per known query: they fit the 5 np words behind at_tiles)
+				HIP_TRY(hipMemcpyAsync(d_xf_tables.p + t.at_tiles, rp.tiles.data(), rp.tiles.size() * sizeof(ExactFilterTile),
+				                       hipMemcpyHostToDevice, stream));
+			if (!index.empty())
+				HIP_TRY(hipMemcpyAsync(d_rg_tile_index.p, index.data(), index.size() * 4, hipMemcpyHostToDevice, stream));
+			HIP_TRY(hipStreamSynchronize(stream)); // (pageable memory: the copies have left it before it goes)
+		}
+		// ---- pass A
+		HIP_TRY(hipMemsetAsync(d_best_s.p, 0x7F, np * k * 4, stream)); // 0x7F7F7F7F = 3.39e38 (acts as +inf)
+		HIP_TRY(hipMemsetAsync(d_best_i.p, 0xFF, np * k * 4, stream));
+		HIP_TRY(hipMemsetAsync(d_e_max.p, 0, 8, stream));
+		ExactCodesPrepareArgs pa;
+		pa.metric = metric, pa.n = V * 4, pa.n_queries = (uint32_t)nq, pa.q_meta = d_rg_q_meta.p, pa.norm_ext = d_norm_ext.p;
+		pa.qc = d_xc_qc.p, pa.e_max = reinterpret_cast<unsigned long long *>(d_e_max.p);
+		HIP_TRY(launch_exact_prepare_codes(pa, stream));
+		const ExactCodesView cv {d_rg_q_codes.p, d_xc_qc.p, d_codes.p, d_code_meta.p};
+		l.lists = d_xf_lists.p;
+		FilteredBoundArgs m;
+		m.order = d_xf_tables.p + t.at_order, m.lists = d_xf_lists.p;
+		m.tiles = reinterpret_cast<const ExactFilterTile *>(d_xf_tables.p + t.at_tiles);
+		m.V = V, m.chunk_stride = (uint32_t)CH, m.metric = metric, m.scores = d_scores.p;
+		SelectListsArgs s;
+		s.scores = d_scores.p, s.chunk_stride = (uint32_t)CH, s.KP = (uint32_t)k;
+		s.offset = d_xf_tables.p + t.at_offset, s.length = d_xf_tables.p + t.at_length, s.lists = d_xf_lists.p;
+		s.best_s = d_best_s.p, s.best_i = d_best_i.p;
+		uint32_t listed_pass = UINT32_MAX;
+		uint64_t launches = 0;
+		for (size_t ps = 0; ps != plan.passes.size(); ++ps) {
+			const ExactFilterPass &pass = plan.passes[ps];
+			const Run &run = runs[ps];
+			if (!(run.n_small + run.n_tall))
+				continue; // (none of its groups admits a row)
+			l.u_begin = pass.group_begin, l.u_end = pass.group_end;
+			g.launch_scatter(l, stream);
+			listed_pass = (uint32_t)ps;
+			s.query_begin = pass.query_begin;
+			for (uint64_t p0 = 0; p0 < pass.longest; p0 += CH) {
+				const uint64_t cols = std::min<uint64_t>(CH, pass.longest - p0);
+				m.pos_begin = s.pos_begin = (uint32_t)p0;
+				// one resident wave of workgroups (two per compute unit) over the shape's tiles; each strides over its tile's blocks
+				auto bound_tiles = [&](bool small, uint32_t begin, uint32_t n) {
+					if (!n)
+						return hipSuccess;
+					const uint64_t blocks = (cols + (small ? 255 : 127)) / (small ? 256 : 128);
+					m.tile_index = d_rg_tile_index.p + begin, m.n_tiles = n;
+					++launches;
+					return launch_exact_filtered_bounds_i8(m, small, cv, (uint32_t)std::min<uint64_t>(blocks, std::max<uint64_t>(1, (2ull * n_cus + n - 1) / n)),
+					                                       stream);
+				};
+				HIP_TRY(bound_tiles(true, run.small_begin, run.n_small));
+				HIP_TRY(bound_tiles(false, run.tall_begin, run.n_tall));
+				hipLaunchKernelGGL(k_exact_select_lists, dim3(pass.query_end - pass.query_begin), dim3(SEL_THREADS), 0, stream, s);
+			}
+		}
+		HIP_TRY(hipGetLastError());
+		// ---- radii: tau of position t belongs to query order[t]; a query in no tile keeps radius 0 and count 0
+		HIP_TRY(hipMemsetAsync(d_rg_radii.p, 0, nq * 4, stream));
+		HIP_TRY(launch_exact_codes_radii(d_best_s.p, (uint32_t)k, (uint32_t)np, d_rg_radii.p, stream, d_xf_tables.p + t.at_order));
+		// ---- pass B
+		uint64_t range_launches = 0;
+		if (const int rc = range_filtered_pairs(plan, rp, l, g, nq, d_rg_radii.p, match_cells, 2, true, listed_pass, d_rg_offsets.p, d_rg_out_ids.p,
+		                                        d_rg_out_d.p, d_rg_offsets.p + nq + 1, range_launches))
+			return rc;
+		uint64_t total = 0, rescored = 0, e_max = 0;
+		HIP_TRY(hipMemcpyAsync(&total, d_rg_offsets.p + nq + 1, 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipMemcpyAsync(&rescored, d_rg_stats.p, 8, hipMemcpyDeviceToHost, stream)); // RangeStats::candidates
+		HIP_TRY(hipMemcpyAsync(&e_max, d_e_max.p, 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		answered = total <= match_cells;
+		if (!answered)
+			return VSS_OK;
+		ExactCodesTopkArgs a;
+		a.k = (uint32_t)k, a.offsets = reinterpret_cast<const unsigned long long *>(d_rg_offsets.p), a.slots = d_rg_out_ids.p, a.dist = d_rg_out_d.p;
+		a.keys = d_keys.p, a.out_keys = out.keys, a.out_d = out.dist, a.out_count = out.count, a.query_map = d_xf_tables.p + t.at_order;
+		HIP_TRY(launch_exact_codes_topk(a, (uint32_t)np, stream));
+		HIP_TRY(hipEventRecord(ev[1], stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		last_exact_filtered_scores[0] = 2, last_exact_filtered_scores[1] = launches;
+		last_exact_filtered_scores[2] = e_max, last_exact_filtered_scores[3] = rescored;
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+		std::lock_guard<std::mutex> lk(stats_mu);
+		timing[0] = ms;
 		return VSS_OK;
 	}
 
@@ -4288,6 +4469,17 @@ const OptionRule OPTION_RULES[] = {
      "exact search answers by bounds from the integer dot product of 8-bit row codes on the int8 matrix pipe: the k-th smallest "
      "upper bound per query, then the metric over the rows whose lower bound is not above it (dimensions whose padding is a "
      "multiple of 32; before exact.split_bf16 where both are set; calls whose candidates do not fit run the other tiles)"},
+    {"exact.filtered_codes_i8", 0, 1,
+     [](vss_index *h, int64_t v) {
+	     h->exact_filtered_codes_i8 = v != 0;
+	     if (!h->codes_held())
+		     h->free_codes();
+	     else if (h->stream)
+		     h->refresh_codes(); // (exclusive lock, as range.codes_i8)
+     },
+     "exact search under per-query predicates answers by bounds from the 8-bit row codes, gathered through the predicates' lists "
+     "on the int8 matrix pipe (dimensions whose padding is a multiple of 32; calls whose candidates do not fit run the metric "
+     "kernel)"},
 };
 // validated assignment (the caller holds the index exclusively, or is vss_create); nullptr = done, else why not
 const char *set_option_checked(vss_index *h, const char *name, int64_t value) {
@@ -5346,6 +5538,14 @@ int vss_search_range_batch_by_label_box64_device(vss_index *h, const float *Q, u
 		label_box64_rows(lo_h.data(), hi_h.data(), nq, box.m, boxes);
 		return h->range_by_box64(false, Q, nq, radii, boxes.data(), box, capacity, out_offsets, out_rowids, out_d, out_total);
 	})
+}
+
+int vss_last_exact_filtered_scores(vss_index *h, uint64_t *out4) {
+	if (!h || !out4)
+		return VSS_ERROR;
+	std::lock_guard<std::mutex> lk(h->exact_mu);
+	std::memcpy(out4, h->last_exact_filtered_scores, sizeof h->last_exact_filtered_scores);
+	return VSS_OK;
 }
 
 int vss_last_range_filtered(vss_index *h, uint64_t *out4) {

@@ -140,6 +140,12 @@ int vss_set_build_reorder(vss_index *index, int on);
  *                                not above it (default 0; same dimensions, same row codes held as range.codes_i8; goes before
  *                                exact.split_bf16 where both are set; a call whose candidates do not fit is answered by the
  *                                other tiles); answers do not depend on it; vss_last_exact_scores reports it
+ *   exact.filtered_codes_i8 (0/1)  the exact search under per-query predicates — vss_search_exact_batch_filtered_groups*, the
+ *                                `exact` mode of the vss_search_batch_by_label* calls and the exact-routed groups of every
+ *                                `auto` call — answers BY BOUNDS in the same way, both passes gathered through the
+ *                                predicates' lists (default 0; same dimensions, same row codes held as range.codes_i8; a call
+ *                                whose candidates do not fit is answered by the metric kernel; exact.codes_i8 keeps its own
+ *                                scope); answers do not depend on it; vss_last_exact_filtered_scores reports it
  * Unknown names and values out of range are refused (VSS_ERROR, vss_last_error says which); the environment variables of the
  * same knobs (tools/README.md) are read once, in vss_create, through the same checks.  DESIGN.md §4.2 describes each mechanism. */
 int vss_set_option(vss_index *index, const char *name, int64_t value);
@@ -221,6 +227,19 @@ int vss_search_exact_batch_filtered_groups_device(vss_index *index, const float 
 /* The last such call: out4[0] = admitted rows listed, summed over the groups that had queries; [1] = (query, row) distances
  * computed; [2] = passes; [3] = bytes of list scratch held.  Results never depend on it. */
 int vss_last_exact_filtered(vss_index *index, uint64_t *out4);
+/* With vss_set_option "exact.filtered_codes_i8" = 1, a dimension whose padding is a multiple of 32 and valid codes of every live
+ * row, the exact part of every call above and below (every call that reports through vss_last_exact_filtered) is answered BY
+ * BOUNDS (csrc/exact_filtered_codes_kernels.h): pass A, k_exact_filtered_bounds_i8, gathers the 8-bit codes of the listed rows
+ * onto v_mfma_i32_32x32x32_i8 and writes, where the metric kernel writes a pair's distance, an UPPER bound of it
+ * (csrc/exact_codes_bound.h), so the unchanged selection leaves each query tau, the k-th smallest upper bound over its list;
+ * pass B is the gathered int8 range search under the radii tau, which re-scores in the metric every listed row whose LOWER
+ * bound is not above tau, into max(1024, 4 k) match cells per query; the k smallest (distance, slot) of a query's matches are
+ * its answer — the same cells, nothing certified or redone.  If the matches do not fit, the call is answered from the start
+ * by the metric kernel.  vss_last_exact_filtered [0..2] do not depend on the option.
+ * The last such call: out4[0] = the kind that answered, 0 = the metric kernel, 2 = bounds; [1] = bound-tile launches of pass A;
+ * [2] = bit pattern (double) of the largest finite slack of a query's bound; [3] = (query, row) pairs re-scored in the metric.
+ * [1..3] are 0 under kind 0. */
+int vss_last_exact_filtered_scores(vss_index *index, uint64_t *out4);
 /* Per-query predicates, every GROUP answered by the cheaper of the two calls above — the call for a chunk that names large and
  * tiny tenants at once, and for a caller that has bitmaps but no idea how many live rows each admits.  Table layout, n_bits and
  * the admission rule are those of the two calls; group_of == NULL is legal (every query takes bitmap 0).
